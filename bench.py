@@ -288,6 +288,27 @@ def parity_sample(args, mod, a, res, mat_host, lo, nct, ks, auto_mode, unsupport
             "against": "oracle/fft64_ref.c (strict build, -ffp-contract=off), bit-exact i64 limbs"}
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: the most one run writes
+
+
+def dump_outputs(out_dir: str, res) -> dict:
+    """Writes the output of the last timed step to out_dir/res.npy as float64 (the i64 digits are far below 2^53: exact) and the indices it
+    holds along axis 0 to out_dir/res_index.npy.  Whole ciphertexts (axis 0 of the output) while they fit DUMP_BYTES, else a fixed, seeded sample
+    of them; if one ciphertext alone is larger, a seeded sample of its rows of N coefficients.  The sample depends on the shape only."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0xD0D0)
+    items = res if res[0].numel() * 8 + 8 <= DUMP_BYTES else res.reshape(-1, res.shape[-1])
+    per = items[0].numel() * 8 + 8                                      # one item of res.npy and its entry in res_index.npy
+    k = min(items.shape[0], DUMP_BYTES // per)
+    idx = np.arange(k) if k == items.shape[0] else np.sort(rng.choice(items.shape[0], size=k, replace=False))
+    sample = items.index_select(0, torch.from_numpy(idx).to(items.device)).cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "res.npy"), sample)
+    np.save(os.path.join(out_dir, "res_index.npy"), idx.astype(np.float64))
+    return {"dir": out_dir, "res": list(sample.shape), "of": list(items.shape), "bytes": int(sample.nbytes + idx.size * 8)}
+
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import multirank   # noqa: E402  (torch-free at module level: the launcher, the refusals, the per-rank block - shared with tools/bench_*.py)
 
@@ -338,7 +359,12 @@ def main():
                     help="after the timed K steps and the parity sample: loop the same step for at least this many seconds of wall time (no events) and "
                          "report the rate beside the headline (`sustained`; the reference's harness measures for 5 s, poulpy-bench/src/lib.rs:41-45); 0 = skip")
     ap.add_argument("--parity-samples", type=int, default=8, help="timed-output ciphertexts checked against the CPU oracle (0 = none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps: write what the last timed step computed (rank 0's shard) to DIR/res.npy (float64, at most 64 MB: "
+                         "a fixed, seeded sample of the ciphertexts when the output is larger) and their indices to DIR/res_index.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global SIZE, DNUM, N, BASE2K
     if args.limbs:
         SIZE = DNUM = args.limbs
@@ -471,6 +497,9 @@ def main():
     if distributed:
         dist.barrier()
     dt = time.perf_counter() - t0
+
+    # timed output of the LAST step, as the caller receives it (before anything below runs the op again)
+    dumped = dump_outputs(args.dump_outputs, res) if (args.dump_outputs and rank == 0) else None
 
     # timed output of the LAST step -> parity sample against the CPU oracle (taken before the instrumented pass re-runs the op)
     parity = parity_sample(args, mod, a, res, mat_host, lo, nct, ks, auto_mode, trace or expand, cols, cols_in, relin, DSIZE) if args.parity_samples else None
@@ -656,6 +685,8 @@ def main():
             "rounding_margin": max([e["rounding_margin"] for e in per_rank if e.get("rounding_margin") is not None], default=margin),   # worst shard
             "sustained": sustained,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline and not ks:
             err = None
             for attempt in range(2):   # a host hiccup (a busy core, an allocation failure) gets one more try before the line reports "failed"

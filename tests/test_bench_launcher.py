@@ -57,6 +57,31 @@ def test_physical_core_selection():
     assert isinstance(b.cpu_model(), str)
 
 
+def test_dump_outputs_is_exact_bounded_and_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: float64 copies of the output (all of it, a seeded sample of whole ciphertexts, or a sample of rows of one ciphertext),
+    never more than DUMP_BYTES, and the same sample for the same shape."""
+    import numpy as np
+    import torch
+    b = _load_bench()
+    res = torch.randint(-2048, 2048, (50, 8, 2, 1024), dtype=torch.int64, generator=torch.Generator().manual_seed(1))
+    for budget, whole in ((10 ** 9, True), (1_000_000, True), (20_000, False)):
+        monkeypatch.setattr(b, "DUMP_BYTES", budget)
+        got = []
+        for run in range(2):
+            d = str(tmp_path / f"{budget}_{run}")
+            info = b.dump_outputs(d, res)
+            x, i = np.load(os.path.join(d, "res.npy")), np.load(os.path.join(d, "res_index.npy"))
+            assert x.dtype == np.float64 and i.dtype == np.float64
+            assert sum(os.path.getsize(os.path.join(d, f)) - 128 for f in os.listdir(d)) == info["bytes"] <= budget   # 128: the .npy header
+            items = res.numpy() if whole else res.numpy().reshape(-1, 1024)
+            assert x.shape[1:] == items.shape[1:] and len(i) == len(x) >= 1
+            assert np.array_equal(x, items[i.astype(np.int64)])
+            got.append((x, i))
+        assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+        if budget == 10 ** 9:
+            assert len(x) == 50
+
+
 @pytest.mark.gpu
 def test_single_rank_rccl_path_through_the_c_abi():
     """`bench.py --gpus 1` with the distributed path forced: process group, pz_comm_init_rank, pz_bcast_key (RCCL inside the C ABI),

@@ -4,12 +4,17 @@ pinned without a compiler:
 * `src/ffi.rs` is exactly what tools/gen_rust_ffi.py generates from include/poulpy_hip.h, and — checked independently of the
   generator — every `extern "C"` declaration has the header's arity and parameter types;
 * `src/hal_impl.rs` defines every required fn of `unsafe trait HalImpl` (poulpy-hal/src/oep/hal_impl.rs:25-755; the names are the
-  fixture tests/golden/hal_impl_fns.txt, re-derived from the reference checkout when it is present), none elided, none
+  fixture tests/golden/hal_impl_fns.txt), none elided, none
   `unimplemented!`, and only calls C functions the header declares;
 * `src/core_impl.rs` covers every required fn of `unsafe trait CoreImpl` (fixture tests/golden/core_impl_fns.txt): three families
   written out, four through the reference's `impl_core_*_default_methods!` macros;
 * `src/tests.rs` instantiates every cross-backend test of the reference's HAL suite for the families this backend implements.
+
+What these tests know about the reference checkout itself (trait and test names, whether an item is public, the generator's output) is
+read from tests/golden/reference_facts.json, written from a checkout by tests/golden/make_reference_facts.py: no test reads the checkout.
 """
+import functools
+import json
 import os
 import re
 import subprocess
@@ -19,7 +24,36 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CRATE = os.path.join(ROOT, "rust", "poulpy-hip-mi355x")
-REF = "/root/reference"
+
+# (file of the reference checkout, regex): the questions the tests below ask about the reference's source; the answers are recorded in
+# tests/golden/reference_facts.json (tests/golden/make_reference_facts.py evaluates exactly this list)
+REF_QUERIES = [
+    # the default feature set only touches public items (test_default_features_only_touch_public_items_of_the_reference)
+    ("poulpy-core/src/layouts/prepared/ggsw.rs", r"pub fn data\(&self\)"),
+    ("poulpy-core/src/layouts/prepared/gglwe.rs", r"pub fn data\(&self\)"),
+    ("poulpy-core/src/layouts/prepared/gglwe.rs", re.escape("pub(crate) data")),
+    ("poulpy-core/src/layouts/prepared/ggsw.rs", r"pub fn data\b"),
+    ("poulpy-core/src/layouts/gglwe.rs", r"pub fn at\b"), ("poulpy-core/src/layouts/ggsw.rs", r"pub fn at\b"),
+    ("poulpy-core/src/layouts/gglwe.rs", r"pub fn at_mut\b"), ("poulpy-core/src/layouts/ggsw.rs", r"pub fn at_mut\b"),
+    # every accessor batched.rs calls is public (test_batched_api_only_uses_public_items_of_the_reference)
+    ("poulpy-core/src/layouts/glwe.rs", r"pub fn data\(&self\) -> &VecZnx<D>"), ("poulpy-core/src/layouts/glwe.rs", r"pub fn data_mut\(&mut self\)"),
+    ("poulpy-core/src/layouts/lwe.rs", r"pub fn data\(&self\) -> &VecZnx<D>"), ("poulpy-core/src/layouts/lwe.rs", r"pub fn data_mut\(&mut self\)"),
+    ("poulpy-core/src/layouts/prepared/ggsw.rs", r"pub fn data\(&self\) -> &VmpPMat<D, B>"),
+    ("poulpy-core/src/layouts/gglwe.rs", r"pub fn data\(&self\) -> &MatZnx<D>"),
+    ("poulpy-core/src/layouts/ggsw.rs", r"pub fn at\(&self, row: usize, col: usize\) -> GLWE<&\[u8\]>"),
+    ("poulpy-hal/src/layouts/mat_znx.rs", r"pub fn cols_in\(&self\)"), ("poulpy-hal/src/layouts/mat_znx.rs", r"pub fn cols_out\(&self\)"),
+    ("poulpy-hal/src/layouts/mat_znx.rs", r"impl<D: DataRef> ZnxView for MatZnx<D>"),
+    ("poulpy-hal/src/layouts/vmp_pmat.rs", r"ZnxView for VmpPMat<D, B>"),
+    ("poulpy-hal/src/layouts/module.rs", r"pub fn n\(&self\) -> usize"),
+    ("poulpy-hal/src/layouts/znx_base.rs", r"fn as_ptr\(&self\) -> \*const Self::Scalar"),
+    # why the batched API is additive and takes device keys instead of the bin-fhe key types
+    ("poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs",
+     r"impl<BE: Backend> BlindRotationExecute<CGGI, BE> for Module<BE>|impl<BE: Backend, .*BlindRotationExecute"),
+    ("poulpy-bin-fhe/src/blind_rotation/layouts/key_prepared.rs", re.escape("pub(crate) data: Vec<GGSWPrepared<D, B>>")),
+    ("poulpy-bin-fhe/src/blind_rotation/layouts/key.rs", re.escape("pub(crate) keys: Vec<GGSW<D>>")),
+    ("poulpy-bin-fhe/src/blind_rotation/layouts/key.rs", r"impl<D: DataRef, BRT: BlindRotationAlgo> WriterTo for BlindRotationKey<D, BRT>"),
+    ("poulpy-bin-fhe/src/blind_rotation/lut.rs", re.escape("pub(crate) data: Vec<VecZnx<Vec<u8>>>")),
+]
 
 
 def read(*p):
@@ -33,6 +67,18 @@ def strip_rust_comments(s):
 
 def fixture(name):
     return [l.strip() for l in read(ROOT, "tests", "golden", name).splitlines() if l.strip() and not l.startswith("#")]
+
+
+@functools.lru_cache(maxsize=None)
+def ref_facts():
+    return json.loads(read(ROOT, "tests", "golden", "reference_facts.json"))
+
+
+def ref_has(path, pattern):
+    """whether `pattern` matches the reference's `path` (a query of REF_QUERIES, answered in the fixture)"""
+    key = f"{path} :: {pattern}"
+    assert key in ref_facts()["queries"], "not in tests/golden/reference_facts.json (run tests/golden/make_reference_facts.py): " + key
+    return ref_facts()["queries"][key]
 
 
 def test_ffi_rs_is_generated_from_the_header():
@@ -144,20 +190,15 @@ def test_hal_impl_defines_every_required_method_of_the_trait():
     assert code.count("{") == code.count("}") and code.count("(") == code.count(")")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 def test_fixtures_are_the_reference_traits():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_rust_shim as g
-    names = [m[0] for m in g.parse_trait(os.path.join(REF, "poulpy-hal", "src", "oep", "hal_impl.rs"))]
-    assert names == fixture("hal_impl_fns.txt")
-    core = [m[0] for m in g.parse_trait_named(os.path.join(REF, "poulpy-core", "src", "oep", "core_impl.rs"), "pub unsafe trait CoreImpl")]
-    assert core == fixture("core_impl_fns.txt")
-    # and the committed sources are what the generator writes today
-    before = {f: read(CRATE, "src", f) for f in ("hal_impl.rs", "core_impl.rs")}
-    g.main()
-    g.core_main(REF)
-    for f, txt in before.items():
-        assert read(CRATE, "src", f) == txt, f + " is stale: run python tools/gen_rust_shim.py"
+    assert ref_facts()["hal_trait_fns"] == fixture("hal_impl_fns.txt")
+    assert ref_facts()["core_trait_fns"] == fixture("core_impl_fns.txt")
+    # and the committed sources are what the generator writes from the reference today: the generator is the one that ran, its output unchanged
+    import hashlib
+    for rel, digest in ref_facts()["sha256"].items():
+        assert hashlib.sha256(open(os.path.join(ROOT, rel), "rb").read()).hexdigest() == digest, \
+            rel + " changed: run python tools/gen_rust_shim.py, then tests/golden/make_reference_facts.py, against the reference checkout"
+    assert sorted(ref_facts()["sha256"]) == sorted(["tools/gen_rust_shim.py", "rust/poulpy-hip-mi355x/src/hal_impl.rs", "rust/poulpy-hip-mi355x/src/core_impl.rs"])
 
 
 def test_core_impl_covers_the_trait():
@@ -179,12 +220,11 @@ def test_core_impl_covers_the_trait():
                                     # matrix-level forms: one batched call over the (row, column) entries
                                     "gglwe_keyswitch", "gglwe_keyswitch_assign", "gglwe_external_product", "gglwe_external_product_assign",
                                     "ggsw_external_product", "ggsw_external_product_assign"])
-    if os.path.isdir(REF):   # the four macro families + the 35 written-out fns are the whole trait
-        n_macro = 0
-        for fam in ("decryption", "conversion", "operations", "encryption"):
-            s = read(REF, "poulpy-core", "src", "oep", fam + ".rs")
-            n_macro += len(re.findall(r"\n        fn (\w+)", s[s.index("macro_rules!"):]))
-        assert n_macro + len(written) == len(want)
+    # the four macro families + the 35 written-out fns are the whole trait
+    macro_fns = ref_facts()["core_macro_fns"]
+    assert sorted(macro_fns) == ["conversion", "decryption", "encryption", "operations"]
+    n_macro = sum(len(v) for v in macro_fns.values())
+    assert n_macro + len(written) == len(want)
     assert code.count("{") == code.count("}") and code.count("(") == code.count(")")
 
 
@@ -196,38 +236,32 @@ def test_lib_znx_and_tests_rs():
     znx = strip_rust_comments(read(CRATE, "src", "znx.rs"))
     traits = re.findall(r"\n    (Znx\w+)::", znx)
     assert len(traits) == len(set(traits)) == 27          # the 27 Znx* impls of poulpy-cpu-ref/src/fft64/znx.rs
-    if os.path.isdir(REF):
-        ref = read(REF, "poulpy-cpu-ref", "src", "fft64", "znx.rs")
-        assert sorted(traits) == sorted(re.findall(r"\nimpl (Znx\w+) for FFT64Ref", ref))
+    assert sorted(traits) == sorted(ref_facts()["cpu_ref_znx_impls"])
     t = strip_rust_comments(read(CRATE, "src", "tests.rs"))
     listed = set(re.findall(r"\b(test_\w+)\b", t))
     assert "cross_backend_test_suite!" in t and "backend_ref = poulpy_cpu_ref::FFT64Ref" in t and "backend_test = crate::FFT64Hip" in t
-    if os.path.isdir(REF):
-        for mod_ in ("vec_znx", "vec_znx_big", "vec_znx_dft", "svp", "vmp"):
-            s = read(REF, "poulpy-hal", "src", "test_suite", mod_ + ".rs")
-            cross = [m.group(1) for m in re.finditer(r"pub fn (test_\w+)(?:<[^>]*>)?\s*\(\s*params", s)]
-            assert cross and set(cross) <= listed, (mod_, set(cross) - listed)
+    assert sorted(ref_facts()["hal_suite_cross_backend_tests"]) == sorted(["vec_znx", "vec_znx_big", "vec_znx_dft", "svp", "vmp"])
+    for mod_, cross in ref_facts()["hal_suite_cross_backend_tests"].items():
+        assert cross and set(cross) <= listed, (mod_, set(cross) - listed)
     for f in ("lib.rs", "znx.rs", "tests.rs"):
         c = strip_rust_comments(read(CRATE, "src", f))
         assert c.count("{") == c.count("}") and c.count("(") == c.count(")"), f
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 def test_cross_backend_suite_lists_every_test_the_avx_backend_lists():
     """module by module, `src/tests.rs` instantiates at least the tests poulpy-cpu-avx/src/fft64/tests.rs instantiates for FFT64Avx
     (Missing 4 read the vec_znx_dft list as shorter: it is the AVX list plus test_vec_znx_copy)."""
-    avx = read(REF, "poulpy-cpu-avx", "src", "fft64", "tests.rs")
     ours = strip_rust_comments(read(CRATE, "src", "tests.rs"))
     mine = {m.group(1): set(re.findall(r"test_\w+", m.group(2))) for m in re.finditer(r"hal_suite!\((\w+):(.*?)\);", ours, re.S)}
     mine["sampling"] = set(re.findall(r"(test_\w+)\s*=>", ours))
     seen = 0
-    for m in re.finditer(r"mod (\w+),.*?tests = \{(.*?)\n    \}", avx, re.S):
-        names = set(re.findall(r"(test_\w+)\s*=>", m.group(2)))
-        assert names and names <= mine.get(m.group(1), set()), (m.group(1), names - mine.get(m.group(1), set()))
+    for mod_, avx_names in ref_facts()["avx_suite_tests"].items():
+        names = set(avx_names)
+        assert names and names <= mine.get(mod_, set()), (mod_, names - mine.get(mod_, set()))
         seen += 1
     assert seen >= 6   # vec_znx, svp, vec_znx_big, vec_znx_dft, vmp, sampling
     for conv in ("test_convolution", "test_convolution_by_const", "test_convolution_pairwise"):
-        assert conv in avx and conv in ours
+        assert ref_facts()["avx_mentions"][conv] and conv in ours
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -274,15 +308,13 @@ def test_default_features_only_touch_public_items_of_the_reference():
     for name in ("glwe_keyswitch", "glwe_keyswitch_assign", "gglwe_keyswitch", "gglwe_keyswitch_assign", "glwe_automorphism",
                  "glwe_automorphism_add_assign", "glwe_automorphism_sub_negate"):
         assert f"::{name}_default(" in default_src, name                  # without the feature: the reference algorithm
-    if os.path.isdir(REF):
-        ggsw = read(REF, "poulpy-core", "src", "layouts", "prepared", "ggsw.rs")
-        gglwe = read(REF, "poulpy-core", "src", "layouts", "prepared", "gglwe.rs")
-        assert re.search(r"pub fn data\(&self\)", ggsw)
-        assert not re.search(r"pub fn data\(&self\)", gglwe) and "pub(crate) data" in gglwe   # the reason for the feature split
-        # every inherent method the default build calls on a prepared key / layout view is `pub` in the reference
-        for meth, files in (("data", ("layouts/prepared/ggsw.rs",)), ("at", ("layouts/gglwe.rs", "layouts/ggsw.rs")),
-                            ("at_mut", ("layouts/gglwe.rs", "layouts/ggsw.rs"))):
-            assert any(re.search(r"pub fn %s\b" % meth, read(REF, "poulpy-core", "src", f)) for f in files), meth
+    prep = "poulpy-core/src/layouts/prepared/"
+    assert ref_has(prep + "ggsw.rs", r"pub fn data\(&self\)")
+    assert not ref_has(prep + "gglwe.rs", r"pub fn data\(&self\)") and ref_has(prep + "gglwe.rs", re.escape("pub(crate) data"))   # the reason for the feature split
+    # every inherent method the default build calls on a prepared key / layout view is `pub` in the reference
+    for meth, files in (("data", ("layouts/prepared/ggsw.rs",)), ("at", ("layouts/gglwe.rs", "layouts/ggsw.rs")),
+                        ("at_mut", ("layouts/gglwe.rs", "layouts/ggsw.rs"))):
+        assert any(ref_has("poulpy-core/src/" + f, r"pub fn %s\b" % meth) for f in files), meth
 
 
 def test_sibling_modules_are_leased_from_a_bounded_pool():
@@ -373,7 +405,6 @@ def test_batched_api_reaches_every_batched_entry_point_without_unsafe_in_its_sig
         assert "pub " not in body, st
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 def test_batched_api_only_uses_public_items_of_the_reference():
     """every accessor of a reference type that batched.rs calls is `pub` upstream; and the facts INTEGRATION.md states about what is NOT."""
     checks = [
@@ -389,14 +420,15 @@ def test_batched_api_only_uses_public_items_of_the_reference():
         ("poulpy-hal/src/layouts/znx_base.rs", r"fn as_ptr\(&self\) -> \*const Self::Scalar"),
     ]
     for path, pat in checks:
-        assert re.search(pat, read(REF, path)), (path, pat)
+        assert ref_has(path, pat), (path, pat)
     # why the API is additive and takes device keys instead of the bin-fhe key types
-    assert re.search(r"impl<BE: Backend> BlindRotationExecute<CGGI, BE> for Module<BE>|impl<BE: Backend, .*BlindRotationExecute", read(REF, "poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs"))
-    assert "pub(crate) data: Vec<GGSWPrepared<D, B>>" in read(REF, "poulpy-bin-fhe/src/blind_rotation/layouts/key_prepared.rs")
-    assert "pub(crate) keys: Vec<GGSW<D>>" in read(REF, "poulpy-bin-fhe/src/blind_rotation/layouts/key.rs")
-    assert re.search(r"impl<D: DataRef, BRT: BlindRotationAlgo> WriterTo for BlindRotationKey<D, BRT>", read(REF, "poulpy-bin-fhe/src/blind_rotation/layouts/key.rs"))
-    assert "pub(crate) data: Vec<VecZnx<Vec<u8>>>" in read(REF, "poulpy-bin-fhe/src/blind_rotation/lut.rs")
-    assert "pub(crate) data" in read(REF, "poulpy-core/src/layouts/prepared/gglwe.rs")
+    assert ref_has("poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs",
+                   r"impl<BE: Backend> BlindRotationExecute<CGGI, BE> for Module<BE>|impl<BE: Backend, .*BlindRotationExecute")
+    assert ref_has("poulpy-bin-fhe/src/blind_rotation/layouts/key_prepared.rs", re.escape("pub(crate) data: Vec<GGSWPrepared<D, B>>"))
+    assert ref_has("poulpy-bin-fhe/src/blind_rotation/layouts/key.rs", re.escape("pub(crate) keys: Vec<GGSW<D>>"))
+    assert ref_has("poulpy-bin-fhe/src/blind_rotation/layouts/key.rs", r"impl<D: DataRef, BRT: BlindRotationAlgo> WriterTo for BlindRotationKey<D, BRT>")
+    assert ref_has("poulpy-bin-fhe/src/blind_rotation/lut.rs", re.escape("pub(crate) data: Vec<VecZnx<Vec<u8>>>"))
+    assert ref_has("poulpy-core/src/layouts/prepared/gglwe.rs", re.escape("pub(crate) data"))
 
 
 def test_batched_per_op_wrappers_check_the_ring_degree_against_the_module():
