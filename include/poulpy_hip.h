@@ -429,6 +429,31 @@ int pz_glwe_tensor_relinearize_batched(pz_module* m, int64_t* res, const int64_t
 int pz_glwe_tensor_mul_relinearize_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
                                            const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, int mode, size_t batch);
 
+/* GLWE x plaintext polynomial on `batch` device-resident ciphertexts (poulpy-core/src/operations/glwe.rs): PZ_MUL_PLAIN glwe_mul_plain
+ * :184-248, PZ_MUL_PLAIN_ASSIGN glwe_mul_plain_assign :250-303.  The tensor params are reused: a / res = batch GLWEs
+ * VecZnx(rank+1, a_size | res_size), pt = VecZnx(1, b_size) with b_effective_k (bottom limbs of both operands masked), one base2k
+ * ab_base2k for the operands; each column is normalized to res_base2k with cnv_offset_lo.  pt_shared != 0: one plaintext for the whole
+ * batch, else one per ciphertext.  PZ_MUL_PLAIN_ASSIGN: res is the operand (a NULL or == res; a_size = res_size, res_base2k =
+ * ab_base2k, a_effective_k = the operand's).  Device pointers; res aliases neither pt nor (PZ_MUL_PLAIN) a. */
+enum { PZ_MUL_PLAIN = 0, PZ_MUL_PLAIN_ASSIGN = 1 };
+size_t pz_glwe_mul_plain_workspace_bytes(const pz_module* m, const pz_glwe_tensor_params* p, int mode, int pt_shared, size_t batch);
+int pz_glwe_mul_plain_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* pt, int pt_shared, const pz_glwe_tensor_params* p,
+                              int mode, size_t batch);
+/* GLWE x constant, one constant for the whole batch: PZ_MUL_CONST glwe_mul_const (operations/glwe.rs:66-96), PZ_MUL_CONST_ASSIGN
+ * glwe_mul_const_assign (:98-133: res_big has res_size limbs; a NULL or == res, a_size = res_size, a_base2k = res_base2k).  re / im:
+ * HOST arrays of b_size digits, either may be NULL.  re alone: the poulpy-core call itself; with im, or with neither, poulpy-ckks's
+ * complex constant (leveled/default/mul.rs:342-415): re product, im product normalized then times X^{N/2}, the two added without
+ * renormalization; neither: res = 0.  Device pointers for res / a. */
+typedef struct {
+    uint64_t rank;
+    uint64_t a_size, a_base2k;
+    uint64_t res_size, res_base2k;
+    uint64_t cnv_offset;
+} pz_glwe_mul_const_params;
+enum { PZ_MUL_CONST = 0, PZ_MUL_CONST_ASSIGN = 1 };
+int pz_glwe_mul_const_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* re, const int64_t* im, size_t b_size,
+                              const pz_glwe_mul_const_params* p, int mode, size_t batch);
+
 /* BlindRotationExecute<CGGI>::blind_rotation_execute (poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs:76-118)
  * on `batch` LWE ciphertexts that share the lookup table and the prepared blind-rotation key:
  *   block_size > 1 : execute_block_binary  (:265-368)       block_size == 1 : execute_standard (:370-440)

@@ -259,6 +259,18 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
     void ggsw_expand_row_batched(int64_t* ggsw, size_t dnum, const double* const* tsk, const pz_glwe_op_params& p, size_t count) {
         check(pz_ggsw_expand_row_batched(m_, ggsw, dnum, tsk, &p, count), "ggsw_expand_row_batched");
     }
+    // GLWE x plaintext (mode PZ_MUL_PLAIN / PZ_MUL_PLAIN_ASSIGN) and GLWE x constant (PZ_MUL_CONST / PZ_MUL_CONST_ASSIGN; re / im on the host)
+    size_t glwe_mul_plain_workspace_bytes(const pz_glwe_tensor_params& p, int mode, bool pt_shared, size_t batch) const {
+        return pz_glwe_mul_plain_workspace_bytes(m_, &p, mode, pt_shared ? 1 : 0, batch);
+    }
+    void glwe_mul_plain_batched(int64_t* res, const int64_t* a, const int64_t* pt, bool pt_shared, const pz_glwe_tensor_params& p, int mode,
+                                size_t batch) {
+        check(pz_glwe_mul_plain_batched(m_, res, a, pt, pt_shared ? 1 : 0, &p, mode, batch), "glwe_mul_plain_batched");
+    }
+    void glwe_mul_const_batched(int64_t* res, const int64_t* a, const int64_t* re, const int64_t* im, size_t b_size,
+                                const pz_glwe_mul_const_params& p, int mode, size_t batch) {
+        check(pz_glwe_mul_const_batched(m_, res, a, re, im, b_size, &p, mode, batch), "glwe_mul_const_batched");
+    }
 
   private:
     pz_module* m_ = nullptr;

@@ -69,6 +69,31 @@ static inline int dev_idft(pz_module* M, int batch, DV res, int res_col, DV a, i
     return PZ_OK;
 }
 
+// convolution.rs:35-80: limbs < min_size - 1 plain forward transforms, limb min_size - 1 with `mask` applied to the coefficients,
+// limbs >= min_size zero.  `a` batched with stride a_bs (scalars), res with stride res_bs.
+static inline int dev_cnv_prepare(pz_module* M, int batch, double* res, long long res_bs, int cols, int res_size, const int64_t* a, long long a_bs,
+                                  int a_cols, int a_size, long long mask, cplx* T) {
+    const long long n = (long long)M->n;
+    const int min_size = std::min(res_size, a_size);
+    if (min_size > 1) {
+        const int nl = min_size - 1;
+        PolyMap sm{nl, cols, a_bs, (long long)a_cols * n, n, 0};
+        PolyMap dm{nl, cols, res_bs, n, (long long)res_size * n, 0};
+        PZ_TRY(launch_fwd_pass1(M, batch * nl * cols, (const long long*)a, sm, T));
+        PZ_TRY(launch_fwd_pass2(M, batch * nl * cols, T, res, dm, nullptr));
+    }
+    if (min_size > 0) {
+        const int last = min_size - 1;
+        PolyMap sm{1, cols, a_bs, 0, n, (long long)last * a_cols * n};
+        PolyMap dm{1, cols, res_bs, 0, (long long)res_size * n, (long long)last * n};
+        PZ_TRY(launch_fwd_pass1(M, batch * cols, (const long long*)a, sm, T, false, mask));
+        PZ_TRY(launch_fwd_pass2(M, batch * cols, T, res, dm, nullptr));
+    }
+    for (int c = 0; c < cols && res_size > min_size; ++c)
+        PZ_TRY(launch_ew(M, EW_ZERO, res + ((long long)c * res_size + min_size) * n, res_bs, n, nullptr, 0, 0, nullptr, 0, 0, res_size - min_size, batch));
+    return PZ_OK;
+}
+
 // ------------------------------------------------------------------------------
 // host/device pointer resolution
 // ------------------------------------------------------------------------------

@@ -217,4 +217,21 @@ int launch_cnv_apply(pz_module* M, int batch, double* res, long long res_bs, int
 int launch_cnv_by_const(pz_module* M, long long* res, int res_cols, int res_col, int min_size, int offset, const long long* a, int a_cols,
                         int a_size, int a_col, const long long* bconst, int b_size);
 
+// ---- launch_plain.hip ---------------------------------------------------------------------------------------------
+// GLWE x constant (k_mul_const_nz, device_plain.hpp): one arm = the host constant b (b_size digits), res_big's limb count and cnv_offset_hi
+struct MulConstArmSpec { const int64_t* b; int b_size, big_size, hi; };
+// GLWE x plaintext middle kernel (k_mid_cnv_pt<AS, BS>, device_plain.hpp): a = the operand columns' T' as k_mid_cnv reads them, b = the
+// plaintext's T' [pt][limb < b_size - 1][m] / [pt][m] with b_bs points between plaintexts (0: shared); T2 = [col][ct][kk < min_size][m]
+bool mid_cnv_pt_supported(const pz_module* M, int cols, int a_size, int b_size, int min_size);
+int launch_mid_cnv_pt(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, bool b_shared, cplx* T2,
+                      int cols, int a_size, int b_size, int min_size, int offset);
+// k_cnv_by_const on every column of `batch` ciphertexts: res_big [ct][limb < res_size][col][n] (limbs >= min_size untouched)
+int launch_cnv_by_const_batched(pz_module* M, int batch, long long* res, long long res_bs, int res_size, int min_size, int offset, const long long* a,
+                                long long a_bs, int cols, int a_size, const long long* bconst, int b_size);
+// same base2k, b_size <= 32, a_size <= 64
+bool mul_const_nz_supported(const pz_module* M, int a_size, int b_size);
+// form 0: arm0; 1: X^{N/2} arm0; 2: arm0 + X^{N/2} arm1 - every column of `batch` ciphertexts (a: a_size limbs, res: res_size limbs, cols columns)
+int launch_mul_const_nz(pz_module* M, int batch, long long* res, long long res_bs, const long long* a, long long a_bs, int cols, int a_size,
+                        int res_size, int base2k, long long res_offset, int form, const MulConstArmSpec* arms);
+
 }  // namespace pz

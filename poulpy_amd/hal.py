@@ -51,6 +51,11 @@ class GlweTensorParams(C.Structure):
                                         "res_base2k", "cnv_offset")]
 
 
+class GlweMulConstParams(C.Structure):
+    """pz_glwe_mul_const_params (include/poulpy_hip.h)"""
+    _fields_ = [(k, c_uint64) for k in ("rank", "a_size", "a_base2k", "res_size", "res_base2k", "cnv_offset")]
+
+
 _lib = None
 PZ_ABI_VERSION = 4   # pz_abi_version() of include/poulpy_hip.h this mirror was written against
 
@@ -88,6 +93,14 @@ def load_library(path: str | None = None) -> C.CDLL:
                  "pz_cnv_pairwise_apply_dft_tmp_bytes", "pz_cnv_by_const_apply_tmp_bytes", "pz_glwe_tensor_apply_workspace_bytes",
                  "pz_comm_unique_id_bytes"):
         getattr(lib, name).restype = c_size_t
+    # GLWE x plaintext / x constant (api_plain.hip)
+    lib.pz_glwe_mul_plain_workspace_bytes.restype = c_size_t
+    lib.pz_glwe_mul_plain_workspace_bytes.argtypes = [c_void_p, c_void_p, c_int, c_int, c_size_t]
+    lib.pz_glwe_mul_plain_batched.restype = c_int
+    lib.pz_glwe_mul_plain_batched.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_size_t]
+    lib.pz_glwe_mul_const_batched.restype = c_int
+    lib.pz_glwe_mul_const_batched.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_size_t, c_void_p, c_int,
+                                              c_size_t]
     if path is None:
         _lib = lib
     return lib
@@ -662,6 +675,30 @@ class Module:
         mode = self.TENSOR_MODES[mode] if isinstance(mode, str) else int(mode)
         self._ck(self.lib.pz_glwe_tensor_mul_relinearize_batched(self.handle, res, a, b if b is not None else a, tsk_pmat, C.byref(tparams),
                                                                  C.byref(rparams), c_int(mode), c_size_t(batch)))
+
+    MUL_PLAIN_MODES = {"into": 0, "assign": 1}
+
+    def glwe_mul_plain_workspace_bytes(self, params: GlweTensorParams, mode, pt_shared: bool, batch: int) -> int:
+        mode = self.MUL_PLAIN_MODES[mode] if isinstance(mode, str) else int(mode)
+        return self.lib.pz_glwe_mul_plain_workspace_bytes(self.handle, C.byref(params), mode, int(bool(pt_shared)), batch)
+
+    def glwe_mul_plain_batched(self, res: c_void_p, a, pt: c_void_p, pt_shared: bool, params: GlweTensorParams, mode, batch: int):
+        """poulpy-core operations/glwe.rs:184-303 (glwe_mul_plain / _assign) on device-resident GLWEs; params: b_size / b_effective_k describe
+        the plaintext VecZnx(1, b_size); pt_shared: one plaintext for the batch; mode: "into" | "assign" (a None: res is the operand)."""
+        mode = self.MUL_PLAIN_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._ck(self.lib.pz_glwe_mul_plain_batched(self.handle, res, a, pt, int(bool(pt_shared)), C.byref(params), mode, batch))
+
+    def glwe_mul_const_batched(self, res: c_void_p, a, re, im, params: GlweMulConstParams, mode, batch: int, b_size: int | None = None):
+        """poulpy-core operations/glwe.rs:66-133 (glwe_mul_const / _assign; `re` alone) and poulpy-ckks leveled/default/mul.rs:342-415 (the
+        complex constant: `im`, or neither); re / im: host digit arrays or None; mode: "into" | "assign" (a None: res is the operand)."""
+        mode = self.MUL_PLAIN_MODES[mode] if isinstance(mode, str) else int(mode)
+        arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in (re, im)]
+        sizes = {x.size for x in arrs if x is not None}
+        assert len(sizes) <= 1, "re and im carry the same number of digits"
+        if b_size is None:
+            b_size = sizes.pop() if sizes else 0
+        ptrs = [None if x is None else x.ctypes.data_as(POINTER(c_int64)) for x in arrs]
+        self._ck(self.lib.pz_glwe_mul_const_batched(self.handle, res, a, ptrs[0], ptrs[1], b_size, C.byref(params), mode, batch))
 
     # -- LWE glue of the gate bootstrap (device-resident batches; an LWE = VecZnx(n_lwe + 1, 1, size)) -------------
     def lwe_mod_switch_2n_batched(self, res: c_void_p, lwe: c_void_p, n_lwe: int, lwe_size: int, base2k: int, n2: int, negate: bool, batch: int):
