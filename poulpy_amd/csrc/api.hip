@@ -244,21 +244,6 @@ int pz_module_new_on_device(uint64_t n, int device, pz_module** out) {
     M->n = n; M->m = n >> 1; M->device = device; M->plan = pl;
     int r = PZ_OK;
     do {
-#ifdef PZ_EXPERIMENT
-        if (const char* cm = getenv("POULPY_DBG_CU_MASK")) {
-            // diagnostic: restrict the module stream to N CUs ("N" or "N,mode": mode 0 = the first N mask bits, 1 = spread evenly)
-            int ncus = atoi(cm), mode = 0;
-            if (const char* c = strchr(cm, ',')) mode = atoi(c + 1);
-            uint32_t mask[8] = {0};
-            int on = 0;
-            for (int i = 0; i < 256; ++i) {
-                const bool en = mode == 0 ? i < ncus : ((long long)(i + 1) * ncus / 256 > (long long)i * ncus / 256);
-                if (en) { mask[i >> 5] |= 1u << (i & 31); ++on; }
-            }
-            if (hipExtStreamCreateWithCUMask(&M->stream, 8, mask) != hipSuccess) { r = fail(PZ_ERR_HIP, "masked stream create failed"); break; }
-            M->cu_count = on;
-        } else
-#endif
         if (hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking) != hipSuccess) { r = fail(PZ_ERR_HIP, "stream create failed"); break; }
         if ((r = build_tables(M)) != PZ_OK) break;
         if (hipMalloc(&M->margin, 16) != hipSuccess) { r = fail(PZ_ERR_HIP, "margin alloc failed"); break; }
@@ -359,13 +344,6 @@ int pz_module_sync(pz_module* M) {
     return PZ_OK;
 }
 void* pz_module_stream(pz_module* M) { return M ? (void*)M->stream : nullptr; }
-int pz_module_set_ws_shift(pz_module* M, size_t bytes) {   // diagnostic (not in the header): extra padding in front of T2'
-    if (!M) return fail(PZ_ERR_INVALID, "null module");
-    std::lock_guard<std::mutex> lock_(M->mu);
-    M->ws_shift = bytes;
-    M->graph_epoch++;
-    return PZ_OK;
-}
 int pz_module_set_chunk(pz_module* M, size_t c) {
     if (!M) return fail(PZ_ERR_INVALID, "null module");
     std::lock_guard<std::mutex> lock_(M->mu);

@@ -80,8 +80,7 @@ static int br_pipeline_path(const BrCall& c, bool* taken) {
     PZ_BR_UNPACK(c)
     *taken = false;
     const int npi = cols * std::min(dnum, rsz), npo = cols * bsz, nrows_key = dnum * cols, ncols_key = cols * bsz;
-    static const int br_mid = exp_knob("POULPY_DBG_BR_MID", 1);
-    if (!(br_mid && M->fuse_mid && M->fuse_tail && tail_supported(M) && M->plan.m2 == 128 && mid_supported(M, npi, npo) && npi == nrows_key && blk <= 16))
+    if (!(M->fuse_mid && M->fuse_tail && tail_supported(M) && M->plan.m2 == 128 && mid_supported(M, npi, npo) && npi == nrows_key && blk <= 16))
         return PZ_OK;
     *taken = true;
     const size_t key_bytes = align256((size_t)blk * nrows_key * ncols_key * n8);
@@ -91,9 +90,8 @@ static int br_pipeline_path(const BrCall& c, bool* taken) {
     const int nblocks = n_lwe / blk;
     const bool acc32 = k <= 31 && nblocks >= 2 && tail_acc32_supported(M);
     // round 6: 16-bit values in the tails' own tile order where the digits fit them (base2k <= 15): a quarter of the i64 bytes, whole 128-byte runs for
-    // pass 1 (k_fwd_pass1_t16) and the tail (TailCall::acc32 bits 3 / 4); POULPY_DBG_BR_ACC16=0: the 32-bit form
-    static const int acc16_knob = exp_knob("POULPY_DBG_BR_ACC16", 1);
-    const bool acc16 = acc32 && acc16_knob && k <= 15;
+    // pass 1 (k_fwd_pass1_t16) and the tail (TailCall::acc32 bits 3 / 4)
+    const bool acc16 = acc32 && k <= 15;
     const size_t d_bytes = acc32 ? align256((size_t)B * res_ct * sizeof(int)) : 0;
     PZ_TRY(ws_reserve(M, key_bytes + t_bytes + t2_bytes + kMidDummyBytes + d_bytes));
     char* base = (char*)M->ws;
@@ -130,8 +128,7 @@ static int br_small_ring_path(const BrCall& c, bool* taken) {
     PZ_BR_UNPACK(c)
     *taken = false;
     const int npi = cols * std::min(dnum, rsz), nrows_key = dnum * cols, ncols_key = cols * bsz;
-    static const int br_small = exp_knob("POULPY_DBG_BR_SMALL", 1);
-    if (!(br_small && M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, bsz) && npi == nrows_key && npi <= 12 && blk <= 64))
+    if (!(M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, bsz) && npi == nrows_key && npi <= 12 && blk <= 64))
         return PZ_OK;
     *taken = true;
     const size_t s_bytes = align256(batch * npi * (size_t)M->m * sizeof(cplx)), a_bytes = align256(batch * ncols_key * (size_t)M->m * sizeof(cplx));
@@ -147,10 +144,10 @@ static int br_small_ring_path(const BrCall& c, bool* taken) {
     PZ_TRY(ws_take(M, base, a_bytes, &A));
     if (acc32) PZ_TRY(ws_take(M, base, d_bytes, &D));
     PolyMap sm{npi / cols, cols, res_ct, (long long)cols * n, n, 0};
-    // the inverse kernel of a block also runs the forward transform of the new accumulator for the next block (POULPY_DBG_BR_SMALL=2:
-    // separate k_small_fwd launches), when its limbs are among the ones the inverse produces
+    // the inverse kernel of a block also runs the forward transform of the new accumulator for the next block, when its limbs are among the
+    // ones the inverse produces
     const int fl = npi / cols;
-    const bool chain = br_small != 2 && fl <= bsz && fl <= rsz && M->n < 4096;   // (N = 4096 - block sizes the pipeline path declines - has no chained form)
+    const bool chain = fl <= bsz && fl <= rsz && M->n < 4096;   // (N = 4096 - block sizes the pipeline path declines - has no chained form)
     // Two halves of the batch on two streams (round 5): the block step is bound by FP64 issue, the inverse / forward kernel around it by
     // HBM and LDS latency - issued back to back on one stream each leaves the other's unit idle; as two independent chains the step of one
     // half overlaps with the transforms of the other (split at a tile boundary of the block step: 8 ciphertexts)
@@ -165,9 +162,8 @@ static int br_small_ring_path(const BrCall& c, bool* taken) {
         // (the separate forward launch of the unchained form reads `res`: i64 throughout there)
         const bool use32 = acc32 && chain;
         const bool in32 = use32 && b0 > 0, out32 = use32 && more;
-        // (round 6: 16-bit digits - natural order here, the small-ring kernels read whole rows - where base2k <= 15; POULPY_DBG_BR_ACC16=0: 32-bit)
-        static const int acc16_knob_s = exp_knob("POULPY_DBG_BR_ACC16", 1);
-        const bool use16 = use32 && acc16_knob_s && k <= 15;
+        // (round 6: 16-bit digits - natural order here, the small-ring kernels read whole rows - where base2k <= 15)
+        const bool use16 = use32 && k <= 15;
         for (int half = 0; half < (hA < B ? 2 : 1); ++half) {
             const int c0 = half ? hA : 0, nb = half ? B - hA : hA;
             ss.on(half == 1);
@@ -332,9 +328,8 @@ static int blind_rotation_extended(pz_module* M, int64_t* res, const int64_t* lw
     DV ad{acc_dft, n * cols * dnum, cols, dnum}, vr{vmp_res, n * cols * bsz, cols, bsz}, aa{acc_add, n * cols * bsz, cols, bsz};
     const bool tail = M->fuse_tail && tail_supported(M);
     // N = 1024 / 2048 / 4096: the transforms of the small-ring pipeline around the per-coefficient steps, as in blind_rotation()
-    static const int br_small = exp_knob("POULPY_DBG_BR_SMALL", 1);
     const int npi = cols * std::min(dnum, rsz);
-    const bool small_tf = br_small && M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, bsz) && npi == dnum * cols;
+    const bool small_tf = M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, bsz) && npi == dnum * cols;
     for (int b0 = 0; b0 + blk <= n_lwe; b0 += blk) {
         if (small_tf) {
             PolyMap sm{npi / cols, cols, res_ct, (long long)cols * n, n, 0};

@@ -324,8 +324,7 @@ struct TensorWave {
         if (!add) {
             // the diagonal launches leave 16-bit copies of their digits beside the tensor columns (base2k <= 16, fused tails): the pairwise
             // launches read those - 2 B per coefficient and diagonal column instead of the 8 B a line of the i64 column costs
-            static const bool d16_on = (exp_knob("POULPY_DBG_TENSOR_D16", 1) != 0);
-            const bool use16 = d16_on && d16 != nullptr && fused;
+            const bool use16 = d16 != nullptr && fused;
             const long long d16_ts = (long long)nb * t.res_size * n;   // one diagonal term's copies
             for (int i = 0; i < t.cols; ++i) {
                 NzCombine cb{1, {0, 0}, {0, 0}};
@@ -451,9 +450,8 @@ int pz_glwe_tensor_mul_relinearize_batched(pz_module* M, int64_t* res, const int
     if (batch == 0) return PZ_OK;
     TensorWave w;
     w.M = M; w.p = tp; w.t = t; w.square = square; w.add = false; w.n = (long long)M->n;
-    static const bool t16_env = (exp_knob("POULPY_DBG_MUL_T16", 1) != 0);
     static const bool combine_env = (rt_knob("POULPY_DBG_TENSOR_COMBINE", 1) != 0), fused_env = (rt_knob("POULPY_DBG_TENSOR_FUSED", 1) != 0);
-    const bool compact = t16_env && combine_env && fused_env && tp->res_base2k <= 14 && tp->res_base2k == tp->ab_base2k && t.cols <= 3 && t.dft_size >= 1 &&
+    const bool compact = combine_env && fused_env && tp->res_base2k <= 14 && tp->res_base2k == tp->ab_base2k && t.cols <= 3 && t.dft_size >= 1 &&
                          mid_cnv_supported(M, t.a_size, t.b_size, std::min(t.dft_size, t.a_size + t.b_size - 1)) && glwe_relin_t16_supported(M, rp);
     const size_t chunk = std::min(tensor_chunk(M, t, batch), glwe_relin_chunk(M, rp, batch));
     const long long a_ct = w.n * t.cols * t.a_size, b_ct = w.n * t.cols * t.b_size, res_ct = w.n * t.cols * (long long)rp->res_size;
@@ -461,7 +459,7 @@ int pz_glwe_tensor_mul_relinearize_batched(pz_module* M, int64_t* res, const int
     // the tensor of a wave: ws2 (the two halves of the call carve the main workspace one after the other).  16-bit form: the columns of a wave
     // sit a fraction of the 4 MiB channel interleave out of phase - the pairwise tail reads two columns and writes the third at the same offset,
     // the relinearization's tail reads one beside its spectrum and result streams (as T2' against the result, kT2Phase in api_glwe.hip)
-    static const long long t16_phase = (long long)exp_knob("POULPY_DBG_T16_PHASE_KIB", 768) * 1024 / 2;
+    static constexpr long long t16_phase = 768 * 1024 / 2;
     const long long t16_cs = (long long)chunk * t.res_size * w.n + t16_phase;
     PZ_TRY(ws2_reserve(M, compact ? (size_t)t16_cs * t.tcols * 2 : chunk * (size_t)tensor_ct * 8));
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {

@@ -141,16 +141,14 @@ static FusedWs fused_ws(const pz_module* M, const pz_glwe_op_params* p, const Op
     w.rtmp = au ? align256(chunk * n8 * std::max((size_t)s.cols_out * p->res_size, body_limbs)) : 0;
     // cross-base output: the tail's key-base digits (cols_out x key_size limbs per ciphertext) before the cross-base pass
     w.small2 = p->res_base2k != p->key_base2k ? align256(chunk * n8 * s.cols_out * ksz) : 0;
-    w.total = w.key + w.conv + w.t + w.t2 + w.rtmp + w.small2 + kMidDummyBytes + align256(M->ws_shift) + (kT2PhaseMask + 1);
+    w.total = w.key + w.conv + w.t + w.t2 + w.rtmp + w.small2 + kMidDummyBytes + (kT2PhaseMask + 1);
     return w;
 }
 // N = 1024 / 2048: the two-kernel pipeline of device_small.hpp (plain products, key switches and the automorphism family; dsize 1, one
 // base2k, <= 4 key limbs); `packed` = no OpLayout (the automorphism family needs it)
 static bool small_ring_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, bool ks, bool tensor, bool au, bool packed) {
-    static const int small_env = exp_knob("POULPY_DBG_SMALL", 1);
-    static const int small_au = exp_knob("POULPY_DBG_SMALL_AUTO", 1);
     const bool cross_out = p->res_base2k != p->key_base2k;   // (with an automorphism: phi and the cross-base pass do not commute)
-    return small_env && M->small_path && M->fuse_mid && M->fuse_tail && M->n < 4096 && (!au || (small_au && ks && packed && !cross_out)) &&
+    return M->small_path && M->fuse_mid && M->fuse_tail && M->n < 4096 && (!au || (ks && packed && !cross_out)) &&
            !tensor && p->dsize == 1 && M->dbg_stages == 7 && small_supported(M, s.cols_in * s.a_size_eff, (int)p->key_size);
 }
 struct SmallWs {
@@ -296,7 +294,6 @@ static int fused_carve(const GlweCall& c, FusedBufs* f) {
     PZ_TRY(ws_take(M, base, fw.conv, &f->a_conv));
     PZ_TRY(ws_take(M, base, fw.t, &f->T));
     base += (kT2Phase - (size_t)(((uintptr_t)base - (uintptr_t)c.res) & kT2PhaseMask)) & kT2PhaseMask;   // see kT2Phase
-    base += align256(M->ws_shift);
     PZ_TRY(ws_take(M, base, fw.t2, &f->T2));
     PZ_TRY(ws_take(M, base, fw.rtmp, &f->res_tmp));
     PZ_TRY(ws_take(M, base, fw.small2, &f->key_digits));
@@ -306,14 +303,11 @@ static int fused_carve(const GlweCall& c, FusedBufs* f) {
 
 // N = 4096, plain external product / key switch / automorphism with <= 4 key limbs: two kernels, the spectra cross HBM once
 // (device_small.hpp).  (round 3: the 8-slot tile of k_mid128r - 8 polynomials in, 8 out, 8 product rows: the external product with 4
-// limbs, BASELINE configs[1] - beats the two-kernel form, 3.25 vs 3.16 M/s, profiles/r03_ab_small_vs_pipeline.txt; POULPY_DBG_SMALL=2
-// forces the two-kernel form there too)
+// limbs, BASELINE configs[1] - beats the two-kernel form, 3.25 vs 3.16 M/s, profiles/r03_ab_small_vs_pipeline.txt)
 static bool n4096_two_kernel(const GlweCall& c) {
-    static const int small_env = exp_knob("POULPY_DBG_SMALL", 1);
-    static const int small_au4 = exp_knob("POULPY_DBG_SMALL_AUTO", 1);
     const pz_module* M = c.M;
-    const bool mid8 = !c.ks && !c.au && c.npi == 8 && c.npo == 8 && std::min(c.nrows, c.npi) == 8 && small_env != 2;
-    return small_env && M->small_path && (!c.au || (small_au4 && c.ks && !c.lay)) && !c.tensor && !c.digits && !c.cross_out &&
+    const bool mid8 = !c.ks && !c.au && c.npi == 8 && c.npo == 8 && std::min(c.nrows, c.npi) == 8;
+    return M->small_path && (!c.au || (c.ks && !c.lay)) && !c.tensor && !c.digits && !c.cross_out &&
            M->dbg_stages == 7 && small_supported(M, c.npi, c.ksz) && !mid8;
 }
 static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av, const PolyMap& sm) {
@@ -330,13 +324,10 @@ static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b
 // affine map of the spectrum index that sends rows of the four-step layout to rows, so the middle kernel writes its product at the
 // permuted position (k_mid128<.., PERM>) and the tail's inverse transform is phi(big) itself.  p = 3 mod 4 (X -> X^-1, the first step of
 // every trace, among them): the spectrum of phi(a) is the CONJUGATE of a permuted spectrum (MidArgs::perm_ysign).
-// POULPY_DBG_AUTO_SPECTRAL: 0 never; 2 not for the plain form (mode 0: key switch + signed permutation pass instead); 3 only p = 1 mod 4.
 struct SpectralPerm { bool on = false; unsigned mul = 0, add = 0; bool conj = false; };
 static SpectralPerm spectral_perm(const GlweCall& c) {
-    static const int au_spec = exp_knob("POULPY_DBG_AUTO_SPECTRAL", 1);
     SpectralPerm sp;
-    sp.on = au_spec && c.au && (c.au_big || au_spec == 1 || au_spec == 3) && ((c.au_p & 3u) == 1u || au_spec != 3) && c.M->plan.m2 == 128 &&
-            c.M->dbg_stages == 7;
+    sp.on = c.au && c.M->plan.m2 == 128 && c.M->dbg_stages == 7;
     if (!sp.on) return sp;
     const unsigned mm = (unsigned)c.M->m;
     if ((c.au_p & 3u) == 1u) {
@@ -358,14 +349,8 @@ static SpectralPerm spectral_perm(const GlweCall& c) {
 static bool spectral_body16(const GlweCall& c) {
     pz_module* M = c.M;
     const long long n = c.n;
-    static const int fold_knob = exp_knob("POULPY_DBG_AUTO_FOLD", 0);
-    static const int b16_knob = exp_knob("POULPY_DBG_AUTO_BODY16", 1);
-    const int64_t* a_end = c.a + (long long)c.batch * c.a_bs;
-    const int64_t* r_end = c.res + (long long)c.batch * c.res_bs;
-    const bool fold = fold_knob != 0 && (c.res >= a_end || c.a >= r_end) && !c.want_rsh;
-    return b16_knob != 0 && !fold && !M->probe && (!c.want_rsh || (c.au_big && (int)c.p->key_base2k <= 14 && (int)c.p->res_base2k <= 29)) &&
-           n >= 4096 && n <= 65536 && (int)c.p->key_base2k <= (c.au_big ? 15 : 16) && (int)c.p->res_base2k <= 31 && tail_rsh_supported(M) &&
-           !(c.au_big && exp_knob("POULPY_DBG_AUTO_BODYADD", 0));
+    return !M->probe && (!c.want_rsh || (c.au_big && (int)c.p->key_base2k <= 14 && (int)c.p->res_base2k <= 29)) &&
+           n >= 4096 && n <= 65536 && (int)c.p->key_base2k <= (c.au_big ? 15 : 16) && (int)c.p->res_base2k <= 31 && tail_rsh_supported(M);
 }
 static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av) {
     pz_module* M = c.M;
@@ -374,15 +359,9 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     PolyMap bsm{bl, 1, av.bs, (long long)av.cols * n, 0, 0}, bdm{bl, 1, (long long)bl * n, n, 0, 0};
     TailCall t = wave_tail(c, nb, f.T2, b0);
     tail_operand(t, av, true);
-    // phi(body): prepared by a pre-pass in the workspace.  POULPY_DBG_AUTO_FOLD=1: gathered by the tail itself instead (round 4, VERDICT r03
-    // item 3) - bit-exact and one kernel and 8.6 GB of traffic less per 1024 ciphertexts, but the tail goes from 5.05 to 8.3 - 8.8 ms
-    // (the pre-pass costs 1.8 - 3.0): 16 dependent 8-byte gathers per thread and limb in front of the carry chain, for every Galois
-    // element tried, conjugation included (profiles/r04_ab_auto_fold.txt).  A copy-rate pre-pass is the cheaper form.
-    static const int fold_knob = exp_knob("POULPY_DBG_AUTO_FOLD", 0);
-    // (never in place: other workgroups would gather from a body that this launch is already overwriting)
-    const int64_t* a_end = c.a + (long long)c.batch * c.a_bs;
-    const int64_t* r_end = c.res + (long long)c.batch * c.res_bs;
-    const bool fold = fold_knob != 0 && (c.res >= a_end || c.a >= r_end) && !c.want_rsh;   // (not for glwe_trace: the shifted-store variant has no gathered form)
+    // phi(body): prepared by a pre-pass in the workspace.  (Gathering it in the tail itself is bit-exact and saves a kernel, but the tail goes
+    // from 5.05 to 8.3 - 8.8 ms against 1.8 - 3.0 for the pre-pass: 16 dependent 8-byte gathers per thread and limb in front of the carry chain,
+    // profiles/r04_ab_auto_fold.txt.)
     // Round 6, plain form: the pre-pass leaves phi(body) as 16-bit values in the tail's own tile order (2 B written and 2 B read per coefficient
     // instead of 8) where the digits are expected to fit - a key base of at most 16 bits - and the body column then rides on the f64 chain of the
     // sign-only tail with that operand (k_inv_tail<.., NZF = 7, SGN>) instead of the operand variant's integer chain.  A value that does not fit
@@ -390,43 +369,33 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     // over the copies (its blocks return at once while the flag is down), the 16-bit form of the tail returns at once and the operand variant, launched
     // beside it and returning at once while the flag is down, does the column.  In-place calls included (both pre-passes read the input before any
     // tail writes); with the shifted store of glwe_trace too (k_inv_tail<..,RSH,7,SGN>: the one-bit shift behind the f64 chain).
-    static const int b16_knob = exp_knob("POULPY_DBG_AUTO_BODY16", 1);
     // (not under the rounding-margin probe: its instantiation of the tail keeps the i64 operand - the values that are rounded are the same)
     // (add / sub forms: the operand phi(body) +- a0 is a sum of two digits - a key base of at most 15 bits; the other columns keep their 8-byte operand)
     // (glwe_trace's steps, want_rsh: their input is the previous step's - or the initial shift's - normalized output, so with a base of at most 14 bits
     //  the operand always fits and the flag-up launches of the shifted-store forms stay what they are there: never taken)
     const bool body16 = spectral_body16(c);   // (glwe_fused zeroed the flag word in front of pass 1: that kernel may raise it too, f.side16)
-    (void)b16_knob;
     short* b16 = body16 ? (short*)f.res_tmp : nullptr;
     if (body16) {
         t.body16 = b16; t.body16_limbs = bl; t.body16_wide = M->wide16();
         if (f.side16 && c.au_big) t.other16 = f.side16;
     }
-    if (fold) { t.body_gather = true; t.gather_mul = c.au_g; }
-    else { t.body_src = (const long long*)f.res_tmp; t.body_bs = (long long)bl * n; t.body_ls = n; }
+    t.body_src = (const long long*)f.res_tmp; t.body_bs = (long long)bl * n; t.body_ls = n;
     const int cond = body16 ? 32 : 0;   // (launch_automorphism: the i64 pre-pass only if the flag is up)
     if (!c.au_big) {
         // plain form, res = phi(normalize(big)) (glwe_ct.rs:65-71): the inverse transform is phi(big) with phi's signs; the tail undoes
         // them in front of the carry chain (auto_mul) and puts them back on the digits (post_neg); only the body column has an operand
         if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, 1, nullptr, PolyMap{1, 1, 0, 0, 0, 0}, b16));
-        if (!fold) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, 1 | cond));
+        PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, 1 | cond));
         t.auto_mul = c.au_g; t.post_neg = true; t.body_only = true;
         return launch_inv_tail(M, t);
     }
     // operand of the body column, one stream: phi(body) + a0 (add) or -phi(body) + a0 (sub forms: the tail negates every operand)
-    // POULPY_DBG_AUTO_BODYADD=1: the pre-pass only permutes (+-phi(body)) and the tail adds a0 from the ciphertext itself (a second operand
-    // stream on the body column) instead of a pre-pass with an add operand; not with the shifted stores of glwe_trace (registers)
-    static const int bodyadd_knob = exp_knob("POULPY_DBG_AUTO_BODYADD", 0);
     const bool rsh = c.want_rsh && tail_rsh_supported(M) && !c.cross_out && c.p->res_base2k <= 29;   // (32-bit shift steps: device_fft.hpp)
     // (16-bit scheme: the pre-pass writes the operand the chain adds - phi(body) + a0 (add), phi(body) - a0 (sub forms; the i64 scheme stores
     //  -phi(body) + a0 and lets the tail negate it))
     if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, c.au->mode == 1 ? 1 : (1 | 16), (const long long*)av.p, bsm, b16));
-    if (fold) t.gather_neg = c.au->mode != 1;
-    else if (bodyadd_knob && !rsh) {
-        PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, c.au->mode == 1 ? 1 : 3));
-        t.body_add = true;
-    } else PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, (c.au->mode == 1 ? 1 : 3) | cond,
-                                      (const long long*)av.p, bsm));
+    PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, (c.au->mode == 1 ? 1 : 3) | cond,
+                               (const long long*)av.p, bsm));
     if (c.au->mode == 3) { t.auto_mul = 2u * (unsigned)n; t.auto_neg = true; }   // a - phi(big): every sign flipped
     t.small_neg = c.au->mode != 1;
     t.post_rsh = rsh;
@@ -449,8 +418,8 @@ static int wave_cross_base_tail(const GlweCall& c, const FusedBufs& f, size_t b0
         PZ_TRY(dev_normalize(c.M, nb, rv, (int)c.p->res_base2k, 0, col, tv, (int)c.p->key_base2k, col));
     return PZ_OK;
 }
-// plain product / key switch / relinearization, and the automorphism family where the spectral form does not apply (m2 = 256 plan,
-// POULPY_DBG_AUTO_SPECTRAL): the tail gathers -+phi^-1(a) (+ body) itself, writes into res_tmp, one permutation pass follows
+// plain product / key switch / relinearization, and the automorphism family where the spectral form does not apply (m2 = 256 plan, or
+// dbg_stages != 7): the tail gathers -+phi^-1(a) (+ body) itself, writes into res_tmp, one permutation pass follows
 static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av) {
     pz_module* M = c.M;
     if (M->dbg_stages & 4) {
@@ -489,9 +458,8 @@ static int glwe_fused(const GlweCall& c) {
             PZ_TRY(launch_zero_bytes(M, M->margin + 1, 8));   // the wide flag (module.hpp: wide16), in front of everything that may raise it
             // add / sub forms at rank 1 (one mask column = the key switch's input): pass 1 also leaves its input as 16-bit values for the tail's other
             // column, behind the body operand's segment of res_tmp when there is room (16 res_size - 8 bl >= 2 a_size limbs' worth per ciphertext)
-            static const int side_knob = exp_knob("POULPY_DBG_AUTO_SIDE16", 1);
             const int bl_ = std::min(av.size, c.ksz);
-            if (side_knob && c.au_big && c.s.cols_in == 1 && c.s.cols_out == 2 && !c.digits && !c.a16 && (M->dbg_stages & 1) &&
+            if (c.au_big && c.s.cols_in == 1 && c.s.cols_out == 2 && !c.digits && !c.a16 && (M->dbg_stages & 1) &&
                 16 * (long long)c.p->res_size - 8 * (long long)bl_ >= 2 * (long long)av.size)
                 f.side16 = (short*)((char*)f.res_tmp + (size_t)nb * bl_ * c.n * 8);
         }
@@ -973,14 +941,12 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
     const int cols = (int)p->rank + 1;
     const long long ct = n * cols * (long long)p->res_size;
     // the one-bit shift in front of step s + 1 rides on the tail of step s where that path has the shifted-store variant
-    // (POULPY_DBG_TRACE_RSH=0: always the separate pass)
-    static const int fuse_rsh = exp_knob("POULPY_DBG_TRACE_RSH", 1);
     bool shifted = false;
     for (size_t s = 0; s < nsteps; ++s) {
         PZ_REQUIRE((gals[s] & 1) != 0, "glwe_trace: Galois elements must be odd");
         if (!shifted) PZ_TRY(launch_rsh(M, (int)batch, (long long*)res, ct, cols, (int)p->res_size, 0, cols, (int)p->res_base2k, 1));
         AutoSpec au{(long long)gals[s], 1};
-        bool rsh = fuse_rsh && s + 1 < nsteps;
+        bool rsh = s + 1 < nsteps;
         PZ_TRY(glwe_op(M, true, res, res, key_pmats[s], p, batch, &au, nullptr, false, &rsh));
         shifted = rsh;
     }

@@ -81,14 +81,10 @@ inline bool br_fused_plan(const pz_module* M, const pz_blind_rotation_params* p,
     // accumulators (m = 128 is only built with one ciphertext per workgroup)
     // Ciphertexts per workgroup against the batch (profiles/r05_ab_br_form.txt, N = 512 / 1024): a workgroup with two ciphertexts shares every key
     // value but takes 1.3 - 1.6 x as long as one with one, so a batch that gives every ciphertext its own CU runs one per workgroup (batch 64 -
-    // 256: 2.4 instead of 4.0 ms); above that two.  POULPY_DBG_BR_FORM (experiment builds): 1 one ciphertext per workgroup, 2 two, 3 the
-    // 256-thread form below.
-    static const int form = exp_knob("POULPY_DBG_BR_FORM", 0);
+    // 256: 2.4 instead of 4.0 ms); above that two.
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
-    if (M->cu_count > 0) ncu = M->cu_count;
-    const bool two = form == 2 || (form == 0 && B > ncu);
-    if (B >= 2 && m != 128 && !pl.std_variant && two) {
+    if (B >= 2 && m != 128 && !pl.std_variant && B > ncu) {
         if (fits(2, false)) pl.ct = 2;
         else if (fits(2, true)) { pl.ct = 2; pl.a32 = true; }
     }
@@ -107,7 +103,7 @@ inline bool br_fused_plan(const pz_module* M, const pz_blind_rotation_params* p,
     // the barriers shared by eight waves nor the shared key values are what bounds this kernel); a third workgroup per CU (32-bit accumulators,
     // 168 registers with 150 - 250 B of scratch) gave + 2 % at multiples of 3 x CUs and lost elsewhere: not built.
     const int ragged = B % (2 * ncu);
-    if ((form == 3 || (form == 0 && B > 2 * ncu && ragged >= 1 && ragged <= ncu)) && m == 256 && !pl.std_variant) {
+    if (B > 2 * ncu && ragged >= 1 && ragged <= ncu && m == 256 && !pl.std_variant) {
         BrFusedPlan h = pl;
         h.nt = 256; h.ct = 1; h.a32 = false; h.lds = lds_for(1, false);
         h.pj = (m * ((ncols + pl.cg - 1) / pl.cg) + 255) / 256;

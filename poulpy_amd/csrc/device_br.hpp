@@ -30,8 +30,8 @@ struct BrFusedArgs {
     long long key_stride;  // points between consecutive keys
     int n_lwe, blk, cols, rsz, dnum, bsz, lut_size, base2k, m, batch;
     unsigned long long* margin;   // rounding-margin probe (margin_note, device_fft.hpp); null = off
-    int dbg_skip;          // (run-time on purpose: with the tests compiled out — PZ_DBG, device_fft.hpp — this kernel's register allocation changes and the
-                           //  N = 1024 two-ciphertext variants spill: 112 000 -> 89 000 rotations/s, round 3)  timing diagnostic (wrong results): 1 no DFT passes, 2 no product, 4 no carry phase, 8 no pack
+    int dbg_skip;          // always 0 (the host sets nothing else).  Run-time on purpose: with these tests compiled out this kernel's register allocation
+                           // changes and the two-ciphertext variants spill (N = 1024: 112 000 -> 89 000 rotations/s, round 3)
 };
 
 template <bool ACC32> struct AccT { typedef long long type; };
@@ -296,8 +296,7 @@ __global__ void __launch_bounds__(NT, 2) k_br_fused(BrFusedArgs g) {
                             for (int r = 0; r < MAXR; ++r)
                                 // (buffer load: the coefficient's key as the resource, the row's byte offset in an SGPR, ONE 32-bit lane offset shared by all
                                 //  CG x MAXR loads - as global loads each had its own 64-bit vector add in front; round 5 ISA)
-                                kv[j][r] = (PZ_DBG(g.dbg_skip) & 16) ? make_double2(1.0, (double)(q + r))
-                                         : br_key_load(krs, (unsigned)q * 16u, (unsigned)((min(r, row_max - 1) * ncols + c) * m) * 16u);
+                                kv[j][r] = br_key_load(krs, (unsigned)q * 16u, (unsigned)((min(r, row_max - 1) * ncols + c) * m) * 16u);
                         }
                         cplx xm[CT];
                         if (!STD) {

@@ -133,8 +133,7 @@ struct BrBlockArgs {
     const long long* lwe;  // [batch][n_lwe+1]
     long long lwe_bs;
     const cplx* w2n;
-    int dbg;               // diagnostic (tools/dbg): bit 0 no key loads, bit 1 no products, bit 2 no accumulator loads, bit 3 no LDS staging
-    int allcg;             // k_br_block_lds: one workgroup walks all gz column groups of its tile (accumulator tile read once)
+    int allcg;             // k_br_block_lds: one workgroup walks all gz column groups of its tile (accumulator tile read once); the host always sets it
     int gx, gy, gz, xcd;   // k_br_block_lds: logical grid (ciphertext tiles, 64-point slices, column groups) of the 1-D launch
 };
 
@@ -252,7 +251,9 @@ __device__ __forceinline__ void brl_fetch(cplx (&nxt)[PER], const BrBlockArgs& g
         const int e = min(u * 4 + w, CG * MAXR - 1);
         const int j = e / MAXR, r = e % MAXR;
         const int c = min(cg * CG + j, g.ncols - 1);
-        nxt[u] = (PZ_DBG(g.dbg) & 1) ? make_double2(1.0, (double)e) : (K + (long long)(min(r, g.row_max - 1) * g.ncols + c) * g.m)[q];
+        // (the constant-false select is deliberate: as a plain assignment from the load the compiler keeps the staged values in scratch,
+        //  80 - 160 B per instantiation)
+        nxt[u] = false ? make_double2(1.0, (double)e) : (K + (long long)(min(r, g.row_max - 1) * g.ncols + c) * g.m)[q];
     }
 }
 template <int PER, int NE>
@@ -308,7 +309,7 @@ __global__ void __launch_bounds__(256, (MAXR == 6 ? 3 : 2)) k_br_block_lds(BrBlo
         const int b = min(b0 + t, g.batch - 1);
 #pragma unroll
         for (int r = 0; r < MAXR; ++r)
-            a[t][r] = (r < g.row_max && !(PZ_DBG(g.dbg) & 4)) ? g.acc_dft[(long long)b * g.a_bs + (long long)r * g.m + q] : make_double2(0.0, (double)b);
+            a[t][r] = r < g.row_max ? g.acc_dft[(long long)b * g.a_bs + (long long)r * g.m + q] : make_double2(0.0, (double)b);
     }
     cplx out[CT][CG];
 #pragma unroll
@@ -362,7 +363,7 @@ __global__ void __launch_bounds__(256, (MAXR == 6 ? 3 : 2)) k_br_block_lds(BrBlo
         //  row inside the unrolled loop, is dropped; round 3, as in k_br_fused)
 #define PZ_BRL_FMAS(GUARD_)                                                                       \
     _Pragma("unroll") for (int r = 0; r < MAXR; ++r) {                                           \
-        if ((!(GUARD_) || r < g.row_max) && !(PZ_DBG(g.dbg) & 2)) {                              \
+        if (!(GUARD_) || r < g.row_max) {                                                      \
             _Pragma("unroll") for (int j = 0; j < CG; ++j) {                                     \
                 const cplx kv = ks[buf][j * MAXR + r][lane];                                     \
                 _Pragma("unroll") for (int t = 0; t < CT; ++t) {                                 \
@@ -378,7 +379,7 @@ __global__ void __launch_bounds__(256, (MAXR == 6 ? 3 : 2)) k_br_block_lds(BrBlo
         // every row in use (the usual shapes): the staged key value of step (r, j) + 1 is read from LDS in front of step (r, j)'s FMAs - written as
         // above the compiler put most reads directly in front of their eight FMAs behind lgkmcnt(0) (round 5 ISA).  Same chains, same order.
 #define PZ_BRL_FMAS_PIPE                                                                          \
-    if (!(PZ_DBG(g.dbg) & 2)) {                                                                  \
+    {                                                                                            \
         cplx kcur = ks[buf][0][lane], knxt;                                                      \
         _Pragma("unroll") for (int r = 0; r < MAXR; ++r) {                                       \
             _Pragma("unroll") for (int j = 0; j < CG; ++j) {                                     \
@@ -422,7 +423,7 @@ __global__ void __launch_bounds__(256, (MAXR == 6 ? 3 : 2)) k_br_block_lds(BrBlo
             }
         }
         PZ_BSTAMP(4)   // result stores (issue)
-        if (!(PZ_DBG(g.dbg) & 8)) brl_stage<PER, NE>(nxt, ks[buf ^ 1], w, lane);
+        brl_stage<PER, NE>(nxt, ks[buf ^ 1], w, lane);
         PZ_BSTAMP(5)   // wait for the next stage's key values + LDS writes
         __syncthreads();
         PZ_BSTAMP(6)   // barrier

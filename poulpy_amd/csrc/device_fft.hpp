@@ -36,14 +36,6 @@ __device__ __forceinline__ cplx cmulc(cplx a, cplx b) {
 template <bool CONJ>
 __device__ __forceinline__ cplx cmul_t(cplx a, cplx b) { return CONJ ? cmulc(a, b) : cmul(a, b); }
 
-// Timing-ablation knobs (POULPY_DBG_MID_SKIP, POULPY_DBG_SMALL_SKIP, POULPY_DBG_BR_SKIP, POULPY_DBG_BRL) are compiled in only with
-// -DPZ_ABLATE=1 (POULPY_BUILD_DEFS=-DPZ_ABLATE=1 POULPY_BUILD_TAG=ablate): a run-time test around a global load inside a software-pipelined
-// loop makes the compiler's s_waitcnt insertion assume the worst case at every join (round 3: the product loop of k_mid128 waited with
-// vmcnt(0) for the key row it had just requested instead of vmcnt(4) for the one requested a row earlier).
-#ifndef PZ_ABLATE
-#define PZ_ABLATE 0
-#endif
-#define PZ_DBG(x) (PZ_ABLATE ? (x) : 0)
 // Streaming hints for data that is touched once per kernel (the i64 limbs, T', T2'): non-temporal loads / stores.  Measured on
 // MI355X (profiles/r02_hbm_copy_tuned.txt): a 16 B-per-lane copy runs at 6.25 TB/s plain and 6.5-6.6 TB/s with both hints.
 // PZ_STREAM_HINTS: bit 0 loads, bit 1 stores (build-time, for A/B runs; default both).
@@ -532,7 +524,9 @@ struct TailArgs {
     // transform is phi(big)); the operand is one stream per column at the natural index: small[col][n], or on the body column
     // body_src[n] (phi(body) +- a0, prepared by k_automorphism in the workspace); small_neg negates it (sub forms)
     int pre_body, small_neg;
-    int body_add;   // body column: the operand is body_src[n] + small[body column][n] (the pre-pass then only permutes, no second operand)
+    // body_add (body column: body_src[n] + small[body column][n]) and the gathered body (pre_body with gather_mul) are never requested by the
+    // host; their run-time tests stay because without them the compiler allocates this kernel worse (up to +19 VGPRs, 68 B of scratch)
+    int body_add;
     const long long* body_src;
     long long body_bs, body_ls;
     // plain glwe_automorphism in the spectral form (res = phi(normalize(big)), glwe_ct.rs:65-71): the inverse transform is phi(big) with

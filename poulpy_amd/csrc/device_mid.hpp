@@ -58,8 +58,8 @@ struct MidArgs {
     const cplx* wL2;    // exp(2*pi*i*t/256)
     const cplx* tw12t;  // [q1][j2]
     cplx* dummy;        // >= 512*256 points of scratch: where rows without an output polynomial store
-    int groups;         // row groups per XCD (see k_mid)
-    int stagger, stagger_mod;  // start delay of workgroup w: ((w >> 3) % stagger_mod) * stagger * s_sleep(127)
+    int groups;         // unused: kept for the layout, on which k_mid128r's register allocation (and profiles/r06_traffic.json's signature) depends
+    int stagger, stagger_mod;  // k_mid128r only, always 0 (see there)
     // k_mid128<.., PERM = true>: the product is written to spectrum position q_out = perm_mul * q_in + perm_add (mod m), so that
     // the inverse transform of the result is phi(big) for X -> X^p with p = 1 mod 4:  DFT(phi(a))[q] = DFT(a)[p q + (p-1)/4],
     // perm_mul = p^-1, perm_add = -p^-1 (p-1)/4.  Rows map to rows (q1_out depends on q1 only), q2 moves inside the row.
@@ -84,8 +84,7 @@ struct MidArgs {
     long long br_lwe_bs;
     int br_i0, br_blk, br_rm;
     const cplx* w2n;
-    int dbg;   // timing ablation of k_mid128 (POULPY_DBG_MID_SKIP; results invalid): 1 no product FMAs, 2 no key loads, 4 no T' loads,
-               // 8 no T2' stores, 16 no row DFTs
+    int dbg;   // always 0; read by k_mid128<.., BR, BRNEST = 0> only (see there)
 };
 
 // Persistent: gridDim.x = 8*W workgroups (one per CU); workgroup (xcd = bid & 7, w = bid >> 3) walks the tiles
@@ -109,24 +108,21 @@ k_mid(MidArgs g) {
     cplx* wl = lds + CT * 16 * RS;
     cplx* twrow = wl + M2;
 
-    // tile enumeration: XCD x owns the rows q1 = 8*k + x; its W workgroups are split into G groups, group gi sweeps
-    // the rows k = gi (mod G) with stride W/G over (row, ciphertext tile).  G > 1 keeps several key slices in flight
-    // per XCD (still L2 resident) and lowers the number of workgroups hammering the same lines at once.
+    // tile enumeration: XCD x owns the rows q1 = 8*k + x; its W workgroups sweep them with stride W over (row, ciphertext tile)
     const bool xcd_map = (g.m1 & 7) == 0 && (gridDim.x & 7) == 0;
     const int xcd = xcd_map ? (blockIdx.x & 7) : 0;
-    const int wx = xcd_map ? (blockIdx.x >> 3) : blockIdx.x;
-    const int Wx = xcd_map ? (gridDim.x >> 3) : gridDim.x;
+    const int w = xcd_map ? (blockIdx.x >> 3) : blockIdx.x;
+    const int W = xcd_map ? (gridDim.x >> 3) : gridDim.x;
     const int rows_x = xcd_map ? g.m1 / 8 : g.m1;
-    const int G = (g.groups > 0 && Wx % g.groups == 0 && rows_x % g.groups == 0) ? g.groups : 1;
-    const int W = Wx / G, gi = wx / W, w = wx % W;
-    const int ntiles = (rows_x / G) * g.n_ct;
+    const int ntiles = rows_x * g.n_ct;
     if (w >= ntiles) return;
     if (tid < M2) wl[tid] = g.wL2[tid];
     __syncthreads();
-    // phase stagger (see launch_mid): workgroups start up to (stagger_mod-1) x stagger x 8128 clocks apart
-    if (g.stagger > 0) {
-        const int k = (blockIdx.x >> 3) % g.stagger_mod;
-        for (int i = 0; i < k * g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
+    // phase stagger: workgroup w starts ((w >> 3) mod 4) x 8128 clocks late, so that the HBM-heavy row passes of some CUs overlap the
+    // L2-heavy product phases of others (middle kernel -3 %)
+    {
+        const int k = (blockIdx.x >> 3) % 4;
+        for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
     }
 
     // Loop shape (software pipeline, one tile per iteration):
@@ -138,7 +134,7 @@ k_mid(MidArgs g) {
     // pass needs them: the compiler can then wait with vmcnt(16) and the stores of tile t drain under the
     // forward pass and the product of tile t+1.
     cplx x[16];
-    auto tile_q1 = [&](int L) { const int k = (L / g.n_ct) * G + gi; return xcd_map ? k * 8 + xcd : k; };
+    auto tile_q1 = [&](int L) { const int k = L / g.n_ct; return xcd_map ? k * 8 + xcd : k; };
     auto src_ptr = [&](int L) {
         const int Lc = min(L, ntiles - 1);
         const int b_ = min((Lc % g.n_ct) * CT + ctl, g.batch - 1);
@@ -335,9 +331,9 @@ k_mid128(MidArgs g) {
     constexpr int RS = kMidRS;
     extern __shared__ cplx lds[];      // CT*16 rows x RS | wL2[128] | tw12t row [128]
     const int tid0 = threadIdx.x;
-    // ablation mask: compile-time zero (PZ_DBG) except in the BR variant, whose register allocation is better WITH the run-time tests
-    // (without them: 36 bytes of scratch and N = 2^14 blind rotation 6 240 -> 5 715/s, round 3)
-    const int dbgv = (BR && BRNEST == 0) ? g.dbg : PZ_DBG(g.dbg);
+    // dbgv: compile-time zero except in the BR variant, which tests the run-time zero g.dbg because its register allocation is better WITH those
+    // tests (without them: 60 bytes of scratch and N = 2^14 blind rotation 6 240 -> 5 715/s, round 3)
+    const int dbgv = (BR && BRNEST == 0) ? g.dbg : 0;
     const long long m = (long long)g.m1 * M2;
     cplx* wl = lds + CT * NP * RS;
     // Lane coordinates are re-derived from an OPAQUE copy of the thread index at the top of every phase (round 3).  Derived once, the
@@ -363,10 +359,6 @@ k_mid128(MidArgs g) {
     if (w >= ntiles) return;
     if (tid0 < M2) wl[tid0] = g.wL2[tid0];
     __syncthreads();
-    if (g.stagger > 0 && g.stagger_mod > 0) {
-        const int k = (blockIdx.x / 256) % g.stagger_mod;
-        for (int i = 0; i < k * g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    }
 
     cplx x[16];
     auto tile_q1 = [&](int L) { const int k = L / g.n_ct; return xcd_map ? k * 8 + xcd : k; };
@@ -865,9 +857,8 @@ __device__ __forceinline__ void mid128r_body(const MidArgs& g) {
     __syncthreads();
     // the threads that move the inter-pass twiddle row (128 entries): waves 0 and 1, or waves 0 and 2 where wave 1 carries no input
     const int tw_e = (HALFIN && NP == 16) ? ((tid0 >> 6) == 0 ? tid0 : ((tid0 >> 6) == 2 ? tid0 - 64 : -1)) : (tid0 < M2 ? tid0 : -1);
-    // experiments (POULPY_DBG_MID_STAGGER = n, POULPY_DBG_MID_STAGGER_MOD = mode bits): n x 128 cycles of delay for the second-dispatched
-    // half of the waves at the top of every inverse pass (mode bit 2: for the first half instead); mode bit 0: static priority 1 for the
-    // second half, bit 1: for the first half
+    // Delaying (stagger = n: n x 128 cycles for one half of the waves at the top of every inverse pass) or de-prioritising one half of the waves did not
+    // pay (profiles/r03_ab_mid_stagger_prio.txt); the host passes 0.  The run-time tests stay: without them the kernel's register allocation changes.
     const bool young = tid0 >= 256;
     if (g.stagger_mod & 1) { if (young) __builtin_amdgcn_s_setprio(1); }
     if (g.stagger_mod & 2) { if (!young) __builtin_amdgcn_s_setprio(1); }
@@ -1400,7 +1391,7 @@ k_mid128r(MidArgs g) {
 // (Round 2 experiment, removed: "k_mid128L" — four extra loader waves that request tile t+1 at the top of iteration t, hold it in
 //  registers and hand it over through LDS once the compute waves release the tile, so that HBM loads never sit in front of the
 //  compute waves' L2-served key loads.  Bit-exact, but 9 % SLOWER (5.19 vs 4.76 ms per 1024 ciphertexts,
-//  profiles/r02_ab_mid_loader_waves.txt): the timing ablation of this kernel (POULPY_DBG_MID_SKIP, profiles/r02_mid_ablation.txt)
+//  profiles/r02_ab_mid_loader_waves.txt): the timing ablation of this kernel (profiles/r02_mid_ablation.txt)
 //  shows why — with every global access, every FMA and every butterfly removed it still takes 1.97 of its 4.96 ms (LDS traffic of
 //  the seven exchange passes + the product's operand reads, barriers), and no single component is worth more than 1 ms: HBM waits
 //  are not the exposed part, so hiding them buys nothing while the extra LDS pass and the 168-VGPR cap cost.)

@@ -276,9 +276,9 @@ struct AutoArgs {
     int npolys, n;
     unsigned mul;          // gather multiplier g (odd, < 2n)
     int flags;
-    // flags & 8: the output leaves as 16-bit values in the fused tail's tile order (k_inv_tail, TailArgs::d16*) at dst16 + map_off(dm) - the body
-    // operand of the spectral automorphism forms at 2 B per coefficient.  A value beyond 16 bits sets *wide: the tail then gathers the body
-    // itself (the older "fold" form) instead of reading the copies - un-normalized inputs stay correct, only slower.
+    // k_automorphism_t16: the output leaves as 16-bit values in the fused tail's tile order (k_inv_tail, TailArgs::d16*) at dst16 + map_off(dm) -
+    // the body operand of the spectral automorphism forms at 2 B per coefficient.  A value beyond 16 bits sets *wide: the wave then runs the
+    // i64 scheme (cond_total) - un-normalized inputs stay correct, only slower.
     short* dst16;
     unsigned* wide;
     int t16_m1, t16_cb, t16_m2sh;   // tile: m1 rows, cb columns per block, log2 m2
@@ -286,14 +286,6 @@ struct AutoArgs {
     // whose blocks return at once otherwise, and walk the cond_total block positions of the plain launch if it is
     int cond_total;
 };
-// tile-order position of coefficient j (TailArgs::d16*): j = h m + j1 m2 + cc  ->  (cc / cb) 2 m1 cb + (h m1 + j1) cb + cc % cb
-__device__ __forceinline__ long long auto_t16_pos(const AutoArgs& g, unsigned j) {
-    const unsigned row = j >> g.t16_m2sh;                       // h m1 + j1
-    const unsigned cc = j & ((1u << g.t16_m2sh) - 1u);
-    return (long long)(cc / (unsigned)g.t16_cb) * (2 * g.t16_m1 * g.t16_cb) + (long long)row * g.t16_cb + (cc % (unsigned)g.t16_cb);
-}
-__device__ __forceinline__ bool auto_wide(unsigned long long v) { return (v + 32768ull) >= 65536ull; }
-
 __device__ __forceinline__ void automorphism_block(const AutoArgs& g, int bid) {
     const int bpp = g.n >= 512 ? g.n / 512 : 1;  // blocks per polynomial, 2 coefficients per thread
     const int xcd = bid & 7, r = bid >> 3;
@@ -319,13 +311,6 @@ __device__ __forceinline__ void automorphism_block(const AutoArgs& g, int bid) {
         const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(add + j);
         out[0] += w.x;
         out[1] += w.y;
-    }
-    if (g.flags & 8) {   // (j even: both values in one row, one column block)
-        short2 s2;
-        s2.x = (short)out[0]; s2.y = (short)out[1];
-        *reinterpret_cast<short2*>(g.dst16 + map_off(g.dm, poly) + auto_t16_pos(g, (unsigned)j)) = s2;
-        if (auto_wide(out[0]) || auto_wide(out[1])) atomicOr(g.wide, 1u);
-        return;
     }
     *reinterpret_cast<ulonglong2*>(dst + j) = make_ulonglong2(out[0], out[1]);
 }
@@ -370,13 +355,6 @@ __device__ __forceinline__ void automorphism_chunk_block(const AutoArgs& g, unsi
     if (has_add) {
         const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(add + j0), w1 = *reinterpret_cast<const ulonglong2*>(add + j0 + 2);
         out[0] += w0.x; out[1] += w0.y; out[2] += w1.x; out[3] += w1.y;
-    }
-    if (g.flags & 8) {   // (j0 a multiple of 4: the four values share a row and a column block)
-        short4 s4;
-        s4.x = (short)out[0]; s4.y = (short)out[1]; s4.z = (short)out[2]; s4.w = (short)out[3];
-        *reinterpret_cast<short4*>(g.dst16 + map_off(g.dm, poly) + auto_t16_pos(g, j0)) = s4;
-        if (auto_wide(out[0]) || auto_wide(out[1]) || auto_wide(out[2]) || auto_wide(out[3])) atomicOr(g.wide, 1u);
-        return;
     }
     *reinterpret_cast<ulonglong2*>(dst + j0) = make_ulonglong2(out[0], out[1]);
     *reinterpret_cast<ulonglong2*>(dst + j0 + 2) = make_ulonglong2(out[2], out[3]);

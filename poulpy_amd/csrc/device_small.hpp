@@ -271,7 +271,6 @@ struct SmallInvArgs {
     cplx* S_out;                 // FWD: spectra of the first fwd_limbs limbs of the NEW res column, standard order, [b][limb * cols_out + col]
     const cplx* tw1;             // FWD: twist of the forward column pass
     int fwd_limbs;               // FWD: <= min(KS, res_size)
-    int dbg;                     // timing ablation (POULPY_DBG_SMALL_SKIP; results invalid): 1 no key loads, 2 no S loads, 4 no stores, 8 no LDS phases
     unsigned long long* margin;  // rounding-margin probe (margin_note, device_fft.hpp); null = off
     int acc32;                   // NOPROD (blind rotation's tail): bit 0 `small` holds 32-bit digits, bit 1 `res` takes 32-bit digits (bits 2 / 3: 16-bit digits) - same
                                  // element strides, half the bytes: between the blocks of a rotation the accumulator only ever holds normalized
@@ -358,8 +357,8 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
         cplx aA, kA[KS], aB, kB[KS];
 #define PZ_SMALL_LOAD(A_, K_, R_, J_)                                                              \
     {                                                                                               \
-        if (!(PZ_DBG(g.dbg) & 2)) A_ = Sb[(long long)(R_) * m + NT * (J_)];                                 \
-        if (!(PZ_DBG(g.dbg) & 1)) { _Pragma("unroll") for (int l = 0; l < KS; ++l) K_[l] = kp[(long long)(R_) * prow + l * lstride + (J_) * qstride]; } \
+        A_ = Sb[(long long)(R_) * m + NT * (J_)];                                                   \
+        _Pragma("unroll") for (int l = 0; l < KS; ++l) K_[l] = kp[(long long)(R_) * prow + l * lstride + (J_) * qstride]; \
     }
 #define PZ_SMALL_USE(A_, K_, J_)                                                                   \
     {                                                                                               \
@@ -371,11 +370,6 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
             c_.y = __builtin_fma(A_.y, K_[l].x, c_.y);                                              \
         }                                                                                           \
     }
-        if (PZ_DBG(g.dbg) & 3) {
-            aA = aB = make_double2(1.0, 2.0);
-#pragma unroll
-            for (int l = 0; l < KS; ++l) kA[l] = kB[l] = make_double2(0.5, 0.25);
-        }
         // (measured and dropped, round 3: warming L2 with the ciphertext's spectra by one dword load per 128-byte line at the top of the
         // kernel - 7 - 10 % slower at every ring degree, profiles/r03_small_inv_stamps.txt)
         // (static priority for the second-dispatched half of the waves, which finishes this phase late - 28 k vs 17 k cycles: no gain, round 3)
@@ -664,7 +658,7 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const long long x1 = x1v[e];
-                if (!(PZ_DBG(g.dbg) & 4) || x1 == 0x7fffffffffffLL) {
+                {
                     // AU mode 0: phi acts on the normalized digits (glwe_ct.rs:69-71)
                     const long long xs = (AU && g.au_mode == 0 && oneg[e]) ? (long long)(0ull - (unsigned long long)x1) : x1;
                     if constexpr (AU) {   // (plain stores: in place the operand's lines are re-read by the next trace step)

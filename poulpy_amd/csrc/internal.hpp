@@ -80,9 +80,6 @@ struct TailCall {
     const long long* body_src = nullptr;
     long long body_bs = 0, body_ls = 0;   // batch / limb strides of body_src
     bool body_only = false;               // only the body column has an operand (plain glwe_automorphism)
-    bool body_add = false;                // body column: body_src[n] + small[body column][n] (spectral add / sub forms: the pre-pass only permutes)
-    bool body_gather = false;             // instead of body_src: the tail gathers +-phi(body) from column 0 of `small` itself (gather_mul,
-                                          // gather_neg) - no pre-pass
     // the pre-pass left the body-column operand as 16-bit values in the tail's tile order, body16[ciphertext][limb][n] with body16_limbs limbs per
     // ciphertext, and raised *body16_wide if a value did not fit; launch_inv_tail then runs that column twice - the 16-bit-operand form (returns at
     // once if the flag is up) and the operand variant on body_src, which a conditional second pre-pass filled (returns at once if the flag is down)

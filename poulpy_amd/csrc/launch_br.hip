@@ -27,7 +27,7 @@ int br_try_fused(pz_module* M, int64_t* res, const int64_t* lwe_2n, const int64_
     g.w2n = M->w2n; g.key_stride = (long long)(pl.pmat_doubles / 2);
     g.n_lwe = (int)p->n_lwe; g.blk = (int)p->block_size; g.cols = (int)p->rank + 1; g.rsz = (int)p->res_size; g.dnum = (int)p->dnum;
     g.bsz = (int)p->brk_size; g.lut_size = (int)p->lut_size; g.base2k = (int)p->base2k; g.m = (int)M->m; g.batch = (int)batch;
-    g.dbg_skip = exp_knob("POULPY_DBG_BR_SKIP", 0); g.margin = M->probe ? M->margin : nullptr;
+    g.dbg_skip = 0; g.margin = M->probe ? M->margin : nullptr;
     KTimer kt(M, PZ_K_FUSED_MID);
     // the rounding-margin instantiation of the same form while the module's probe is on (launch_br_probe.hip)
     PZ_TRY(M->probe ? br_fused_launch_probe(M, g, pl) : br_fused_launch<false>(M, g, pl));
@@ -47,8 +47,7 @@ int br_block_step(pz_module* M, const double* acc_dft, long long a_bs, double* a
                 g.brk = (const cplx*)brk; g.key_stride = (long long)(pmat_doubles / 2);
                 g.row_max = row_max; g.ncols = ncols; g.m = (int)M->m; g.batch = B; g.i0 = i0; g.blk = blk;
                 g.lwe = (const long long*)lwe_2n; g.lwe_bs = lwe_bs; g.w2n = M->w2n;
-                static const int brl_dbg = exp_knob("POULPY_DBG_BRL", 0);
-                g.dbg = brl_dbg; g.gx = g.gy = g.gz = 1; g.xcd = 0; g.allcg = 0;
+                g.gx = g.gy = g.gz = 1; g.xcd = 0; g.allcg = 0;
                 constexpr int CT = 2;
                 KTimer kt(M, PZ_K_VMP);
                 const int nc = ncols;
@@ -61,20 +60,15 @@ int br_block_step(pz_module* M, const double* acc_dft, long long a_bs, double* a
                 else if (nc % 3 == 0 && nc % 4 != 0) { mr = row_max <= 6 ? 6 : 8; cgs = 3; }   // 3, 6 columns: groups of 3
                 else { mr = row_max <= 4 ? 4 : 8; cgs = 4; }
                 const int ngroups = (nc + cgs - 1) / cgs;
-                // keys staged in LDS once per 4 waves x 2 ciphertexts (k_br_block_lds): POULPY_DBG_BR_LDS = 0 never, 1 only for
-                // more than 8 inputs, 2 always
+                // keys staged in LDS once per 4 waves x 2 ciphertexts (k_br_block_lds) wherever m % 64 == 0
                 // (four ciphertexts per wave for <= 6 inputs - every staged key value serving 16 ciphertexts instead of 8, at 256 registers -
                 //  measured slower at N = 2048: 11.06 vs 9.68 ms per 82 block steps)
-                static const int br_lds = exp_knob("POULPY_DBG_BR_LDS", 2);
-                const bool use_lds = M->m % 64 == 0 && (br_lds >= 2 || (br_lds == 1 && row_max > 8));
+                const bool use_lds = M->m % 64 == 0;
                 bool launched = false;
                 if (use_lds) {
                     g.gx = (B + 7) / 8; g.gy = (int)(M->m / 64); g.gz = ngroups;
-                    static const int br_xcd = exp_knob("POULPY_DBG_BR_XCD", 1);
-                    g.xcd = (br_xcd && (g.gx * g.gy) % 8 == 0) ? 1 : 0;
-                    static const int br_allcg = exp_knob("POULPY_DBG_BR_ALLCG", 1);
-                    g.allcg = br_allcg ? 1 : 0;
-                    const unsigned total = (unsigned)(g.gx * g.gy * (g.allcg ? 1 : g.gz));
+                    g.allcg = 1;   // (one workgroup per tile and column group, placed by XCD, was 2-3 % slower: NOTEBOOK.md section 4)
+                    const unsigned total = (unsigned)(g.gx * g.gy);
 #define PZ_BRB(MR_, CG_)                                                                                           \
     if (!launched && mr == MR_ && cgs == CG_) {                                                                    \
         hipLaunchKernelGGL((k_br_block_lds<2, MR_, CG_>), dim3(total), dim3(256), 0, M->stream, g);                \

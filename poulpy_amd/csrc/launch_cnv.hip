@@ -19,9 +19,9 @@ int launch_cnv_apply(pz_module* M, int batch, double* res, long long res_bs, int
     g.a_size = a_size; g.a_i = a_i; g.a_j = a_j; g.b_size = b_size; g.b_i = b_i; g.b_j = b_j;
     g.m = (int)M->m; g.batch = batch;
     KTimer kt(M, PZ_K_VMP);
-    // operands staged in LDS, all output limbs per workgroup (POULPY_DBG_CNV_LDS=0: one thread per (point, output limb), operands from L2)
-    static const bool cnv_lds = (exp_knob("POULPY_DBG_CNV_LDS", 1) != 0);
-    if (cnv_lds && (M->m % 128) == 0 && a_size + b_size <= 64 && a != (const double*)res && b != (const double*)res) {
+    // operands staged in LDS, all output limbs per workgroup; otherwise (small rings, long operands, in place) one thread per
+    // (point, output limb), operands from L2
+    if ((M->m % 128) == 0 && a_size + b_size <= 64 && a != (const double*)res && b != (const double*)res) {
         const size_t lds = (size_t)(a_size + b_size) * 128 * sizeof(cplx);
         PZ_TRY(set_lds(k_cnv_apply_lds, lds));
         for (int b0 = 0; b0 < batch; b0 += 65535) {   // gridDim.y limit
@@ -85,7 +85,6 @@ int launch_mid_cnv3(pz_module* M, int batch, const cplx* a_main, const cplx* a_l
     KTimer kt(M, PZ_K_FUSED_MID);
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
-    if (M->cu_count > 0) ncu = M->cu_count;
     const dim3 grid((unsigned)std::min<long long>((long long)batch * g.m1, ncu));   // persistent: one workgroup per CU
     // b = a (glwe_tensor_square_apply): the square form - half the operand rows, symmetric limb products
     const bool sq = a_main == b_main && a_last == b_last;

@@ -21,18 +21,17 @@ int launch_permute_pmat(pz_module* M, const double* P, cplx* Pp, int npolys) {
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }
-template <int CT>
-static int launch_mid_ct(pz_module* M, MidArgs g, int batch) {
+// m2 = 256 plans: k_mid, two ciphertexts per tile (one ciphertext per tile, two workgroups per CU, measured slower: NOTEBOOK.md section 4)
+static int launch_mid256(pz_module* M, MidArgs g, int batch) {
+    constexpr int CT = 2;
     g.n_ct = (batch + CT - 1) / CT;
     const size_t lds = ((size_t)CT * 16 * 17 * 16 + 512) * sizeof(cplx);
     KTimer kt(M, PZ_K_FUSED_MID);
     PZ_TRY(set_lds(k_mid<CT>, lds));
-    // persistent: as many workgroups as fit (LDS-bound: 144 KiB -> 1 per CU at CT = 2, 76 KiB -> 2 per CU at CT = 1)
+    // persistent: as many workgroups as fit (LDS-bound: 144 KiB -> 1 per CU)
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
-        if (M->cu_count > 0) ncu = (M->cu_count / 8) * 8 > 0 ? (M->cu_count / 8) * 8 : M->cu_count;
-    const int per_cu = CT == 1 ? 2 : 1;
-    const int grid = std::min(ncu * per_cu, g.m1 * g.n_ct);
+    const int grid = std::min(ncu, g.m1 * g.n_ct);
     hipLaunchKernelGGL((k_mid<CT>), dim3(grid), dim3(CT * 256), lds, M->stream, g);
     PZ_HIP(hipGetLastError());
     return PZ_OK;
@@ -43,9 +42,7 @@ static int launch_mid_ct(pz_module* M, MidArgs g, int batch) {
 static int launch_mid128(pz_module* M, MidArgs& g, int batch, int npi, int npo, bool perm, bool ds, bool br) {
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
-    if (M->cu_count > 0) ncu = (M->cu_count / 8) * 8 > 0 ? (M->cu_count / 8) * 8 : M->cu_count;
     static const bool mid_r = (rt_knob("POULPY_DBG_MID_R", 1) != 0);   // 0: k_mid128 (the kernel of rounds 1-2) instead of k_mid128r (A/B)
-    static const bool br_nc3 = (exp_knob("POULPY_DBG_BR_NC3", 1) != 0);   // 0: 4 outputs per thread also for 6-column block steps (A/B)
     KTimer kt(M, PZ_K_FUSED_MID);
 #define PZ_MID128_GO(CT_, NP_, PERM_, SKIPW_)                                                                              \
 {                                                                                                                      \
@@ -76,27 +73,12 @@ if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {   
     if (perm_) { if (skipw_) PZ_MID128_GO(CT_, NP_, true, true) else PZ_MID128_GO(CT_, NP_, true, false) }             \
     else       { if (skipw_) PZ_MID128_GO(CT_, NP_, false, true) else PZ_MID128_GO(CT_, NP_, false, false) }           \
 }
-#ifdef PZ_EXPERIMENT
-    // experiment (POULPY_DBG_MID_CT2=1): the plain 16 x 16 product on 256-thread workgroups - two ciphertexts per tile, two workgroups per
-    // CU that are not coupled by barriers (k_mid128r<2,16>; twice the key fetches per ciphertext)
-    static const bool mid_ct2 = (exp_knob("POULPY_DBG_MID_CT2", 0) == 1);
-    if (mid_ct2 && mid_r && !br && !ds && !perm && npi == 16 && npo == 16 && g.row_max == 16 && g.ncomp == 16) {
-        g.n_ct = (batch + 1) / 2;
-        const size_t lds = ((size_t)2 * 16 * kMidRS + 384 + 32) * sizeof(cplx);
-        const dim3 grid_(std::min({2 * ncu, 512, g.m1 * g.n_ct}));
-        PZ_TRY(set_lds((k_mid128r<2, 16, false, 16, false>), lds));
-        hipLaunchKernelGGL((k_mid128r<2, 16, false, 16, false>), grid_, dim3(256), lds, M->stream, g);
-        dispatch_note(M, "k_mid128r<CT=2,NP=16,NR=16,KR=3> (256 threads, two workgroups per CU)");
-        PZ_HIP(hipGetLastError());
-        return PZ_OK;
-    }
-#endif
 #define PZ_MID128_LAUNCH(CT_, NP_)                                                                                         \
 {                                                                                                                      \
     g.n_ct = (batch + CT_ - 1) / CT_;                                                                                  \
     const size_t lds = ((size_t)CT_ * NP_ * kMidRS + 384 + 32) * sizeof(cplx);   /* tile | wL2 | two twiddle rows | exponents */                                         \
     const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));   /* <= 256: one scratch tile per workgroup (kMidDummyBytes) */ \
-    if (br && NP_ == 8 && (g.br_rm & 1) == 0 && g.ncomp == 6 && npi <= 6 && br_nc3) {   /* six output columns in an 8-slot tile: 2 x 3 per thread */ \
+    if (br && NP_ == 8 && (g.br_rm & 1) == 0 && g.ncomp == 6 && npi <= 6) {   /* six output columns in an 8-slot tile: 2 x 3 per thread */ \
         PZ_TRY(set_lds((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), lds));  \
         hipLaunchKernelGGL((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), grid_, dim3(512), lds, M->stream, g); \
         dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1,BRNEST=2,NCO=3> (%d ciphertexts per key value)", CT_, NP_, CT_);   \
@@ -137,9 +119,8 @@ if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {   
 }
     // 16 polynomials in, 32 = 16 limbs x 2 columns out, 16 key rows of 32 columns (rank-1 key switch / automorphism / relinearization at 16 limbs:
     // BASELINE configs[4]): 4 ciphertexts per tile and the two output columns as two passes over the same inputs - every key value serves 4
-    // ciphertexts instead of the 32-slot tile's 2 (k_mid128r<.., C2>; POULPY_DBG_MID_C2=0 in an experiment build: the 32-slot tile)
-    static const bool c2_on = (exp_knob("POULPY_DBG_MID_C2", 1) != 0);
-    if (c2_on && mid_r && !br && !ds && npi == 16 && npo == 32 && g.row_max == 16 && g.ncols == 32 && g.ncomp == 32) {
+    // ciphertexts instead of the 32-slot tile's 2 (k_mid128r<.., C2>; profiles/r06_ab_mid_c2.txt)
+    if (mid_r && !br && !ds && npi == 16 && npo == 32 && g.row_max == 16 && g.ncols == 32 && g.ncomp == 32) {
         g.n_ct = (batch + 3) / 4;
         const size_t lds = ((size_t)4 * 16 * kMidRS + 384 + 32) * sizeof(cplx);
         const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));
@@ -187,8 +168,7 @@ int launch_mid(pz_module* M, int batch, const cplx* T, cplx* T2, const cplx* Pp,
         for (int t = 0; t < dg->n; ++t) { g.ds_in[t] = dg->in[t]; g.ds_row[t] = dg->row[t]; g.ds_coff[t] = dg->coff[t]; g.ds_cb[t] = dg->cb[t]; }
     }
     g.perm_mul = perm_mul; g.perm_add = perm_add; g.perm_ysign = perm_conj ? -1.0 : 1.0; g.log_m1 = 0;
-    static const int mid_skip = exp_knob("POULPY_DBG_MID_SKIP", 0);
-    g.dbg = mid_skip;
+    g.dbg = 0;
     while ((1 << g.log_m1) < M->plan.m1) ++g.log_m1;
     const bool perm = perm_mul != 0;
     g.T = T; g.T2 = T2; g.P = Pp; g.npi = npi; g.npo = npo; g.nrows = nrows; g.ncols = ncols;
@@ -198,18 +178,9 @@ int launch_mid(pz_module* M, int batch, const cplx* T, cplx* T2, const cplx* Pp,
         return fail(PZ_ERR_INVALID, "launch_mid: no product term (rows %d, npi %d, ds_n %d)", nrows, npi, g.ds_n);
     g.batch = batch; g.m1 = M->plan.m1; g.n_ct = 0;
     g.wL2 = M->wL2; g.tw12t = M->tw12t; g.dummy = dummy;
-    static const int groups = exp_knob("POULPY_DBG_MID_GROUPS", 1);
-    g.groups = groups;
-    // phase stagger: workgroup w starts (w mod 4) x ~3.4 us late so that the HBM-heavy row passes of some CUs overlap
-    // the L2-heavy product phases of others (measured: middle kernel -3 %); off for the m2 = 128 form, where it did not pay
-    static const int stg = exp_knob("POULPY_DBG_MID_STAGGER", -1);
-    static const int stm = exp_knob("POULPY_DBG_MID_STAGGER_MOD", 4);
-    g.stagger = stg >= 0 ? stg : (M->plan.m2 == 128 ? 0 : 1);
-    g.stagger_mod = M->plan.m2 == 128 ? (exp_knob("POULPY_DBG_MID_STAGGER_MOD", -1) >= 0 ? stm : 0) : std::max(1, stm);   // m2 = 128: mode bits of k_mid128r's experiments
+    g.groups = 1; g.stagger = 0; g.stagger_mod = 0;
     if (M->plan.m2 == 128) return launch_mid128(M, g, batch, npi, npo, perm, ds, br != nullptr);
-    static const int ct = exp_knob("POULPY_DBG_MID_CT", 2);  // diagnostic knob
-    if (ct == 1) return launch_mid_ct<1>(M, g, batch);
-    return launch_mid_ct<2>(M, g, batch);
+    return launch_mid256(M, g, batch);
 }
 
 

@@ -43,25 +43,19 @@ int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap 
     g.t16_m1 = M->plan.f1a * M->plan.f1b; g.t16_cb = M->plan.cb; g.t16_m2sh = 0;
     while ((1 << g.t16_m2sh) < M->plan.m2) ++g.t16_m2sh;
     if (dst16) {   // 16-bit tile-order output (the spectral automorphism forms' body operand; dm addresses limbs of n int16)
-        if (M->n < 1024 || (M->plan.m2 % M->plan.cb) != 0 || M->plan.cb % 4 != 0) return fail(PZ_ERR_UNSUPPORTED, "automorphism pre-pass: no 16-bit tile-order output on this plan");
-        g.flags |= 8;
-        // through LDS (one workgroup per polynomial, every source line read once) where the polynomial fits it as int16 and no second operand is added;
-        // POULPY_DBG_AUTO_T16_LDS=0: the gather kernels with a 16-bit store
-        static const int lds_knob = exp_knob("POULPY_DBG_AUTO_T16_LDS", 1);
-        if (lds_knob && M->n <= 65536 && M->n >= 4096) {
-            KTimer kt(M, PZ_K_ELEMENTWISE);
-            const size_t lds = (size_t)M->n * sizeof(short);
-            PZ_TRY(set_lds(k_automorphism_t16, lds));
-            hipLaunchKernelGGL(k_automorphism_t16, dim3(npolys), dim3(1024), lds, M->stream, g);
-            PZ_HIP(hipGetLastError());
-            return PZ_OK;
-        }
-        if (g.flags & 16) return fail(PZ_ERR_UNSUPPORTED, "automorphism pre-pass: the subtracting 16-bit form exists through LDS only");
+        // through LDS: one workgroup per polynomial, every source line read once, the polynomial held as int16
+        if (M->n < 4096 || M->n > 65536 || (M->plan.m2 % M->plan.cb) != 0 || M->plan.cb % 4 != 0)
+            return fail(PZ_ERR_UNSUPPORTED, "automorphism pre-pass: no 16-bit tile-order output on this plan");
+        KTimer kt(M, PZ_K_ELEMENTWISE);
+        const size_t lds = (size_t)M->n * sizeof(short);
+        PZ_TRY(set_lds(k_automorphism_t16, lds));
+        hipLaunchKernelGGL(k_automorphism_t16, dim3(npolys), dim3(1024), lds, M->stream, g);
+        PZ_HIP(hipGetLastError());
+        return PZ_OK;
     }
     KTimer kt(M, PZ_K_ELEMENTWISE);
     // Galois elements whose gather has no locality (neither g nor -g small): chunks of 4 outputs per thread, sources read in runs
-    // (k_automorphism_chunk; POULPY_DBG_AUTO_CHUNK=0: always the plain gather, =2: always the chunked form)
-    static const int chunk_knob = exp_knob("POULPY_DBG_AUTO_CHUNK", 1);
+    // (k_automorphism_chunk)
     const unsigned two_n = 2u * (unsigned)M->n, gm = mul & (two_n - 1u);
     unsigned hinv = gm;   // g^-1 mod 2N by Newton's iteration (g odd): x <- x (2 - g x), 3 -> 6 -> 12 -> 24 -> 48 correct bits
     for (int it = 0; it < 5; ++it) hinv *= 2u - gm * hinv;
@@ -69,7 +63,7 @@ int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap 
     // (the plain gather has locality when the multiplier OR its inverse is small in absolute value: sources g apart share lines, or
     //  outputs g^-1 apart do and the workgroup's 512 outputs cover the 16 of a line: measured equal or better up to 25, profiles/r04_ab_auto_chunk.txt)
     const unsigned dist = std::min(std::min(gm, two_n - gm), std::min(hinv, two_n - hinv));
-    if (M->n >= 1024 && (chunk_knob == 2 || (chunk_knob == 1 && dist > 32))) {
+    if (M->n >= 1024 && dist > 32) {
         const int bpp = (int)(M->n / 1024);
         const int blocks = ((npolys + 7) / 8) * 8 * bpp;
         if (cond) {

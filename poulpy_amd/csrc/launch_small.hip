@@ -65,8 +65,7 @@ int launch_small_permute(pz_module* M, const double* P, cplx* Pp, int npolys) {
 // N = 1024 / 2048 / 4096: the per-op transforms in one kernel each (whole polynomial in LDS)
 bool small_transform_supported(const pz_module* M) {
     const int m1 = small_m1(M);
-    static const int on = exp_knob("POULPY_DBG_SMALL_FFT", 1);   // 0: two-pass per-op transforms (A/B)
-    return on && (M->m % kSmallM2) == 0 && (m1 == 4 || m1 == 8 || m1 == 16);
+    return (M->m % kSmallM2) == 0 && (m1 == 4 || m1 == 8 || m1 == 16);
 }
 int launch_small_idft(pz_module* M, int npolys, const double* a, PolyMap smap, long long* res, PolyMap dmap) {
     if (npolys <= 0) return PZ_OK;
@@ -124,8 +123,7 @@ int launch_small_inv(pz_module* M, int batch, const cplx* S, const cplx* Pp, int
     g.batch = batch; g.npi = npi; g.nrows = nrows; g.ncols = ncols; g.cols_out = cols_out; g.ksz = ksz;
     g.res_cols = res_cols; g.res_size = res_size; g.small_cols = small_cols; g.small_size = small_size; g.base2k = base2k; g.body_col = body_col;
     g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv;
-    static const int skip = exp_knob("POULPY_DBG_SMALL_SKIP", 0);
-    g.dbg = skip; g.margin = M->probe ? M->margin : nullptr;
+    g.margin = M->probe ? M->margin : nullptr;
     if (acc32 && !(noprod && base2k <= 31)) return fail(PZ_ERR_INVALID, "small-ring pipeline: 32-bit accumulator digits need the product-free form and base2k <= 31");
     g.acc32 = acc32;
     g.S_out = fwd_S; g.tw1 = M->s_tw1; g.fwd_limbs = fwd_S ? fwd_limbs : 0;
@@ -176,17 +174,16 @@ int launch_small_inv(pz_module* M, int batch, const cplx* S, const cplx* Pp, int
 
 // N = 1024 / 2048, plain product / key switch of a rank-1 ciphertext: ONE kernel per call (device_small_one.hpp)
 bool small_one_supported(const pz_module* M, int npi, int nrows, int ncols, int cols_out, int ksz, int batch) {
-    static const bool on = (exp_knob("POULPY_DBG_SMALL_ONE", 1) != 0);
     const int m1 = small_m1(M);
     // measured (profiles/r06_ab_small_one.txt, 1024 per call): N = 1024 + 7 ... + 20 % on every shape; N = 2048 + 4 % for the external product (8 input
     // polynomials), - 5 ... 8 % for the key switch (4 inputs: the two-kernel pipeline has two workgroups per CU there, this kernel one) - which stays on two kernels
     // below ~3000 ciphertexts per call (at 4096 the one-kernel form is + 7 %: the two-kernel path's spectra no longer sit in the Infinity Cache).  After the
-    // both-columns form (tools/dbg/r6_run35.sh): the key switch still - 3 ... 4 % at 4 / 3 limbs, but the 2-limb external product (4 inputs, 2 key limbs) + 15 %:
+    // both-columns form: the key switch still - 3 ... 4 % at 4 / 3 limbs, but the 2-limb external product (4 inputs, 2 key limbs) + 15 %:
     // shapes with at most two key limbs take the one-kernel form too
 #ifndef PZ_SMALL_ONE_ALL
 #define PZ_SMALL_ONE_ALL 0   // A/B builds: 1 = also the N = 2048 shapes with <= 4 input polynomials
 #endif
-    return on && (M->m % kSmallM2) == 0 && (m1 == 4 || (m1 == 8 && (npi > 4 || batch >= 3072 || (npi == 4 && ksz <= 2) || PZ_SMALL_ONE_ALL))) && cols_out == 2 && ksz >= 1 && ksz <= 4 && ncols == ksz * cols_out && npi >= 1 &&
+    return (M->m % kSmallM2) == 0 && (m1 == 4 || (m1 == 8 && (npi > 4 || batch >= 3072 || (npi == 4 && ksz <= 2) || PZ_SMALL_ONE_ALL))) && cols_out == 2 && ksz >= 1 && ksz <= 4 && ncols == ksz * cols_out && npi >= 1 &&
            npi <= 8 && nrows >= 1;
 }
 int launch_small_one(pz_module* M, int batch, const long long* src, PolyMap smap, const cplx* Pp, int npi, int nrows, int ncols, int ksz, long long* res,

@@ -36,9 +36,9 @@ static TailArgs tail_args(const pz_module* M, const TailCall& c, int col_base, i
     g.small_all = c.small_all ? 1 : 0; g.auto_mul = c.auto_mul; g.auto_neg = c.auto_neg ? 1 : 0;
     g.col_base = col_base; g.col_count = col_count; g.body_col = c.body_col;
     g.gather_mul = c.gather_mul; g.gather_neg = c.gather_neg ? 1 : 0;
-    g.pre_body = (c.body_src != nullptr || c.body_gather) ? 1 : 0; g.small_neg = c.small_neg ? 1 : 0;
+    g.pre_body = c.body_src != nullptr ? 1 : 0; g.small_neg = c.small_neg ? 1 : 0;
     g.body_src = c.body_src; g.body_bs = c.body_bs; g.body_ls = c.body_ls;
-    g.body_add = c.body_add ? 1 : 0; g.post_neg = c.post_neg ? 1 : 0; g.body_only = c.body_only ? 1 : 0; g.raw = raw ? 1 : 0;
+    g.body_add = 0; g.post_neg = c.post_neg ? 1 : 0; g.body_only = c.body_only ? 1 : 0; g.raw = raw ? 1 : 0;
     g.nz = nz ? 1 : 0;
     g.nz_lsh = nz ? nz->lsh : 0; g.nz_res_end = nz ? nz->res_end : 0; g.nz_res_start = nz ? nz->res_start : 0; g.nz_a_end = nz ? nz->a_end : 0;
     g.nz_a_start = nz ? nz->a_start : 0; g.nz_zero_from = nz ? nz->zero_from : 0; g.nz_col = nz ? nz->col : 0; g.nz_mode = nz ? nz->mode : 0;
@@ -71,7 +71,7 @@ static int launch_inv_tail_cols(pz_module* M, const TailCall& c, int col_base, i
     f.rowmajor = c.rowmajor; f.has_small = has_small;
     if (c.acc32) {   // 32-bit accumulator digits: the plain every-column-operand form, nothing else
         if (!(tail_acc32_supported(M) && c.rowmajor && has_small && c.small_all && !c.post_rsh && !raw && !nz && c.auto_mul == 0 && c.gather_mul == 0 &&
-              c.body_src == nullptr && !c.body_gather && c.base2k <= 31 && (!(c.acc32 & 4) || (c.acc32 == 4 && c.small16 != nullptr))))
+              c.body_src == nullptr && c.base2k <= 31 && (!(c.acc32 & 4) || (c.acc32 == 4 && c.small16 != nullptr))))
             return fail(PZ_ERR_UNSUPPORTED, "fused tail: no 32-bit-accumulator variant for this call");
         f.kind = TailForm::ACC32;
     } else if (c.post_rsh && c.body16 && !has_small) {   // the 16-bit-operand form with the shifted store (glwe_trace's body column)
@@ -115,7 +115,7 @@ int launch_inv_tail(pz_module* M, const TailCall& c) {
     if (c.small != nullptr && !c.small_all && c.ncols > 1) {
         TailCall body = c;       // the body column: operand, and the signs that go with it
         body.gather_mul = 0; body.gather_neg = false; body.body_src = nullptr; body.body_bs = body.body_ls = 0;
-        body.small_neg = body.post_rsh = body.post_neg = body.body_only = body.body_add = false;
+        body.small_neg = body.post_rsh = body.post_neg = body.body_only = false;
         PZ_TRY(launch_inv_tail_cols(M, body, c.body_col, 1));
         TailCall plain = body;   // every other column: no operand, no signs
         plain.small = nullptr; plain.small_bs = 0; plain.auto_mul = 0; plain.auto_neg = false; plain.body_col = 0;
@@ -123,16 +123,15 @@ int launch_inv_tail(pz_module* M, const TailCall& c) {
         return launch_inv_tail_cols(M, plain, c.body_col + 1, c.ncols - 1 - c.body_col);
     }
     // plain spectral glwe_automorphism (only the body column has an operand): that column on the operand variant, the others on the
-    // sign-only variant of the f64 chain (POULPY_DBG_AUTO_SGN=0: every column on the operand variant, as in round 3)
-    static const int sgn_knob = exp_knob("POULPY_DBG_AUTO_SGN", 1);
-    if (sgn_knob && c.small != nullptr && c.small_all && c.body_only && c.auto_mul != 0 && c.ncols > 1 && !c.post_rsh && c.rowmajor &&
+    // sign-only variant of the f64 chain (profiles/r04_ab_auto_sgn.txt)
+    if (c.small != nullptr && c.small_all && c.body_only && c.auto_mul != 0 && c.ncols > 1 && !c.post_rsh && c.rowmajor &&
         tail_rsh_supported(M)) {
         // (body16: the body column twice - the operand variant returns at once unless the pre-pass raised the flag, the 16-bit-operand form
         //  of the sign-only tail returns at once if it did; exactly one of them writes the column)
         PZ_TRY(launch_inv_tail_cols(M, c, c.body_col, 1));
         TailCall rest = c;
         rest.small = nullptr; rest.small_bs = 0; rest.small_all = false;
-        rest.body_src = nullptr; rest.body_bs = rest.body_ls = 0; rest.body_only = false; rest.body_add = false; rest.body_gather = false; rest.gather_mul = 0;
+        rest.body_src = nullptr; rest.body_bs = rest.body_ls = 0; rest.body_only = false; rest.gather_mul = 0;
         if (c.body16) PZ_TRY(launch_inv_tail_cols(M, rest, c.body_col, 1));   // (small_size: the operand's limbs)
         rest.small_size = 0; rest.body16 = nullptr; rest.body16_wide = nullptr; rest.body16_limbs = 0;
         if (c.body_col > 0) PZ_TRY(launch_inv_tail_cols(M, rest, 0, c.body_col));
@@ -145,7 +144,7 @@ int launch_inv_tail(pz_module* M, const TailCall& c) {
         PZ_TRY(launch_inv_tail_cols(M, c, c.body_col, 1));   // (returns at once unless the pre-pass raised the flag)
         TailCall b16 = c;
         b16.small = nullptr; b16.small_bs = 0; b16.small_all = false; b16.small_neg = false;   // (the sign of the operand is the pre-pass's)
-        b16.body_src = nullptr; b16.body_bs = b16.body_ls = 0; b16.body_add = false; b16.body_gather = false; b16.gather_mul = 0; b16.gather_neg = false;
+        b16.body_src = nullptr; b16.body_bs = b16.body_ls = 0; b16.gather_mul = 0; b16.gather_neg = false;
         PZ_TRY(launch_inv_tail_cols(M, b16, c.body_col, 1));
         TailCall rest = c;
         if (c.other16 && c.ncols == 2 && c.body_col == 0) {

@@ -21,21 +21,12 @@
 
 namespace pz {
 
-// Run-time switches.  rt_knob: the few a product build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
-// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS).  exp_knob: the switches of
-// measured experiments (A/B records under profiles/): the default, as a constant, unless the library is built with -DPZ_EXPERIMENT
-// (POULPY_BUILD_DEFS=-DPZ_EXPERIMENT POULPY_BUILD_TAG=exp ..., like -DPZ_ABLATE for the result-invalidating timing ablations).
+// Run-time switches: the nine a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
+// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED;
+// DESIGN.md section 9).
 inline int rt_knob(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
-}
-inline int exp_knob(const char* name, int dflt) {
-#ifdef PZ_EXPERIMENT
-    return rt_knob(name, dflt);
-#else
-    (void)name;
-    return dflt;
-#endif
 }
 
 inline std::string& last_error_ref() {
@@ -124,9 +115,6 @@ inline bool make_plan(uint64_t n, FftPlan& pl) {
     if (pl.m1 == 128) { pl.f1a = 8; pl.f1b = 16; }
     pl.cb = pl.m2 >= 16 ? 16 : std::min(4, pl.m2);
     pl.qb = pl.m1 >= 16 ? 16 : std::min(4, pl.m1);
-#ifdef PZ_EXPERIMENT
-    if (const char* e = getenv("POULPY_DBG_CB")) pl.cb = atoi(e);  // experiment builds: column-block width of pass 1 / tail
-#endif
     return true;
 }
 
@@ -141,7 +129,6 @@ struct pz_module {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t stream_out = nullptr;   // device -> host copies of the duplex host path (api_glwe.hip: glwe_entry_duplex); stream2 carries its host -> device copies
-    int cu_count = 0;   // CUs the module stream may use (0 = all; diagnostic POULPY_DBG_CU_MASK): grid of the persistent kernels
     // device tables (cplx): tw1[m1], tw1inv[m1], wL1[m1], wL2[m2], tw12[m] ([j2][q1])
     pz::cplx *tw1 = nullptr, *tw1inv = nullptr, *wL1 = nullptr, *wL2 = nullptr, *tw12 = nullptr;
     pz::cplx* tw12t = nullptr;  // the same table as [q1][j2] (row-major pipeline)
@@ -169,7 +156,6 @@ struct pz_module {
     unsigned* wide16() const { return reinterpret_cast<unsigned*>(margin + 1); }
     bool probe = false;
     size_t chunk = 0;
-    size_t ws_shift = 0;   // diagnostic: extra bytes of padding in front of T2' in the fused workspace (placement experiments)
     int dbg_stages = 7;  // diagnostic: bit 0 pass 1, bit 1 middle, bit 2 tail of the fused pipeline (results invalid unless 7)
     // prepared keys the caller declared immutable (pz_module_pin_key): their row-sliced copies for the fused pipeline
     struct PinnedKey { const void* key; pz::cplx* sliced; size_t bytes; };
@@ -246,13 +232,6 @@ inline void dispatch_note(pz_module* M, const char* fmt, ...) {
     va_end(ap);
     for (auto& s : M->notes) if (s == buf) return;
     if (M->notes.size() < 32) M->notes.emplace_back(buf);
-#ifdef PZ_EXPERIMENT
-    // experiment builds (-DPZ_EXPERIMENT): every new note of a module also goes to the file POULPY_DBG_DISPATCH_LOG names - the census of
-    // instantiations a test / bench run dispatches (what tools/dbg/dispatch_census.sh collects before instantiations are pruned)
-    if (const char* path = getenv("POULPY_DBG_DISPATCH_LOG")) {
-        if (FILE* f = fopen(path, "a")) { fprintf(f, "%s\n", buf); fclose(f); }
-    }
-#endif
 }
 
 // Two-stream section of one API call: independent halves of a batch whose kernels are bound by different units (a compute-bound product beside a

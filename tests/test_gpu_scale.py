@@ -141,8 +141,7 @@ def test_one_kernel_product_pool_parity_at_bench_batch(mods, n, size, base2k, ks
         hip.dispatch_notes(reset=True)
         assert _pool_parity(hip, ref, ks, n, 1, size, base2k, size, batch=1027, pool=23, seed=7000 + n + size + int(ks), pin=pin) == 0
         notes = hip.dispatch_notes()
-        if os.environ.get("POULPY_DBG_SMALL_ONE", "1") != "0":
-            assert ("k_small_one<M1=%d,KS=%d>" % (n // 256, size) in notes) == one_kernel, notes
+        assert ("k_small_one<M1=%d,KS=%d>" % (n // 256, size) in notes) == one_kernel, notes
 
 
 def test_config5_shape_keyswitch_16_limbs_at_batch_256(mods):
