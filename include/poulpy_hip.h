@@ -454,6 +454,31 @@ enum { PZ_MUL_CONST = 0, PZ_MUL_CONST_ASSIGN = 1 };
 int pz_glwe_mul_const_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* re, const int64_t* im, size_t b_size,
                               const pz_glwe_mul_const_params* p, int mode, size_t batch);
 
+/* GLWE linear combination on `batch` device-resident ciphertexts, one pass over HBM (the CKKS linear operations of poulpy-ckks
+ * leveled/default/{add,sub,neg,pow2,rescale}.rs; the mapping is poulpy_amd/ckks.py and DESIGN.md 4.6c).  res = batch GLWEs
+ * VecZnx(res_cols, res_size), overwritten with the terms applied in order to a zero container, column by column:
+ *   PZ_TERM_RAW  res += sign * a (limbs as stored, 0 past a_size: vec_znx_add_into / sub / add_assign / negate); k must be 0
+ *   PZ_TERM_LSH  vec_znx_lsh_add_into (sign +1) / vec_znx_lsh_sub (-1) of a by k bits (poulpy-cpu-ref vec_znx/shift.rs:68-180)
+ *   PZ_TERM_RSH  vec_znx_rsh_add_into / vec_znx_rsh_sub of a by k bits (shift.rs:245-...): adds the shifted digits and renormalizes
+ *                the limbs of res above them with the shift's carry, so it depends on the terms before it
+ * then, with normalize = 1, vec_znx_normalize_assign(base2k) on every column (glwe_normalize_assign).  operands[t] is term t's
+ * operand: batch GLWEs VecZnx(res_cols, a_size) back to back, or one when shared = 1; col0_only = 1: a has ONE column and the term applies to column
+ * 0 only (a plaintext).  base2k of a term: 0 or res's (one base2k per call, operations/glwe.rs:1150).  A term may be res itself (same
+ * pointer, a_size = res_size, not col0_only / shared): the in-place forms; an in-place LSH then holds at most 32 limbs.  Any other
+ * overlap with res: PZ_ERR_ALIAS.  1 to 4 terms.  Device pointers, 16-byte aligned.  No workspace; kernel nodes only. */
+enum { PZ_TERM_RAW = 0, PZ_TERM_LSH = 1, PZ_TERM_RSH = 2 };
+typedef struct {
+    size_t a_size;
+    size_t k;
+    size_t base2k;
+    int kind;
+    int sign;
+    int col0_only;
+    int shared;
+} pz_glwe_term;
+int pz_glwe_combine_batched(pz_module* m, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                            const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch);
+
 /* BlindRotationExecute<CGGI>::blind_rotation_execute (poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs:76-118)
  * on `batch` LWE ciphertexts that share the lookup table and the prepared blind-rotation key:
  *   block_size > 1 : execute_block_binary  (:265-368)       block_size == 1 : execute_standard (:370-440)
@@ -638,6 +663,17 @@ int pz_vec_znx_lsh_batched(pz_module* m, size_t batch, size_t base2k, size_t k, 
                            size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
 int pz_vec_znx_rsh_batched(pz_module* m, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,
                            size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
+/* the accumulating shifts (poulpy-cpu-ref vec_znx/shift.rs): lsh_add_into = vec_znx_lsh::<false> :68-135, lsh_sub :137-180,
+ * rsh_add_into = vec_znx_rsh::<false> :245-342, rsh_sub :344-...; limbs the reference leaves alone stay as they are.  One launch of
+ * pz_glwe_combine_batched's kernel (RAW(res) + shifted a).  a may be res (same column: the in-place walk; another column: plain read). */
+int pz_vec_znx_lsh_add_into_batched(pz_module* m, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,
+                                    size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
+int pz_vec_znx_lsh_sub_batched(pz_module* m, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,
+                               size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
+int pz_vec_znx_rsh_add_into_batched(pz_module* m, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,
+                                    size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
+int pz_vec_znx_rsh_sub_batched(pz_module* m, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,
+                               size_t res_col, const int64_t* a, size_t a_cols, size_t a_size, size_t a_col);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- *
  * One process per GPU; independent ciphertexts are block-sharded over the ranks by the caller and never exchanged.  The only

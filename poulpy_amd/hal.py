@@ -56,6 +56,12 @@ class GlweMulConstParams(C.Structure):
     _fields_ = [(k, c_uint64) for k in ("rank", "a_size", "a_base2k", "res_size", "res_base2k", "cnv_offset")]
 
 
+class GlweTerm(C.Structure):
+    """pz_glwe_term (include/poulpy_hip.h): one term of pz_glwe_combine_batched"""
+    _fields_ = [("a_size", c_size_t), ("k", c_size_t), ("base2k", c_size_t), ("kind", c_int), ("sign", c_int),
+                ("col0_only", c_int), ("shared", c_int)]
+
+
 _lib = None
 PZ_ABI_VERSION = 4   # pz_abi_version() of include/poulpy_hip.h this mirror was written against
 
@@ -101,6 +107,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.pz_glwe_mul_const_batched.restype = c_int
     lib.pz_glwe_mul_const_batched.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_size_t, c_void_p, c_int,
                                               c_size_t]
+    # GLWE linear combination and the accumulating shifts (api_combine.hip)
+    lib.pz_glwe_combine_batched.restype = c_int
+    lib.pz_glwe_combine_batched.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_void_p), POINTER(GlweTerm), c_size_t, c_int,
+                                            c_size_t]
+    for name in ("pz_vec_znx_lsh_add_into_batched", "pz_vec_znx_lsh_sub_batched", "pz_vec_znx_rsh_add_into_batched", "pz_vec_znx_rsh_sub_batched"):
+        getattr(lib, name).restype = c_int
+        getattr(lib, name).argtypes = [c_void_p] + [c_size_t] * 3 + [c_void_p] + [c_size_t] * 3 + [c_void_p] + [c_size_t] * 3
     if path is None:
         _lib = lib
     return lib
@@ -699,6 +712,41 @@ class Module:
             b_size = sizes.pop() if sizes else 0
         ptrs = [None if x is None else x.ctypes.data_as(POINTER(c_int64)) for x in arrs]
         self._ck(self.lib.pz_glwe_mul_const_batched(self.handle, res, a, ptrs[0], ptrs[1], b_size, C.byref(params), mode, batch))
+
+    TERM_KINDS = {"raw": 0, "lsh": 1, "rsh": 2}
+
+    def glwe_combine_batched(self, res: c_void_p, res_cols: int, res_size: int, base2k: int, terms, normalize: bool, batch: int):
+        """res = the terms applied in order to a zero GLWE batch, then optionally glwe_normalize_assign (include/poulpy_hip.h,
+        DESIGN.md 4.6c).  terms: dicts with keys a (device pointer), a_size, kind ("raw" | "lsh" | "rsh"), and optional
+        k, sign (+1 / -1), col0_only, shared, base2k (0 = res's)."""
+        arr = (GlweTerm * max(len(terms), 1))()
+        ops = (c_void_p * max(len(terms), 1))()
+        for i, t in enumerate(terms):
+            kind = self.TERM_KINDS[t["kind"]] if isinstance(t["kind"], str) else int(t["kind"])
+            a = t["a"]
+            ops[i] = a.value if isinstance(a, c_void_p) else a
+            arr[i] = GlweTerm(int(t["a_size"]), int(t.get("k", 0)), int(t.get("base2k", 0)), kind, int(t.get("sign", 1)),
+                              int(bool(t.get("col0_only", False))), int(bool(t.get("shared", False))))
+        self._ck(self.lib.pz_glwe_combine_batched(self.handle, res, res_cols, res_size, base2k, ops, arr, len(terms), int(bool(normalize)), batch))
+
+    def _shift_acc(self, name, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col):
+        self._ck(getattr(self.lib, name)(self.handle, *_sz(batch, base2k, k), res, *_sz(res_cols, res_size, res_col), a, *_sz(a_cols, a_size, a_col)))
+
+    def vec_znx_lsh_add_into_batched(self, batch, base2k, k, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
+        """vec_znx_lsh::<false> (poulpy-cpu-ref vec_znx/shift.rs:68-135) on every object of the batch."""
+        self._shift_acc("pz_vec_znx_lsh_add_into_batched", batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col)
+
+    def vec_znx_lsh_sub_batched(self, batch, base2k, k, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
+        """vec_znx_lsh_sub (shift.rs:137-180) on every object of the batch."""
+        self._shift_acc("pz_vec_znx_lsh_sub_batched", batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col)
+
+    def vec_znx_rsh_add_into_batched(self, batch, base2k, k, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
+        """vec_znx_rsh::<false> (shift.rs:245-342) on every object of the batch."""
+        self._shift_acc("pz_vec_znx_rsh_add_into_batched", batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col)
+
+    def vec_znx_rsh_sub_batched(self, batch, base2k, k, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
+        """vec_znx_rsh_sub (shift.rs:344-...) on every object of the batch."""
+        self._shift_acc("pz_vec_znx_rsh_sub_batched", batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col)
 
     # -- LWE glue of the gate bootstrap (device-resident batches; an LWE = VecZnx(n_lwe + 1, 1, size)) -------------
     def lwe_mod_switch_2n_batched(self, res: c_void_p, lwe: c_void_p, n_lwe: int, lwe_size: int, base2k: int, n2: int, negate: bool, batch: int):
