@@ -124,7 +124,9 @@ def test_convolution_by_const(mods, n):
                 assert np.array_equal(wh.data, wr.data), (a_col, off)
 
 
-def _run_tensor(hip, ref, n, rank, a_size, b_size, res_size, ab_base2k, res_base2k, cnv_offset, mode, batch, seed, chunk=0, a_bits_off=0):
+def _run_tensor(hip, ref, n, rank, a_size, b_size, res_size, ab_base2k, res_base2k, cnv_offset, mode, batch, seed, chunk=0, a_bits_off=0,
+                a_fill=None, b_fill=None):
+    """a_fill / b_fill(t, data, rng): overwrite the operands' digits of pair t in place (tests/unnormalized.py)"""
     from poulpy_amd.hal import GlweTensorParams
     rng = seeded(seed)
     cols = rank + 1
@@ -139,6 +141,10 @@ def _run_tensor(hip, ref, n, rank, a_size, b_size, res_size, ab_base2k, res_base
     for t in range(batch):
         a = VecZnx(n, cols, a_size).fill_uniform(ab_base2k, rng)
         b = a if square else VecZnx(n, cols, b_size).fill_uniform(ab_base2k, rng)
+        if a_fill is not None:
+            a_fill(t, a.data, rng)
+        if b_fill is not None and not square:
+            b_fill(t, b.data, rng)
         a_all[t], b_all[t] = a.data, b.data
         r = VecZnx(n, tcols, res_size, prev[t].copy())
         if square:
@@ -207,7 +213,7 @@ def test_glwe_tensor_apply_n65536_16_limbs(mods):
 
 
 def _run_relinearize(hip, ref, n, rank, a_size, a_base2k, key_size, key_base2k, dnum, dsize, res_size, res_base2k, batch, seed, fuse=(True, True),
-                     chunk=0, pin=False):
+                     chunk=0, pin=False, a_fill=None):
     from poulpy_amd.hal import GlweOpParams
     rng = seeded(seed)
     cols, pairs = rank + 1, rank * (rank + 1) // 2
@@ -219,6 +225,8 @@ def _run_relinearize(hip, ref, n, rank, a_size, a_base2k, key_size, key_base2k, 
     want = np.empty((batch, res_size, cols, n), dtype=np.int64)
     for t in range(batch):
         a = VecZnx(n, cols + pairs, a_size).fill_uniform(a_base2k, rng)
+        if a_fill is not None:
+            a_fill(t, a.data, rng)
         a_all[t] = a.data
         r = VecZnx(n, cols, res_size)
         ref.glwe_tensor_relinearize(r, res_base2k, a, a_base2k, pr, dsize, key_base2k)
@@ -271,7 +279,7 @@ def test_config5_relinearize_n65536_16_limbs(mods):
 
 
 def _run_mul_relinearize(hip, ref, n, rank, a_size, b_size, t_size, base2k, cnv_offset, key_size, key_base2k, dnum, dsize, res_size, res_base2k, mode, batch,
-                         seed, chunk=0, a_bits_off=0, pin=False):
+                         seed, chunk=0, a_bits_off=0, pin=False, a_fill=None, b_fill=None):
     """glwe_tensor_apply / _square_apply into a scratch tensor (t_size limbs, base2k) + glwe_tensor_relinearize: poulpy-ckks's
     ckks_mul_into_default / square (leveled/default/mul.rs:49-85, :131-170), oracle = the two reference operations one after the other."""
     from poulpy_amd.hal import GlweOpParams, GlweTensorParams
@@ -291,6 +299,10 @@ def _run_mul_relinearize(hip, ref, n, rank, a_size, b_size, t_size, base2k, cnv_
     for t in range(batch):
         a = VecZnx(n, cols, a_size).fill_uniform(base2k, rng)
         b = a if square else VecZnx(n, cols, b_size).fill_uniform(base2k, rng)
+        if a_fill is not None:
+            a_fill(t, a.data, rng)
+        if b_fill is not None and not square:
+            b_fill(t, b.data, rng)
         a_all[t], b_all[t] = a.data, b.data
         tmp = VecZnx(n, tcols, t_size)
         if square:

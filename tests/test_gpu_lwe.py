@@ -113,7 +113,7 @@ def test_lwe_keyswitch(mods, n, n_in, n_out, a_size, res_size, a_b, key_b, res_b
 
 @pytest.mark.parametrize("n,n_lwe,lwe_size,lwe_b,key_b,rank_out", [(256, 100, 3, 12, 12, 1), (4096, 512, 2, 13, 13, 2), (4096, 700, 2, 17, 12, 1),
                                                                   (2048, 33, 3, 11, 14, 2)])
-def test_glwe_from_lwe(mods, n, n_lwe, lwe_size, lwe_b, key_b, rank_out):
+def test_glwe_from_lwe(mods, n, n_lwe, lwe_size, lwe_b, key_b, rank_out, fill=None):
     """conversion/lwe_to_glwe.rs:46-121, same base and cross-base embedding, rank-1 and rank-2 outputs"""
     from poulpy_amd.hal import GlweOpParams
     ref, hip = mods(n)
@@ -123,6 +123,8 @@ def test_glwe_from_lwe(mods, n, n_lwe, lwe_size, lwe_b, key_b, rank_out):
     key_size, dnum, res_size = glwe_size + 1, glwe_size, glwe_size
     pr, ph = prepared(ref, hip, rng, n, dnum, 1, rank_out + 1, key_size, key_b)
     lwe = rand_lwe(rng, batch, lwe_size, n_lwe, lwe_b)
+    for b in range(batch if fill is not None else 0):
+        fill(b, lwe[b], rng)
     want = np.empty((batch, res_size, rank_out + 1, n), dtype=np.int64)
     for b in range(batch):
         r = VecZnx(n, rank_out + 1, res_size)
@@ -142,7 +144,7 @@ def test_glwe_from_lwe(mods, n, n_lwe, lwe_size, lwe_b, key_b, rank_out):
 
 
 @pytest.mark.parametrize("n,rank,a_idx,n_lwe", [(256, 1, 0, 100), (4096, 1, 5, 640), (4096, 2, 4095, 33), (2048, 3, 1, 2048)])
-def test_lwe_from_glwe(mods, n, rank, a_idx, n_lwe):
+def test_lwe_from_glwe(mods, n, rank, a_idx, n_lwe, fill=None):
     """conversion/glwe_to_lwe.rs:42-90: coefficient a_idx of a rank-`rank` GLWE to an LWE"""
     from poulpy_amd.hal import GlweOpParams
     ref, hip = mods(n)
@@ -151,6 +153,8 @@ def test_lwe_from_glwe(mods, n, rank, a_idx, n_lwe):
     key_size, dnum = size + 1, size
     pr, ph = prepared(ref, hip, rng, n, dnum, rank, 2, key_size, base2k)
     a = rng.integers(-2048, 2048, (batch, size, rank + 1, n), dtype=np.int64)
+    for b in range(batch if fill is not None else 0):
+        fill(b, a[b], rng)
     want = np.stack([ref.lwe_from_glwe(n_lwe, size, base2k, VecZnx(n, rank + 1, size, a[b].copy()), base2k, a_idx, pr, 1, base2k)
                      for b in range(batch)])
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,

@@ -27,8 +27,10 @@ def mods():
     return get
 
 
-def _run_plain(hip, ref, n, rank, a_size, b_size, res_size, ab, rb, off, mode, shared, batch, seed, chunk=0, abo=0, bbo=0, pool=None):
-    """`pool` distinct inputs (default: batch) tiled over the batch: every output is checked against its input's oracle result."""
+def _run_plain(hip, ref, n, rank, a_size, b_size, res_size, ab, rb, off, mode, shared, batch, seed, chunk=0, abo=0, bbo=0, pool=None, a_fill=None,
+               pt_fill=None):
+    """`pool` distinct inputs (default: batch) tiled over the batch: every output is checked against its input's oracle result.  a_fill /
+    pt_fill(t, data, rng) overwrite input t's ciphertext / plaintext digits in place (tests/unnormalized.py)."""
     from poulpy_amd.hal import GlweTensorParams
     rng = seeded(seed)
     cols = rank + 1
@@ -39,6 +41,11 @@ def _run_plain(hip, ref, n, rank, a_size, b_size, res_size, ab, rb, off, mode, s
     a_k, b_k = ab * a_size - abo, ab * b_size - bbo
     a_p = np.stack([VecZnx(n, cols, a_size).fill_uniform(ab, rng).data for _ in range(pool)])
     pt_p = np.stack([VecZnx(n, 1, b_size).fill_uniform(ab, rng).data for _ in range(1 if shared else pool)])
+    for t in range(pool):
+        if a_fill is not None:
+            a_fill(t, a_p[t], rng)
+        if pt_fill is not None and t < len(pt_p):
+            pt_fill(t, pt_p[t], rng)
     want_p = np.empty((pool, res_size, cols, n), dtype=np.int64)
     for t in range(pool):
         pt = VecZnx(n, 1, b_size, pt_p[0 if shared else t].copy())
@@ -233,7 +240,8 @@ def test_glwe_mul_plain_n65536_bench_shape(mods):
     assert np.array_equal(got, want)
 
 
-def _run_const(hip, ref, n, rank, a_size, res_size, ab, rb, off, mode, re, im, batch, seed, chunk=0, pool=None):
+def _run_const(hip, ref, n, rank, a_size, res_size, ab, rb, off, mode, re, im, batch, seed, chunk=0, pool=None, a_fill=None):
+    """a_fill(t, data, rng): overwrite input t's digits in place (tests/unnormalized.py)"""
     from poulpy_amd.hal import GlweMulConstParams
     rng = seeded(seed)
     cols = rank + 1
@@ -242,6 +250,9 @@ def _run_const(hip, ref, n, rank, a_size, res_size, ab, rb, off, mode, re, im, b
         a_size, ab = res_size, rb
     pool = pool or batch
     a_p = np.stack([VecZnx(n, cols, a_size).fill_uniform(ab, rng).data for _ in range(pool)])
+    if a_fill is not None:
+        for t in range(pool):
+            a_fill(t, a_p[t], rng)
     want_p = np.empty((pool, res_size, cols, n), dtype=np.int64)
     for t in range(pool):
         if assign:

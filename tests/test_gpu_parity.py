@@ -248,9 +248,11 @@ def test_big_add_small_assign(mods, n):
 # batched, device-resident GLWE operations (CoreImpl-level boundary)
 # ------------------------------------------------------------------------------------------
 def _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, a_base2k, key_size, key_base2k, dnum, dsize, res_size, res_base2k, batch,
-                 seed, chunk=0, fuse=(True, True), auto=None, in_place=False, pin=False, wide_in=None):
+                 seed, chunk=0, fuse=(True, True), auto=None, in_place=False, pin=False, wide_in=None, a_fill=None, out=None):
     """auto = (galois element, mode) runs the glwe_automorphism family on top of the key switch.  wide_in = (ciphertext, bits): that ciphertext's
-    digits are drawn from +-2^(bits-1) instead of the balanced a_base2k range (an un-normalized input)."""
+    digits are drawn from +-2^(bits-1) instead of the balanced a_base2k range (an un-normalized input).  a_fill(b, data, rng) may overwrite
+    ciphertext b's digits in place (tests/unnormalized.py).  out (a dict) receives the key digits `mat`, the inputs `a`, and the rounding
+    margins of the oracle and of the device on the same call (`oracle_margin`, `gpu_margin`), and the dispatch notes of the main call (`notes`)."""
     from poulpy_amd.hal import GlweOpParams
     rng = seeded(seed)
     cols_a = rank + 1
@@ -266,14 +268,22 @@ def _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, a_base2k, key_size, ke
         a = VecZnx(n, cols_a, a_size).fill_uniform(a_base2k, rng)
         if wide_in is not None and b == wide_in[0]:
             a.data[...] = rng.integers(-(1 << (wide_in[1] - 1)), 1 << (wide_in[1] - 1), a.data.shape, dtype=np.int64)
+        if a_fill is not None:
+            a_fill(b, a.data, rng)
         a_all[b] = a.data
         res = VecZnx(n, cols_out, res_size)
-        if auto is not None:
-            ref.glwe_automorphism(res, res_base2k, a, a_base2k, pr, dsize, key_base2k, auto[0], auto[1])
-        elif ks:
-            ref.glwe_keyswitch(res, res_base2k, a, a_base2k, pr, dsize, key_base2k)
+
+        def oracle_op():
+            if auto is not None:
+                ref.glwe_automorphism(res, res_base2k, a, a_base2k, pr, dsize, key_base2k, auto[0], auto[1])
+            elif ks:
+                ref.glwe_keyswitch(res, res_base2k, a, a_base2k, pr, dsize, key_base2k)
+            else:
+                ref.glwe_external_product(res, res_base2k, a, a_base2k, pr, dsize, key_base2k)
+        if out is not None:
+            out["oracle_margin"] = max(out.get("oracle_margin", 0.0), ref.rounding_margin_of(oracle_op))
         else:
-            ref.glwe_external_product(res, res_base2k, a, a_base2k, pr, dsize, key_base2k)
+            oracle_op()
         want[b] = res.data
     d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
     d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
@@ -300,6 +310,20 @@ def _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, a_base2k, key_size, ke
     got = d_res.download(np.int64, want.size).reshape(want.shape)
     if pin:
         hip.unpin_key(d_key.ptr)
+    if out is not None:
+        out["notes"] = hip.dispatch_notes()
+        # the same call once more under the margin probe, on fresh copies of the inputs (in place: the first call overwrote them)
+        d_a2, d_r2 = hip.device_alloc(a_all.nbytes).upload(a_all), hip.device_alloc(want.nbytes)
+        if auto is not None:
+            run = lambda: hip.glwe_automorphism_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, auto[0], auto[1], batch)   # noqa: E731
+        elif ks:
+            run = lambda: hip.glwe_keyswitch_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
+        else:
+            run = lambda: hip.glwe_external_product_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
+        out["gpu_margin"] = hip.rounding_margin_of(run)
+        d_a2.free()
+        d_r2.free()
+        out["mat"], out["a"] = mat.data.copy(), a_all.copy()
     hip.set_chunk(0)
     hip.set_fusion(True, True)
     for buf in ((d_a, d_key) if in_place else (d_a, d_key, d_res)):
@@ -576,8 +600,9 @@ def test_plain_automorphism_spectral_form(mods, n, in_place):
         assert np.array_equal(got, want), (rank, gal, a_size, key_size, res_size)
 
 
-def test_ggsw_external_product(mods):
-    """external_product/ggsw.rs:54-58: a loop of GLWE external products over the (row, column) entries of a GGSW."""
+def test_ggsw_external_product(mods, fill=None):
+    """external_product/ggsw.rs:54-58: a loop of GLWE external products over the (row, column) entries of a GGSW.  fill(i, data, rng)
+    (tests/unnormalized.py) may overwrite the inputs' digits."""
     from poulpy_amd.hal import GlweOpParams
     n, rank, dnum_a, size, base2k, dnum = 256, 1, 3, 4, 13, 4
     ref, hip = mods(n)
@@ -588,6 +613,8 @@ def test_ggsw_external_product(mods):
     ref.vmp_prepare(pr, mat)
     hip.vmp_prepare(ph, mat)
     a = MatZnx(n, dnum_a, cols, cols, size).fill_uniform(base2k, rng)   # the GGSW being multiplied
+    if fill is not None:
+        fill(0, a.data, rng)
     want = np.empty_like(a.data)
     flat_a = a.data.reshape(dnum_a * cols, size, cols, n)
     flat_w = want.reshape(dnum_a * cols, size, cols, n)
@@ -619,9 +646,9 @@ def test_ggsw_external_product(mods):
     (1024, 1, 2, 4, 2, 5, 12, 2, 2),    # dsize 2
     (65536, 1, 2, 8, 8, 8, 12, 1, 1),   # metric-shape ring
 ])
-def test_ggsw_expand_row_batched(mods, n, rank, dnum, size, key_dnum, key_size, base2k, dsize, count):
+def test_ggsw_expand_row_batched(mods, n, rank, dnum, size, key_dnum, key_size, base2k, dsize, count, fill=None):
     """conversion/gglwe_to_ggsw.rs:116-268 in place on `count` contiguous device GGSWs vs the oracle's restatement; column 0
-    entries must come back untouched."""
+    entries must come back untouched.  fill(i, data, rng) (tests/unnormalized.py) may overwrite the inputs' digits."""
     from poulpy_amd.hal import GlweOpParams
     ref, hip = mods(n)
     rng = seeded(900 + n + rank)
@@ -636,6 +663,8 @@ def test_ggsw_expand_row_batched(mods, n, rank, dnum, size, key_dnum, key_size, 
         keys_r.append(pr)
         keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
     ggsws = [MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
+    for i, g in enumerate(ggsws if fill is not None else ()):
+        fill(i, g.data, rng)
     flat = np.stack([g.data for g in ggsws])
     d = hip.device_alloc(flat.nbytes).upload(flat)
     for g in ggsws:
@@ -653,8 +682,9 @@ def test_ggsw_expand_row_batched(mods, n, rank, dnum, size, key_dnum, key_size, 
 
 
 @pytest.mark.parametrize("n,rank,cols_in", [(256, 1, 1), (4096, 2, 2), (4096, 1, 3)])
-def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in):
-    """conversion/gglwe_to_ggsw.rs:32-61: strided copy of the a.at(row, 0) entries + ggsw_expand_row, two GGLWEs per call."""
+def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in, fill=None):
+    """conversion/gglwe_to_ggsw.rs:32-61: strided copy of the a.at(row, 0) entries + ggsw_expand_row, two GGLWEs per call.  fill(i, data,
+    rng) (tests/unnormalized.py) may overwrite the inputs' digits."""
     from poulpy_amd.hal import GlweOpParams
     dnum, size, key_dnum, key_size, base2k, count = 2, 3, 3, 4, 13, 2
     ref, hip = mods(n)
@@ -670,6 +700,8 @@ def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in):
         keys_r.append(pr)
         keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
     gglwes = [MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
+    for i, g in enumerate(gglwes if fill is not None else ()):
+        fill(i, g.data, rng)
     want = []
     for a in gglwes:
         g = MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng)   # stale contents must be overwritten
@@ -692,12 +724,17 @@ def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in):
 # ------------------------------------------------------------------------------------------
 # SURVEY.md 8f rank 2 / BASELINE configs[3]: CGGI blind rotation on a batch of LWE ciphertexts
 # ------------------------------------------------------------------------------------------
-def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, res_size, base2k, batch, seed, fuse=(True, True), lut_size=None):
+def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, res_size, base2k, batch, seed, fuse=(True, True), lut_size=None,
+                        lut_fill=None, out=None):
+    """lut_fill(0, data, rng) overwrites the test vector's digits in place (tests/unnormalized.py); out (a dict) receives the rounding margins
+    of the oracle and of the device (`oracle_margin`, `gpu_margin`), and the dispatch notes of the main call (`notes`)."""
     from poulpy_amd.hal import BlindRotationParams
     rng = seeded(seed)
     cols = rank + 1
     lut_size = res_size if lut_size is None else lut_size
     lut = VecZnx(n, 1, lut_size).fill_uniform(base2k, rng)
+    if lut_fill is not None:
+        lut_fill(0, lut.data, rng)
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * brk_size), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):
@@ -714,7 +751,13 @@ def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, re
     want = np.empty((batch, res_size, cols, n), dtype=np.int64)
     for b in range(batch):
         res = VecZnx(n, cols, res_size)
-        ref.blind_rotation_execute(res, base2k, np.ascontiguousarray(lwe[b]), lut, brk_r, dnum, brk_size, block_size, xpa)
+
+        def oracle_op():
+            ref.blind_rotation_execute(res, base2k, np.ascontiguousarray(lwe[b]), lut, brk_r, dnum, brk_size, block_size, xpa)
+        if out is not None:
+            out["oracle_margin"] = max(out.get("oracle_margin", 0.0), ref.rounding_margin_of(oracle_op))
+        else:
+            oracle_op()
         want[b] = res.data
     d_lwe = hip.device_alloc(lwe.nbytes).upload(lwe)
     d_lut = hip.device_alloc(lut.data.nbytes).upload(lut.data)
@@ -726,6 +769,11 @@ def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, re
     hip.set_fusion(*fuse)
     hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
     hip.sync()
+    if out is not None:
+        out["notes"] = hip.dispatch_notes()
+        d_r2 = hip.device_alloc(want.nbytes)
+        out["gpu_margin"] = hip.rounding_margin_of(lambda: hip.blind_rotation_execute_batched(d_r2.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch))
+        d_r2.free()
     hip.set_fusion(True, True)
     got = d_res.download(np.int64, want.size).reshape(want.shape)
     for buf in (d_lwe, d_lut, d_brk, d_res):
@@ -1887,7 +1935,7 @@ def test_vec_znx_shifts(mods, n):
     (4096, 1, 3, 9, [0, 512, 1024, 2048, 3584], 2),                                  # fused automorphism pipeline
     (64, 1, 2, 6, [0], 2),                                                           # nothing to pack: the final trace is empty too
 ])
-def test_glwe_pack_batched(mods, n, rank, size, log_gap_out, indices, batch):
+def test_glwe_pack_batched(mods, n, rank, size, log_gap_out, indices, batch, fill=None):
     """glwe_packing.rs:122-176 through the C ABI vs the oracle's restatement (tree walk, pack_internal's three cases, final partial
     trace); every ciphertext of the batch is an independent problem with the same occupancy pattern."""
     from poulpy_amd.hal import GlweOpParams
@@ -1907,6 +1955,9 @@ def test_glwe_pack_batched(mods, n, rank, size, log_gap_out, indices, batch):
         keys_r.append(pr)
         keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
     data = {j: rng.integers(-(1 << (base2k - 1)), 1 << (base2k - 1), (batch, size, cols, n), dtype=np.int64) for j in indices}
+    for j in (indices if fill is not None else ()):
+        for b in range(batch):
+            fill(b, data[j][b], rng)
     want = np.empty((batch, size, cols, n), dtype=np.int64)
     for b in range(batch):
         cts = {j: VecZnx(n, cols, size, data[j][b].copy()) for j in indices}
@@ -2088,7 +2139,7 @@ def test_circuit_bootstrapping_one_base2k_per_object(mods, n, rank, bases, res_l
     (256, 1, 4, 6, 3, 2, 2, 3, 3, False),
     (512, 1, 2, 224, 7, 2, 3, 2, 2, True),     # blind_rotation/tests/fft64_ref.rs:36-40 `block_binary_extended` (base2k 19, all 224 coefficients)
 ])
-def test_blind_rotation_extended(mods, n, rank, ext, n_lwe, blk, dnum, bsz, rsz, batch, fuse):
+def test_blind_rotation_extended(mods, n, rank, ext, n_lwe, blk, dnum, bsz, rsz, batch, fuse, fill=None):
     """execute_block_binary_extended (algorithm.rs:121-273, extension_factor > 1) vs the oracle's literal restatement; the LWE
     values include every special case of the reference (a = 0, a multiple of ext, ai_hi = 0 with ai_lo != 0, ai_hi + 1 = 2n)."""
     from poulpy_amd.hal import BlindRotationParams
@@ -2097,6 +2148,8 @@ def test_blind_rotation_extended(mods, n, rank, ext, n_lwe, blk, dnum, bsz, rsz,
     rng = seeded(9900 + n + ext)
     cols = rank + 1
     luts = rng.integers(-(1 << (k - 1)), 1 << (k - 1), (ext, rsz, 1, n), dtype=np.int64)
+    if fill is not None:
+        fill(0, luts, rng)
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * bsz), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):

@@ -16,6 +16,7 @@ import pytest
 from oracle import exact
 from oracle.ref import RefModule
 from poulpy_amd.layouts import MatZnx, ScalarZnx, SvpPPol, VecZnx, VecZnxBig, VecZnxDft
+from tests import unnormalized as un
 from tests.helpers import normalize_all, seeded
 
 
@@ -161,13 +162,27 @@ def test_dft_apply_step_offset_semantics():
 def test_external_product_and_keyswitch_match_exact(dsize):
     """poulpy-core glue restated in the oracle (external_product/glwe.rs, keyswitching/glwe.rs) vs the
     exact bivariate product + big-int normalize, incl. dsize > 1 folding (zero-tail semantics)."""
+    _external_product_vs_exact(dsize, 40 + dsize)
+
+
+@pytest.mark.parametrize("dsize", [1, 2, 3])
+@pytest.mark.parametrize("fill", [un.sums(12, 1), un.sums(12, 6), un.wide_at("body", 12, 5), un.wide_at("mask", 12, 5), un.wide_at("top", 12, 6),
+                                  un.wide_at("bottom", 12, 6)], ids=lambda f: f.label)
+def test_external_product_on_unnormalized_input_matches_exact(dsize, fill):
+    """The same on un-normalized digits (tests/unnormalized.py classes 1 and 3): the oracle the GPU is compared against stays exact there."""
+    _external_product_vs_exact(dsize, 60 + dsize, fill)
+
+
+def _external_product_vs_exact(dsize, seed, fill=None):
     n, base2k, rank = 32, 12, 1
     cols = rank + 1
     R = RefModule(n)
-    rng = seeded(40 + dsize)
+    rng = seeded(seed)
     a_size, dnum = 4, 2 if dsize > 1 else 4
     key_size = 5
     a = VecZnx(n, cols, a_size).fill_uniform(base2k, rng)
+    if fill is not None:
+        fill(0, a.data, rng)
     mat = MatZnx(n, dnum, cols, cols, key_size).fill_uniform(base2k, rng)
     pm = R.vmp_pmat_alloc(dnum, cols, cols, key_size)
     R.vmp_prepare(pm, mat)
@@ -183,6 +198,28 @@ def test_external_product_and_keyswitch_match_exact(dsize):
     want = np.zeros((4, cols, n), dtype=np.int64)
     for c in range(cols):
         want[:, c, :] = exact.normalize_exact(big[:, c, :], base2k, 4)
+    assert np.array_equal(res.data, want)
+
+
+@pytest.mark.parametrize("rank_in,rank_out", [(1, 1), (2, 1), (1, 2)])
+@pytest.mark.parametrize("fill", [None, un.sums(13, 2), un.sums(13, 6), un.wide_at("body", 13, 6), un.wide_at("mask", 13, 6),
+                                  un.wide_at("bottom", 13, 4)], ids=lambda f: f.label if f else "normalized")
+def test_keyswitch_matches_exact(rank_in, rank_out, fill):
+    """keyswitching/glwe.rs (dsize 1): big = mask x key + body, big-int normalize; normalized and un-normalized input digits."""
+    n, base2k, a_size, key_size, res_size = 32, 13, 3, 4, 3
+    R = RefModule(n)
+    rng = seeded(70 + rank_in * 3 + rank_out)
+    a = VecZnx(n, rank_in + 1, a_size).fill_uniform(base2k, rng)
+    if fill is not None:
+        fill(0, a.data, rng)
+    mat = MatZnx(n, a_size, rank_in, rank_out + 1, key_size).fill_uniform(base2k, rng)
+    pm = R.vmp_pmat_alloc(a_size, rank_in, rank_out + 1, key_size)
+    R.vmp_prepare(pm, mat)
+    res = VecZnx(n, rank_out + 1, res_size)
+    R.glwe_keyswitch(res, base2k, a, base2k, pm, 1, base2k)
+    big = exact.vmp_exact(np.ascontiguousarray(a.data[:, 1:, :]), mat.data, 0, key_size)
+    big[:a_size, 0, :] += a.data[:, 0, :].astype(object)
+    want = np.stack([exact.normalize_exact(big[:, c, :], base2k, res_size) for c in range(rank_out + 1)], axis=1)
     assert np.array_equal(res.data, want)
 
 
@@ -242,12 +279,26 @@ def test_P5_vec_znx_automorphism_direct(n):
 def test_P5_glwe_automorphism_family_matches_exact(mode, rank):
     """automorphism/glwe_ct.rs:51-275 restated in the oracle vs exact integers: big = exact key-switch value (mask x key
     + body), then phi / +-a / big-int normalize in the order the reference applies them."""
+    _automorphism_vs_exact(mode, rank, 500 + rank)
+
+
+@pytest.mark.parametrize("fill", [un.sums(13, 2), un.sums(13, 6), un.wide_at("body", 13, 6), un.wide_at("mask", 13, 6), un.wide_at("top", 13, 4),
+                                  un.wide_at("bottom", 13, 4)], ids=lambda f: f.label)
+@pytest.mark.parametrize("mode", ["automorphism", "add", "sub", "sub_negate"])
+@pytest.mark.parametrize("rank", [1, 2])
+def test_P5_automorphism_family_on_unnormalized_input_matches_exact(mode, rank, fill):
+    _automorphism_vs_exact(mode, rank, 520 + rank, fill)
+
+
+def _automorphism_vs_exact(mode, rank, seed, fill=None):
     n, base2k = 32, 13
     cols = rank + 1
     R = RefModule(n)
-    rng = seeded(500 + rank)
+    rng = seeded(seed)
     a_size, dnum, key_size, res_size = 3, 3, 4, 4
     a = VecZnx(n, cols, a_size).fill_uniform(base2k, rng)
+    if fill is not None:
+        fill(0, a.data, rng)
     mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(base2k, rng)
     pm = R.vmp_pmat_alloc(dnum, rank, cols, key_size)
     R.vmp_prepare(pm, mat)
@@ -269,10 +320,12 @@ def test_P5_glwe_automorphism_family_matches_exact(mode, rank):
         assert np.array_equal(res.data, want), (mode, rank, p)
 
 
-def _blind_rotation_inputs(n, rank, n_lwe, dnum, brk_size, res_size, base2k, seed):
+def _blind_rotation_inputs(n, rank, n_lwe, dnum, brk_size, res_size, base2k, seed, lut_fill=None):
     rng = seeded(seed)
     cols = rank + 1
     lut = VecZnx(n, 1, res_size).fill_uniform(base2k, rng)
+    if lut_fill is not None:
+        lut_fill(0, lut.data, rng)
     mats = [MatZnx(n, dnum, cols, cols, brk_size).fill_uniform(base2k, rng) for _ in range(n_lwe)]
     lwe_2n = rng.integers(-n, n, n_lwe + 1, dtype=np.int64)   # what mod_switch_2n produces: values in [-n, n)
     return lut, mats, lwe_2n
@@ -305,10 +358,21 @@ def test_P6_rotate_and_normalize_assign(n):
 def test_P6_blind_rotation_matches_exact(block_size, rank):
     """algorithm.rs:265-368 (block binary) / :370-440 (standard) restated in the oracle vs the same recurrence on
     exact integers: acc <- normalize(acc + sum_i (X^a_i - 1) * (acc (x) BRK_i))."""
+    _blind_rotation_vs_exact(block_size, rank, 900 + rank)
+
+
+@pytest.mark.parametrize("fill", [un.sums(10, 3), un.sums(10, 6), un.wide_at("top", 10, 6), un.wide_at("bottom", 10, 6)], ids=lambda f: f.label)
+@pytest.mark.parametrize("block_size", [1, 3])
+@pytest.mark.parametrize("rank", [1, 2])
+def test_P6_blind_rotation_on_an_unnormalized_test_vector_matches_exact(block_size, rank, fill):
+    _blind_rotation_vs_exact(block_size, rank, 920 + rank, fill)
+
+
+def _blind_rotation_vs_exact(block_size, rank, seed, lut_fill=None):
     n, base2k, n_lwe, dnum, brk_size, res_size = 32, 10, 6, 2, 3, 2
     cols = rank + 1
     R = RefModule(n)
-    lut, mats, lwe_2n = _blind_rotation_inputs(n, rank, n_lwe, dnum, brk_size, res_size, base2k, 900 + rank)
+    lut, mats, lwe_2n = _blind_rotation_inputs(n, rank, n_lwe, dnum, brk_size, res_size, base2k, seed, lut_fill)
     brk = np.stack([R.vmp_pmat_alloc(dnum, cols, cols, brk_size).data for _ in range(n_lwe)])
     for i, mt in enumerate(mats):
         pm = R.vmp_pmat_alloc(dnum, cols, cols, brk_size)
@@ -372,10 +436,46 @@ def test_P7_rsh_assign_is_a_rounded_shift():
 def test_P7_glwe_trace_matches_exact():
     """glwe_trace.rs:164-174 restated in the oracle vs exact integers: per step res <- normalize(phi_p(KS_p(rsh(res))) + rsh(res))
     with the exact key-switch value (mask x key + body) and the oracle's own rsh (pinned above)."""
-    n, base2k, rank = 32, 13, 1
+    _trace_vs_exact(13, 77)
+
+
+@pytest.mark.parametrize("base2k", [12, 14])
+@pytest.mark.parametrize("fill", ["sum", "body", "bottom"])
+def test_P7_glwe_trace_on_unnormalized_input_matches_exact(base2k, fill):
+    """digits up to 2^16 at base2k 12 and 14 (what would not fit the device's 16-bit operand): the first rsh and the steps after it"""
+    s = 17 - base2k
+    _trace_vs_exact(base2k, 80 + base2k, un.sums(base2k, s) if fill == "sum" else un.wide_at(fill, base2k, s))
+
+
+@pytest.mark.parametrize("base2k", [5, 12, 14])
+def test_P7_rsh_assign_on_unnormalized_input_is_a_rounded_shift(base2k):
+    """vec_znx_rsh_assign on wide digits: the value (sum of d_j 2^(-j base2k), any d_j) shifted by k bits, rounded, in balanced digits -
+    modulo the torus, since the wide top digit carries out of it."""
+    n = 16
+    R = RefModule(n)
+    rng = seeded(31 + base2k)
+    for k in (1, 2, base2k):
+        for size in (1, 3):
+            for fill in (un.sums(base2k, 4), un.wide_at("top", base2k, 6), un.wide_at("bottom", base2k, 6)):
+                a = VecZnx(n, 2, size).fill_uniform(base2k, rng)
+                fill(0, a.data, rng)
+                b = a.copy()
+                R.vec_znx_rsh_assign(base2k, k, b, 1)
+                assert np.array_equal(a.data[:, 0], b.data[:, 0])
+                assert np.abs(b.data[:, 1]).max() <= 1 << (base2k - 1)
+                mod = 1 << (base2k * size + k)      # vb = va / 2^k modulo the torus
+                for i in range(n):
+                    va, vb = _val(a.data[:, 1, i], base2k), _val(b.data[:, 1, i], base2k)
+                    d = (va - (vb << k)) % mod
+                    d = d - mod if d >= mod >> 1 else d
+                    assert abs(d) <= 1 << (k - 1), (base2k, k, size, fill.label)
+
+
+def _trace_vs_exact(base2k, seed, fill=None):
+    n, rank = 32, 1
     cols = rank + 1
     R = RefModule(n)
-    rng = seeded(77)
+    rng = seeded(seed)
     size, dnum, key_size = 3, 3, 4
     gals = [-1, 5, 25 % (2 * n)]
     mats = [MatZnx(n, dnum, rank, cols, key_size).fill_uniform(base2k, rng) for _ in gals]
@@ -385,6 +485,8 @@ def test_P7_glwe_trace_matches_exact():
         R.vmp_prepare(pm, mt)
         pms.append(pm)
     res = VecZnx(n, cols, size).fill_uniform(base2k, rng)
+    if fill is not None:
+        fill(0, res.data, rng)
     cur = res.copy()
     R.glwe_trace_assign(res, base2k, gals, pms)
     for p, mt in zip(gals, mats):
