@@ -42,6 +42,86 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.pz_abi_version() == PZ_ABI_VERSION
 
 
+def _expected_ctype(ctype, ret=False):
+    """the fixed C -> ctypes mapping of the binding (poulpy_amd/abi.py), restated"""
+    from poulpy_amd import abi
+    scalars = {"size_t": C.c_size_t, "uint64_t": C.c_uint64, "int64_t": C.c_int64, "int": C.c_int, "uint32_t": C.c_uint32,
+               "double": C.c_double, "float": C.c_float}
+    toks = ctype.replace("*", " * ").split()
+    base, stars = [t for t in toks if t not in ("const", "*")][0], toks.count("*")
+    if stars == 0:
+        return None if base == "void" else scalars[base]
+    if stars == 1 and base in abi.STRUCTS:
+        return C.POINTER(abi.STRUCTS[base])
+    if ret and stars == 1 and base == "char":
+        return C.c_char_p
+    return C.c_void_p
+
+
+def test_every_prototype_is_typed_from_the_header(lib):
+    from tests.test_rust_shim import header_functions      # a parser of the header independent of poulpy_amd/abi.py
+    from poulpy_amd import abi
+    hdr = header_functions()
+    assert set(hdr) == set(abi.PROTOTYPES)
+    for name, (ret, params) in hdr.items():
+        fn = getattr(lib, name)
+        assert fn.restype is _expected_ctype(ret, ret=True), (name, ret, fn.restype)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, params, fn.argtypes)
+        for t, have in zip(params, fn.argtypes):
+            assert have is _expected_ctype(t), (name, t, have)
+    # the two non-int returns that used to be read as a 32-bit int
+    assert lib.pz_module_host_key_mirrors.restype is C.c_size_t and lib.pz_kernel_class_name.restype is C.c_char_p
+    from poulpy_amd.hal import GlweOpParams, GlweTerm
+    assert lib.pz_glwe_external_product_batched.argtypes[4] is C.POINTER(GlweOpParams)
+    assert lib.pz_glwe_combine_batched.argtypes[6] is C.POINTER(GlweTerm)
+
+
+def test_typed_prototypes_reject_bad_calls_before_the_library(lib):
+    with pytest.raises(TypeError):
+        lib.pz_bytes_of_vec_znx(4096, 2)                    # one argument too few
+    with pytest.raises(C.ArgumentError):
+        lib.pz_bytes_of_vec_znx(4096, 2.0, 4)               # a float where the header has size_t
+    with pytest.raises(C.ArgumentError):
+        lib.pz_glwe_pack_tmp_bytes(None, C.c_void_p(0), 1)  # an untyped pointer where the header has a struct pointer
+    assert lib.pz_bytes_of_vec_znx(4096, 2, 4) == 4096 * 2 * 4 * 8
+
+
+def test_structs_match_the_c_compiler(tmp_path):
+    """sizeof and every field offset of the generated ctypes structs, against g++ on the same header"""
+    import subprocess
+    from poulpy_amd import abi
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "poulpy_hip.h"', 'int main() {']
+    want = []
+    for name, cls in abi.STRUCTS.items():
+        lines.append(f'    std::printf("%zu\\n", sizeof({name}));')
+        want.append(C.sizeof(cls))
+        for f, _ in cls._fields_:
+            lines.append(f'    std::printf("%zu\\n", offsetof({name}, {f}));')
+            want.append(getattr(cls, f).offset)
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == want
+    assert list(abi.STRUCTS) == ["pz_glwe_op_params", "pz_glwe_tensor_params", "pz_glwe_mul_const_params", "pz_glwe_term",
+                                 "pz_blind_rotation_params", "pz_circuit_bootstrapping_params"]
+    assert abi.pz_circuit_bootstrapping_params.br.offset == 0
+    assert dict(abi.pz_circuit_bootstrapping_params._fields_)["br"] is abi.pz_blind_rotation_params
+
+
+def test_mode_tables_come_from_the_header():
+    from poulpy_amd import abi
+    from poulpy_amd.hal import Module
+    assert Module.AUTO_MODES == {"automorphism": 0, "add": 1, "sub": 2, "sub_negate": 3}
+    assert Module.TENSOR_MODES == {"apply": 0, "add_assign": 1, "square": 2}
+    assert Module.MUL_PLAIN_MODES == {"into": 0, "assign": 1}
+    assert Module.TERM_KINDS == {"raw": 0, "lsh": 1, "rsh": 2}
+    assert Module.KERNEL_CLASSES == ("fwd_pass1", "fwd_pass2", "vmp", "inv_pass2", "inv_pass1", "normalize", "elementwise", "fused_mid",
+                                     "fused_tail")
+    assert (abi.PZ_OK, abi.PZ_ERR_INVALID, abi.PZ_AUTO_ADD, abi.PZ_K_FUSED_TAIL, abi.PZ_KCLASS_COUNT) == (0, -1, 1, 8, 9)
+
+
 def test_byte_sizes_match_reference_formulas(lib):
     # poulpy-hal/src/layouts/module.rs:51-65
     n = 1 << 12
@@ -50,7 +130,6 @@ def test_byte_sizes_match_reference_formulas(lib):
     assert lib.pz_bytes_of_svp_ppol(C.c_uint64(n), C.c_size_t(3)) == n * 3 * 8
     assert lib.pz_bytes_of_vmp_pmat(C.c_uint64(n), C.c_size_t(4), C.c_size_t(2), C.c_size_t(2), C.c_size_t(4)) == n * 4 * 2 * 2 * 4 * 8
     # scratch sizes the callers assume; module pointer may be NULL for the shape-only ones
-    lib.pz_vmp_apply_dft_to_dft_tmp_bytes.argtypes = [C.c_void_p] + [C.c_size_t] * 6
     assert lib.pz_vmp_apply_dft_to_dft_tmp_bytes(None, 4, 3, 5, 2, 2, 4) == (16 + 8 * 3 * 2) * 8
 
 

@@ -10,11 +10,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROBE = r"""
-import ctypes as C, sys
+import sys
 sys.path.insert(0, %r)
 from poulpy_amd.hal import Module
 m = Module(4096, device=0)
-m.lib.pz_debug_workspace_overrun.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
 rc = m.lib.pz_debug_workspace_overrun(m.handle, 1 << 20, int(sys.argv[1]))
 print("rc", rc, flush=True)
 """

@@ -1308,7 +1308,6 @@ def test_freed_host_key_gives_its_device_mirrors_back_at_once(mods):
     B.glwe_external_product_batched(hp(got), hp(a.data), hp(ph2.data), p, 1)
     B.sync()
     free2, _ = torch.cuda.mem_get_info()
-    lib.pz_vmp_zero.argtypes = [C.c_void_p, C.c_void_p] + [C.c_size_t] * 4
     assert lib.pz_vmp_zero(A.handle, hp(ph2.data), size, cols, cols, size) == 0     # publishes; B is idle: swept right here
     free3, _ = torch.cuda.mem_get_info()
     assert free3 - free2 >= key_bytes, (free2, free3)
@@ -2442,8 +2441,6 @@ def test_glwe_ops_on_host_containers(mods, n):
         assert hip.lib.pz_module_forget_host_key(hip.handle, hp(ph.data)) == 0
         # a key inside a pz_alloc_bytes block (Backend::OwnedBuf of the Rust shim): releasing the block drops its mirror
         lib = hip.lib
-        lib.pz_module_host_key_mirrors.restype = C.c_size_t
-        lib.pz_module_host_key_mirrors.argtypes = [C.c_void_p]
         before = lib.pz_module_host_key_mirrors(hip.handle)
         blk = lib.pz_alloc_bytes(ph.data.nbytes + 4096)
         inner = np.ctypeslib.as_array(C.cast(blk + 4096, C.POINTER(C.c_double)), shape=(ph.data.size,))
