@@ -13,6 +13,11 @@ one pz_glwe_external_product_batched() over `--batch` ciphertexts resident in HB
 GPU (weak scaling: per-GPU work fixed).  The evaluation key is prepared on rank 0 and
 broadcast with RCCL; there is no other collective on the data path.
 
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs if given, and the
+JSON line.  --full adds everything else the line can carry, after the timed steps: the parity sample of the timed output against
+the CPU oracle, the sustained leg (with clock / power samples), the per-kernel timing pass and its roofline / ceilings objects,
+the rounding margin, the output-digit check and the CPU baseline.
+
 PyTorch is plumbing only (device buffers for the synthetic inputs, torch.distributed).
 The measured code is libpoulpy_hip.so through its C ABI.
 """
@@ -348,6 +353,10 @@ def main():
     ap.add_argument("--galois", type=int, default=5, help="Galois element of --op automorphism / automorphism_add (odd; negative = mod 2N)")
     ap.add_argument("--dsize", type=int, default=1, help="digit size of the key (dnum = limbs / dsize rows); > 1 runs the digit-selected middle kernel")
     ap.add_argument("--no-pin-key", action="store_true", help="rebuild the key's row-sliced copy on every call (pz_module_pin_key not used)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the parity sample, the sustained leg, the per-kernel timing pass (roofline, ceilings), "
+                         "the rounding margin, the output-digit check and the CPU baseline (--no-cpu-baseline, --no-margin, --no-kernel-timing, "
+                         "--timing-steps, --sustained-seconds and --parity-samples act only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-margin", action="store_true", help="skip the extra untimed step that measures the rounding margin")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the separate per-kernel-class timing pass (no roofline object)")
@@ -381,7 +390,7 @@ def main():
     R = multirank.enter(__file__, args.gpus, sys.argv[1:])
     world, rank, local_rank, distributed = R.world, R.rank, R.local_rank, R.distributed
     # clock / power / busy samples for the sustained leg: a helper process, started before this one imports torch or touches the GPU
-    smi_proc, smi_path = start_smi_sampler(local_rank) if (rank == 0 and args.sustained_seconds > 0) else (None, None)
+    smi_proc, smi_path = start_smi_sampler(local_rank) if (rank == 0 and args.full and args.sustained_seconds > 0) else (None, None)
 
     torch, dist = R.init()   # device checks (exit 4: fewer HIP devices than local ranks), set_device, process group "nccl" = RCCL
 
@@ -412,7 +421,7 @@ def main():
         g.manual_seed(0x6657)
         mat = torch.randint(-half, half, (key_elems,), dtype=torch.int64, device=dev, generator=g)
         torch.cuda.synchronize()
-        mat_host = mat.cpu().numpy() if args.parity_samples else None
+        mat_host = mat.cpu().numpy() if (args.full and args.parity_samples) else None
         mod._ck(mod.lib.pz_vmp_prepare(mod.handle, C.c_void_p(pmat.data_ptr()), C.c_void_p(mat.data_ptr()),
                                        C.c_size_t(DNUM), C.c_size_t(cols_in), C.c_size_t(cols), C.c_size_t(SIZE)))
         mod.sync()
@@ -501,9 +510,11 @@ def main():
     # timed output of the LAST step, as the caller receives it (before anything below runs the op again)
     dumped = dump_outputs(args.dump_outputs, res) if (args.dump_outputs and rank == 0) else None
 
+    # the legs below (parity sample, sustained leg, per-kernel timing, rounding margin) run only under --full
     # timed output of the LAST step -> parity sample against the CPU oracle (taken before the instrumented pass re-runs the op)
-    parity = parity_sample(args, mod, a, res, mat_host, lo, nct, ks, auto_mode, trace or expand, cols, cols_in, relin, DSIZE) if args.parity_samples else None
-    if trace and args.parity_samples and mat_host is not None:   # (the rank that holds the key material on the host)
+    check = args.full and args.parity_samples
+    parity = parity_sample(args, mod, a, res, mat_host, lo, nct, ks, auto_mode, trace or expand, cols, cols_in, relin, DSIZE) if check else None
+    if trace and check and mat_host is not None:   # (the rank that holds the key material on the host)
         # the timed traces run in place on their own output; the check is one more (untimed) call from the original input - same
         # pointers, batch and keys, so the same launches (and graph) - on two ciphertexts: log2(N) key switches each on the CPU
         import numpy as np
@@ -527,9 +538,9 @@ def main():
         parity = {"n": len(picks), "ok": not bad, "indices": [int(lo + i) for i in picks], "mismatched": bad,
                   "against": "oracle/fft64_ref.c, bit-exact i64 limbs; one extra untimed call from the original input (the timed calls run in place)"}
 
-    # sustained leg (always on): the same step() looped for >= --sustained-seconds of wall time, no events; the headline stays the K-step figure
+    # sustained leg: the same step() looped for >= --sustained-seconds of wall time, no events; the headline stays the K-step figure
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         if trace:
             res.copy_(a)
         if distributed:
@@ -575,7 +586,7 @@ def main():
 
     # roofline leg: the same steps again with one HIP-event pair per launch on the module stream
     stats = {}
-    timing = (not args.no_kernel_timing)
+    timing = args.full and not args.no_kernel_timing
     if timing:
         if trace:
             res.copy_(a)
@@ -590,7 +601,7 @@ def main():
     # rounding margin of this configuration (one more untimed step with the probing instantiations of the rounding kernels): how far the
     # f64 transforms stay from a wrong i64 limb on THESE inputs - 0.5 would be one (backend_safety_contract.md:25-27)
     margin = None
-    if not args.no_margin:
+    if args.full and not args.no_margin:
         if trace:
             res.copy_(a)
             torch.cuda.synchronize()
@@ -623,8 +634,10 @@ def main():
     # cheap size-independent sanity on the timed output: digits are balanced base-2^12
     # (glwe_automorphism permutes AFTER normalizing, so a digit -2^(k-1) may come out negated: closed interval there,
     # exactly as in the reference, automorphism/glwe_ct.rs:65-71)
-    hi_ok = (res.max() <= half) if auto_mode == "automorphism" else (res.max() < half)
-    ok = bool((res.min() >= -half).item() and hi_ok.item())
+    ok = None
+    if args.full:
+        hi_ok = (res.max() <= half) if auto_mode == "automorphism" else (res.max() < half)
+        ok = bool((res.min() >= -half).item() and hi_ok.item())
 
     if rank == 0:
         total_units = args.batch * world * args.steps // (DNUM if expand else 1)
@@ -648,17 +661,18 @@ def main():
                         "kernel_ms": {k: round(v[1], 3) for k, v in stats.items() if v[0]}}
         # the whole call against the three ceilings that can bound it (tools/roofline_models.py), with the kernel instantiation that ran
         ceilings = None
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import roofline_models as rm
-            notes = mod.dispatch_notes()
-            unit_model = rm.glwe_op(N, cols_in, cols, SIZE, SIZE, DNUM, args.batch, a_cols=a_cols, extra_in_polys=(SIZE if auto_mode == "add" else 0))
-            per_unit = (DNUM * RANK_GLWE if expand else (N.bit_length() - 1) if trace else 1)   # key switches inside one unit
-            model = {k: unit_model[k] * per_unit for k in ("hbm_bytes", "flops", "key_stream_bytes")}
-            ceilings = rm.roofline(value / world, model, rm.key_share(notes) if "k_mid" in notes else 1)
-            ceilings["dispatch"] = notes
-        except Exception as e:   # reporting only
-            ceilings = {"error": str(e)}
+        if args.full:
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import roofline_models as rm
+                notes = mod.dispatch_notes()
+                unit_model = rm.glwe_op(N, cols_in, cols, SIZE, SIZE, DNUM, args.batch, a_cols=a_cols, extra_in_polys=(SIZE if auto_mode == "add" else 0))
+                per_unit = (DNUM * RANK_GLWE if expand else (N.bit_length() - 1) if trace else 1)   # key switches inside one unit
+                model = {k: unit_model[k] * per_unit for k in ("hbm_bytes", "flops", "key_stream_bytes")}
+                ceilings = rm.roofline(value / world, model, rm.key_share(notes) if "k_mid" in notes else 1)
+                ceilings["dispatch"] = notes
+            except Exception as e:   # reporting only
+                ceilings = {"error": str(e)}
         line = {
             "metric": (f"GLWE tensor relinearizations/sec (N=2^{N.bit_length() - 1}, {SIZE} limbs)" if relin else
                        f"GGSW expand-rows/sec (N=2^{N.bit_length() - 1}, {SIZE} limbs, {DNUM} rows)" if expand else
@@ -687,7 +701,7 @@ def main():
         }
         if dumped is not None:
             line["dumped_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline and not ks:
+        if args.full and world == 1 and not args.no_cpu_baseline and not ks:
             err = None
             for attempt in range(2):   # a host hiccup (a busy core, an allocation failure) gets one more try before the line reports "failed"
                 try:

@@ -84,16 +84,33 @@ def test_dump_outputs_is_exact_bounded_and_fixed(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_single_rank_rccl_path_through_the_c_abi():
-    """`bench.py --gpus 1` with the distributed path forced: process group, pz_comm_init_rank, pz_bcast_key (RCCL inside the C ABI),
+    """`bench.py --gpus 1 --full` with the distributed path forced: process group, pz_comm_init_rank, pz_bcast_key (RCCL inside the C ABI),
     global-index shard, per-rank parity sample — everything the N-rank run does, with one rank."""
     env = dict(os.environ, POULPY_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--setup-calls", "1", "--bcast", "cabi",
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--setup-calls", "1", "--bcast", "cabi", "--full",
                           "--no-cpu-baseline", "--parity-samples", "2", "--timing-steps", "1"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1
     assert "cabi" in line["config"]["parallelism"]
     assert line["parity_sample"]["ok"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone(tmp_path):
+    """Without --full a run sets up, warms up, times its steps, writes --dump-outputs and prints the line: no parity sample, sustained leg,
+    per-kernel timing pass, rounding margin, output-digit check or CPU baseline runs behind the timed steps."""
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["unit"] == "external-products/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 64) < 1e-6 * 64      # 64 products per step
+    for leg in ("parity_sample", "sustained", "roofline", "ceilings", "rounding_margin"):
+        assert line[leg] is None, leg
+    assert "cpu_baseline" not in line and line["config"]["output_digits_balanced"] is None
+    assert line["dumped_outputs"]["dir"] == str(tmp_path) and os.path.exists(tmp_path / "res.npy") and os.path.exists(tmp_path / "res_index.npy")
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 #!/bin/bash
 # secondary bench.py lines at HEAD (run on the GPU box through gpurun): one JSON line each into gpurun_out/bench_lines.jsonl
 OUT=gpurun_out/bench_lines.jsonl; : > $OUT
-B="python bench.py --no-cpu-baseline --parity-samples 4 --steps 30 --sustained-seconds 0"   # (the sustained leg belongs to the default run: profiles/rNN_bench_default.json)
+B="python bench.py --full --no-cpu-baseline --parity-samples 4 --steps 30 --sustained-seconds 0"   # (the sustained leg belongs to the headline's own --full run: profiles/rNN_bench_default.json)
 $B >> $OUT 2>/dev/null
 $B --op keyswitch >> $OUT 2>/dev/null
 $B --op keyswitch --batch 4096 --steps 10 >> $OUT 2>/dev/null

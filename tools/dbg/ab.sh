@@ -5,6 +5,6 @@ for lib in "$@"; do
   echo "== $lib"
   timeout 600 python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "glwe or config or metric or vmp" 2>&1 | tail -1
   for i in 1 2; do
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f' % d['value'], d['roofline']['kernel_ms'])"
+  python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f' % d['value'], d['roofline']['kernel_ms'])"
   done
 done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of environment knobs on one library and one box: tools/dbg/ab_env.sh [--args "bench args"] "VAR=a" "VAR=b" ...
-ARGS="--steps 20 --warmup 3 --no-cpu-baseline --parity-samples 2"
+ARGS="--steps 20 --warmup 3 --full --no-cpu-baseline --parity-samples 2"
 if [ "$1" = "--args" ]; then ARGS="$ARGS $2"; shift 2; fi
 for kv in "$@"; do
   for i in 1 2; do

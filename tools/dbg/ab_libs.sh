@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B library builds on the same box: `tools/dbg/ab_libs.sh [--ops "extra bench args"] lib1.so lib2.so ...` (paths relative to poulpy_amd/)
 # prints products/s and the per-class kernel times of bench.py for each, two processes per library.
-ARGS="--steps 20 --warmup 3 --no-cpu-baseline --parity-samples 2"
+ARGS="--steps 20 --warmup 3 --full --no-cpu-baseline --parity-samples 2"
 if [ "$1" = "--args" ]; then ARGS="$ARGS $2"; shift 2; fi
 for lib in "$@"; do
   export POULPY_HIP_LIB=$PWD/poulpy_amd/$lib

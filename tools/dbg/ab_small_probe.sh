@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of the small-ring kernels over library builds: tools/dbg/ab_small_probe.sh lib1.so lib2.so (relative to poulpy_amd/)
-B="python bench.py --no-cpu-baseline --no-margin --steps 200"
+B="python bench.py --full --no-cpu-baseline --no-margin --steps 200"
 line() { tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -7,6 +7,6 @@ for n in 1024 2048; do
   echo "== N = $n"; cat $OUT/n$n.txt | cut -c1-400 | head -10
 done
 unset POULPY_HIP_LIB
-for n in 1024 2048; do python bench.py --n $n --limbs 4 --base2k 17 --batch 4096 --steps 50 --no-cpu-baseline --parity-samples 2 --sustained-seconds 0 2>/dev/null | grep "^{" | tail -1 | python -c "
+for n in 1024 2048; do python bench.py --n $n --limbs 4 --base2k 17 --batch 4096 --steps 50 --full --no-cpu-baseline --parity-samples 2 --sustained-seconds 0 2>/dev/null | grep "^{" | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('N=$n %9.0f %s frac=%.3f %s' % (d['value'], d['unit'], d['roofline']['frac'] if d.get('roofline') else 0, (d.get('roofline') or {}).get('kernel_ms')))"; done

@@ -1,6 +1,6 @@
 #!/bin/bash
 for c in 4 8 16 32 64 128; do
-  python bench.py --steps 3 --warmup 1 --chunk $c --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --steps 3 --warmup 1 --chunk $c --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # everything profiles/rNN_* is made from, in one call on the GPU box (about 10 minutes): tools/measure_all.sh NN
 R=${1:-05}; O=gpurun_out
-python bench.py > $O/r${R}_bench_default.json 2> $O/r${R}_bench_default.err
+python bench.py --full > $O/r${R}_bench_default.json 2> $O/r${R}_bench_default.err
 bash tools/bench_lines.sh > $O/r${R}_bench_lines.txt 2>&1; cp $O/bench_lines.jsonl $O/r${R}_bench_lines.jsonl; cp $O/tensor_lines.jsonl $O/r${R}_tensor_lines.jsonl
 bash tools/bench_lines_br.sh > $O/r${R}_bench_lines_br.txt 2>&1; cp $O/bench_lines_br.jsonl $O/r${R}_bench_lines_br.jsonl
 bash tools/bench_lines_hal.sh > $O/r${R}_bench_lines_hal.txt 2>&1; cp $O/bench_lines_hal.jsonl $O/r${R}_bench_lines_hal.jsonl

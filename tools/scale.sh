@@ -26,6 +26,7 @@ out=gpurun_out; mkdir -p "$out"; : > "$out/scale_lines.jsonl"
 ref=0
 for n in "${counts[@]}"; do
     args=(--gpus "$n" "$@")
+    [ "$bench" = bench.py ] && args+=(--full)   # the parity column of the table
     [ "$ref" != 0 ] && args+=(--ref-value "$ref")
     # bench.py's own exit status (not tail's): 4 = fewer devices than ranks ("skipped"); anything else non-zero is a FAILED run
     python $bench "${args[@]}" > "$out/scale_n$n.out" 2> "$out/scale_n$n.err"
