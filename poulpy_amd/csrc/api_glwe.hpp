@@ -46,6 +46,9 @@ static int with_graph(pz_module* M, uint64_t key, F&& body) {
         if (M->graphs.size() >= 16) {
             size_t lru = 0;
             for (size_t i = 1; i < M->graphs.size(); ++i) if (M->graphs[i].stamp < M->graphs[lru].stamp) lru = i;
+            // the evicted graph may still be executing on the stream, and HIP does not document destroying an executable graph
+            // in flight: wait for it (at most one sync per 16 new argument sets)
+            if (M->graphs[lru].exec) PZ_HIP(hipStreamSynchronize(M->stream));
             graph_drop(M->graphs[lru]);
             M->graphs.erase(M->graphs.begin() + (long)lru);
         }
