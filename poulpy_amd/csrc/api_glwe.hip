@@ -374,6 +374,7 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     // (glwe_trace's steps, want_rsh: their input is the previous step's - or the initial shift's - normalized output, so with a base of at most 14 bits
     //  the operand always fits and the flag-up launches of the shifted-store forms stay what they are there: never taken)
     const bool body16 = spectral_body16(c);   // (glwe_fused zeroed the flag word in front of pass 1: that kernel may raise it too, f.side16)
+    if (body16) dispatch_note(M, "spectral tail: 16-bit body operand (%s form)", c.au_big ? "add / sub" : "plain");
     short* b16 = body16 ? (short*)f.res_tmp : nullptr;
     if (body16) {
         t.body16 = b16; t.body16_limbs = bl; t.body16_wide = M->wide16();

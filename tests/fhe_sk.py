@@ -1,0 +1,258 @@
+"""Secret-key toolkit in exact arithmetic (tests/ only): secrets, encryption, phase and noise, restated from poulpy-core.
+
+It calls neither the oracle (oracle/fft64_ref.c) nor the device (poulpy_amd): every product a * s is an exact integer product in
+Z[X]/(X^N+1) on the limbs of a, and every phase and noise is computed on integers, so a convention shared by the oracle and the device
+(which key column multiplies which input column, phi_p against phi_p^-1, the limb of a GGLWE row's message) is checked against the
+reference's own encryption procedures rather than against itself.
+
+Layouts are those of poulpy_amd/layouts.py: a GLWE is a (size, rank + 1, n) int64 array (VecZnx, limb-major), a GGSW / GGLWE a
+(rows, cols_in, size, cols_out, n) int64 array (MatZnx), which vmp_prepare takes as it is.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+# poulpy-core/src/encryption/mod.rs:76-80
+SIGMA = 3.2
+BOUND = 6.0 * SIGMA
+
+# above this ring degree the products go through numpy.fft (checked to lie within 1/4 of an integer before rounding)
+SCHOOLBOOK_MAX_N = 4096
+
+
+def limbs_for(k: int, base2k: int) -> int:
+    return -(-k // base2k)
+
+
+# ---- secrets (poulpy-core layouts/glwe_secret.rs fill_ternary_prob) ----
+def ternary_secret(n: int, rank: int, rng: np.random.Generator, prob: float = 0.5) -> np.ndarray:
+    """(rank, n) int64 in {-1, 0, 1}: non-zero with probability `prob`, then a uniform sign."""
+    nz = rng.random((rank, n)) < prob
+    sign = np.where(rng.random((rank, n)) < 0.5, -1, 1)
+    return (nz * sign).astype(np.int64)
+
+
+# ---- exact arithmetic in Z[X]/(X^N+1) ----
+def rotate(a: np.ndarray, k: int) -> np.ndarray:
+    """X^k * a (negacyclic), along the last axis."""
+    n = a.shape[-1]
+    k %= 2 * n
+    sign = 1
+    if k >= n:
+        k -= n
+        sign = -1
+    r = np.roll(a, k, axis=-1)
+    r[..., :k] *= -1
+    return sign * r
+
+
+def automorphism(a: np.ndarray, p: int) -> np.ndarray:
+    """phi_p: X^i -> X^(i p mod 2N), the sign flipped past N (poulpy-cpu-ref/src/reference/znx/automorphism.rs:1-17), along the last
+    axis; p odd, any sign."""
+    n = a.shape[-1]
+    idx = (np.arange(n, dtype=np.int64) * int(p)) % (2 * n)
+    out = np.zeros_like(a)
+    pos = idx < n
+    out[..., idx[pos]] = a[..., pos]
+    out[..., idx[~pos] - n] = -a[..., ~pos]
+    return out
+
+
+def galois_inv(p: int, n: int) -> int:
+    return pow(int(p) % (2 * n), -1, 2 * n)
+
+
+def mul_small(a: np.ndarray, s: np.ndarray) -> np.ndarray:
+    """a * s in Z[X]/(X^N+1) along the last axis, exactly: a int64 digits (|a| < 2^17), s a small secret polynomial (|s| <= 1)."""
+    a = np.asarray(a, dtype=np.int64)
+    s = np.asarray(s, dtype=np.int64)
+    n = a.shape[-1]
+    assert s.shape == (n,) and np.abs(s).max(initial=0) <= 1
+    if n <= SCHOOLBOOK_MAX_N:
+        out = np.zeros_like(a)
+        for k in np.flatnonzero(s):
+            r = np.roll(a, int(k), axis=-1)
+            r[..., :k] *= -1
+            if s[k] > 0:
+                out += r
+            else:
+                out -= r
+        return out
+    # negacyclic product by a twisted cyclic FFT: |result| <= N 2^17 < 2^34, far below 2^52
+    assert np.abs(a).max(initial=0) < (1 << 17)
+    w = np.exp(1j * np.pi * np.arange(n) / n)
+    c = np.fft.ifft(np.fft.fft(a * w, axis=-1) * np.fft.fft(s * w), axis=-1) / w
+    r = np.rint(c.real)
+    assert np.abs(c.real - r).max(initial=0) < 0.25 and np.abs(c.imag).max(initial=0) < 0.25
+    return r.astype(np.int64)
+
+
+def normalize(limbs: np.ndarray, base2k: int) -> np.ndarray:
+    """Balanced base-2^base2k digits in [-2^(base2k-1), 2^(base2k-1)) of the limb vector (axis 0, limb 0 most significant); the carry
+    out of limb 0 is dropped (the torus is mod 1)."""
+    x = np.array(limbs, dtype=np.int64, copy=True)
+    half, mask = 1 << (base2k - 1), (1 << base2k) - 1
+    carry = np.zeros(x.shape[1:], dtype=np.int64)
+    for j in reversed(range(x.shape[0])):
+        v = x[j] + carry
+        d = ((v + half) & mask) - half
+        carry = (v - d) >> base2k
+        x[j] = d
+    return x
+
+
+def to_int(limbs: np.ndarray, base2k: int) -> np.ndarray:
+    """The integers sum_j limbs[j] 2^(base2k (size - 1 - j)) (Python ints, object array): the torus value times 2^(base2k size)."""
+    acc = np.zeros(limbs.shape[1:], dtype=object)
+    for j in range(limbs.shape[0]):
+        acc = acc * (1 << base2k) + limbs[j].astype(object)
+    return acc
+
+
+def uniform_digits(shape, base2k: int, rng: np.random.Generator) -> np.ndarray:
+    """vec_znx_fill_uniform: digits in [-2^(base2k-1), 2^(base2k-1))."""
+    h = 1 << (base2k - 1)
+    return rng.integers(-h, h, shape, dtype=np.int64)
+
+
+def gaussian(n: int, rng: np.random.Generator, sigma: float = SIGMA, bound: float = BOUND) -> np.ndarray:
+    e = np.rint(rng.normal(0.0, sigma, n))
+    return np.clip(e, -bound, bound).astype(np.int64)
+
+
+# ---- encryption (poulpy-core/src/encryption) ----
+def glwe_encrypt(sk: np.ndarray, pt: np.ndarray, base2k: int, k: int, rng: np.random.Generator, col: int = 0,
+                 sigma: float = SIGMA) -> np.ndarray:
+    """glwe.rs:426-512 (glwe_encrypt_sk_internal): the mask columns uniform, the body -sum_i (c_i - [i = col] pt) s_i + e (+ pt if
+    col = 0), e of deviation sigma at 2^-k; so the phase is pt + e (col 0) or pt s_col + e.  pt: (size, n) message limbs at base2k
+    (fewer limbs are zero-extended).  Returns the (size, rank + 1, n) normalized ciphertext, size = ceil(k / base2k)."""
+    rank, n = sk.shape
+    size = limbs_for(k, base2k)
+    m = np.zeros((size, n), dtype=np.int64)
+    m[:min(size, pt.shape[0])] = pt[:size]
+    ct = np.empty((size, rank + 1, n), dtype=np.int64)
+    body = np.zeros((size, n), dtype=np.int64)
+    for i in range(1, rank + 1):
+        ci = uniform_digits((size, n), base2k, rng)
+        ct[:, i] = ci
+        body -= mul_small(ci - m if col == i else ci, sk[i - 1])
+    body[size - 1] += gaussian(n, rng, sigma) << (base2k * size - k)
+    if col == 0:
+        body += m
+    ct[:, 0] = normalize(body, base2k)
+    return ct
+
+
+def _row_plaintext(msg: np.ndarray, size: int, limb: int, base2k: int) -> np.ndarray:
+    assert 0 <= limb < size
+    pt = np.zeros((size, msg.shape[-1]), dtype=np.int64)
+    pt[limb] = msg
+    return normalize(pt, base2k)
+
+
+def ggsw_encrypt(sk: np.ndarray, msg: np.ndarray, base2k: int, k: int, dnum: int, dsize: int, rng: np.random.Generator,
+                 limb_shift: int = 0) -> np.ndarray:
+    """ggsw.rs:92-118: row i carries msg in limb (dsize - 1) + i dsize, column j encrypts it against column j (msg s_j for j >= 1).
+    limb_shift moves every row's message (a negative control).  (dnum, rank + 1, size, rank + 1, n)."""
+    rank, n = sk.shape
+    size = limbs_for(k, base2k)
+    assert dnum * dsize <= size   # ggsw.rs / gglwe.rs: dnum dsize base2k <= max_k
+    out = np.zeros((dnum, rank + 1, size, rank + 1, n), dtype=np.int64)
+    for row in range(dnum):
+        pt = _row_plaintext(msg, size, (dsize - 1) + row * dsize + limb_shift, base2k)
+        for c in range(rank + 1):
+            out[row, c] = glwe_encrypt(sk, pt, base2k, k, rng, col=c)
+    return out
+
+
+def gglwe_encrypt(sk_out: np.ndarray, msgs: np.ndarray, base2k: int, k: int, dnum: int, dsize: int, rng: np.random.Generator,
+                  limb_shift: int = 0) -> np.ndarray:
+    """gglwe.rs:114-147: input column i, row r is a GLWE under sk_out of msgs[i] in limb (dsize - 1) + r dsize (:131-135).
+    (dnum, rank_in, size, rank_out + 1, n)."""
+    rank_in = msgs.shape[0]
+    rank_out, n = sk_out.shape
+    size = limbs_for(k, base2k)
+    assert dnum * dsize <= size
+    out = np.zeros((dnum, rank_in, size, rank_out + 1, n), dtype=np.int64)
+    for c in range(rank_in):
+        for row in range(dnum):
+            pt = _row_plaintext(msgs[c], size, (dsize - 1) + row * dsize + limb_shift, base2k)
+            out[row, c] = glwe_encrypt(sk_out, pt, base2k, k, rng, col=0)
+    return out
+
+
+def switching_key(sk_in: np.ndarray, sk_out: np.ndarray, base2k: int, k: int, dnum: int, dsize: int, rng, **kw) -> np.ndarray:
+    """glwe_switching_key.rs:58-105: the GGLWE of sk_in under sk_out."""
+    return gglwe_encrypt(sk_out, sk_in, base2k, k, dnum, dsize, rng, **kw)
+
+
+def automorphism_key(sk: np.ndarray, p: int, base2k: int, k: int, dnum: int, dsize: int, rng, encrypt_for: int | None = None) -> np.ndarray:
+    """glwe_automorphism_key.rs:88-108: the GGLWE of sk under phi_{p^-1}(sk) (:94-96).  encrypt_for replaces p^-1 (a negative
+    control: p itself)."""
+    n = sk.shape[1]
+    g = galois_inv(p, n) if encrypt_for is None else encrypt_for
+    return gglwe_encrypt(automorphism(sk, g), sk, base2k, k, dnum, dsize, rng)
+
+
+# ---- phase and noise (poulpy-core decryption/glwe.rs, noise/glwe.rs:28-46, poulpy-hal layouts/stats.rs:27-57) ----
+def glwe_phase(ct: np.ndarray, sk: np.ndarray) -> np.ndarray:
+    """c_0 + sum_i c_i s_i per limb (un-normalized, exact): (size, n)."""
+    body = np.array(ct[:, 0], dtype=np.int64, copy=True)
+    for i in range(1, ct.shape[1]):
+        body += mul_small(ct[:, i], sk[i - 1])
+    return body
+
+
+def torus_diff(a: np.ndarray, a_base2k: int, b: np.ndarray, b_base2k: int) -> np.ndarray:
+    """a - b as centred torus values in [-1/2, 1/2), computed on integers at the finer of the two precisions and converted to
+    float64 only at the end (a difference near 2^-80 of values of order 1 keeps its digits)."""
+    ka, kb = a_base2k * a.shape[0], b_base2k * b.shape[0]
+    kk = max(ka, kb)
+    d = (to_int(a, a_base2k) << (kk - ka)) - (to_int(b, b_base2k) << (kk - kb))
+    q = 1 << kk
+    d = (d + q // 2) % q - q // 2
+    return np.ldexp(np.array([float(x) for x in d.reshape(-1)], dtype=np.float64), -kk).reshape(d.shape)
+
+
+def noise_log2(ct: np.ndarray, ct_base2k: int, sk: np.ndarray, pt_want: np.ndarray, pt_base2k: int) -> float:
+    """log2 of the standard deviation over the coefficients of phase(ct) - pt_want (glwe_noise(...).std().log2())."""
+    e = torus_diff(glwe_phase(ct, sk), ct_base2k, pt_want, pt_base2k)
+    sd = float(np.std(e))
+    return math.log2(sd) if sd > 0 else -math.inf
+
+
+# ---- closed-form noise bounds (poulpy-core/src/noise/mod.rs) ----
+def var_noise_gglwe_product_v2(n, k_ksk, dnum, dsize, base2k, var_xs, var_msg, var_a_err, var_gct_err_lhs, var_gct_err_rhs, rank_in):
+    """noise/mod.rs:50-72"""
+    var_base = (2.0 ** (dsize * base2k)) ** 2 / 12.0
+    scale = 2.0 ** k_ksk
+    noise = dnum * n * var_base * (var_gct_err_lhs + var_xs * var_gct_err_rhs)
+    noise += var_msg * var_a_err * var_base * n
+    noise *= rank_in
+    return noise / (scale * scale)
+
+
+def noise_ggsw_product(n, base2k, var_xs, var_msg, var_a0_err, var_a1_err, var_gct_err_lhs, var_gct_err_rhs, rank, k_in, k_ggsw):
+    """noise/mod.rs:106-136"""
+    a_logq = min(k_in, k_ggsw)
+    a_cols = -(-a_logq // base2k)
+    b_scale = 2.0 ** k_ggsw
+    a_scale = 2.0 ** (k_ggsw - a_logq)
+    var_base = (2.0 ** base2k) ** 2 / 12.0
+    noise = (rank + 1.0) * a_cols * n * var_base * (var_gct_err_lhs + var_xs * var_gct_err_rhs)
+    noise += var_msg * var_a0_err * a_scale * a_scale * n
+    noise += var_msg * var_a1_err * a_scale * a_scale * n * var_xs * rank
+    return min(math.log2(math.sqrt(noise) / b_scale), -1.0)
+
+
+def keyswitch_bound(n, k_ksk, dnum, dsize, key_base2k, rank_in) -> float:
+    """The bound of keyswitch/glwe_ct.rs:132-147 and automorphism/glwe_ct.rs:126-150 (with the dsize each test passes)."""
+    v = var_noise_gglwe_product_v2(n, k_ksk, dnum, dsize, key_base2k, 0.5, 0.5, 0.0, SIGMA * SIGMA, 0.0, rank_in)
+    return math.log2(math.sqrt(v)) + 1.0
+
+
+def external_product_bound(n, base2k, rank, k_in, k_ggsw) -> float:
+    """The bound of external_product/glwe_ct.rs:133-152 (message X^k, var_msg = 1/n); base2k = key_base2k * max_dsize there."""
+    return noise_ggsw_product(n, base2k, 0.5, 1.0 / n, SIGMA * SIGMA, 1.0 / 12.0, SIGMA * SIGMA, 0.0, rank, k_in, k_ggsw) + 1.0
