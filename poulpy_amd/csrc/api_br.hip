@@ -15,6 +15,15 @@ static TailCall acc_tail(int batch, const cplx* T, bool rowmajor, int nlimbs, in
     c.small = (const long long*)acc; c.small_bs = acc_bs; c.small_cols = cols; c.small_size = acc_size; c.small_all = true;
     return c;
 }
+// the same on the small-ring inverse kernel, product-free form: `spectra` = the block step's ncols_key output polynomials per ciphertext
+static SmallInvCall acc_small_inv(const cplx* spectra, int ncols_key, int cols, int brk_size, int64_t* acc, long long acc_bs, int acc_size, int base2k) {
+    SmallInvCall c;
+    c.S = spectra; c.noprod = true;
+    c.key.npi = ncols_key; c.key.cols_out = cols; c.key.ksz = brk_size;
+    c.res = SmallRes{(long long*)acc, acc_bs, cols, acc_size, base2k};
+    c.small = SmallOperand{(const long long*)acc, acc_bs, cols, acc_size, -1};
+    return c;
+}
 
 extern "C" {
 
@@ -55,44 +64,37 @@ struct BrCall {
     int cols, dnum, bsz, rsz, B, n_lwe, blk, k;
     size_t pmat_doubles, n8;
 };
-#define PZ_BR_UNPACK(c)                                                                                                                  \
-    pz_module* const M = (c).M; int64_t* const res = (c).res; const int64_t* const lwe_2n = (c).lwe_2n; const double* const brk = (c).brk;   \
-    const pz_blind_rotation_params* const p = (c).p; const size_t batch = (c).batch; const long long n = (c).n, lwe_bs = (c).lwe_bs, res_ct = (c).res_ct; \
-    const int cols = (c).cols, dnum = (c).dnum, bsz = (c).bsz, rsz = (c).rsz, B = (c).B, n_lwe = (c).n_lwe, blk = (c).blk, k = (c).k;      \
-    const size_t pmat_doubles = (c).pmat_doubles, n8 = (c).n8;                                                                              \
-    (void)p; (void)batch; (void)n; (void)lwe_bs; (void)res_ct; (void)cols; (void)dnum; (void)bsz; (void)rsz; (void)B; (void)n_lwe; (void)blk; (void)k; \
-    (void)pmat_doubles; (void)n8; (void)res; (void)lwe_2n; (void)brk; (void)M;
 
 // acc = X^b * LUT in column 0, zero elsewhere (:298-301 / :413-416)
 static int br_init_accumulator(const BrCall& c) {
-    PZ_BR_UNPACK(c)
-    PZ_TRY(launch_zero_bytes(M, res, (size_t)B * res_ct * 8));
-    const int nl = std::min(rsz, (int)p->lut_size);
-    PolyMap sm{nl, 1, 0, n, 0, 0};                     // the LUT is shared: batch stride 0, VecZnx(1, lut_size)
-    PolyMap dm{nl, 1, res_ct, (long long)cols * n, 0, 0};
-    return launch_rotate(M, B * nl, (const long long*)c.lut, sm, (long long*)res, dm, 0, nl, (const long long*)lwe_2n, lwe_bs, 0, 0);
+    pz_module* const M = c.M;
+    PZ_TRY(launch_zero_bytes(M, c.res, (size_t)c.B * c.res_ct * 8));
+    const int nl = std::min(c.rsz, (int)c.p->lut_size);
+    PolyMap sm{nl, 1, 0, c.n, 0, 0};                     // the LUT is shared: batch stride 0, VecZnx(1, lut_size)
+    PolyMap dm{nl, 1, c.res_ct, (long long)c.cols * c.n, 0, 0};
+    return launch_rotate(M, c.B * nl, (const long long*)c.lut, sm, (long long*)c.res, dm, 0, nl, (const long long*)c.lwe_2n, c.lwe_bs, 0, 0);
 }
 
 // plans with 128-point rows (N >= 4096): the block step on the three-kernel pipeline of the GLWE products - pass 1 of the accumulator limbs |
 // k_mid128<.., BR> (row DFT, the block's blk products weighted by DFT(X^a_i - 1), inverse row DFT) | tail (inverse column pass + accumulator +
 // carry chain): the spectra never reach HBM and one launch covers the whole block.  *taken = false: the shape is not covered
 static int br_pipeline_path(const BrCall& c, bool* taken) {
-    PZ_BR_UNPACK(c)
+    pz_module* const M = c.M;
     *taken = false;
-    const int npi = cols * std::min(dnum, rsz), npo = cols * bsz, nrows_key = dnum * cols, ncols_key = cols * bsz;
-    if (!(M->fuse_mid && M->fuse_tail && tail_supported(M) && M->plan.m2 == 128 && mid_supported(M, npi, npo) && npi == nrows_key && blk <= 16))
+    const int npi = c.cols * std::min(c.dnum, c.rsz), npo = c.cols * c.bsz, nrows_key = c.dnum * c.cols, ncols_key = c.cols * c.bsz;
+    if (!(M->fuse_mid && M->fuse_tail && tail_supported(M) && M->plan.m2 == 128 && mid_supported(M, npi, npo) && npi == nrows_key && c.blk <= 16))
         return PZ_OK;
     *taken = true;
-    const size_t key_bytes = align256((size_t)blk * nrows_key * ncols_key * n8);
-    const size_t t_bytes = align256(batch * npi * (size_t)M->m * sizeof(cplx)), t2_bytes = align256(batch * npo * (size_t)M->m * sizeof(cplx));
+    const size_t key_bytes = align256((size_t)c.blk * nrows_key * ncols_key * c.n8);
+    const size_t t_bytes = align256(c.batch * npi * (size_t)M->m * sizeof(cplx)), t2_bytes = align256(c.batch * npo * (size_t)M->m * sizeof(cplx));
     // between two blocks the accumulator holds normalized digits: 32-bit values in the workspace (base2k <= 31) - pass 1 and the tail
     // move them at half the bytes; the caller's `res` is the operand of the first block and the destination of the last
-    const int nblocks = n_lwe / blk;
-    const bool acc32 = k <= 31 && nblocks >= 2 && tail_acc32_supported(M);
+    const int nblocks = c.n_lwe / c.blk;
+    const bool narrow = c.k <= 31 && nblocks >= 2 && tail_narrow_supported(M);
     // round 6: 16-bit values in the tails' own tile order where the digits fit them (base2k <= 15): a quarter of the i64 bytes, whole 128-byte runs for
-    // pass 1 (k_fwd_pass1_t16) and the tail (TailCall::acc32 bits 3 / 4)
-    const bool acc16 = acc32 && k <= 15;
-    const size_t d_bytes = acc32 ? align256((size_t)B * res_ct * sizeof(int)) : 0;
+    // pass 1 (k_fwd_pass1_t16) and the tail
+    const Digits held = !narrow ? Digits::I64 : c.k <= 15 ? Digits::I16 : Digits::I32;
+    const size_t d_bytes = narrow ? align256((size_t)c.B * c.res_ct * sizeof(int)) : 0;
     PZ_TRY(ws_reserve(M, key_bytes + t_bytes + t2_bytes + kMidDummyBytes + d_bytes));
     char* base = (char*)M->ws;
     cplx* Pp; cplx* T; cplx* T2; cplx* mid_dummy; int* D = nullptr;
@@ -100,21 +102,26 @@ static int br_pipeline_path(const BrCall& c, bool* taken) {
     PZ_TRY(ws_take(M, base, t_bytes, &T));
     PZ_TRY(ws_take(M, base, t2_bytes, &T2));
     PZ_TRY(ws_take(M, base, kMidDummyBytes, &mid_dummy));
-    if (acc32) PZ_TRY(ws_take(M, base, d_bytes, &D));
-    PolyMap sm{npi / cols, cols, res_ct, (long long)cols * n, n, 0};
+    if (narrow) PZ_TRY(ws_take(M, base, d_bytes, &D));
+    PolyMap sm{npi / c.cols, c.cols, c.res_ct, (long long)c.cols * c.n, c.n, 0};
+    MidCall mc;
+    mc.T = T; mc.T2 = T2; mc.Pp = Pp; mc.dummy = mid_dummy; mc.npi = npi; mc.npo = npo; mc.nrows = nrows_key; mc.ncols = ncols_key;
     // (round 5, measured and dropped: the two-stream split of the small-ring path below applied here - the persistent middle kernel holds every
     //  CU's LDS, so the other half's pass 1 / tail cannot run beside it: N = 4096 -3.6 %, N = 2^14 +-0; profiles/r05_ab_br_two_streams_pipe.txt)
-    for (int b0 = 0; b0 + blk <= n_lwe; b0 += blk) {
-        const bool in32 = acc32 && b0 > 0, out32 = acc32 && b0 + 2 * blk <= n_lwe;
-        PZ_TRY(launch_permute_pmat(M, brk + (size_t)b0 * pmat_doubles, Pp, blk * nrows_key * ncols_key));
-        if (in32 && acc16) PZ_TRY(launch_fwd_pass1_t16(M, B * npi, (const short*)D, sm, T));
-        else PZ_TRY(launch_fwd_pass1(M, B * npi, in32 ? (const long long*)D : (const long long*)res, sm, T, true, -1, in32));
-        MidBr mb{(const long long*)lwe_2n, lwe_bs, b0, blk};
-        PZ_TRY(launch_mid(M, B, T, T2, Pp, npi, npo, nrows_key, ncols_key, mid_dummy, 0, 0, nullptr, &mb));
-        TailCall tc = acc_tail(B, T2, true, bsz, cols, res, res_ct, rsz, k);
-        if (in32) tc.small = (const long long*)D;
-        if (out32) tc.res = (long long*)D;
-        tc.acc32 = acc16 ? ((in32 ? 8 : 0) | (out32 ? 16 : 0)) : ((in32 ? 1 : 0) | (out32 ? 2 : 0));
+    for (int b0 = 0; b0 + c.blk <= c.n_lwe; b0 += c.blk) {
+        // the operand: `res` in the first block, the narrow digits afterwards; the destination: the narrow digits while blocks follow
+        const Digits in = b0 > 0 ? held : Digits::I64, out = b0 + 2 * c.blk <= c.n_lwe ? held : Digits::I64;
+        const long long* src = in != Digits::I64 ? (const long long*)D : (const long long*)c.res;
+        PZ_TRY(launch_permute_pmat(M, c.brk + (size_t)b0 * c.pmat_doubles, Pp, c.blk * nrows_key * ncols_key));
+        if (in == Digits::I16) PZ_TRY(launch_fwd_pass1_t16(M, c.B * npi, (const short*)D, sm, T));
+        else PZ_TRY(launch_fwd_pass1(M, c.B * npi, src, sm, T, true, -1, in));
+        MidBr mb{(const long long*)c.lwe_2n, c.lwe_bs, b0, c.blk};
+        mc.br = &mb;
+        PZ_TRY(launch_mid(M, c.B, mc));
+        TailCall tc = acc_tail(c.B, T2, true, c.bsz, c.cols, c.res, c.res_ct, c.rsz, c.k);
+        tc.small = src; tc.small_digits = in;
+        if (out != Digits::I64) tc.res = (long long*)D;
+        tc.res_digits = out;
         PZ_TRY(launch_inv_tail(M, tc));
     }
     return PZ_OK;
@@ -125,61 +132,63 @@ static int br_pipeline_path(const BrCall& c, bool* taken) {
 // standard spectrum order | the block step on the standard keys | whole inverse transform + accumulator + carry chain per (ciphertext, column) -
 // instead of pass 1 / pass 2 and pass 2 / tail.  *taken = false: the shape is not covered
 static int br_small_ring_path(const BrCall& c, bool* taken) {
-    PZ_BR_UNPACK(c)
+    pz_module* const M = c.M;
     *taken = false;
-    const int npi = cols * std::min(dnum, rsz), nrows_key = dnum * cols, ncols_key = cols * bsz;
-    if (!(M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, bsz) && npi == nrows_key && npi <= 12 && blk <= 64))
+    const int npi = c.cols * std::min(c.dnum, c.rsz), nrows_key = c.dnum * c.cols, ncols_key = c.cols * c.bsz;
+    if (!(M->small_path && M->fuse_mid && M->fuse_tail && small_supported(M, npi, c.bsz) && npi == nrows_key && npi <= 12 && c.blk <= 64))
         return PZ_OK;
     *taken = true;
-    const size_t s_bytes = align256(batch * npi * (size_t)M->m * sizeof(cplx)), a_bytes = align256(batch * ncols_key * (size_t)M->m * sizeof(cplx));
+    const size_t s_bytes = align256(c.batch * npi * (size_t)M->m * sizeof(cplx)), a_bytes = align256(c.batch * ncols_key * (size_t)M->m * sizeof(cplx));
     // between two blocks the accumulator holds normalized digits: kept as 32-bit values in the workspace (base2k <= 31), read and
     // written by the inverse kernel at half the bytes; the caller's `res` receives the i64 limbs from the last block
-    const int nblocks = n_lwe / blk;
-    const bool acc32 = k <= 31 && nblocks >= 2;
-    const size_t d_bytes = acc32 ? align256((size_t)B * res_ct * sizeof(int)) : 0;
+    const int nblocks = c.n_lwe / c.blk;
+    const bool narrow = c.k <= 31 && nblocks >= 2;
+    const size_t d_bytes = narrow ? align256((size_t)c.B * c.res_ct * sizeof(int)) : 0;
     PZ_TRY(ws_reserve(M, s_bytes + a_bytes + d_bytes));
     char* base = (char*)M->ws;
     cplx* S; cplx* A; int* D = nullptr;
     PZ_TRY(ws_take(M, base, s_bytes, &S));
     PZ_TRY(ws_take(M, base, a_bytes, &A));
-    if (acc32) PZ_TRY(ws_take(M, base, d_bytes, &D));
-    PolyMap sm{npi / cols, cols, res_ct, (long long)cols * n, n, 0};
+    if (narrow) PZ_TRY(ws_take(M, base, d_bytes, &D));
+    PolyMap sm{npi / c.cols, c.cols, c.res_ct, (long long)c.cols * c.n, c.n, 0};
     // the inverse kernel of a block also runs the forward transform of the new accumulator for the next block, when its limbs are among the
     // ones the inverse produces
-    const int fl = npi / cols;
-    const bool chain = fl <= bsz && fl <= rsz && M->n < 4096;   // (N = 4096 - block sizes the pipeline path declines - has no chained form)
+    const int fl = npi / c.cols;
+    const bool chain = fl <= c.bsz && fl <= c.rsz && M->n < 4096;   // (N = 4096 - block sizes the pipeline path declines - has no chained form)
     // Two halves of the batch on two streams (round 5): the block step is bound by FP64 issue, the inverse / forward kernel around it by
     // HBM and LDS latency - issued back to back on one stream each leaves the other's unit idle; as two independent chains the step of one
     // half overlaps with the transforms of the other (split at a tile boundary of the block step: 8 ciphertexts)
     // (measured, profiles/r05_ab_br_two_streams*.txt: N = 2048 at 1024 / 512 / 256 per call +5.5 % / +10 % / -16 %; rank 2 at N = 1024:
     //  1024 per call +1 %, 512 -4 % - a half must still fill the chip: >= 2^19 coefficients per column)
-    const int hA = ((long long)(B / 2) * n >= (1ll << 19) && !M->timing) ? ((B / 2 + 7) / 8) * 8 : B;
+    const int hA = ((long long)(c.B / 2) * c.n >= (1ll << 19) && !M->timing) ? ((c.B / 2 + 7) / 8) * 8 : c.B;
     SideStream ss(M);
-    if (hA < B) PZ_TRY(ss.fork());
-    for (int b0 = 0; b0 + blk <= n_lwe; b0 += blk) {
-        const bool more = b0 + 2 * blk <= n_lwe;
+    if (hA < c.B) PZ_TRY(ss.fork());
+    for (int b0 = 0; b0 + c.blk <= c.n_lwe; b0 += c.blk) {
+        const bool more = b0 + 2 * c.blk <= c.n_lwe;
         // operand: `res` in the first block, the 32-bit digits afterwards; destination: the 32-bit digits while blocks follow
         // (the separate forward launch of the unchained form reads `res`: i64 throughout there)
-        const bool use32 = acc32 && chain;
-        const bool in32 = use32 && b0 > 0, out32 = use32 && more;
         // (round 6: 16-bit digits - natural order here, the small-ring kernels read whole rows - where base2k <= 15)
-        const bool use16 = use32 && k <= 15;
-        for (int half = 0; half < (hA < B ? 2 : 1); ++half) {
-            const int c0 = half ? hA : 0, nb = half ? B - hA : hA;
+        const Digits held = !(narrow && chain) ? Digits::I64 : c.k <= 15 ? Digits::I16 : Digits::I32;
+        const Digits in = b0 > 0 ? held : Digits::I64, out = more ? held : Digits::I64;
+        for (int half = 0; half < (hA < c.B ? 2 : 1); ++half) {
+            const int c0 = half ? hA : 0, nb = half ? c.B - hA : hA;
             ss.on(half == 1);
-            int64_t* res_h = res + (long long)c0 * res_ct;
-            int* D_h = D ? D + (long long)c0 * res_ct : nullptr;
+            int64_t* res_h = c.res + (long long)c0 * c.res_ct;
+            int* D_h = D ? D + (long long)c0 * c.res_ct : nullptr;
             cplx* S_h = S + (size_t)c0 * npi * M->m;
             cplx* A_h = A + (size_t)c0 * ncols_key * M->m;
             if (b0 == 0 || !chain) PZ_TRY(launch_small_fwd(M, nb * npi, (const long long*)res_h, sm, S_h, true));
             bool done = false;
-            PZ_TRY(br_block_step(M, (const double*)S_h, (long long)npi * n, (double*)A_h, (long long)ncols_key * n, brk, pmat_doubles, npi, ncols_key,
-                                 nb, b0, blk, lwe_2n + (long long)c0 * lwe_bs, lwe_bs, &done));
+            PZ_TRY(br_block_step(M, (const double*)S_h, (long long)npi * c.n, (double*)A_h, (long long)ncols_key * c.n, c.brk, c.pmat_doubles, npi, ncols_key,
+                                 nb, b0, c.blk, c.lwe_2n + (long long)c0 * c.lwe_bs, c.lwe_bs, &done));
             if (!done) return fail(PZ_ERR_UNSUPPORTED, "blind_rotation: block step not launched");
-            PZ_TRY(launch_small_inv(M, nb, A_h, nullptr, ncols_key, 0, 0, cols, bsz, out32 ? (long long*)D_h : (long long*)res_h, res_ct, cols, rsz,
-                                    in32 ? (const long long*)D_h : (const long long*)res_h, res_ct, cols, rsz, k, -1, true,
-                                    (chain && more) ? S_h : nullptr, fl, false, 0, 0, false,
-                                    use16 ? ((in32 ? 4 : 0) | (out32 ? 8 : 0)) : ((in32 ? 1 : 0) | (out32 ? 2 : 0))));
+            SmallInvCall sc = acc_small_inv(A_h, ncols_key, c.cols, c.bsz, res_h, c.res_ct, c.rsz, c.k);
+            if (out != Digits::I64) sc.res.p = (long long*)D_h;
+            if (in != Digits::I64) sc.small.p = (const long long*)D_h;
+            sc.small_digits = in; sc.res_digits = out;
+            if (chain && more) sc.fwd_S = S_h;
+            sc.fwd_limbs = fl;
+            PZ_TRY(launch_small_inv(M, nb, sc));
         }
     }
     return ss.join();
@@ -187,11 +196,11 @@ static int br_small_ring_path(const BrCall& c, bool* taken) {
 
 // every other block-binary shape: per-op transforms around the fused block step (or, without it, the reference's own op sequence)
 static int br_composed_path(const BrCall& c) {
-    PZ_BR_UNPACK(c)
-    DV rv{res, res_ct, cols, rsz};
-    const size_t acc_dft_bytes = align256(batch * n8 * cols * dnum), vr_bytes = align256(batch * n8 * cols * bsz);
-    const size_t tp = (size_t)cols * std::max({dnum, bsz, rsz});
-    const size_t t_bytes = align256(batch * tp * (size_t)M->m * sizeof(cplx));
+    pz_module* const M = c.M;
+    DV rv{c.res, c.res_ct, c.cols, c.rsz};
+    const size_t acc_dft_bytes = align256(c.batch * c.n8 * c.cols * c.dnum), vr_bytes = align256(c.batch * c.n8 * c.cols * c.bsz);
+    const size_t tp = (size_t)c.cols * std::max({c.dnum, c.bsz, c.rsz});
+    const size_t t_bytes = align256(c.batch * tp * (size_t)M->m * sizeof(cplx));
     PZ_TRY(ws_reserve(M, acc_dft_bytes + 2 * vr_bytes + t_bytes));
     char* base = (char*)M->ws;
     double* acc_dft; double* vmp_res; double* acc_add; cplx* T;
@@ -199,32 +208,32 @@ static int br_composed_path(const BrCall& c) {
     PZ_TRY(ws_take(M, base, vr_bytes, &vmp_res));
     PZ_TRY(ws_take(M, base, vr_bytes, &acc_add));
     PZ_TRY(ws_take(M, base, t_bytes, &T));
-    DV ad{acc_dft, n * cols * dnum, cols, dnum}, vr{vmp_res, n * cols * bsz, cols, bsz}, aa{acc_add, n * cols * bsz, cols, bsz};
+    DV ad{acc_dft, c.n * c.cols * c.dnum, c.cols, c.dnum}, vr{vmp_res, c.n * c.cols * c.bsz, c.cols, c.bsz}, aa{acc_add, c.n * c.cols * c.bsz, c.cols, c.bsz};
     const bool tail = M->fuse_tail && tail_supported(M);
-    for (int b0 = 0; b0 + blk <= n_lwe; b0 += blk) {  // chunks_exact: a trailing partial block is ignored, as in the reference
-        PZ_TRY(dev_dft_apply(M, B, 1, 0, ad, 0, rv, 0, cols, nullptr, T));                      // :319-321
-        const int row_max = std::min(dnum * cols, cols * std::min(dnum, rsz));
+    for (int b0 = 0; b0 + c.blk <= c.n_lwe; b0 += c.blk) {  // chunks_exact: a trailing partial block is ignored, as in the reference
+        PZ_TRY(dev_dft_apply(M, c.B, 1, 0, ad, 0, rv, 0, c.cols, nullptr, T));                      // :319-321
+        const int row_max = std::min(c.dnum * c.cols, c.cols * std::min(c.dnum, c.rsz));
         bool block_done = false;
-        if (M->fuse_mid) PZ_TRY(br_block_step(M, acc_dft, ad.bs, acc_add, aa.bs, brk, pmat_doubles, row_max, cols * bsz, B, b0, blk, lwe_2n, lwe_bs, &block_done));
+        if (M->fuse_mid) PZ_TRY(br_block_step(M, acc_dft, ad.bs, acc_add, aa.bs, c.brk, c.pmat_doubles, row_max, c.cols * c.bsz, c.B, b0, c.blk, c.lwe_2n, c.lwe_bs, &block_done));
         if (!block_done) {
-        PZ_TRY(launch_zero_bytes(M, acc_add, (size_t)B * aa.bs * 8));                     // :321
-        for (int i = b0; i < b0 + blk; ++i) {                                                       // :324-337
-            PZ_TRY(dev_vmp(M, B, vr, ad, brk + (size_t)i * pmat_doubles, dnum, cols, cols, bsz, 0));
-            PZ_TRY(launch_xai_acc(M, acc_add, aa.bs, vmp_res, vr.bs, cols * bsz, B, lwe_2n, lwe_bs, i));
+        PZ_TRY(launch_zero_bytes(M, acc_add, (size_t)c.B * aa.bs * 8));                     // :321
+        for (int i = b0; i < b0 + c.blk; ++i) {                                                       // :324-337
+            PZ_TRY(dev_vmp(M, c.B, vr, ad, c.brk + (size_t)i * c.pmat_doubles, c.dnum, c.cols, c.cols, c.bsz, 0));
+            PZ_TRY(launch_xai_acc(M, acc_add, aa.bs, vmp_res, vr.bs, c.cols * c.bsz, c.B, c.lwe_2n, c.lwe_bs, i));
         }
         }
         // acc = normalize(idft(acc_add) + acc)  (:342-346)
         if (tail) {
-            PolyMap sm{bsz, cols, aa.bs, (long long)cols * n, n, 0};
-            PZ_TRY(launch_inv_pass2(M, B * bsz * cols, acc_add, sm, T));
-            PZ_TRY(launch_inv_tail(M, acc_tail(B, T, false, bsz, cols, res, res_ct, rsz, k)));
+            PolyMap sm{c.bsz, c.cols, aa.bs, (long long)c.cols * c.n, c.n, 0};
+            PZ_TRY(launch_inv_pass2(M, c.B * c.bsz * c.cols, acc_add, sm, T));
+            PZ_TRY(launch_inv_tail(M, acc_tail(c.B, T, false, c.bsz, c.cols, c.res, c.res_ct, c.rsz, c.k)));
         } else {
-            PZ_TRY(dev_idft(M, B, aa, 0, aa, 0, cols, bsz, T));
-            for (int c = 0; c < cols; ++c) {
-                PZ_TRY(launch_ew(M, EW_ADD_I64, (int64_t*)acc_add + (long long)c * n, aa.bs, (long long)cols * n,
-                                 (int64_t*)acc_add + (long long)c * n, aa.bs, (long long)cols * n, res + (long long)c * n, res_ct,
-                                 (long long)cols * n, std::min(bsz, rsz), B));
-                PZ_TRY(dev_normalize(M, B, rv, k, 0, c, aa, k, c));
+            PZ_TRY(dev_idft(M, c.B, aa, 0, aa, 0, c.cols, c.bsz, T));
+            for (int col = 0; col < c.cols; ++col) {
+                PZ_TRY(launch_ew(M, EW_ADD_I64, (int64_t*)acc_add + (long long)col * c.n, aa.bs, (long long)c.cols * c.n,
+                                 (int64_t*)acc_add + (long long)col * c.n, aa.bs, (long long)c.cols * c.n, c.res + (long long)col * c.n, c.res_ct,
+                                 (long long)c.cols * c.n, std::min(c.bsz, c.rsz), c.B));
+                PZ_TRY(dev_normalize(M, c.B, rv, c.k, 0, col, aa, c.k, col));
             }
         }
     }
@@ -233,24 +242,24 @@ static int br_composed_path(const BrCall& c) {
 
 // execute_standard (block size 1): acc += (X^a_i - 1) * (acc (x) BRK_i) per coefficient, one normalization at the end (:423-437)
 static int br_standard_path(const BrCall& c) {
-    PZ_BR_UNPACK(c)
-    DV rv{res, res_ct, cols, rsz};
+    pz_module* const M = c.M;
+    DV rv{c.res, c.res_ct, c.cols, c.rsz};
     pz_glwe_op_params ep;
-    ep.rank = p->rank; ep.dnum = p->dnum; ep.dsize = 1; ep.key_size = p->brk_size; ep.key_base2k = p->base2k;
-    ep.a_size = p->res_size; ep.a_base2k = p->base2k; ep.res_size = p->res_size; ep.res_base2k = p->base2k; ep.rank_out = p->rank;
+    ep.rank = c.p->rank; ep.dnum = c.p->dnum; ep.dsize = 1; ep.key_size = c.p->brk_size; ep.key_base2k = c.p->base2k;
+    ep.a_size = c.p->res_size; ep.a_base2k = c.p->base2k; ep.res_size = c.p->res_size; ep.res_base2k = c.p->base2k; ep.rank_out = c.p->rank;
     // acc_tmp lives in the module's second workspace: the external product owns the first one
-    PZ_TRY(ws2_reserve(M, (size_t)B * res_ct * 8));
+    PZ_TRY(ws2_reserve(M, (size_t)c.B * c.res_ct * 8));
     int64_t* acc_tmp = (int64_t*)M->ws2;
-    PolyMap pm{rsz, cols, res_ct, (long long)cols * n, n, 0};
-    for (int i = 0; i < n_lwe; ++i) {
-        PZ_TRY(glwe_op(M, false, acc_tmp, res, brk + (size_t)i * pmat_doubles, &ep, batch));
-        PZ_TRY(launch_rotate(M, B * rsz * cols, (const long long*)acc_tmp, pm, (long long*)res, pm, 2, rsz * cols, (const long long*)lwe_2n,
-                             lwe_bs, 1 + i, 0));
+    PolyMap pm{c.rsz, c.cols, c.res_ct, (long long)c.cols * c.n, c.n, 0};
+    for (int i = 0; i < c.n_lwe; ++i) {
+        PZ_TRY(glwe_op(M, GlweKind::ExternalProduct, acc_tmp, c.res, c.brk + (size_t)i * c.pmat_doubles, &ep, c.batch));
+        PZ_TRY(launch_rotate(M, c.B * c.rsz * c.cols, (const long long*)acc_tmp, pm, (long long*)c.res, pm, 2, c.rsz * c.cols, (const long long*)c.lwe_2n,
+                             c.lwe_bs, 1 + i, 0));
     }
     // vec_znx_normalize_assign (normalize.rs:403-425) == out-of-place same-base normalize of a copy
-    PZ_TRY(launch_ew(M, EW_COPY, acc_tmp, res_ct, n, res, res_ct, n, nullptr, 0, 0, cols * rsz, B));   // (a kernel node, not a memcpy node: see launch_zero_bytes)
-    DV tv{acc_tmp, res_ct, cols, rsz};
-    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, k, 0, c, tv, k, c));
+    PZ_TRY(launch_ew(M, EW_COPY, acc_tmp, c.res_ct, c.n, c.res, c.res_ct, c.n, nullptr, 0, 0, c.cols * c.rsz, c.B));   // (a kernel node, not a memcpy node: see launch_zero_bytes)
+    DV tv{acc_tmp, c.res_ct, c.cols, c.rsz};
+    for (int col = 0; col < c.cols; ++col) PZ_TRY(dev_normalize(M, c.B, rv, c.k, 0, col, tv, c.k, col));
     return PZ_OK;
 }
 
@@ -342,8 +351,7 @@ static int blind_rotation_extended(pz_module* M, int64_t* res, const int64_t* lw
             PZ_TRY(launch_xai_ext(M, acc_add, vmp_res, cols * bsz, log_ext, B, lwe_2n, lwe_bs, i));
         }
         if (small_tf) {
-            PZ_TRY(launch_small_inv(M, BE, (const cplx*)acc_add, nullptr, cols * bsz, 0, 0, cols, bsz, (long long*)acc, res_ct, cols, rsz,
-                                    (const long long*)acc, res_ct, cols, rsz, k, -1, true));
+            PZ_TRY(launch_small_inv(M, BE, acc_small_inv((const cplx*)acc_add, cols * bsz, cols, bsz, acc, res_ct, rsz, k)));
         } else if (tail) {                                                                             // :260-266
             PolyMap sm{bsz, cols, aa.bs, (long long)cols * n, n, 0};
             PZ_TRY(launch_inv_pass2(M, BE * bsz * cols, acc_add, sm, T));
@@ -435,8 +443,7 @@ static int cbt_repack_rows(pz_module* M, int64_t* tr, const int64_t** row_src, s
     for (size_t sidx = 0; sidx < steps; ++sidx) {
         cts[sidx] = (int64_t*)(base + sidx * rows_ct);
         idx[sidx] = (uint64_t)(sidx << rp->log_gap_out);
-        PZ_TRY(launch_rotate(M, count * tsz * cols, (const long long*)tr, pm, (long long*)cts[sidx], pm, 0, tsz * cols, nullptr, 0, 0,
-                             -(long long)(sidx << rp->log_gap_in)));
+        PZ_TRY(launch_rotate(M, count * tsz * cols, (const long long*)tr, pm, (long long*)cts[sidx], pm, -(long long)(sidx << rp->log_gap_in)));
     }
     int64_t* packed = (int64_t*)(base + steps * rows_ct);
     void* pack_tmp = (void*)(base + (steps + 1) * rows_ct);
@@ -488,8 +495,7 @@ static int circuit_bootstrapping(pz_module* M, int64_t* ggsw, const int64_t* lwe
     for (int i = 0; i < rows; ++i) {
         PolyMap sm{gsz, cols, ct_g, (long long)cols * n, n, 0};
         PolyMap dm{gsz, cols, (long long)rows * ct_t, (long long)cols * n, n, (long long)i * ct_t};
-        PZ_TRY(launch_rotate(M, B * gsz * cols, (const long long*)acc, sm, (long long*)tr, dm, 0, gsz * cols, nullptr, 0, 0,
-                             -(long long)i * (long long)p->gap));
+        PZ_TRY(launch_rotate(M, B * gsz * cols, (const long long*)acc, sm, (long long*)tr, dm, -(long long)i * (long long)p->gap));
     }
     pz_glwe_op_params tp;
     tp.rank = p->br.rank; tp.dnum = p->atk_dnum; tp.dsize = 1; tp.key_size = p->atk_size; tp.key_base2k = (uint64_t)k_atk;
@@ -581,7 +587,7 @@ struct PackStep {
     int64_t *tmp_b, *t1, *t2;
     PolyMap pm() const { return PolyMap{size, cols, ct, (long long)cols * n, n, 0}; }
     int rotate_to(long long kk, int64_t* dst, const int64_t* src) {
-        return launch_rotate(M, B * size * cols, (const long long*)src, pm(), (long long*)dst, pm(), 0, size * cols, nullptr, 0, 0, kk);
+        return launch_rotate(M, B * size * cols, (const long long*)src, pm(), (long long*)dst, pm(), kk);
     }
     int rotate_assign(long long kk, int64_t* x) {
         PZ_TRY(rotate_to(kk, t1, x));
@@ -608,7 +614,7 @@ struct PackStep {
             PZ_TRY(rsh1(a));
             PZ_TRY(normalize_assign(tmp_b));
             AutoSpec au{(long long)gal, 0};
-            PZ_TRY(glwe_op(M, true, tmp_b, tmp_b, key, p, batch, &au));
+            PZ_TRY(glwe_op(M, GlweKind::Automorphism, tmp_b, tmp_b, key, p, batch, &au));
             PZ_TRY(ew3(EW_SUB_I64, a, a, tmp_b));
             PZ_TRY(normalize_assign(a));
             PZ_TRY(rotate_assign((long long)tt, a));
@@ -616,13 +622,13 @@ struct PackStep {
         } else if (a) {                                                     // :71-75
             PZ_TRY(rsh1(a));
             AutoSpec au{(long long)gal, 1};
-            PZ_TRY(glwe_op(M, true, a, a, key, p, batch, &au));
+            PZ_TRY(glwe_op(M, GlweKind::Automorphism, a, a, key, p, batch, &au));
             *out = a;
         } else if (b) {                                                     // :76-86
             PZ_TRY(rotate_to((long long)tt, tmp_b, b));
             PZ_TRY(rsh1(tmp_b));
             AutoSpec au{(long long)gal, 3};
-            PZ_TRY(glwe_op(M, true, b, tmp_b, key, p, batch, &au));
+            PZ_TRY(glwe_op(M, GlweKind::Automorphism, b, tmp_b, key, p, batch, &au));
             *out = b;
         }
         return PZ_OK;

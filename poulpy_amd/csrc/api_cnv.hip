@@ -214,6 +214,7 @@ struct TensorWave {
     int64_t* rb = nullptr;
     bool fused = false, all3 = false;
     cplx *ta_main = nullptr, *ta_last = nullptr, *tb_main = nullptr, *tb_last = nullptr;
+    MidCnvCall mid;   // the fused row pass of this wave: operands, the product window (prepare)
 
     int take_workspace(size_t chunk) {
         const size_t s_pa = align256(chunk * t.prep_a), s_pb = square ? 0 : align256(chunk * t.prep_b), s_rd = align256(chunk * t.res_dft);
@@ -269,8 +270,9 @@ struct TensorWave {
             if (!square) PZ_TRY(dev_cnv_prepare(M, nb, pb, pb_bs, t.cols, t.b_size, bb, b_ct, t.cols, t.b_size, b_mask, T));
         }
         const int ms_all = std::min(t.dft_size, bound), off_all = std::min(t.hi, bound);
+        mid = MidCnvCall{ta_main, ta_last, tb_main, tb_last, T, t.cols, t.a_size, t.b_size, ms_all, off_all};
         all3 = fused && mid_cnv3_supported(M, t.cols, t.a_size, t.b_size, ms_all);
-        if (all3) PZ_TRY(launch_mid_cnv3(M, nb, ta_main, ta_last, tb_main, tb_last, T, t.a_size, ms_all, off_all));
+        if (all3) PZ_TRY(launch_mid_cnv3(M, nb, mid));
         return PZ_OK;
     }
     // one product term (i, j): convolution -> inverse transform in place -> normalize(res_base2k, cnv_offset_lo) into `dst` column dcol
@@ -280,10 +282,12 @@ struct TensorWave {
         if (fused) {
             const cplx* Tt = T;
             if (all3) Tt = T + (size_t)(i == j ? i : 2) * nb * min_size * (size_t)M->m;
-            else PZ_TRY(launch_mid_cnv(M, nb, ta_main, ta_last, tb_main, tb_last, T, t.cols, t.a_size, t.b_size, i, i == j ? -1 : j, i, i == j ? -1 : j,
-                                       min_size, off));
+            else {
+                mid.col_i = i; mid.col_j = i == j ? -1 : j;
+                PZ_TRY(launch_mid_cnv(M, nb, mid));
+            }
             // the inverse column pass normalizes on its way out (bit offset, combination and all: TailArgs::nz)
-            return launch_inv_tail_nz(M, nb, Tt, min_size, (long long*)dst, dst_bs, dst_cols, t.res_size, dcol, (int)p->res_base2k, t.lo, t.dft_size, cb, d16s);
+            return launch_inv_tail_nz(M, nb, NzTailCall{Tt, min_size, (long long*)dst, dst_bs, dst_cols, t.res_size, dcol, (int)p->res_base2k, t.lo, t.dft_size, cb, d16s});
         }
         PZ_TRY(launch_cnv_apply(M, nb, rd, rd_bs, 1, 0, min_size, off, pa, pa_bs, t.a_size, i, i == j ? -1 : j, pb, pb_bs, t.b_size, i, i == j ? -1 : j));
         if (t.dft_size > min_size)
@@ -468,7 +472,7 @@ int pz_glwe_tensor_mul_relinearize_batched(pz_module* M, int64_t* res, const int
         if (!compact) {
             // (not through the public entry points: the module lock is held)
             PZ_TRY(tensor_apply_nolock(M, (int64_t*)M->ws2, a + (long long)b0 * a_ct, b + (long long)b0 * b_ct, tp, mode, nb));
-            PZ_TRY(glwe_op(M, true, r0, (const int64_t*)M->ws2, tsk_pmat, rp, nb, nullptr, nullptr, true));
+            PZ_TRY(glwe_op(M, GlweKind::TensorRelin, r0, (const int64_t*)M->ws2, tsk_pmat, rp, nb));
             continue;
         }
         PZ_TRY(w.take_workspace(nb));
@@ -601,7 +605,7 @@ int pz_vec_znx_rotate_batched(pz_module* M, size_t batch, int64_t k, int64_t* re
     if (mn > 0 && batch > 0) {
         PolyMap sm{mn, 1, av.bs, (long long)a_cols * n, 0, n * (long long)a_col};
         PolyMap dm{mn, 1, r.bs, (long long)res_cols * n, 0, n * (long long)res_col};
-        PZ_TRY(launch_rotate(M, (int)batch * mn, (const long long*)a, sm, (long long*)res, dm, 0, mn, nullptr, 0, 0, (long long)k));
+        PZ_TRY(launch_rotate(M, (int)batch * mn, (const long long*)a, sm, (long long*)res, dm, (long long)k));
     }
     return ewb(M, EW_ZERO, (int)batch, r, (int)res_col, mn, nullptr, 0, 0, nullptr, 0, 0, (int)res_size - mn);
 }

@@ -82,8 +82,7 @@ int run_combine(pz_module* M, int64_t* res, long long res_bs, long long res_ls, 
     const long long threads = (long long)batch * cols * (M->n / 2);
     const size_t lds = staged >= 0 ? (size_t)g.t[staged].size * kCombBlock * sizeof(ulonglong2) : 0;
     KTimer kt(M, PZ_K_NORMALIZE);
-    PZ_TRY(set_lds(k_glwe_combine, lds));
-    hipLaunchKernelGGL(k_glwe_combine, dim3((unsigned)((threads + kCombBlock - 1) / kCombBlock)), dim3(kCombBlock), lds, M->stream, g);
+    PZ_TRY(launch_k(k_glwe_combine, dim3((unsigned)((threads + kCombBlock - 1) / kCombBlock)), dim3(kCombBlock), lds, M->stream, g));
     dispatch_note(M, "k_glwe_combine (%d terms, %d cols, %d limbs, normalize %d, lds=%zu)", nterms, cols, res_size, normalize, lds);
     PZ_HIP(hipGetLastError());
     return PZ_OK;

@@ -60,12 +60,14 @@ struct OpShape {
     int a_size_eff;                 // limbs of `a` in the key's base (after optional conversion)
     bool convert;
 };
-// kind: 0 external product, 1 key switch (mask columns 1.. of a GLWE), 2 tensor relinearization (operations/glwe.rs:541-607: `a` is
+// external product; key switch / automorphism (mask columns 1.. of a GLWE); tensor relinearization (operations/glwe.rs:541-607: `a` is
 // a GLWETensor of cols + pairs columns, the pairs = rank (rank + 1) / 2 columns behind the first cols = rank + 1 are key-switched
 // and the first cols are added to every column of the big value)
-static OpShape op_shape(const pz_glwe_op_params* p, bool ks, bool tensor = false) {
+static inline bool kind_ks(GlweKind k) { return k != GlweKind::ExternalProduct; }   // the product is gglwe_product_dft, as for a key switch
+static OpShape op_shape(const pz_glwe_op_params* p, GlweKind kind) {
     OpShape s;
-    if (tensor) {
+    const bool ks = kind_ks(kind);
+    if (kind == GlweKind::TensorRelin) {
         const int cols = (int)p->rank + 1, pairs = (int)(p->rank * (p->rank + 1) / 2);
         s.cols_a = cols + pairs; s.cols_in = pairs; s.cols_out = cols; s.a_col0 = cols;
         s.convert = p->a_base2k != p->key_base2k;
@@ -84,8 +86,9 @@ static OpShape op_shape(const pz_glwe_op_params* p, bool ks, bool tensor = false
 struct OpWs {
     size_t a_conv, a_dft, res_dft, tmp_dft, T, res_tmp, total;
 };
-static OpWs op_ws(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, size_t chunk, bool ks, bool au = false) {
+static OpWs op_ws(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, size_t chunk, GlweKind kind) {
     OpWs w;
+    const bool ks = kind_ks(kind), au = kind == GlweKind::Automorphism;
     const size_t n8 = (size_t)M->n * 8;
     const size_t dsz = p->dsize;
     w.a_conv = s.convert ? align256(chunk * n8 * s.cols_a * s.a_size_eff) : 0;
@@ -110,7 +113,8 @@ static size_t pick_chunk(const pz_module* M, const pz_glwe_op_params* p, const O
 }
 
 // which pipeline glwe_op takes for a shape, and what it reserves there (one definition for the call and for the workspace query)
-static bool fused_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, bool tensor, bool au) {
+static bool fused_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind) {
+    const bool tensor = kind == GlweKind::TensorRelin, au = kind == GlweKind::Automorphism;
     const int npi = s.cols_in * s.a_size_eff, npo = s.cols_out * (int)p->key_size;
     const bool digits = p->dsize > 1, cross_out = p->res_base2k != p->key_base2k;
     return M->fuse_mid && M->fuse_tail && tail_supported(M) && mid_supported(M, npi, npo) && !(tensor && s.convert) &&
@@ -146,7 +150,8 @@ static FusedWs fused_ws(const pz_module* M, const pz_glwe_op_params* p, const Op
 }
 // N = 1024 / 2048: the two-kernel pipeline of device_small.hpp (plain products, key switches and the automorphism family; dsize 1, one
 // base2k, <= 4 key limbs); `packed` = no OpLayout (the automorphism family needs it)
-static bool small_ring_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, bool ks, bool tensor, bool au, bool packed) {
+static bool small_ring_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind, bool packed) {
+    const bool ks = kind_ks(kind), tensor = kind == GlweKind::TensorRelin, au = kind == GlweKind::Automorphism;
     const bool cross_out = p->res_base2k != p->key_base2k;   // (with an automorphism: phi and the cross-base pass do not commute)
     return M->small_path && M->fuse_mid && M->fuse_tail && M->n < 4096 && (!au || (ks && packed && !cross_out)) &&
            !tensor && p->dsize == 1 && M->dbg_stages == 7 && small_supported(M, s.cols_in * s.a_size_eff, (int)p->key_size);
@@ -170,7 +175,8 @@ struct GlweCall {
     pz_module* M;
     const pz_glwe_op_params* p;
     OpShape s;
-    bool ks, tensor;
+    GlweKind kind;
+    bool ks, tensor;       // kind != ExternalProduct, kind == TensorRelin
     const AutoSpec* au;
     const OpLayout* lay;
     int64_t* res; const int64_t* a; const double* pmat;
@@ -200,13 +206,14 @@ extern "C" {
 // costs its row-sliced copy, which is included.
 size_t pz_glwe_op_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch, int keyswitch) {
     if (!M || !p || p->key_size == 0 || p->a_size == 0) return 0;
-    const bool tensor = keyswitch == 3, ks = keyswitch != 0, au = keyswitch == 2;
-    const OpShape s = op_shape(p, ks, tensor);
+    if (keyswitch < 0 || keyswitch > 3) return 0;
+    const GlweKind kind = (GlweKind)keyswitch;
+    const OpShape s = op_shape(p, kind);
     const size_t chunk = pick_chunk(M, p, s, batch);
     size_t bytes;
-    if (fused_applies(M, p, s, tensor, au)) bytes = fused_ws(M, p, s, chunk, au).total;
-    else if (small_ring_applies(M, p, s, ks, tensor, au, true)) bytes = small_ws(M, p, s, chunk).total;
-    else bytes = op_ws(M, p, s, chunk, ks, au).total;
+    if (fused_applies(M, p, s, kind)) bytes = fused_ws(M, p, s, chunk, kind == GlweKind::Automorphism).total;
+    else if (small_ring_applies(M, p, s, kind, true)) bytes = small_ws(M, p, s, chunk).total;
+    else bytes = op_ws(M, p, s, chunk, kind).total;
     return bytes + (bytes >> 3);
 }
 }
@@ -247,6 +254,18 @@ static TailCall wave_tail(const GlweCall& c, int nb, const cplx* T2, size_t b0) 
 }
 static void tail_operand(TailCall& t, const DV& av, bool every_column) {
     t.small = (const long long*)av.p; t.small_bs = av.bs; t.small_cols = av.cols; t.small_size = av.size; t.small_all = every_column;
+}
+// the same for a wave on the small-ring kernels: the key and shape, the result at its defaults (res, in its own base), the key switch's operand
+static SmallKey small_key(const GlweCall& c, const cplx* Pp) { return SmallKey{Pp, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz}; }
+static SmallRes small_res(const GlweCall& c, size_t b0) {
+    return SmallRes{(long long*)c.res_at(b0), c.res_bs, c.s.cols_out, (int)c.p->res_size, (int)c.p->res_base2k};
+}
+static SmallOperand small_operand(const GlweCall& c, const DV& av) {
+    return SmallOperand{c.ks ? (const long long*)av.p : nullptr, av.bs, c.s.cols_a, av.size, c.body_col};
+}
+// ... and the automorphism form of the inverse kernel, with glwe_trace's shifted store where asked for
+static void small_inv_auto(SmallInvCall& sc, const GlweCall& c, bool rsh) {
+    sc.au = c.au != nullptr; sc.au_p = c.au_p; sc.au_mode = c.au ? c.au->mode : 0; sc.post_rsh = rsh;
 }
 
 // dsize > 1 (external_product/glwe.rs:235-267, keyswitching/glwe.rs:332-379) as a table for the middle kernel: limb l of `a` is digit
@@ -313,9 +332,10 @@ static bool n4096_two_kernel(const GlweCall& c) {
 static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av, const PolyMap& sm) {
     const bool rsh = c.want_rsh && c.au && c.au->mode != 0 && c.p->res_base2k <= 29;
     PZ_TRY(launch_small_fwd(c.M, nb * c.npi, (const long long*)av.p, sm, f.T));
-    PZ_TRY(launch_small_inv(c.M, nb, f.T, f.Pp, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, (long long*)c.res_at(b0), c.res_bs, c.s.cols_out,
-                            (int)c.p->res_size, c.ks ? (const long long*)av.p : nullptr, av.bs, c.s.cols_a, av.size, (int)c.p->res_base2k,
-                            c.body_col, false, nullptr, 0, c.au != nullptr, c.au_p, c.au ? c.au->mode : 0, rsh));
+    SmallInvCall sc;
+    sc.S = f.T; sc.key = small_key(c, f.Pp); sc.res = small_res(c, b0); sc.small = small_operand(c, av);
+    small_inv_auto(sc, c, rsh);
+    PZ_TRY(launch_small_inv(c.M, nb, sc));
     if (rsh) *c.post_rsh = true;
     return PZ_OK;
 }
@@ -323,8 +343,7 @@ static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b
 // Spectral form of the automorphism family (m2 = 128 plans).  X -> X^p with p = 1 mod 4: DFT(phi(a))[q] = DFT(a)[p q + (p-1)/4 mod m] is an
 // affine map of the spectrum index that sends rows of the four-step layout to rows, so the middle kernel writes its product at the
 // permuted position (k_mid128<.., PERM>) and the tail's inverse transform is phi(big) itself.  p = 3 mod 4 (X -> X^-1, the first step of
-// every trace, among them): the spectrum of phi(a) is the CONJUGATE of a permuted spectrum (MidArgs::perm_ysign).
-struct SpectralPerm { bool on = false; unsigned mul = 0, add = 0; bool conj = false; };
+// every trace, among them): the spectrum of phi(a) is the CONJUGATE of a permuted spectrum (MidArgs::perm_ysign).  (SpectralPerm: internal.hpp)
 static SpectralPerm spectral_perm(const GlweCall& c) {
     SpectralPerm sp;
     sp.on = c.au && c.M->plan.m2 == 128 && c.M->dbg_stages == 7;
@@ -381,12 +400,12 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
         if (f.side16 && c.au_big) t.other16 = f.side16;
     }
     t.body_src = (const long long*)f.res_tmp; t.body_bs = (long long)bl * n; t.body_ls = n;
-    const int cond = body16 ? 32 : 0;   // (launch_automorphism: the i64 pre-pass only if the flag is up)
+    const int cond = body16 ? AUTO_IF_WIDE : 0;   // (the i64 pre-pass only if the flag is up)
     if (!c.au_big) {
         // plain form, res = phi(normalize(big)) (glwe_ct.rs:65-71): the inverse transform is phi(big) with phi's signs; the tail undoes
         // them in front of the carry chain (auto_mul) and puts them back on the digits (post_neg); only the body column has an operand
-        if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, 1, nullptr, PolyMap{1, 1, 0, 0, 0, 0}, b16));
-        PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, 1 | cond));
+        if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, AUTO_SIGN, nullptr, PolyMap{1, 1, 0, 0, 0, 0}, b16));
+        PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, AUTO_SIGN | cond));
         t.auto_mul = c.au_g; t.post_neg = true; t.body_only = true;
         return launch_inv_tail(M, t);
     }
@@ -394,8 +413,8 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     const bool rsh = c.want_rsh && tail_rsh_supported(M) && !c.cross_out && c.p->res_base2k <= 29;   // (32-bit shift steps: device_fft.hpp)
     // (16-bit scheme: the pre-pass writes the operand the chain adds - phi(body) + a0 (add), phi(body) - a0 (sub forms; the i64 scheme stores
     //  -phi(body) + a0 and lets the tail negate it))
-    if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, c.au->mode == 1 ? 1 : (1 | 16), (const long long*)av.p, bsm, b16));
-    PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, (c.au->mode == 1 ? 1 : 3) | cond,
+    if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, c.au->mode == 1 ? AUTO_SIGN : (AUTO_SIGN | AUTO_SUB16), (const long long*)av.p, bsm, b16));
+    PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, (c.au->mode == 1 ? AUTO_SIGN : (AUTO_SIGN | AUTO_NEGATE)) | cond,
                                (const long long*)av.p, bsm));
     if (c.au->mode == 3) { t.auto_mul = 2u * (unsigned)n; t.auto_neg = true; }   // a - phi(big): every sign flipped
     t.small_neg = c.au->mode != 1;
@@ -427,7 +446,7 @@ static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int
         TailCall t = wave_tail(c, nb, f.T2, b0);
         if (c.au) { t.res = (long long*)f.res_tmp; t.res_bs = c.res_ct; }
         if (c.ks) tail_operand(t, av, c.au_big || c.tensor);
-        if (c.a16) { t.acc32 = 4; t.small16 = c.a16 + (long long)b0 * av.size * c.n; t.small16_cs = c.a16_cs; t.small_bs = 0; }
+        if (c.a16) { t.small16 = c.a16 + (long long)b0 * av.size * c.n; t.small16_cs = c.a16_cs; t.small_bs = 0; }
         if (c.au_big) { t.auto_mul = c.au_p; t.gather_mul = c.au_p; t.gather_neg = c.au->mode != 1; }
         t.auto_neg = c.au && c.au->mode == 3;
         PZ_TRY(launch_inv_tail(M, t));
@@ -435,7 +454,7 @@ static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int
     if (c.au) {
         PolyMap tm{(int)c.p->res_size, c.s.cols_out, c.res_ct, (long long)c.s.cols_out * c.n, c.n, 0};
         PZ_TRY(launch_automorphism(M, nb * (int)c.p->res_size * c.s.cols_out, (const long long*)f.res_tmp, tm, (long long*)c.res_at(b0), tm, c.au_g,
-                                   c.au->mode == 0 ? 1 : 0));
+                                   c.au->mode == 0 ? AUTO_SIGN : AUTO_PLAIN));
     }
     return PZ_OK;
 }
@@ -475,8 +494,10 @@ static int glwe_fused(const GlweCall& c) {
         if (c.digits && dg.n == 0) {   // nothing reaches the product (e.g. dsize > a.size): the big value is the body alone
             PZ_TRY(launch_zero_bytes(M, f.T2, (size_t)nb * c.npo * M->m * sizeof(cplx)));
         } else if (M->dbg_stages & 2) {
-            PZ_TRY(launch_mid(M, nb, f.T, f.T2, f.Pp, c.npi, c.npo, c.nrows, c.ncols, f.mid_dummy, sp.mul, sp.add, c.digits ? &dg : nullptr, nullptr,
-                              sp.conj));
+            MidCall mc;
+            mc.T = f.T; mc.T2 = f.T2; mc.Pp = f.Pp; mc.dummy = f.mid_dummy; mc.npi = c.npi; mc.npo = c.npo; mc.nrows = c.nrows; mc.ncols = c.ncols;
+            mc.perm = sp; mc.digits = c.digits ? &dg : nullptr;
+            PZ_TRY(launch_mid(M, nb, mc));
         }
         if (sp.on) PZ_TRY(wave_spectral_tail(c, f, b0, nb, av));
         else if (c.cross_out) PZ_TRY(wave_cross_base_tail(c, f, b0, nb, av));
@@ -509,26 +530,27 @@ static int glwe_small_ring(const GlweCall& c) {
         DV av;
         PZ_TRY(wave_input(c, b0, nb, a_conv, &av));
         PolyMap sm{av.size, c.s.cols_in, av.bs, (long long)av.cols * c.n, c.n, c.n * c.s.a_col0};
-        const long long* body = c.ks ? (const long long*)av.p : nullptr;
+        const SmallKey key = small_key(c, Pp);
+        const SmallOperand body = small_operand(c, av);
         // plain product / key switch of a rank-1 ciphertext: one kernel, the spectra never leave the CU (round 6, device_small_one.hpp)
         if (!c.au && !c.cross_out && small_one_supported(M, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, nb)) {
-            PZ_TRY(launch_small_one(M, nb, (const long long*)av.p, sm, Pp, c.npi, c.nrows, c.ncols, c.ksz, (long long*)c.res_at(b0), c.res_bs, c.s.cols_out,
-                                    (int)c.p->res_size, body, av.bs, c.s.cols_a, av.size, (int)c.p->res_base2k, c.body_col));
+            PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body}));
             continue;
         }
         PZ_TRY(launch_small_fwd(M, nb * c.npi, (const long long*)av.p, sm, S));
+        SmallInvCall sc;
+        sc.S = S; sc.key = key; sc.res = small_res(c, b0); sc.small = body;
         if (c.cross_out) {
             const long long tmp_ct = c.n * c.s.cols_out * (long long)c.ksz;
-            PZ_TRY(launch_small_inv(M, nb, S, Pp, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, (long long*)key_digits, tmp_ct, c.s.cols_out, c.ksz,
-                                    body, av.bs, c.s.cols_a, av.size, (int)c.p->key_base2k, c.body_col));
+            sc.res = SmallRes{(long long*)key_digits, tmp_ct, c.s.cols_out, c.ksz, (int)c.p->key_base2k};
+            PZ_TRY(launch_small_inv(M, nb, sc));
             DV tv{key_digits, tmp_ct, c.s.cols_out, c.ksz}, rv{c.res_at(b0), c.res_bs, c.s.cols_out, (int)c.p->res_size};
             for (int col = 0; col < c.s.cols_out; ++col)
                 PZ_TRY(dev_normalize(M, nb, rv, (int)c.p->res_base2k, 0, col, tv, (int)c.p->key_base2k, col));
             continue;
         }
-        PZ_TRY(launch_small_inv(M, nb, S, Pp, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, (long long*)c.res_at(b0), c.res_bs, c.s.cols_out,
-                                (int)c.p->res_size, body, av.bs, c.s.cols_a, av.size, (int)c.p->res_base2k, c.body_col, false, nullptr, 0,
-                                c.au != nullptr, c.au_p, c.au ? c.au->mode : 0, rsh));
+        small_inv_auto(sc, c, rsh);
+        PZ_TRY(launch_small_inv(M, nb, sc));
     }
     if (rsh) *c.post_rsh = true;
     return PZ_OK;
@@ -587,7 +609,7 @@ static int wave_unfused_auto(const GlweCall& c, const UnfusedBufs& u, int nb, co
     if (c.au_big) {
         int64_t* big2 = (int64_t*)u.T;  // free again: same bytes as the big value
         PolyMap bm{L, c.s.cols_out, rb.bs, big_ls, n, 0};
-        PZ_TRY(launch_automorphism(M, nb * L * c.s.cols_out, (const long long*)u.res_dft, bm, (long long*)big2, bm, c.au_g, 1));
+        PZ_TRY(launch_automorphism(M, nb * L * c.s.cols_out, (const long long*)u.res_dft, bm, (long long*)big2, bm, c.au_g, AUTO_SIGN));
         const int sum = std::min(L, a_size);
         for (int col = 0; col < c.s.cols_out; ++col) {
             int64_t* bc = big2 + (long long)col * n;
@@ -607,14 +629,14 @@ static int wave_unfused_auto(const GlweCall& c, const UnfusedBufs& u, int nb, co
         PZ_TRY(dev_normalize(M, nb, nd, (int)c.p->res_base2k, 0, col, nsrc, (int)c.p->key_base2k, col));
     if (c.au->mode == 0) {
         PolyMap tm{(int)c.p->res_size, c.s.cols_out, c.res_ct, (long long)c.s.cols_out * n, n, 0};
-        PZ_TRY(launch_automorphism(M, nb * (int)c.p->res_size * c.s.cols_out, (const long long*)u.res_tmp, tm, (long long*)rv.p, tm, c.au_g, 1));
+        PZ_TRY(launch_automorphism(M, nb * (int)c.p->res_size * c.s.cols_out, (const long long*)u.res_tmp, tm, (long long*)rv.p, tm, c.au_g, AUTO_SIGN));
     }
     return PZ_OK;
 }
 static int glwe_unfused(const GlweCall& c) {
     pz_module* M = c.M;
     const long long n = c.n;
-    const OpWs w = op_ws(M, c.p, c.s, c.chunk, c.ks, c.au != nullptr);
+    const OpWs w = op_ws(M, c.p, c.s, c.chunk, c.kind);
     PZ_TRY(ws_reserve(M, w.total));
     char* base = (char*)M->ws;
     UnfusedBufs u;
@@ -682,8 +704,9 @@ static int glwe_unfused(const GlweCall& c) {
 //  (profiles/r02_cu_mask_scaling.txt), so chunk c+1's pass 1, chunk c's middle kernel and chunk c-1's tail were run concurrently on
 //  disjoint CU sets, chained by events.  Bit-exact, but slower in every split tried (best 73 500/s against 88 700/s back to back,
 //  profiles/r02_overlap_sweep.txt): under concurrency the three kernels share HBM at ~4.7 TB/s aggregate.)
-static int glwe_call_init(GlweCall& c, pz_module* M, bool ks, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
-                          size_t batch, const AutoSpec* au, const OpLayout* lay, bool tensor, bool* post_rsh) {
+static int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
+                          size_t batch, const AutoSpec* au, const OpLayout* lay, bool* post_rsh) {
+    const bool ks = kind_ks(kind), tensor = kind == GlweKind::TensorRelin;
     c.want_rsh = post_rsh && *post_rsh;
     c.post_rsh = post_rsh;
     if (post_rsh) *post_rsh = false;
@@ -691,9 +714,9 @@ static int glwe_call_init(GlweCall& c, pz_module* M, bool ks, int64_t* res, cons
     PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
     PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && is_device_ptr(pmat), "batched entry points take device pointers");
     PZ_REQUIRE(!(tensor && (au || lay)), "glwe_tensor_relinearize: packed tensors, no automorphism");
-    if (tensor) ks = true;   // the product is gglwe_product_dft, as for a key switch
-    c.M = M; c.p = p; c.ks = ks; c.tensor = tensor; c.au = au; c.lay = lay; c.res = res; c.a = a; c.pmat = pmat; c.batch = batch;
-    c.s = op_shape(p, ks, tensor);
+    PZ_REQUIRE((kind == GlweKind::Automorphism) == (au != nullptr), "glwe op: the automorphism family and its Galois element go together");
+    c.M = M; c.p = p; c.kind = kind; c.ks = ks; c.tensor = tensor; c.au = au; c.lay = lay; c.res = res; c.a = a; c.pmat = pmat; c.batch = batch;
+    c.s = op_shape(p, kind);
     c.chunk = pick_chunk(M, p, c.s, std::max<size_t>(batch, 1));
     c.n = (long long)M->n;
     c.dsize = (int)p->dsize; c.dnum = (int)p->dnum; c.ksz = (int)p->key_size;
@@ -719,15 +742,15 @@ static int glwe_call_init(GlweCall& c, pz_module* M, bool ks, int64_t* res, cons
 
 extern "C" {
 
-int glwe_op(pz_module* M, bool ks, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
-            const AutoSpec* au, const OpLayout* lay, bool tensor, bool* post_rsh) {
+int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
+            const AutoSpec* au, const OpLayout* lay, bool* post_rsh) {
     GlweCall c;
-    PZ_TRY(glwe_call_init(c, M, ks, res, a, pmat, p, batch, au, lay, tensor, post_rsh));
+    PZ_TRY(glwe_call_init(c, M, kind, res, a, pmat, p, batch, au, lay, post_rsh));
     if (batch == 0) return PZ_OK;
     // dsize > 1 (digit-selected product inside the middle kernel) and res_base2k != key_base2k (the tail normalizes into the key's base,
     // one cross-base pass follows) ride on the fused pipeline too; both need the 128-point-row plans and no automorphism (fused_applies)
-    if (fused_applies(M, p, c.s, c.tensor, au != nullptr)) return glwe_fused(c);
-    if (small_ring_applies(M, p, c.s, c.ks, c.tensor, au != nullptr, lay == nullptr)) return glwe_small_ring(c);
+    if (fused_applies(M, p, c.s, kind)) return glwe_fused(c);
+    if (small_ring_applies(M, p, c.s, kind, lay == nullptr)) return glwe_small_ring(c);
     return glwe_unfused(c);
 }
 
@@ -735,13 +758,13 @@ int glwe_op(pz_module* M, bool ks, int64_t* res, const int64_t* a, const double*
 // columns, the tail adds the first rank + 1 columns - both from a16 (GlweCall::a16)
 bool glwe_relin_t16_supported(const pz_module* M, const pz_glwe_op_params* p) {
     if (!p || p->dsize != 1 || p->a_base2k != p->key_base2k || p->res_base2k != p->key_base2k || p->rank_out != p->rank || p->rank < 1) return false;
-    const OpShape s = op_shape(p, true, true);
-    return fused_applies(M, p, s, true, false) && tail_d16_only_supported(M) && M->dbg_stages == 7;
+    const OpShape s = op_shape(p, GlweKind::TensorRelin);
+    return fused_applies(M, p, s, GlweKind::TensorRelin) && tail_d16_only_supported(M) && M->dbg_stages == 7;
 }
-size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch) { return pick_chunk(M, p, op_shape(p, true, true), std::max<size_t>(batch, 1)); }
+size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch) { return pick_chunk(M, p, op_shape(p, GlweKind::TensorRelin), std::max<size_t>(batch, 1)); }
 int glwe_relin_t16(pz_module* M, int64_t* res, const short* a16, long long a16_cs, const double* pmat, const pz_glwe_op_params* p, size_t batch) {
     GlweCall c;
-    PZ_TRY(glwe_call_init(c, M, true, res, reinterpret_cast<const int64_t*>(a16), pmat, p, batch, nullptr, nullptr, true, nullptr));
+    PZ_TRY(glwe_call_init(c, M, GlweKind::TensorRelin, res, reinterpret_cast<const int64_t*>(a16), pmat, p, batch, nullptr, nullptr, nullptr));
     PZ_REQUIRE(glwe_relin_t16_supported(M, p) && !n4096_two_kernel(c), "glwe_relin_t16: the pipeline path only");
     if (batch == 0) return PZ_OK;
     c.a16 = a16; c.a16_cs = a16_cs;
@@ -761,7 +784,7 @@ static bool is_pinned_host(const void* p) {
 // the device (stream2) while wave k runs on the module stream and wave k - 1 travels back (stream_out).  PCIe is full duplex: the serial form
 // (everything up, kernels, everything down) used one direction at a time - 3 200 external products/s at 16 ciphertexts per call at the metric
 // shape, 53 GB/s summed over both directions.  Logically synchronous like every host-pointer call: returns when the last wave is back.
-static int glwe_entry_duplex(pz_module* M, bool ks, bool tensor, int64_t* res, const int64_t* a, const double* key, const pz_glwe_op_params* p,
+static int glwe_entry_duplex(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* key, const pz_glwe_op_params* p,
                              size_t batch, const AutoSpec* au, size_t res_ct_bytes, size_t a_ct_bytes) {
     if (!M->stream2) {
         SideStream probe(M);   // (creates the side stream and its events)
@@ -801,7 +824,7 @@ static int glwe_entry_duplex(pz_module* M, bool ks, bool tensor, int64_t* res, c
         char* rd = (char*)r_dev + b0 * res_ct_bytes;
         if (hipMemcpyAsync(ad, (const char*)a + b0 * a_ct_bytes, nb * a_ct_bytes, hipMemcpyHostToDevice, M->stream2) != hipSuccess ||
             hipEventRecord(eu, M->stream2) != hipSuccess || hipStreamWaitEvent(M->stream, eu, 0) != hipSuccess) { rc = fail(PZ_ERR_HIP, "duplex host path: upload failed"); break; }
-        rc = glwe_op(M, ks, (int64_t*)rd, (const int64_t*)ad, key, p, nb, au, nullptr, tensor);
+        rc = glwe_op(M, kind, (int64_t*)rd, (const int64_t*)ad, key, p, nb, au);
         if (rc != PZ_OK) break;
         if (hipEventRecord(ed, M->stream) != hipSuccess || hipStreamWaitEvent(M->stream_out, ed, 0) != hipSuccess ||
             hipMemcpyAsync((char*)res + b0 * res_ct_bytes, rd, nb * res_ct_bytes, hipMemcpyDeviceToHost, M->stream_out) != hipSuccess) { rc = fail(PZ_ERR_HIP, "duplex host path: download failed"); break; }
@@ -814,11 +837,11 @@ static int glwe_entry_duplex(pz_module* M, bool ks, bool tensor, int64_t* res, c
     if (rc == PZ_OK && (s1 != hipSuccess || s2 != hipSuccess || s3 != hipSuccess)) { (void)hipGetLastError(); rc = fail(PZ_ERR_HIP, "duplex host path: a stream failed"); }
     return rc;
 }
-static int glwe_entry(pz_module* M, bool ks, bool tensor, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
+static int glwe_entry(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
                       size_t batch, const AutoSpec* au) {
     PZ_REQUIRE(p != nullptr, "null params");
     PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
-    const OpShape s = op_shape(p, ks || tensor, tensor);
+    const OpShape s = op_shape(p, kind);
     const size_t n8 = (size_t)M->n * 8;
     // in place (*_assign forms): one layout for a and res - checked HERE, in front of both host paths (the duplex path below does not go through
     // glwe_args_in: with res == a and a larger res every wave's kernels would write past the a-sized arena block).  Host ranges that overlap
@@ -830,28 +853,28 @@ static int glwe_entry(pz_module* M, bool ks, bool tensor, int64_t* res, const in
     if (batch >= 2 && res != nullptr && a != nullptr && pmat != nullptr && !partial_overlap && !M->timing && !canary_mode() && is_pinned_host(a) && is_pinned_host(res)) {
         const double* key = nullptr;
         PZ_TRY(resolve_key(M, pmat, n8 * p->dnum * s.cols_in * s.cols_out * p->key_size, &key));
-        return glwe_entry_duplex(M, ks, tensor, res, a, key, p, batch, au, res_ct_bytes, a_ct_bytes);
+        return glwe_entry_duplex(M, kind, res, a, key, p, batch, au, res_ct_bytes, a_ct_bytes);
     }
     GlweArgs g;
     PZ_TRY(glwe_args_in(M, g, res, a, pmat, batch * res_ct_bytes, batch * a_ct_bytes, n8 * p->dnum * s.cols_in * s.cols_out * p->key_size));
-    PZ_TRY(glwe_op(M, ks, g.res, g.a, g.key, p, batch, au, nullptr, tensor));
+    PZ_TRY(glwe_op(M, kind, g.res, g.a, g.key, p, batch, au));
     return glwe_args_out(M, g);
 }
 int pz_glwe_external_product_batched(pz_module* M, int64_t* res, const int64_t* a, const double* ggsw_pmat,
                                      const pz_glwe_op_params* p, size_t batch) {
     PZ_ENTER(M);
-    return glwe_entry(M, false, false, res, a, ggsw_pmat, p, batch, nullptr);
+    return glwe_entry(M, GlweKind::ExternalProduct, res, a, ggsw_pmat, p, batch, nullptr);
 }
 int pz_glwe_keyswitch_batched(pz_module* M, int64_t* res, const int64_t* a, const double* key_pmat, const pz_glwe_op_params* p,
                               size_t batch) {
     PZ_ENTER(M);
-    return glwe_entry(M, true, false, res, a, key_pmat, p, batch, nullptr);
+    return glwe_entry(M, GlweKind::KeySwitch, res, a, key_pmat, p, batch, nullptr);
 }
 int pz_glwe_automorphism_batched(pz_module* M, int64_t* res, const int64_t* a, const double* key_pmat, const pz_glwe_op_params* p,
                                  int64_t gal, int mode, size_t batch) {
     PZ_ENTER(M);
     AutoSpec au{(long long)gal, mode};
-    return glwe_entry(M, true, false, res, a, key_pmat, p, batch, &au);
+    return glwe_entry(M, GlweKind::Automorphism, res, a, key_pmat, p, batch, &au);
 }
 // glwe_tensor_relinearize (poulpy-core/src/operations/glwe.rs:541-607) on `batch` GLWETensors sharing one prepared tensor key
 int pz_glwe_tensor_relinearize_batched(pz_module* M, int64_t* res, const int64_t* a, const double* tsk_pmat, const pz_glwe_op_params* p,
@@ -859,7 +882,7 @@ int pz_glwe_tensor_relinearize_batched(pz_module* M, int64_t* res, const int64_t
     PZ_ENTER(M);
     PZ_REQUIRE(p != nullptr, "null params");
     PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_tensor_relinearize: the tensor key maps rank (rank + 1) / 2 -> rank");
-    return glwe_entry(M, true, true, res, a, tsk_pmat, p, batch, nullptr);
+    return glwe_entry(M, GlweKind::TensorRelin, res, a, tsk_pmat, p, batch, nullptr);
 }
 // ggsw_external_product (external_product/ggsw.rs:54-58): every (row, column) entry of the GGSW `a` is a GLWE and the entries
 // are contiguous in the MatZnx layout, so the operation is one batched external product over dnum_a * (rank+1) ciphertexts
@@ -867,7 +890,7 @@ int pz_ggsw_external_product(pz_module* M, int64_t* res, const int64_t* a, size_
                              const pz_glwe_op_params* p) {
     PZ_ENTER(M);
     PZ_REQUIRE(p != nullptr, "null params");
-    return glwe_op(M, false, res, a, ggsw_pmat, p, a_dnum * (p->rank + 1));
+    return glwe_op(M, GlweKind::ExternalProduct, res, a, ggsw_pmat, p, a_dnum * (p->rank + 1));
 }
 
 // ggsw_expand_row (conversion/gglwe_to_ggsw.rs:116-268): column `col` >= 1 of every row is the key switch of the mask of
@@ -883,7 +906,7 @@ int ggsw_expand_row(pz_module* M, int64_t* ggsw, size_t dnum, const double* cons
     for (size_t col = 1; col < cols; ++col) {
         PZ_REQUIRE(tsk_pmat[col - 1] != nullptr, "ggsw_expand_row: null tensor key");
         OpLayout lay{ct * (long long)cols, ct * (long long)cols, (int)col};
-        PZ_TRY(glwe_op(M, true, ggsw + (long long)col * ct, ggsw, tsk_pmat[col - 1], p, count * dnum, nullptr, &lay));
+        PZ_TRY(glwe_op(M, GlweKind::KeySwitch, ggsw + (long long)col * ct, ggsw, tsk_pmat[col - 1], p, count * dnum, nullptr, &lay));
     }
     return PZ_OK;
 }
@@ -948,7 +971,7 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
         if (!shifted) PZ_TRY(launch_rsh(M, (int)batch, (long long*)res, ct, cols, (int)p->res_size, 0, cols, (int)p->res_base2k, 1));
         AutoSpec au{(long long)gals[s], 1};
         bool rsh = s + 1 < nsteps;
-        PZ_TRY(glwe_op(M, true, res, res, key_pmats[s], p, batch, &au, nullptr, false, &rsh));
+        PZ_TRY(glwe_op(M, GlweKind::Automorphism, res, res, key_pmats[s], p, batch, &au, nullptr, &rsh));
         shifted = rsh;
     }
     return PZ_OK;
@@ -969,6 +992,6 @@ int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64
 // api_lwe.hip composes the LWE <-> GLWE conversions around the batched key switch while holding the module lock
 namespace pz {
 int glwe_keyswitch_nolock(pz_module* M, int64_t* res, const int64_t* a, const double* key_pmat, const pz_glwe_op_params* p, size_t batch) {
-    return glwe_entry(M, true, false, res, a, key_pmat, p, batch, nullptr);
+    return glwe_entry(M, GlweKind::KeySwitch, res, a, key_pmat, p, batch, nullptr);
 }
 }  // namespace pz

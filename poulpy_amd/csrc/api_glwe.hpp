@@ -1,4 +1,4 @@
-// api_glwe.hpp — what the C-ABI translation units share above the launch layer: the batched GLWE product (api.hip), the composite
+// api_glwe.hpp — what the C-ABI translation units share above the launch layer: the batched GLWE product (api_glwe.hip), the composite
 // calls built on it (api_br.hip: blind rotation, circuit bootstrapping, packing) and the HIP-graph cache for launch-bound chains.
 #pragma once
 #include "api_common.hpp"
@@ -82,7 +82,7 @@ static int with_graph(pz_module* M, uint64_t key, F&& body) {
 }
 
 
-// Automorphism family on top of the key switch / strided ciphertexts: see glwe_op in api.hip
+// Automorphism family on top of the key switch / strided ciphertexts: see glwe_op in api_glwe.hip
 struct AutoSpec {
     long long p;
     int mode;
@@ -99,12 +99,15 @@ void host_key_invalidate(const void* p, size_t bytes);   // api.hip: process-wid
 // api.hip: device pointer of a prepared key - itself when it is one, else its validated (possibly refreshed) device mirror
 int resolve_key(pz_module* M, const double* pmat, size_t bytes, const double** out);
 
-// Defined inside api.hip's extern "C" block (C linkage, internal use; the caller holds the module lock):
+// what a call of glwe_op computes; the values are the `keyswitch` argument of pz_glwe_op_workspace_bytes
+enum class GlweKind : int { ExternalProduct = 0, KeySwitch = 1, Automorphism = 2, TensorRelin = 3 };
+
+// Defined inside api_glwe.hip's extern "C" block (C linkage, internal use; the caller holds the module lock):
 extern "C" {
-// the batched GLWE product on device-resident data: external product (ks = false), key switch, automorphism family (au), strided
+// the batched GLWE product on device-resident data: external product, key switch, automorphism family (kind Automorphism, with au), strided
 // ciphertexts with the body landing in another column (lay), tensor relinearization
-int glwe_op(pz_module* M, bool ks, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
-            const AutoSpec* au = nullptr, const OpLayout* lay = nullptr, bool tensor = false, bool* post_rsh = nullptr);
+int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
+            const AutoSpec* au = nullptr, const OpLayout* lay = nullptr, bool* post_rsh = nullptr);
 // post_rsh (glwe_trace): in: the caller would like the result shifted right by one bit (vec_znx_rsh_assign on every column) as it is
 // stored; out: whether the path taken did that (spectral automorphism forms on the 256 x 128 plan) - otherwise the caller shifts itself
 // glwe_trace_assign on a batch (poulpy-core glwe_trace.rs:129-176): one prepared key per step

@@ -644,7 +644,7 @@ static int automorphism_into(pz_module* M, int64_t p, int64_t* res, size_t res_c
     const long long n = (long long)M->n;
     PolyMap sm{std::max(min_size, 1), 1, 0, (long long)a_cols * n, 0, n * (long long)a_col};
     PolyMap dm{std::max(min_size, 1), 1, 0, (long long)res_cols * n, 0, n * (long long)res_col};
-    PZ_TRY(launch_automorphism(M, min_size, (const long long*)t.da.p, sm, (long long*)t.dr.p, dm, inv_mod_2n(p, n), 1));
+    PZ_TRY(launch_automorphism(M, min_size, (const long long*)t.da.p, sm, (long long*)t.dr.p, dm, inv_mod_2n(p, n), AUTO_SIGN));
     PZ_TRY(ew_limbs(M, EW_ZERO, t.dr, (int)res_col, min_size, nullptr, 0, 0, nullptr, 0, 0, (int)res_size - min_size));  // automorphism.rs:32-34
     return tri_out(M, t);
 }
@@ -662,7 +662,7 @@ static int automorphism_assign(pz_module* M, int64_t p, int64_t* res, size_t col
         PZ_TRY(launch_ew(M, EW_COPY, M->ws, 0, n, poly_ptr(M, dr, (int)col, 0), 0, limb_stride(M, dr), nullptr, 0, 0, (int)size, 1));
         PolyMap sm{(int)size, 1, 0, n, 0, 0};
         PolyMap dm{(int)size, 1, 0, (long long)cols * n, 0, n * (long long)col};
-        PZ_TRY(launch_automorphism(M, (int)size, (const long long*)M->ws, sm, (long long*)sr.dev, dm, inv_mod_2n(p, n), 1));
+        PZ_TRY(launch_automorphism(M, (int)size, (const long long*)M->ws, sm, (long long*)sr.dev, dm, inv_mod_2n(p, n), AUTO_SIGN));
     }
     const bool host = sr.owned;
     PZ_TRY(sr.finish());
@@ -704,7 +704,7 @@ int pz_vec_znx_rotate(pz_module* M, int64_t k, int64_t* res, size_t res_cols, si
     const long long n = (long long)M->n;
     PolyMap sm{std::max(min_size, 1), 1, 0, (long long)a_cols * n, 0, n * (long long)a_col};
     PolyMap dm{std::max(min_size, 1), 1, 0, (long long)res_cols * n, 0, n * (long long)res_col};
-    PZ_TRY(launch_rotate(M, min_size, (const long long*)t.da.p, sm, (long long*)t.dr.p, dm, 0, std::max(min_size, 1), nullptr, 0, 0, (long long)k));
+    PZ_TRY(launch_rotate(M, min_size, (const long long*)t.da.p, sm, (long long*)t.dr.p, dm, (long long)k));
     PZ_TRY(ew_limbs(M, EW_ZERO, t.dr, (int)res_col, min_size, nullptr, 0, 0, nullptr, 0, 0, (int)res_size - min_size));
     return tri_out(M, t);
 }
@@ -720,7 +720,7 @@ int pz_vec_znx_rotate_assign(pz_module* M, int64_t k, int64_t* res, size_t cols,
         PZ_TRY(launch_ew(M, EW_COPY, M->ws, 0, n, poly_ptr(M, dr, (int)col, 0), 0, limb_stride(M, dr), nullptr, 0, 0, (int)size, 1));
         PolyMap sm{(int)size, 1, 0, n, 0, 0};
         PolyMap dm{(int)size, 1, 0, (long long)cols * n, 0, n * (long long)col};
-        PZ_TRY(launch_rotate(M, (int)size, (const long long*)M->ws, sm, (long long*)sr.dev, dm, 0, (int)size, nullptr, 0, 0, (long long)k));
+        PZ_TRY(launch_rotate(M, (int)size, (const long long*)M->ws, sm, (long long*)sr.dev, dm, (long long)k));
     }
     const bool host = sr.owned;
     PZ_TRY(sr.finish());

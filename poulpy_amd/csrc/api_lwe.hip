@@ -229,7 +229,7 @@ int pz_lwe_from_glwe_batched(pz_module* M, int64_t* res, size_t res_n_lwe, const
     if (a_idx) {
         const int npolys = (int)(batch * cols * p->a_size);
         PolyMap mp{1, 1, (long long)n, 0, 0, 0};
-        PZ_TRY(launch_rotate(M, npolys, src, mp, rot, mp, 0, 1, nullptr, 0, 0, -(long long)a_idx));
+        PZ_TRY(launch_rotate(M, npolys, src, mp, rot, mp, -(long long)a_idx));
         src = rot;
     }
     PZ_TRY(glwe_keyswitch_nolock(M, (int64_t*)glwe1, (const int64_t*)src, ksk_pmat, p, batch));

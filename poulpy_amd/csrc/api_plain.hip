@@ -110,10 +110,11 @@ int mul_plain_wave(pz_module* M, const PlainPlan& t, const pz_glwe_tensor_params
             PolyMap sbl{1, 1, n * t.bs, 0, 0, (long long)(t.bs - 1) * n};
             PZ_TRY(launch_fwd_pass1(M, npt, (const long long*)pt, sbl, tb_last, true, t.b_mask));
         }
-        PZ_TRY(launch_mid_cnv_pt(M, nb, ta, ta_last, tb, tb_last, shared, T2, t.cols, t.as, t.bs, t.min_size, t.off));
-        for (int c = 0; c < t.cols; ++c)
-            PZ_TRY(launch_inv_tail_nz(M, nb, T2 + (size_t)c * nb * t.min_size * M->m, t.min_size, (long long*)res, r_ct, t.cols, t.res_size, c,
-                                      (int)p->res_base2k, t.lo, t.dft_size, nullptr));
+        MidCnvCall mc{ta, ta_last, tb, tb_last, T2, t.cols, t.as, t.bs, t.min_size, t.off};
+        mc.b_shared = shared;
+        PZ_TRY(launch_mid_cnv_pt(M, nb, mc));
+        NzTailCall nz{T2, t.min_size, (long long*)res, r_ct, t.cols, t.res_size, 0, (int)p->res_base2k, t.lo, t.dft_size};
+        for (int c = 0; c < t.cols; ++c, ++nz.res_col, nz.T += (size_t)nb * t.min_size * M->m) PZ_TRY(launch_inv_tail_nz(M, nb, nz));
         return PZ_OK;
     }
     if (t.mid) {
@@ -138,10 +139,12 @@ int mul_plain_wave(pz_module* M, const PlainPlan& t, const pz_glwe_tensor_params
         }
         PolyMap sbl{1, t.cols, pt_ct, 0, 0, (long long)(t.bs - 1) * n};
         PZ_TRY(launch_fwd_pass1(M, nb * t.cols, (const long long*)pt, sbl, tb_last, true, t.b_mask));
+        MidCnvCall mc{ta, ta_last, tb, tb_last, T2, t.cols, t.as, t.bs, t.min_size, t.off};
+        NzTailCall nz{T2, t.min_size, (long long*)res, r_ct, t.cols, t.res_size, 0, (int)p->res_base2k, t.lo, t.dft_size};
         for (int c = 0; c < t.cols; ++c) {
-            PZ_TRY(launch_mid_cnv(M, nb, ta, ta_last, tb, tb_last, T2, t.cols, t.as, t.bs, c, -1, c, -1, t.min_size, t.off));
-            PZ_TRY(launch_inv_tail_nz(M, nb, T2, t.min_size, (long long*)res, r_ct, t.cols, t.res_size, c, (int)p->res_base2k, t.lo, t.dft_size,
-                                      nullptr));
+            mc.col_i = nz.res_col = c;
+            PZ_TRY(launch_mid_cnv(M, nb, mc));
+            PZ_TRY(launch_inv_tail_nz(M, nb, nz));
         }
         return PZ_OK;
     }
@@ -302,7 +305,7 @@ int pz_glwe_mul_const_batched(pz_module* M, int64_t* res, const int64_t* a, cons
         PZ_HIP(hipStreamSynchronize(M->stream));   // (bdev is refilled from the host by the next arm)
         int64_t* rot_dst = form == 2 ? (int64_t*)rot : r0;
         PolyMap sm{rs * cols, 1, r_ct, n, 0, 0};
-        PZ_TRY(launch_rotate(M, nb * rs * cols, (const long long*)im_dst, sm, (long long*)rot_dst, sm, 0, rs * cols, nullptr, 0, 0, n / 2));
+        PZ_TRY(launch_rotate(M, nb * rs * cols, (const long long*)im_dst, sm, (long long*)rot_dst, sm, n / 2));
         if (form == 2) {
             PZ_TRY(const_arm_composed(M, nb, w_re, bsz, r0, r_ct, a0, a_ct, cols, as, rs, (int)p->res_base2k, big, bdev));
             PZ_TRY(launch_ew(M, EW_ADD_I64, r0, r_ct, n, r0, r_ct, n, rot, r_ct, n, cols * rs, nb));   // glwe_add_assign, no normalization

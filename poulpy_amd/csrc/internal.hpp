@@ -3,11 +3,13 @@
 //   launch_fft.hip   the four passes of the two-pass negacyclic FFT (device_fft.hpp)
 //   launch_tail.hip  fused inverse column pass + carry chain (k_inv_tail)
 //   launch_mid.hip   fused row pass + VMP + inverse row pass (device_mid.hpp), key re-slicing
-//   launch_small.hip two-kernel pipeline for N = 4096: whole polynomials in LDS (device_small.hpp)
+//   launch_small.hip small-ring pipelines for N = 1024 / 2048 / 4096: whole polynomials in LDS (device_small.hpp, device_small_one.hpp)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
-//   api.hip          C ABI: module, memory, the batched GLWE product (glwe_op) and its direct callers, key pinning / mirrors
+//   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp)
+//   api.hip          C ABI: module, memory, key pinning / mirrors
+//   api_glwe.hip     C ABI: the batched GLWE product (glwe_op) and its direct callers
 //   api_hal.hip      C ABI: the per-op HalImpl methods (VecZnxDft, SVP, VMP, VecZnxBig, i64 VecZnx family)
 //   api_br.hip       C ABI: blind rotation, circuit bootstrapping, GLWE packing (composites on glwe_op; HIP-graph replay)
 //   api_cnv.hip      C ABI: convolution family, GLWE tensoring, batched i64 family
@@ -29,7 +31,17 @@ inline int set_lds(K kernel, size_t bytes) {
         PZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return PZ_OK;
 }
+// one launch of `kernel` with `lds` bytes of dynamic shared memory: a dispatch arm names its instantiation once
+template <typename K, typename... A>
+inline int launch_k(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    PZ_TRY(set_lds(kernel, lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return PZ_OK;
+}
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// what a buffer of normalized digits holds per coefficient (the blind rotation keeps its accumulator narrow between two blocks); each kernel's own bit
+// mask is made from these in one place: tail_args (launch_tail.hip) and launch_small_inv
+enum class Digits { I64, I32, I16 };
 
 struct DV {          // a batched VecZnx-like container on the device
     void* p;
@@ -42,14 +54,15 @@ inline void* poly_ptr(const pz_module* M, const DV& v, int col, int limb) {
 }
 
 // ---- launch_fft.hip -----------------------------------------------------------------------------------------------
+// src_digits = I32 (row-major, 128-point-row plans): `src` holds 32-bit digits at the same element offsets
 int launch_fwd_pass1(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* T, bool rowmajor = false, long long mask = -1,
-                     bool src32 = false);
+                     Digits src_digits = Digits::I64);
 // the row-major form on 16-bit digits in the fused tail's tile order (TailD16; smap addresses limbs of n int16)
 int launch_fwd_pass1_t16(pz_module* M, int npolys, const short* src, PolyMap smap, cplx* T);
 // the row-major form on i64 coefficients that also leaves them as 16-bit values in the tile order, polynomial p at w16 + p n, and raises the module's
 // wide flag (module.hpp: wide16) for a value beyond 16 bits
 int launch_fwd_pass1_w16(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* T, short* w16);
-bool tail_d16_only_supported(const pz_module* M);   // the tensoring tails that leave 16-bit digits only + the operand form that reads them   // src32 (row-major, 128-point-row plans): `src` holds 32-bit digits at the same element offsets
+bool tail_d16_only_supported(const pz_module* M);   // the tensoring tails that leave 16-bit digits only + the operand form that reads them
 int launch_fwd_pass2(pz_module* M, int npolys, const cplx* T, double* dst, PolyMap dmap, const cplx* mul);
 int launch_inv_pass2(pz_module* M, int npolys, const double* src, PolyMap smap, cplx* T);
 int launch_inv_pass1(pz_module* M, int npolys, const cplx* T, long long* dst, PolyMap dmap);
@@ -95,9 +108,9 @@ struct TailCall {
     bool post_neg = false;            // put s(n) back on the digits (plain form: phi acts on the normalized value)
     unsigned gather_mul = 0;          // != 0: the operand is -+phi^-1(small), gathered inside the tail (older, non-spectral scheme)
     bool gather_neg = false;
-    // ---- blind rotation's accumulator between two blocks: 32-bit digits (bit 0: `small`, bit 1: `res`; same element strides) ----
-    int acc32 = 0;
-    // bit 2 (with small_all): the operand is a GLWETensor held as 16-bit digits in the tail's tile order, small16[column][ciphertext][limb][n],
+    // ---- blind rotation's accumulator between two blocks: 32-bit digits at the same element strides, or 16-bit digits in the tail's tile order ----
+    Digits small_digits = Digits::I64, res_digits = Digits::I64;
+    // non-null (with small_all): the operand is a GLWETensor held as 16-bit digits in the tail's tile order, small16[column][ciphertext][limb][n],
     // small16_cs int16 elements between columns (`small` only has to be non-null then)
     const short* small16 = nullptr;
     long long small16_cs = 0;
@@ -106,14 +119,24 @@ struct TailCall {
 };
 int launch_inv_tail(pz_module* M, const TailCall& c);
 bool tail_rsh_supported(const pz_module* M);
-bool tail_acc32_supported(const pz_module* M);   // 32-bit accumulator digits (TailCall::acc32; launch_fwd_pass1's src32 covers the same plans)
+bool tail_narrow_supported(const pz_module* M);   // 32- / 16-bit accumulator digits (TailCall::small_digits / res_digits; launch_fwd_pass1's I32 source covers the same plans)
+// One launch of a convolution middle kernel (k_mid_cnv, k_mid_cnv3: launch_cnv.hip; k_mid_cnv_pt: launch_plain.hip); a wave fills it once.
+struct MidCnvCall {
+    // ---- T' of the operand limbs as pass 1 left them: all limbs but the last, and the last one (masked) ----
+    const cplx *a_main = nullptr, *a_last = nullptr, *b_main = nullptr, *b_last = nullptr;
+    cplx* T2 = nullptr;
+    // ---- columns per operand, limbs of a / b, and the product limbs [offset, offset + min_size) that are kept ----
+    int cols = 0, a_size = 0, b_size = 0, min_size = 0, offset = 0;
+    // ---- k_mid_cnv: the term, columns (col_i, col_j) of both operands; col_j = -1: the diagonal term ----
+    int col_i = 0, col_j = -1;
+    // ---- k_mid_cnv_pt: one plaintext for every ciphertext ----
+    bool b_shared = false;
+};
 bool mid_cnv_supported(const pz_module* M, int a_size, int b_size, int min_size);
-int launch_mid_cnv(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, cplx* T2, int cols,
-                   int a_size, int b_size, int a_i, int a_j, int b_i, int b_j, int min_size, int offset);
+int launch_mid_cnv(pz_module* M, int batch, const MidCnvCall& c);
 // k_mid_cnv3: the three terms of a rank-1 tensoring in one launch; T2 = [term][pair][limb < min_size][m] (launch_cnv.hip)
 bool mid_cnv3_supported(const pz_module* M, int cols, int a_size, int b_size, int min_size);
-int launch_mid_cnv3(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, cplx* T2, int a_size,
-                    int min_size, int offset);
+int launch_mid_cnv3(pz_module* M, int batch, const MidCnvCall& c);
 struct NzCombine;
 // 16-bit side copies of the diagonal terms' digits (round 6; base2k <= 16): [pair][res limb][n] int16 in the tail's own tile order.  A diagonal
 // launch (NZ1) mirrors every digit it stores into `w`; the pairwise launch (mode 5) reads `ra` / `rb` instead of the low dwords of the two
@@ -121,8 +144,21 @@ struct NzCombine;
 // only: the digits leave ONLY as those copies, the i64 column is not written (the fused multiply + relinearize, api_cnv.hip: the pairwise launch
 // then writes its own values pair - d_i - d_j into `w` too, base2k <= 14)
 struct TailD16 { short* w = nullptr; const short* ra = nullptr; const short* rb = nullptr; bool only = false; };
-int launch_inv_tail_nz(pz_module* M, int batch, const cplx* T, int nlimbs, long long* res, long long res_bs, int res_cols, int res_size, int res_col,
-                       int base2k, long long res_offset, int a_size, const NzCombine* cb, const TailD16* d16 = nullptr);
+// The inverse column pass on the row-major T with vec_znx_normalize's same-base steps in its stores (launch_tail.hip)
+struct NzTailCall {
+    const cplx* T = nullptr;
+    int nlimbs = 0;                   // limbs of T that are transformed; the other a_size - nlimbs are zero
+    // ---- where the digits go: column res_col of `res`, shifted by res_offset bits ----
+    long long* res = nullptr;
+    long long res_bs = 0;
+    int res_cols = 0, res_size = 0, res_col = 0;
+    int base2k = 0;
+    long long res_offset = 0;
+    int a_size = 0;
+    const NzCombine* cb = nullptr;    // how they reach res_col and up to two more columns; null: plain stores
+    const TailD16* d16 = nullptr;     // 16-bit side copies
+};
+int launch_inv_tail_nz(pz_module* M, int batch, const NzTailCall& c);
 
 // ---- launch_mid.hip -----------------------------------------------------------------------------------------------
 // scratch rows behind T2: one 64-row x 128-point tile per persistent workgroup of k_mid128 (<= 256 of them: 32 MiB), which also covers
@@ -130,7 +166,9 @@ int launch_inv_tail_nz(pz_module* M, int batch, const cplx* T, int nlimbs, long 
 constexpr size_t kMidDummyBytes = (size_t)256 * 64 * 128 * sizeof(cplx) + (1 << 20);
 bool mid_supported(const pz_module* M, int npi, int npo);
 int launch_permute_pmat(pz_module* M, const double* P, cplx* Pp, int npolys);
-// perm_mul != 0: spectrum permutation of X -> X^p folded into the middle kernel (m2 = 128 plans only; see MidArgs)
+// mul != 0: spectrum permutation of X -> X^p folded into the middle kernel (m2 = 128 plans only; see MidArgs and spectral_perm in api_glwe.hip);
+// conj: the spectrum of phi(a) is the conjugate of the permuted one (p = 3 mod 4)
+struct SpectralPerm { bool on = false; unsigned mul = 0, add = 0; bool conj = false; };
 // digit-selected product (dsize > 1, m2 = 128 plans): term t = input polynomial in[t] x key row row[t], columns shifted by coff[t],
 // reaching the first cb[t] output polynomials
 struct MidDigits {
@@ -144,8 +182,20 @@ struct MidBr {
     long long lwe_bs;
     int i0, blk;            // first coefficient of the block, block size (<= 16)
 };
-int launch_mid(pz_module* M, int batch, const cplx* T, cplx* T2, const cplx* Pp, int npi, int npo, int nrows, int ncols, cplx* dummy,
-               unsigned perm_mul = 0, unsigned perm_add = 0, const MidDigits* dg = nullptr, const MidBr* br = nullptr, bool perm_conj = false);
+struct MidCall {
+    // ---- T' in, T2' out, the row-sliced key; scratch rows (kMidDummyBytes) ----
+    const cplx* T = nullptr;
+    cplx* T2 = nullptr;
+    const cplx* Pp = nullptr;
+    cplx* dummy = nullptr;
+    int npi = 0, npo = 0;             // polynomials per ciphertext in / out
+    int nrows = 0, ncols = 0;         // the key matrix
+    // ---- the product form: plain, or one of ----
+    SpectralPerm perm;
+    const MidDigits* digits = nullptr;
+    const MidBr* br = nullptr;
+};
+int launch_mid(pz_module* M, int batch, const MidCall& c);
 
 // ---- launch_small.hip ---------------------------------------------------------------------------------------------
 // two-kernel pipeline for N = 1024 / 2048 / 4096 (device_small.hpp): full forward transform -> S[poly][q1][q2]; product with the row-sliced key +
@@ -157,16 +207,53 @@ int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap sma
                      const PolyMap* dmap = nullptr, const cplx* mul = nullptr);
 bool small_transform_supported(const pz_module* M);   // N = 1024 / 2048 / 4096: per-op transforms in one kernel (launch_small.hip)
 int launch_small_idft(pz_module* M, int npolys, const double* a, PolyMap smap, long long* res, PolyMap dmap);
-int launch_small_inv(pz_module* M, int batch, const cplx* S, const cplx* Pp, int npi, int nrows, int ncols, int cols_out, int ksz,
-                     long long* res, long long res_bs, int res_cols, int res_size, const long long* small, long long small_bs,
-                     int small_cols, int small_size, int base2k, int body_col, bool noprod = false, cplx* fwd_S = nullptr, int fwd_limbs = 0,
-                     bool au = false, unsigned au_p = 0, int au_mode = 0, bool post_rsh = false, int acc32 = 0);
+// the groups both small-ring product launchers share; glwe_small_ring fills them once per wave
+struct SmallKey {                     // the re-sliced key and the product's shape
+    const cplx* Pp = nullptr;
+    int npi = 0, nrows = 0, ncols = 0, cols_out = 0, ksz = 0;
+};
+struct SmallRes {                     // where the normalized digits go
+    long long* p = nullptr;
+    long long bs = 0;                 // i64 elements between consecutive ciphertexts
+    int cols = 0, size = 0, base2k = 0;
+};
+struct SmallOperand {                 // added in front of the carry chain; p = null: none (external product)
+    const long long* p = nullptr;
+    long long bs = 0;
+    int cols = 0, size = 0;
+    int body_col = 0;                 // < 0: column c of the operand lands on column c
+};
+struct SmallInvCall {
+    const cplx* S = nullptr;          // the spectra k_small_fwd left (product-free form: the big value's own spectrum)
+    SmallKey key;
+    SmallRes res;
+    SmallOperand small;
+    // ---- product-free form (blind rotation: the block step made the product), optionally with the forward transform of the first fwd_limbs
+    //      limbs of the new accumulator chained behind the carry chain, into fwd_S ----
+    bool noprod = false;
+    cplx* fwd_S = nullptr;
+    int fwd_limbs = 0;
+    // ---- automorphism family: X -> X^au_p, au_mode as AutoSpec::mode ----
+    bool au = false;
+    unsigned au_p = 0;
+    int au_mode = 0;
+    // ---- glwe_trace: the digits leave through a one-bit shift ----
+    bool post_rsh = false;
+    // ---- blind rotation's accumulator between two blocks (product-free form) ----
+    Digits small_digits = Digits::I64, res_digits = Digits::I64;
+};
+int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c);
 // ONE kernel per call for N = 1024 / 2048 (device_small_one.hpp): forward transforms, product, inverse transforms and carry chains of a ciphertext in
 // one workgroup; rank 1 (2 output columns), <= 8 input polynomials, <= 4 key limbs, key columns = ksz * 2
 bool small_one_supported(const pz_module* M, int npi, int nrows, int ncols, int cols_out, int ksz, int batch);
-int launch_small_one(pz_module* M, int batch, const long long* src, PolyMap smap, const cplx* Pp, int npi, int nrows, int ncols, int ksz, long long* res,
-                     long long res_bs, int res_cols, int res_size, const long long* small, long long small_bs, int small_cols, int small_size, int base2k,
-                     int body_col);
+struct SmallOneCall {
+    const long long* src = nullptr;   // the input limbs, addressed by smap
+    PolyMap smap{1, 1, 0, 0, 0, 0};
+    SmallKey key;
+    SmallRes res;
+    SmallOperand small;
+};
+int launch_small_one(pz_module* M, int batch, const SmallOneCall& c);
 
 // ---- launch_ops.hip -----------------------------------------------------------------------------------------------
 int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_ls, const void* a, long long a_bs,
@@ -174,10 +261,24 @@ int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_l
 // zero-fill as a kernel node (not hipMemsetAsync: see launch_ops.hip) - for everything that can run under graph capture
 int launch_zero_bytes(pz_module* M, void* ptr, size_t bytes);
 // dst = +-src(X^p-gather with multiplier mul) [+ add]; see k_automorphism
+// `flags`: the first three reach the kernel as AutoArgs::flags (device_ops.hpp), the other two choose the launch
+enum AutoFlags : int {
+    AUTO_PLAIN = 0,        // the gather alone, no signs
+    AUTO_SIGN = 1,         // apply the sign X -> X^p gives each coefficient
+    AUTO_NEGATE = 2,       // negate every output
+    AUTO_ADD_FIRST = 4,    // `add` only for polynomials whose innermost PolyMap index is 0
+    AUTO_SUB16 = 16,       // 16-bit output (dst16) only: `add` is subtracted
+    AUTO_IF_WIDE = 32,     // the i64 fallback of the 16-bit body pre-pass: runs only if the module's wide flag is up
+};
 int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, unsigned mul,
                         int flags, const long long* add = nullptr, PolyMap am = PolyMap{1, 1, 0, 0, 0, 0}, short* dst16 = nullptr);
+// per-ciphertext shift: polynomial i turns by shift[(i / polys_per_batch) * shift_bs + shift_idx] (mode: see k_rotate)
 int launch_rotate(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, int mode,
                   int polys_per_batch, const long long* shift, long long shift_bs, long long shift_idx, long long shift_const);
+// dst = X^k src on every polynomial
+inline int launch_rotate(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, long long k) {
+    return launch_rotate(M, npolys, src, sm, dst, dm, 0, npolys, nullptr, 0, 0, k);
+}
 int launch_rsh(pz_module* M, int batch, long long* data, long long bs, int cols, int size, int col0, int ncols, int base2k, int k);
 // vmp_apply_dft_to_dft  [vmp.rs:144-264, zero-tail semantics for limb_offset > 0]
 int dev_vmp(pz_module* M, int batch, DV res, DV a, const double* pmat, int rows, int cols_in, int cols_out, int size, int limb_offset);
@@ -220,8 +321,7 @@ struct MulConstArmSpec { const int64_t* b; int b_size, big_size, hi; };
 // GLWE x plaintext middle kernel (k_mid_cnv_pt<AS, BS>, device_plain.hpp): a = the operand columns' T' as k_mid_cnv reads them, b = the
 // plaintext's T' [pt][limb < b_size - 1][m] / [pt][m] with b_bs points between plaintexts (0: shared); T2 = [col][ct][kk < min_size][m]
 bool mid_cnv_pt_supported(const pz_module* M, int cols, int a_size, int b_size, int min_size);
-int launch_mid_cnv_pt(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, bool b_shared, cplx* T2,
-                      int cols, int a_size, int b_size, int min_size, int offset);
+int launch_mid_cnv_pt(pz_module* M, int batch, const MidCnvCall& c);
 // k_cnv_by_const on every column of `batch` ciphertexts: res_big [ct][limb < res_size][col][n] (limbs >= min_size untouched)
 int launch_cnv_by_const_batched(pz_module* M, int batch, long long* res, long long res_bs, int res_size, int min_size, int offset, const long long* a,
                                 long long a_bs, int cols, int a_size, const long long* bconst, int b_size);

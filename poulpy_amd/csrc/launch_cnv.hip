@@ -23,14 +23,13 @@ int launch_cnv_apply(pz_module* M, int batch, double* res, long long res_bs, int
     // (point, output limb), operands from L2
     if ((M->m % 128) == 0 && a_size + b_size <= 64 && a != (const double*)res && b != (const double*)res) {
         const size_t lds = (size_t)(a_size + b_size) * 128 * sizeof(cplx);
-        PZ_TRY(set_lds(k_cnv_apply_lds, lds));
         for (int b0 = 0; b0 < batch; b0 += 65535) {   // gridDim.y limit
             CnvArgs gb = g;
             gb.res = res + (long long)b0 * res_bs;
             gb.a = g.a + (long long)b0 * g.a_bs;
             gb.b = g.b + (long long)b0 * g.b_bs;
             const int nb = std::min(65535, batch - b0);
-            hipLaunchKernelGGL(k_cnv_apply_lds, dim3((unsigned)(M->m / 128), (unsigned)nb), dim3(256), lds, M->stream, gb);
+            PZ_TRY(launch_k(k_cnv_apply_lds, dim3((unsigned)(M->m / 128), (unsigned)nb), dim3(256), lds, M->stream, gb));
         }
         PZ_HIP(hipGetLastError());
         return PZ_OK;
@@ -53,17 +52,16 @@ bool mid_cnv_supported(const pz_module* M, int a_size, int b_size, int min_size)
            a_size >= 1 && b_size >= 1 && min_size >= 1 && min_size <= 32 &&
            ((size_t)std::max(a_size + b_size, min_size) * kMidCnvRS + 256) * sizeof(cplx) <= (size_t)160 * 1024;
 }
-int launch_mid_cnv(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, cplx* T2, int cols,
-                   int a_size, int b_size, int a_i, int a_j, int b_i, int b_j, int min_size, int offset) {
+int launch_mid_cnv(pz_module* M, int batch, const MidCnvCall& c) {
+    const int a_size = c.a_size, b_size = c.b_size, min_size = c.min_size;
     if (batch <= 0 || min_size <= 0) return PZ_OK;
     MidCnvArgs g;
-    g.a_main = a_main; g.a_last = a_last; g.b_main = b_main; g.b_last = b_last; g.T2 = T2; g.cols = cols;
-    g.a_size = a_size; g.b_size = b_size; g.a_i = a_i; g.a_j = a_j; g.b_i = b_i; g.b_j = b_j; g.min_size = min_size; g.offset = offset;
+    g.a_main = c.a_main; g.a_last = c.a_last; g.b_main = c.b_main; g.b_last = c.b_last; g.T2 = c.T2; g.cols = c.cols;
+    g.a_size = a_size; g.b_size = b_size; g.a_i = c.col_i; g.a_j = c.col_j; g.b_i = c.col_i; g.b_j = c.col_j; g.min_size = min_size; g.offset = c.offset;
     g.m1 = M->plan.m1; g.batch = batch; g.wL2 = M->wL2; g.tw12t = M->tw12t;
     const size_t lds = ((size_t)std::max(a_size + b_size, min_size) * kMidCnvRS + 256) * sizeof(cplx);
     KTimer kt(M, PZ_K_FUSED_MID);
-    PZ_TRY(set_lds(k_mid_cnv, lds));
-    hipLaunchKernelGGL(k_mid_cnv, dim3((unsigned)((long long)batch * g.m1)), dim3(256), lds, M->stream, g);
+    PZ_TRY(launch_k(k_mid_cnv, dim3((unsigned)((long long)batch * g.m1)), dim3(256), lds, M->stream, g));
     dispatch_note(M, "k_mid_cnv (a %d + b %d limbs -> %d, lds=%zu)", a_size, b_size, min_size, lds);
     PZ_HIP(hipGetLastError());
     return PZ_OK;
@@ -75,11 +73,11 @@ bool mid_cnv3_supported(const pz_module* M, int cols, int a_size, int b_size, in
     return on && cols == 2 && mid_cnv_supported(M, a_size, b_size, min_size) && a_size == b_size && (a_size == 16 || a_size == 8) && min_size <= 21 &&
            3 * min_size <= 64;
 }
-int launch_mid_cnv3(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, cplx* T2, int a_size,
-                    int min_size, int offset) {
+int launch_mid_cnv3(pz_module* M, int batch, const MidCnvCall& c) {
+    const int a_size = c.a_size, min_size = c.min_size, offset = c.offset;
     if (batch <= 0 || min_size <= 0) return PZ_OK;
     MidCnv3Args g;
-    g.a_main = a_main; g.a_last = a_last; g.b_main = b_main; g.b_last = b_last; g.T2 = T2;
+    g.a_main = c.a_main; g.a_last = c.a_last; g.b_main = c.b_main; g.b_last = c.b_last; g.T2 = c.T2;
     g.min_size = min_size; g.offset = offset; g.m1 = M->plan.m1; g.batch = batch; g.wL2 = M->wL2; g.tw12t = M->tw12t;
     const size_t lds = ((size_t)64 * kMidCnvRS + 384) * sizeof(cplx);   // tile | wL2 | two twiddle rows
     KTimer kt(M, PZ_K_FUSED_MID);
@@ -87,11 +85,11 @@ int launch_mid_cnv3(pz_module* M, int batch, const cplx* a_main, const cplx* a_l
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
     const dim3 grid((unsigned)std::min<long long>((long long)batch * g.m1, ncu));   // persistent: one workgroup per CU
     // b = a (glwe_tensor_square_apply): the square form - half the operand rows, symmetric limb products
-    const bool sq = a_main == b_main && a_last == b_last;
+    const bool sq = c.a_main == c.b_main && c.a_last == c.b_last;
     // the static window: multiply-adds with i + j < WLO are not compiled in; WLO = a_size - 4 when the offset allows it (CKKS keeps the top limbs
     // of the product: offset ~ a_size), else 0
     const int wlo = offset >= a_size - 4 ? a_size - 4 : 0;
-#define PZ_CNV3_LAUNCH(K_) { PZ_TRY(set_lds((K_), lds)); hipLaunchKernelGGL((K_), grid, dim3(512), lds, M->stream, g); }
+#define PZ_CNV3_LAUNCH(K_) { PZ_TRY(launch_k((K_), grid, dim3(512), lds, M->stream, g)); }
 #define PZ_CNV3_FORMS(AS_)                                                                                                  \
     {                                                                                                                       \
         if (sq && wlo) PZ_CNV3_LAUNCH((k_mid_cnv3<AS_, AS_, true, AS_ - 4>))                                                \

@@ -13,7 +13,7 @@ namespace pz {
 #define PZ_P2_CASES(X) X(2, 1, 2) X(4, 1, 2) X(4, 1, 4) X(8, 1, 4) X(16, 1, 4) X(16, 1, 16) X(8, 4, 16) X(8, 8, 16) X(16, 8, 16) X(16, 16, 16)
 
 
-int launch_fwd_pass1(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* T, bool rowmajor, long long mask, bool src32) {
+int launch_fwd_pass1(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* T, bool rowmajor, long long mask, Digits src_digits) {
     const FftPlan& pl = M->plan;
     if (npolys == 0) return PZ_OK;
     KTimer kt(M, PZ_K_FWD_PASS1);
@@ -26,14 +26,14 @@ int launch_fwd_pass1(pz_module* M, int npolys, const long long* src, PolyMap sma
     // row-major (pipeline) launches use the XCD-aware block order of k_fwd_pass1: grid padded to whole groups of 8 polynomials
     const int npx = rowmajor ? npolys : 0;
     const int blocks_rm = npx ? ((npolys + 7) / 8) * 8 * ncb : blocks;
-    if (src32) {   // 32-bit source digits: the row-major form of the 128-point-row plans (the blind rotation's pipeline path)
+    if (src_digits == Digits::I16) return fail(PZ_ERR_INVALID, "forward pass 1: 16-bit source digits take launch_fwd_pass1_t16");
+    if (src_digits == Digits::I32) {   // 32-bit source digits: the row-major form of the 128-point-row plans (the blind rotation's pipeline path)
         if (!(rowmajor && mask == -1)) return fail(PZ_ERR_INVALID, "forward pass 1: 32-bit source digits need the row-major form");
 #define X(A, B, C)                                                                                              \
     if (pl.f1a == A && pl.f1b == B && pl.cb == C) {                                                             \
         const size_t lds = ((size_t)(A + 1) * C * B + 2 * A * B) * sizeof(cplx);                                \
-        PZ_TRY(set_lds((k_fwd_pass1<A, B, C, true, true>), lds));                                               \
-        hipLaunchKernelGGL((k_fwd_pass1<A, B, C, true, true>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, \
-                           T, pl.m2, M->tw1, M->wL1, M->tw12t, mask, npx);                                      \
+        PZ_TRY(launch_k((k_fwd_pass1<A, B, C, true, true>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, \
+                           T, pl.m2, M->tw1, M->wL1, M->tw12t, mask, npx));                                      \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
     }
@@ -45,13 +45,11 @@ int launch_fwd_pass1(pz_module* M, int npolys, const long long* src, PolyMap sma
     if (pl.f1a == A && pl.f1b == B && pl.cb == C) {                                                             \
         const size_t lds = ((size_t)(A + 1) * C * B + 2 * A * B) * sizeof(cplx);                                              \
         if (rowmajor) {                                                                                         \
-            PZ_TRY(set_lds(k_fwd_pass1<A, B, C, true>, lds));                                                   \
-            hipLaunchKernelGGL((k_fwd_pass1<A, B, C, true>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, \
-                               T, pl.m2, M->tw1, M->wL1, M->tw12t, mask, npx);                                        \
+            PZ_TRY(launch_k((k_fwd_pass1<A, B, C, true>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, \
+                               T, pl.m2, M->tw1, M->wL1, M->tw12t, mask, npx));                                        \
         } else {                                                                                                \
-            PZ_TRY(set_lds(k_fwd_pass1<A, B, C>, lds));                                                         \
-            hipLaunchKernelGGL((k_fwd_pass1<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, \
-                               pl.m2, M->tw1, M->wL1, M->tw12, mask, 0);                                              \
+            PZ_TRY(launch_k((k_fwd_pass1<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, \
+                               pl.m2, M->tw1, M->wL1, M->tw12, mask, 0));                                              \
         }                                                                                                       \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
@@ -70,9 +68,8 @@ int launch_fwd_pass1_w16(pz_module* M, int npolys, const long long* src, PolyMap
 #define X(A, B, C)                                                                                              \
     if (pl.f1a == A && pl.f1b == B && pl.cb == C) {                                                             \
         const size_t lds = ((size_t)(A + 1) * C * B + 2 * A * B) * sizeof(cplx);                                \
-        PZ_TRY(set_lds((k_fwd_pass1_w16<A, B, C>), lds));                                                       \
-        hipLaunchKernelGGL((k_fwd_pass1_w16<A, B, C>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, pl.m2, M->tw1, M->wL1, \
-                           M->tw12t, npolys, w16, M->wide16());                                                 \
+        PZ_TRY(launch_k((k_fwd_pass1_w16<A, B, C>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, pl.m2, M->tw1, M->wL1, \
+                           M->tw12t, npolys, w16, M->wide16()));                                                 \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
     }
@@ -90,9 +87,8 @@ int launch_fwd_pass1_t16(pz_module* M, int npolys, const short* src, PolyMap sma
 #define X(A, B, C)                                                                                              \
     if (pl.f1a == A && pl.f1b == B && pl.cb == C) {                                                             \
         const size_t lds = ((size_t)(A + 1) * C * B + 2 * A * B) * sizeof(cplx);                                \
-        PZ_TRY(set_lds((k_fwd_pass1_t16<A, B, C>), lds));                                                       \
-        hipLaunchKernelGGL((k_fwd_pass1_t16<A, B, C>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream,  \
-                           reinterpret_cast<const long long*>(src), smap, T, pl.m2, M->tw1, M->wL1, M->tw12t, npolys);  \
+        PZ_TRY(launch_k((k_fwd_pass1_t16<A, B, C>), dim3(blocks_rm), dim3((A > B ? A : B) * C), lds, M->stream,  \
+                           reinterpret_cast<const long long*>(src), smap, T, pl.m2, M->tw1, M->wL1, M->tw12t, npolys));  \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
     }
@@ -109,9 +105,8 @@ int launch_fwd_pass2(pz_module* M, int npolys, const cplx* T, double* dst, PolyM
 #define X(A, B, C)                                                                                              \
     if (pl.r2a == A && pl.r2b == B && pl.qb == C) {                                                             \
         const size_t lds = (size_t)A * B * C * sizeof(cplx);                                                    \
-        PZ_TRY(set_lds(k_fwd_pass2<A, B, C>, lds));                                                             \
-        hipLaunchKernelGGL((k_fwd_pass2<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, dst, dmap, \
-                           pl.m1, M->wL2, mul);                                                                 \
+        PZ_TRY(launch_k((k_fwd_pass2<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, dst, dmap, \
+                           pl.m1, M->wL2, mul));                                                                 \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
     }
@@ -128,9 +123,8 @@ int launch_inv_pass2(pz_module* M, int npolys, const double* src, PolyMap smap, 
 #define X(A, B, C)                                                                                              \
     if (pl.r2a == A && pl.r2b == B && pl.qb == C) {                                                             \
         const size_t lds = (size_t)A * B * C * sizeof(cplx);                                                    \
-        PZ_TRY(set_lds(k_inv_pass2<A, B, C>, lds));                                                             \
-        hipLaunchKernelGGL((k_inv_pass2<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, \
-                           pl.m1, M->wL2, M->tw12);                                                             \
+        PZ_TRY(launch_k((k_inv_pass2<A, B, C>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, src, smap, T, \
+                           pl.m1, M->wL2, M->tw12));                                                             \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \
     }
@@ -148,13 +142,11 @@ int launch_inv_pass1(pz_module* M, int npolys, const cplx* T, long long* dst, Po
     if (pl.r1a == A && pl.r1b == B && pl.cb == C) {                                                             \
         const size_t lds = (size_t)(A + 1) * C * B * sizeof(cplx);                                              \
         if (M->probe) {                                                                                         \
-            PZ_TRY(set_lds(k_inv_pass1<A, B, C, true>, lds));                                                   \
-            hipLaunchKernelGGL((k_inv_pass1<A, B, C, true>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, \
-                               dst, dmap, pl.m2, M->tw1inv, M->wL1, M->margin);                                 \
+            PZ_TRY(launch_k((k_inv_pass1<A, B, C, true>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, \
+                               dst, dmap, pl.m2, M->tw1inv, M->wL1, M->margin));                                 \
         } else {                                                                                                \
-            PZ_TRY(set_lds(k_inv_pass1<A, B, C, false>, lds));                                                  \
-            hipLaunchKernelGGL((k_inv_pass1<A, B, C, false>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, \
-                               dst, dmap, pl.m2, M->tw1inv, M->wL1, M->margin);                                 \
+            PZ_TRY(launch_k((k_inv_pass1<A, B, C, false>), dim3(blocks), dim3((A > B ? A : B) * C), lds, M->stream, T, \
+                               dst, dmap, pl.m2, M->tw1inv, M->wL1, M->margin));                                 \
         }                                                                                                       \
         PZ_HIP(hipGetLastError());                                                                              \
         return PZ_OK;                                                                                           \

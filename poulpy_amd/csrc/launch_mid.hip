@@ -27,16 +27,14 @@ static int launch_mid256(pz_module* M, MidArgs g, int batch) {
     g.n_ct = (batch + CT - 1) / CT;
     const size_t lds = ((size_t)CT * 16 * 17 * 16 + 512) * sizeof(cplx);
     KTimer kt(M, PZ_K_FUSED_MID);
-    PZ_TRY(set_lds(k_mid<CT>, lds));
     // persistent: as many workgroups as fit (LDS-bound: 144 KiB -> 1 per CU)
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
     const int grid = std::min(ncu, g.m1 * g.n_ct);
-    hipLaunchKernelGGL((k_mid<CT>), dim3(grid), dim3(CT * 256), lds, M->stream, g);
+    PZ_TRY(launch_k(k_mid<CT>, dim3(grid), dim3(CT * 256), lds, M->stream, g));
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }
-// perm_mul != 0: spectrum permutation of X -> X^p folded into the middle kernel (m2 = 128 plans only; see MidArgs)
 // m2 = 128 plans: the persistent tile kernels k_mid128 / k_mid128r - which instantiation for this shape (tile geometry by the polynomials in and
 // out, the product form: plain / permuted / digit-selected / CGGI block step)
 static int launch_mid128(pz_module* M, MidArgs& g, int batch, int npi, int npo, bool perm, bool ds, bool br) {
@@ -46,14 +44,12 @@ static int launch_mid128(pz_module* M, MidArgs& g, int batch, int npi, int npo, 
     KTimer kt(M, PZ_K_FUSED_MID);
 #define PZ_MID128_GO(CT_, NP_, PERM_, SKIPW_)                                                                              \
 {                                                                                                                      \
-    PZ_TRY(set_lds((k_mid128<CT_, NP_, PERM_, false, false, ((SKIPW_) && (NP_ > 8))>), lds));                           \
-    hipLaunchKernelGGL((k_mid128<CT_, NP_, PERM_, false, false, ((SKIPW_) && (NP_ > 8))>), grid_, dim3(512), lds, M->stream, g); \
+    PZ_TRY(launch_k((k_mid128<CT_, NP_, PERM_, false, false, ((SKIPW_) && (NP_ > 8))>), grid_, dim3(512), lds, M->stream, g)); \
     dispatch_note(M, "k_mid128<CT=%d,NP=%d,PERM=%d,DS=0,BR=0,SKIPW=%d>", CT_, NP_, (int)(PERM_), (int)((SKIPW_) && (NP_ > 8))); \
 }
 #define PZ_MID128_GOR1(CT_, NP_, PERM_, NR_, HALF_)                                                                        \
 {                                                                                                                      \
-    PZ_TRY(set_lds((k_mid128r<CT_, NP_, PERM_, NR_, ((HALF_) && (NP_ >= 16))>), lds));                                  \
-    hipLaunchKernelGGL((k_mid128r<CT_, NP_, PERM_, NR_, ((HALF_) && (NP_ >= 16))>), grid_, dim3(512), lds, M->stream, g); \
+    PZ_TRY(launch_k((k_mid128r<CT_, NP_, PERM_, NR_, ((HALF_) && (NP_ >= 16))>), grid_, dim3(512), lds, M->stream, g)); \
     dispatch_note(M, "k_mid128r<CT=%d,NP=%d,PERM=%d,NR=%d,HALFIN=%d,KR=%d>", CT_, NP_, (int)(PERM_), NR_, (int)((HALF_) && (NP_ >= 16)), NP_ == 32 ? 3 : PZ_MIDR_KR); \
 }
 /* k_mid128r: product rows = NP (no idle waves) or NP / 2 with the upper half of the slots without input (key switch) */ \
@@ -79,36 +75,30 @@ if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {   
     const size_t lds = ((size_t)CT_ * NP_ * kMidRS + 384 + 32) * sizeof(cplx);   /* tile | wL2 | two twiddle rows | exponents */                                         \
     const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));   /* <= 256: one scratch tile per workgroup (kMidDummyBytes) */ \
     if (br && NP_ == 8 && (g.br_rm & 1) == 0 && g.ncomp == 6 && npi <= 6) {   /* six output columns in an 8-slot tile: 2 x 3 per thread */ \
-        PZ_TRY(set_lds((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), lds));  \
-        hipLaunchKernelGGL((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), grid_, dim3(512), lds, M->stream, g); \
+        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), grid_, dim3(512), lds, M->stream, g)); \
         dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1,BRNEST=2,NCO=3> (%d ciphertexts per key value)", CT_, NP_, CT_);   \
     } else if (br && NP_ < 32 && (g.br_rm & 1) == 0) {   /* an even number of key rows per coefficient: the nested form of the product loop */ \
-        PZ_TRY(set_lds((k_mid128<CT_, NP_, false, false, true, false, (NP_ < 32 ? 2 : 0)>), lds));                     \
-        hipLaunchKernelGGL((k_mid128<CT_, NP_, false, false, true, false, (NP_ < 32 ? 2 : 0)>), grid_, dim3(512), lds, M->stream, g); \
+        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true, false, (NP_ < 32 ? 2 : 0)>), grid_, dim3(512), lds, M->stream, g)); \
         dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1,BRNEST=2> (%d ciphertexts per key value)", CT_, NP_, CT_);         \
     } else if (br) {                                                                                                   \
-        PZ_TRY(set_lds((k_mid128<CT_, NP_, false, false, true>), lds));                                                \
-        hipLaunchKernelGGL((k_mid128<CT_, NP_, false, false, true>), grid_, dim3(512), lds, M->stream, g);             \
+        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true>), grid_, dim3(512), lds, M->stream, g)); \
         dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1> (%d ciphertexts per key value)", CT_, NP_, CT_);                  \
     } else if (ds) {                                                                                                          \
         /* 16-slot tile with 16 terms on 16 inputs (external product) or 8 terms on <= 8 inputs (key switch): k_mid128r */     \
         bool done_ = false;                                                                                            \
         if constexpr (CT_ == 4 && NP_ == 16) {                                                                         \
             if (mid_r && g.ds_n == 16 && npi == 16) {                                                                  \
-                PZ_TRY(set_lds((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, true>), lds));                          \
-                hipLaunchKernelGGL((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g); \
+                PZ_TRY(launch_k((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g)); \
                 dispatch_note(M, "k_mid128r<CT=4,NP=16,NR=16,HALFIN=0,KR=%d,DS=1>", PZ_MIDR_KR);                       \
                 done_ = true;                                                                                          \
             } else if (mid_r && g.ds_n == 8 && npi <= 8 && npo > 8) {                                                  \
-                PZ_TRY(set_lds((k_mid128r<4, 16, false, 8, true, PZ_MIDR_KR, true>), lds));                            \
-                hipLaunchKernelGGL((k_mid128r<4, 16, false, 8, true, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g); \
+                PZ_TRY(launch_k((k_mid128r<4, 16, false, 8, true, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g)); \
                 dispatch_note(M, "k_mid128r<CT=4,NP=16,NR=8,HALFIN=1,KR=%d,DS=1>", PZ_MIDR_KR);                        \
                 done_ = true;                                                                                          \
             }                                                                                                          \
         }                                                                                                              \
         if (!done_) {                                                                                                  \
-            PZ_TRY(set_lds((k_mid128<CT_, NP_, false, true>), lds));                                                   \
-            hipLaunchKernelGGL((k_mid128<CT_, NP_, false, true>), grid_, dim3(512), lds, M->stream, g);                \
+            PZ_TRY(launch_k((k_mid128<CT_, NP_, false, true>), grid_, dim3(512), lds, M->stream, g)); \
             dispatch_note(M, "k_mid128<CT=%d,NP=%d,DS=1>", CT_, NP_);                                                  \
         }                                                                                                              \
     } else {                                                                                                           \
@@ -125,11 +115,9 @@ if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {   
         const size_t lds = ((size_t)4 * 16 * kMidRS + 384 + 32) * sizeof(cplx);
         const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));
         if (perm) {
-            PZ_TRY(set_lds((k_mid128r<4, 16, true, 16, false, PZ_MIDR_KR, false, true>), lds));
-            hipLaunchKernelGGL((k_mid128r<4, 16, true, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g);
+            PZ_TRY(launch_k((k_mid128r<4, 16, true, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g));
         } else {
-            PZ_TRY(set_lds((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, false, true>), lds));
-            hipLaunchKernelGGL((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g);
+            PZ_TRY(launch_k((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g));
         }
         dispatch_note(M, "k_mid128r<CT=4,NP=16,PERM=%d,NR=16,HALFIN=0,KR=%d,C2=1> (two output-column passes per tile of 4 ciphertexts)", (int)perm, PZ_MIDR_KR);
         PZ_HIP(hipGetLastError());
@@ -152,8 +140,11 @@ if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {   
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }
-int launch_mid(pz_module* M, int batch, const cplx* T, cplx* T2, const cplx* Pp, int npi, int npo, int nrows, int ncols, cplx* dummy,
-               unsigned perm_mul, unsigned perm_add, const MidDigits* dg, const MidBr* br, bool perm_conj) {
+int launch_mid(pz_module* M, int batch, const MidCall& c) {
+    const MidDigits* dg = c.digits;
+    const MidBr* br = c.br;
+    const int npi = c.npi, npo = c.npo, ncols = c.ncols;
+    int nrows = c.nrows;
     MidArgs g;
     g.br_lwe = nullptr; g.br_lwe_bs = 0; g.br_i0 = 0; g.br_blk = 0; g.br_rm = 0; g.w2n = M->w2n;
     if (br) {
@@ -167,17 +158,17 @@ int launch_mid(pz_module* M, int batch, const cplx* T, cplx* T2, const cplx* Pp,
         g.ds_n = dg->n;
         for (int t = 0; t < dg->n; ++t) { g.ds_in[t] = dg->in[t]; g.ds_row[t] = dg->row[t]; g.ds_coff[t] = dg->coff[t]; g.ds_cb[t] = dg->cb[t]; }
     }
-    g.perm_mul = perm_mul; g.perm_add = perm_add; g.perm_ysign = perm_conj ? -1.0 : 1.0; g.log_m1 = 0;
+    g.perm_mul = c.perm.mul; g.perm_add = c.perm.add; g.perm_ysign = c.perm.conj ? -1.0 : 1.0; g.log_m1 = 0;
     g.dbg = 0;
     while ((1 << g.log_m1) < M->plan.m1) ++g.log_m1;
-    const bool perm = perm_mul != 0;
-    g.T = T; g.T2 = T2; g.P = Pp; g.npi = npi; g.npo = npo; g.nrows = nrows; g.ncols = ncols;
+    const bool perm = c.perm.mul != 0;
+    g.T = c.T; g.T2 = c.T2; g.P = c.Pp; g.npi = npi; g.npo = npo; g.nrows = nrows; g.ncols = ncols;
     g.row_max = br ? nrows : std::min(nrows, npi);
     g.ncomp = std::min(npo, ncols);
     if ((ds ? g.ds_n : g.row_max) < 1)   // k_mid128 assumes at least one product term
         return fail(PZ_ERR_INVALID, "launch_mid: no product term (rows %d, npi %d, ds_n %d)", nrows, npi, g.ds_n);
     g.batch = batch; g.m1 = M->plan.m1; g.n_ct = 0;
-    g.wL2 = M->wL2; g.tw12t = M->tw12t; g.dummy = dummy;
+    g.wL2 = M->wL2; g.tw12t = M->tw12t; g.dummy = c.dummy;
     g.groups = 1; g.stagger = 0; g.stagger_mod = 0;
     if (M->plan.m2 == 128) return launch_mid128(M, g, batch, npi, npo, perm, ds, br != nullptr);
     return launch_mid256(M, g, batch);

@@ -35,11 +35,11 @@ int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap 
     if (npolys <= 0) return PZ_OK;
     AutoArgs g;
     g.src = src; g.dst = dst; g.add = add; g.sm = sm; g.dm = dm; g.am = am;
-    g.npolys = npolys; g.n = (int)M->n; g.mul = mul; g.flags = flags & 7;
-    if (dst16 && (flags & 16)) g.flags |= 16;   // (16-bit output only: `add` is subtracted)
+    g.npolys = npolys; g.n = (int)M->n; g.mul = mul; g.flags = flags & (AUTO_SIGN | AUTO_NEGATE | AUTO_ADD_FIRST);
+    if (dst16 && (flags & AUTO_SUB16)) g.flags |= 16;   // (16-bit output only: `add` is subtracted)
     g.dst16 = dst16; g.wide = M->wide16();
     g.cond_total = 0;
-    const bool cond = (flags & 32) != 0;   // the i64 fallback of the 16-bit body pre-pass: only if the flag is up (k_automorphism: cond_total)
+    const bool cond = (flags & AUTO_IF_WIDE) != 0;   // the i64 fallback of the 16-bit body pre-pass: only if the flag is up (k_automorphism: cond_total)
     g.t16_m1 = M->plan.f1a * M->plan.f1b; g.t16_cb = M->plan.cb; g.t16_m2sh = 0;
     while ((1 << g.t16_m2sh) < M->plan.m2) ++g.t16_m2sh;
     if (dst16) {   // 16-bit tile-order output (the spectral automorphism forms' body operand; dm addresses limbs of n int16)
@@ -48,8 +48,7 @@ int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap 
             return fail(PZ_ERR_UNSUPPORTED, "automorphism pre-pass: no 16-bit tile-order output on this plan");
         KTimer kt(M, PZ_K_ELEMENTWISE);
         const size_t lds = (size_t)M->n * sizeof(short);
-        PZ_TRY(set_lds(k_automorphism_t16, lds));
-        hipLaunchKernelGGL(k_automorphism_t16, dim3(npolys), dim3(1024), lds, M->stream, g);
+        PZ_TRY(launch_k(k_automorphism_t16, dim3(npolys), dim3(1024), lds, M->stream, g));
         PZ_HIP(hipGetLastError());
         return PZ_OK;
     }

@@ -41,8 +41,7 @@ int launch_mul_const_nz(pz_module* M, int batch, long long* res, long long res_b
     const long long threads = (long long)batch * npts;
     const size_t lds = (size_t)a_size * (form == 0 ? 1 : 2) * kMulConstBlock * sizeof(long long);
     KTimer kt(M, PZ_K_NORMALIZE);
-    PZ_TRY(set_lds(k_mul_const_nz, lds));
-    hipLaunchKernelGGL(k_mul_const_nz, dim3((unsigned)((threads + kMulConstBlock - 1) / kMulConstBlock)), dim3(kMulConstBlock), lds, M->stream, g);
+    PZ_TRY(launch_k(k_mul_const_nz, dim3((unsigned)((threads + kMulConstBlock - 1) / kMulConstBlock)), dim3(kMulConstBlock), lds, M->stream, g));
     dispatch_note(M, "k_mul_const_nz (form %d, a %d limbs x %d digits -> %d, lds=%zu)", form, a_size, arms[0].b_size, res_size, lds);
     PZ_HIP(hipGetLastError());
     return PZ_OK;
@@ -55,19 +54,20 @@ bool mid_cnv_pt_supported(const pz_module* M, int cols, int a_size, int b_size, 
     return on && (a_size == 8 || a_size == 16) && bs_ok && cols >= 2 && cols <= 3 && mid_cnv_supported(M, a_size, b_size, min_size) && min_size <= 32 &&
            ((size_t)mid_pt_rows(a_size, b_size, cols, min_size) * kMidPtRS + 256) * sizeof(cplx) <= (size_t)160 * 1024;
 }
-int launch_mid_cnv_pt(pz_module* M, int batch, const cplx* a_main, const cplx* a_last, const cplx* b_main, const cplx* b_last, bool b_shared, cplx* T2,
-                      int cols, int a_size, int b_size, int min_size, int offset) {
+int launch_mid_cnv_pt(pz_module* M, int batch, const MidCnvCall& c) {
+    const int cols = c.cols, a_size = c.a_size, b_size = c.b_size, min_size = c.min_size, offset = c.offset;
+    const bool b_shared = c.b_shared;
     if (batch <= 0 || min_size <= 0) return PZ_OK;
     if (!mid_cnv_pt_supported(M, cols, a_size, b_size, min_size)) return fail(PZ_ERR_INVALID, "k_mid_cnv_pt: shape outside the kernel");
     MidCnvPtArgs g;
-    g.a_main = a_main; g.a_last = a_last; g.b_main = b_main; g.b_last = b_last;
+    g.a_main = c.a_main; g.a_last = c.a_last; g.b_main = c.b_main; g.b_last = c.b_last;
     g.b_main_bs = b_shared ? 0 : (long long)(b_size - 1) * M->m;
     g.b_last_bs = b_shared ? 0 : (long long)M->m;
-    g.T2 = T2; g.cols = cols; g.min_size = min_size; g.offset = offset; g.m1 = M->plan.m1; g.batch = batch; g.wL2 = M->wL2; g.tw12t = M->tw12t;
+    g.T2 = c.T2; g.cols = cols; g.min_size = min_size; g.offset = offset; g.m1 = M->plan.m1; g.batch = batch; g.wL2 = M->wL2; g.tw12t = M->tw12t;
     const size_t lds = ((size_t)mid_pt_rows(a_size, b_size, cols, min_size) * kMidPtRS + 256) * sizeof(cplx);
     const dim3 grid((unsigned)((long long)batch * g.m1));
     KTimer kt(M, PZ_K_FUSED_MID);
-#define PZ_PT_LAUNCH(AS_, BS_) { PZ_TRY(set_lds((k_mid_cnv_pt<AS_, BS_>), lds)); hipLaunchKernelGGL((k_mid_cnv_pt<AS_, BS_>), grid, dim3(256), lds, M->stream, g); }
+#define PZ_PT_LAUNCH(AS_, BS_) { PZ_TRY(launch_k((k_mid_cnv_pt<AS_, BS_>), grid, dim3(256), lds, M->stream, g)); }
 #define PZ_PT_FORMS(AS_)                                                                                                          \
     {                                                                                                                             \
         if (b_size == AS_) PZ_PT_LAUNCH(AS_, AS_)                                                                                 \

@@ -79,8 +79,7 @@ int launch_small_idft(pz_module* M, int npolys, const double* a, PolyMap smap, l
     const dim3 grid((unsigned)((npolys + 1) / 2));
 #define X(M1_)                                                                                      \
     if (m1 == M1_) {                                                                                \
-        PZ_TRY(set_lds(k_small_idft<M1_>, lds));                                                    \
-        hipLaunchKernelGGL(k_small_idft<M1_>, grid, dim3(256), lds, M->stream, g);                  \
+        PZ_TRY(launch_k(k_small_idft<M1_>, grid, dim3(256), lds, M->stream, g));                    \
         PZ_HIP(hipGetLastError());                                                                  \
         return PZ_OK;                                                                               \
     }
@@ -102,8 +101,7 @@ int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap sma
     const dim3 grid((unsigned)((npolys + 1) / 2));
 #define X(M1_)                                                                                      \
     if (m1 == M1_) {                                                                                \
-        PZ_TRY(set_lds(k_small_fwd<M1_>, lds));                                                     \
-        hipLaunchKernelGGL(k_small_fwd<M1_>, grid, dim3(256), lds, M->stream, g);                   \
+        PZ_TRY(launch_k(k_small_fwd<M1_>, grid, dim3(256), lds, M->stream, g));                     \
         PZ_HIP(hipGetLastError());                                                                  \
         return PZ_OK;                                                                               \
     }
@@ -112,21 +110,24 @@ int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap sma
     return fail(PZ_ERR_UNSUPPORTED, "small-ring pipeline: m1 = %d", m1);
 }
 
-int launch_small_inv(pz_module* M, int batch, const cplx* S, const cplx* Pp, int npi, int nrows, int ncols, int cols_out, int ksz,
-                     long long* res, long long res_bs, int res_cols, int res_size, const long long* small, long long small_bs,
-                     int small_cols, int small_size, int base2k, int body_col, bool noprod, cplx* fwd_S, int fwd_limbs,
-                     bool au, unsigned au_p, int au_mode, bool post_rsh, int acc32) {
+int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c) {
     if (batch <= 0) return PZ_OK;
     PZ_TRY(ensure_small_tables(M));
+    const bool noprod = c.noprod, au = c.au, post_rsh = c.post_rsh;
+    const int ksz = c.key.ksz, cols_out = c.key.cols_out, base2k = c.res.base2k, fwd_limbs = c.fwd_limbs, au_mode = c.au_mode;
+    const unsigned au_p = c.au_p;
     SmallInvArgs g;
-    g.S = S; g.Pp = Pp; g.res = res; g.small = small; g.res_bs = res_bs; g.small_bs = small_bs;
-    g.batch = batch; g.npi = npi; g.nrows = nrows; g.ncols = ncols; g.cols_out = cols_out; g.ksz = ksz;
-    g.res_cols = res_cols; g.res_size = res_size; g.small_cols = small_cols; g.small_size = small_size; g.base2k = base2k; g.body_col = body_col;
+    g.S = c.S; g.Pp = c.key.Pp; g.res = c.res.p; g.small = c.small.p; g.res_bs = c.res.bs; g.small_bs = c.small.bs;
+    g.batch = batch; g.npi = c.key.npi; g.nrows = c.key.nrows; g.ncols = c.key.ncols; g.cols_out = cols_out; g.ksz = ksz;
+    g.res_cols = c.res.cols; g.res_size = c.res.size; g.small_cols = c.small.cols; g.small_size = c.small.size; g.base2k = base2k; g.body_col = c.small.body_col;
     g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv;
     g.margin = M->probe ? M->margin : nullptr;
-    if (acc32 && !(noprod && base2k <= 31)) return fail(PZ_ERR_INVALID, "small-ring pipeline: 32-bit accumulator digits need the product-free form and base2k <= 31");
-    g.acc32 = acc32;
-    g.S_out = fwd_S; g.tw1 = M->s_tw1; g.fwd_limbs = fwd_S ? fwd_limbs : 0;
+    // k_small_inv's own mask (device_small.hpp): bits 0 / 1 = 32-bit operand / result, bits 2 / 3 = 16-bit operand / result
+    g.acc32 = (c.small_digits == Digits::I32 ? 1 : 0) | (c.res_digits == Digits::I32 ? 2 : 0) | (c.small_digits == Digits::I16 ? 4 : 0) |
+              (c.res_digits == Digits::I16 ? 8 : 0);
+    const bool narrow = c.small_digits != Digits::I64 || c.res_digits != Digits::I64;
+    if (narrow && !(noprod && base2k <= 31)) return fail(PZ_ERR_INVALID, "small-ring pipeline: 32-bit accumulator digits need the product-free form and base2k <= 31");
+    g.S_out = c.fwd_S; g.tw1 = M->s_tw1; g.fwd_limbs = c.fwd_S ? fwd_limbs : 0;
     g.au_p = au_p; g.au_mode = au_mode; g.post_rsh = (post_rsh && au) ? 1 : 0;
     {   // p^-1 mod 2^32 by Newton steps (p odd), reduced mod 2n in the kernel
         unsigned x = au_p | 1u;
@@ -134,20 +135,16 @@ int launch_small_inv(pz_module* M, int batch, const cplx* S, const cplx* Pp, int
         g.au_pinv = x;
     }
     if (post_rsh && !(au && au_mode != 0 && base2k <= 29)) return fail(PZ_ERR_INVALID, "small-ring pipeline: shifted stores need an automorphism form with an operand, base2k <= 29");
-    if (au && (noprod || fwd_S || small == nullptr || small_cols != cols_out))
+    if (au && (noprod || c.fwd_S || c.small.p == nullptr || c.small.cols != cols_out))
         return fail(PZ_ERR_INVALID, "small-ring pipeline: the automorphism variant needs the key-switch operand");
-    if (fwd_S && !(noprod && fwd_limbs >= 1 && fwd_limbs <= ksz && fwd_limbs <= res_size && fwd_limbs <= 8))
+    if (c.fwd_S && !(noprod && fwd_limbs >= 1 && fwd_limbs <= ksz && fwd_limbs <= c.res.size && fwd_limbs <= 8))
         return fail(PZ_ERR_INVALID, "small-ring pipeline: forward transform of %d limbs behind the inverse of %d", fwd_limbs, ksz);
     const int m1 = small_m1(M);
     const size_t lds = ((size_t)ksz * m1 * small_inv_rs(m1, noprod) + kSmallM2 + m1) * sizeof(cplx);   // tile + wL2 + tw1inv
     // workgroup id -> (xcd = id & 7, slot = id >> 3): ciphertext (slot / cols_out) * 8 + xcd, column slot % cols_out
     const int grid = ((batch + 7) / 8) * 8 * cols_out;
     KTimer kt(M, PZ_K_FUSED_TAIL);
-#define XL(K_)                                                                                                \
-    {                                                                                                         \
-        PZ_TRY(set_lds((K_), lds));                                                                           \
-        hipLaunchKernelGGL((K_), dim3(grid), dim3(64 * m1), lds, M->stream, g);                               \
-    }
+#define XL(K_) { PZ_TRY(launch_k((K_), dim3(grid), dim3(64 * m1), lds, M->stream, g)); }
     // (the product-free form with the chained forward transform - the blind rotation's tail - exists for N <= 2048: at N = 4096 the rotation runs
     //  on the three-kernel pipeline, and these four instantiations carried 28 B of scratch each)
     if (noprod && g.fwd_limbs && m1 == 16) return fail(PZ_ERR_UNSUPPORTED, "small-ring pipeline: no chained forward transform at N = 4096");
@@ -186,23 +183,21 @@ bool small_one_supported(const pz_module* M, int npi, int nrows, int ncols, int 
     return (M->m % kSmallM2) == 0 && (m1 == 4 || (m1 == 8 && (npi > 4 || batch >= 3072 || (npi == 4 && ksz <= 2) || PZ_SMALL_ONE_ALL))) && cols_out == 2 && ksz >= 1 && ksz <= 4 && ncols == ksz * cols_out && npi >= 1 &&
            npi <= 8 && nrows >= 1;
 }
-int launch_small_one(pz_module* M, int batch, const long long* src, PolyMap smap, const cplx* Pp, int npi, int nrows, int ncols, int ksz, long long* res,
-                     long long res_bs, int res_cols, int res_size, const long long* small, long long small_bs, int small_cols, int small_size, int base2k,
-                     int body_col) {
+int launch_small_one(pz_module* M, int batch, const SmallOneCall& c) {
     if (batch <= 0) return PZ_OK;
     PZ_TRY(ensure_small_tables(M));
+    const int npi = c.key.npi, ksz = c.key.ksz;
     SmallOneArgs g;
-    g.src = src; g.smap = smap; g.Pp = Pp; g.res = res; g.small = small; g.res_bs = res_bs; g.small_bs = small_bs;
-    g.batch = batch; g.npi = npi; g.nrows = nrows; g.ncols = ncols; g.ksz = ksz;
-    g.res_cols = res_cols; g.res_size = res_size; g.small_cols = small_cols; g.small_size = small_size; g.base2k = base2k; g.body_col = body_col;
+    g.src = c.src; g.smap = c.smap; g.Pp = c.key.Pp; g.res = c.res.p; g.small = c.small.p; g.res_bs = c.res.bs; g.small_bs = c.small.bs;
+    g.batch = batch; g.npi = npi; g.nrows = c.key.nrows; g.ncols = c.key.ncols; g.ksz = ksz;
+    g.res_cols = c.res.cols; g.res_size = c.res.size; g.small_cols = c.small.cols; g.small_size = c.small.size; g.base2k = c.res.base2k; g.body_col = c.small.body_col;
     g.tw1 = M->s_tw1; g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv; g.margin = M->probe ? M->margin : nullptr;
     const int m1 = small_m1(M);
     const size_t lds = ((size_t)8 * m1 * kSmallRS + kSmallM2 + m1) * sizeof(cplx);   // tile of 8 polynomials + wL2 + tw1inv
     KTimer kt(M, PZ_K_FUSED_TAIL);
 #define X(M1_, KS_)                                                                                           \
     if (m1 == M1_ && ksz == KS_) {                                                                            \
-        PZ_TRY(set_lds((k_small_one<M1_, KS_>), lds));                                                        \
-        hipLaunchKernelGGL((k_small_one<M1_, KS_>), dim3(batch), dim3(512), lds, M->stream, g);               \
+        PZ_TRY(launch_k((k_small_one<M1_, KS_>), dim3(batch), dim3(512), lds, M->stream, g));                 \
         dispatch_note(M, "k_small_one<M1=%d,KS=%d> (one kernel per ciphertext, %d input polynomials)", M1_, KS_, npi); \
         PZ_HIP(hipGetLastError());                                                                            \
         return PZ_OK;                                                                                         \

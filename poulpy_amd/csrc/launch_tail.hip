@@ -11,13 +11,13 @@ namespace pz {
 
 // the two roles of k_inv_tail must be whole waves
 bool tail_supported(const pz_module* M) { return (M->plan.f1b * M->plan.cb) % 64 == 0; }
-bool tail_acc32_supported(const pz_module* M) {
+bool tail_narrow_supported(const pz_module* M) {
 #define X(A, B, C) if (M->plan.f1a == A && M->plan.f1b == B && M->plan.cb == C) return true;
     PZ_ACC32_CASES(X)
 #undef X
     return false;
 }
-bool tail_d16_only_supported(const pz_module* M) { return tail_rsh_supported(M) && tail_acc32_supported(M); }
+bool tail_d16_only_supported(const pz_module* M) { return tail_rsh_supported(M) && tail_narrow_supported(M); }
 bool tail_rsh_supported(const pz_module* M) {
 #define X(A, B, C) if (M->plan.f1a == A && M->plan.f1b == B && M->plan.cb == C) return true;
     PZ_RSH_CASES(X)
@@ -43,10 +43,13 @@ static TailArgs tail_args(const pz_module* M, const TailCall& c, int col_base, i
     g.nz_lsh = nz ? nz->lsh : 0; g.nz_res_end = nz ? nz->res_end : 0; g.nz_res_start = nz ? nz->res_start : 0; g.nz_a_end = nz ? nz->a_end : 0;
     g.nz_a_start = nz ? nz->a_start : 0; g.nz_zero_from = nz ? nz->zero_from : 0; g.nz_col = nz ? nz->col : 0; g.nz_mode = nz ? nz->mode : 0;
     for (int u = 0; u < 2; ++u) { g.nz_col2[u] = nz ? nz->col2[u] : 0; g.nz_mode2[u] = nz ? nz->mode2[u] : 0; }
-    g.acc32 = c.acc32;
+    // k_inv_tail's own mask (TailArgs, device_fft.hpp): bits 0 / 1 = 32-bit operand / result, bit 2 = the operand is a 16-bit GLWETensor,
+    // bits 3 / 4 = 16-bit operand / result
+    g.acc32 = (c.small_digits == Digits::I32 ? 1 : 0) | (c.res_digits == Digits::I32 ? 2 : 0) | (c.small16 ? 4 : 0) |
+              (c.small_digits == Digits::I16 ? 8 : 0) | (c.res_digits == Digits::I16 ? 16 : 0);
     g.xcd_map = 0;
     g.d16w = nz ? nz->d16.w : nullptr; g.d16a = nz ? nz->d16.ra : nullptr; g.d16b = nz ? nz->d16.rb : nullptr;
-    if (c.acc32 & 4) { g.d16a = c.small16; g.body_bs = c.small16_cs; }
+    if (c.small16) { g.d16a = c.small16; g.body_bs = c.small16_cs; }
     g.body16_wide = nullptr;
     if (c.body16) { g.d16a = c.body16; g.body_bs = (long long)c.body16_limbs * (long long)M->n; g.body16_wide = c.body16_wide; }
     return g;
@@ -69,9 +72,10 @@ static int launch_inv_tail_cols(pz_module* M, const TailCall& c, int col_base, i
     const bool has_small = c.small != nullptr;
     TailForm f;
     f.rowmajor = c.rowmajor; f.has_small = has_small;
-    if (c.acc32) {   // 32-bit accumulator digits: the plain every-column-operand form, nothing else
-        if (!(tail_acc32_supported(M) && c.rowmajor && has_small && c.small_all && !c.post_rsh && !raw && !nz && c.auto_mul == 0 && c.gather_mul == 0 &&
-              c.body_src == nullptr && c.base2k <= 31 && (!(c.acc32 & 4) || (c.acc32 == 4 && c.small16 != nullptr))))
+    const bool narrow = c.small_digits != Digits::I64 || c.res_digits != Digits::I64;
+    if (narrow || c.small16) {   // 32-bit accumulator digits: the plain every-column-operand form, nothing else
+        if (!(tail_narrow_supported(M) && c.rowmajor && has_small && c.small_all && !c.post_rsh && !raw && !nz && c.auto_mul == 0 && c.gather_mul == 0 &&
+              c.body_src == nullptr && c.base2k <= 31 && !(narrow && c.small16)))
             return fail(PZ_ERR_UNSUPPORTED, "fused tail: no 32-bit-accumulator variant for this call");
         f.kind = TailForm::ACC32;
     } else if (c.post_rsh && c.body16 && !has_small) {   // the 16-bit-operand form with the shifted store (glwe_trace's body column)
@@ -166,8 +170,11 @@ int launch_inv_tail(pz_module* M, const TailCall& c) {
 // the inverse column pass on the row-major T2' with vec_znx_normalize's same-base steps (bit offset res_offset, a.size = a_size limbs of which
 // the first nlimbs are transformed and the rest are zero) and NzCombine's stores into `res` (GLWE tensoring: raw inverse pass + normalize
 // kernel in one; TailArgs::nz)
-int launch_inv_tail_nz(pz_module* M, int batch, const cplx* T, int nlimbs, long long* res, long long res_bs, int res_cols, int res_size, int res_col,
-                       int base2k, long long res_offset, int a_size, const NzCombine* cb, const TailD16* d16) {
+int launch_inv_tail_nz(pz_module* M, int batch, const NzTailCall& s) {
+    const int nlimbs = s.nlimbs, res_size = s.res_size, base2k = s.base2k, a_size = s.a_size;
+    const long long res_offset = s.res_offset;
+    const NzCombine* cb = s.cb;
+    const TailD16* d16 = s.d16;
     const long long k = base2k;
     long long lsh = res_offset % k, lo = res_offset / k;
     if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
@@ -179,7 +186,7 @@ int launch_inv_tail_nz(pz_module* M, int batch, const cplx* T, int nlimbs, long 
     nz.a_end = (int)cl(lo, 0, a_size);
     nz.a_start = (int)cl((long long)res_size + lo, 0, a_size);
     nz.zero_from = nz.res_start - std::max(0, nz.a_start - std::max(nlimbs, nz.a_end));
-    nz.col = res_col;
+    nz.col = s.res_col;
     nz.mode = cb ? cb->mode : 1;
     for (int u = 0; u < 2; ++u) { nz.col2[u] = cb ? cb->col2[u] : 0; nz.mode2[u] = cb ? cb->mode2[u] : 0; }
     if (d16) {
@@ -188,8 +195,8 @@ int launch_inv_tail_nz(pz_module* M, int batch, const cplx* T, int nlimbs, long 
         nz.d16 = *d16;
     }
     TailCall c;
-    c.batch = batch; c.T = T; c.rowmajor = true; c.nlimbs = nlimbs; c.ncols = 1;
-    c.res = res; c.res_bs = res_bs; c.res_cols = res_cols; c.res_size = res_size; c.base2k = base2k;
+    c.batch = batch; c.T = s.T; c.rowmajor = true; c.nlimbs = nlimbs; c.ncols = 1;
+    c.res = s.res; c.res_bs = s.res_bs; c.res_cols = s.res_cols; c.res_size = res_size; c.base2k = base2k;
     return launch_inv_tail_cols(M, c, 0, 1, false, &nz);
 }
 
