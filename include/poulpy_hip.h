@@ -359,6 +359,26 @@ int pz_ggsw_expand_row_batched(pz_module* m, int64_t* ggsw, size_t dnum, const d
  * GGSW) -> `count` contiguous GGSWs: entries (row, 0) are copied from a.at(row, 0), then pz_ggsw_expand_row_batched. */
 int pz_ggsw_from_gglwe_batched(pz_module* m, int64_t* ggsw, const int64_t* a, size_t a_cols_in, size_t dnum,
                                const double* const* tsk_pmat, const pz_glwe_op_params* p, size_t count);
+/* CoreImpl glwe_automorphism_key_automorphism / _assign (poulpy-core/src/automorphism/gglwe_atk.rs:42-155) on `count` contiguous
+ * device GGLWEs `a` (automorphism keys of Galois element a_gal; MatZnx layout, rows = a_dnum, cols_in = rank, cols_out = rank+1,
+ * size = p->a_size) sharing one prepared automorphism key (device or host-resident): every entry (row < res_dnum, col) of `res`
+ * (rows = res_dnum <= a_dnum, size = p->res_size) becomes phi_g(glwe_keyswitch(phi_p(a.at(row, col)), key)), p = a_gal (odd),
+ * g = p^-1 mod 2N (:77-107).  p->rank_out = p->rank, p->res_base2k = p->a_base2k (asserted by the reference).  res == a with equal
+ * layouts is the _assign form.  The Galois element of the result is a_gal * key_gal mod 2N (res.set_p, :110): the applying key's own
+ * element takes no part in the arithmetic, the bindings return the product. */
+int pz_glwe_automorphism_key_automorphism_batched(pz_module* m, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum,
+                                                  int64_t a_gal, const double* key_pmat, const pz_glwe_op_params* p, size_t count);
+/* CoreImpl ggsw_keyswitch / _assign (poulpy-core/src/keyswitching/ggsw.rs:37-85) on `count` contiguous device GGSWs (MatZnx layout,
+ * rows = dnum, cols_in = cols_out = rank+1): entries (row, 0) go through glwe_keyswitch (:52-54, :80-82; kp describes that key
+ * switch, a's GLWE layout -> res's), then pz_ggsw_expand_row_batched on res (tsk_pmat, tp: its arguments).  res == a with equal
+ * layouts is the _assign form. */
+int pz_ggsw_keyswitch_batched(pz_module* m, int64_t* res, const int64_t* a, size_t dnum, const double* key_pmat,
+                              const double* const* tsk_pmat, const pz_glwe_op_params* kp, const pz_glwe_op_params* tp, size_t count);
+/* CoreImpl ggsw_automorphism / _assign (poulpy-core/src/automorphism/ggsw_ct.rs:32-82): the same with glwe_automorphism (PZ_AUTO,
+ * gal = key.p(); :54-56, :77-79) on the entries (row, 0), row < res_dnum <= a_dnum. */
+int pz_ggsw_automorphism_batched(pz_module* m, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, const double* key_pmat,
+                                 int64_t gal, const double* const* tsk_pmat, const pz_glwe_op_params* kp, const pz_glwe_op_params* tp,
+                                 size_t count);
 /* ---- convolution family (BASELINE configs[4], CKKS tensoring) ----------------------------- *
  * Bivariate convolution over Z[X, Y]/(X^N + 1), Y = 2^-base2k (poulpy-hal/src/api/convolution.rs; reference
  * poulpy-cpu-ref/src/reference/fft64/convolution.rs).  CnvPVecL / CnvPVecR (ScalarPrep = f64) are opaque prepared operands of

@@ -259,6 +259,25 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
     void ggsw_expand_row_batched(int64_t* ggsw, size_t dnum, const double* const* tsk, const pz_glwe_op_params& p, size_t count) {
         check(pz_ggsw_expand_row_batched(m_, ggsw, dnum, tsk, &p, count), "ggsw_expand_row_batched");
     }
+    // glwe_automorphism_key_automorphism (automorphism/gglwe_atk.rs:42-155) on `count` GGLWEs of Galois element a_gal; returns the Galois
+    // element of the result, a_gal * key_gal mod 2N (res.set_p, :110)
+    int64_t glwe_automorphism_key_automorphism_batched(int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, int64_t a_gal,
+                                                       const double* key, int64_t key_gal, const pz_glwe_op_params& p, size_t count) {
+        check(pz_glwe_automorphism_key_automorphism_batched(m_, res, res_dnum, a, a_dnum, a_gal, key, &p, count),
+              "glwe_automorphism_key_automorphism_batched");
+        const uint64_t mask = 2 * n() - 1;
+        return (int64_t)((((uint64_t)a_gal & mask) * ((uint64_t)key_gal & mask)) & mask);
+    }
+    // ggsw_keyswitch (keyswitching/ggsw.rs:37-85) / ggsw_automorphism (automorphism/ggsw_ct.rs:32-82) on `count` GGSWs: kp the key switch of
+    // the entries (row, 0), tsk / tp the arguments of ggsw_expand_row_batched
+    void ggsw_keyswitch_batched(int64_t* res, const int64_t* a, size_t dnum, const double* key, const double* const* tsk,
+                                const pz_glwe_op_params& kp, const pz_glwe_op_params& tp, size_t count) {
+        check(pz_ggsw_keyswitch_batched(m_, res, a, dnum, key, tsk, &kp, &tp, count), "ggsw_keyswitch_batched");
+    }
+    void ggsw_automorphism_batched(int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, const double* key, int64_t gal,
+                                   const double* const* tsk, const pz_glwe_op_params& kp, const pz_glwe_op_params& tp, size_t count) {
+        check(pz_ggsw_automorphism_batched(m_, res, res_dnum, a, a_dnum, key, gal, tsk, &kp, &tp, count), "ggsw_automorphism_batched");
+    }
     // GLWE x plaintext (mode PZ_MUL_PLAIN / PZ_MUL_PLAIN_ASSIGN) and GLWE x constant (PZ_MUL_CONST / PZ_MUL_CONST_ASSIGN; re / im on the host)
     size_t glwe_mul_plain_workspace_bytes(const pz_glwe_tensor_params& p, int mode, bool pt_shared, size_t batch) const {
         return pz_glwe_mul_plain_workspace_bytes(m_, &p, mode, pt_shared ? 1 : 0, batch);

@@ -196,6 +196,11 @@ struct GlweCall {
     // a16[column][ciphertext of this call][limb][n], a16_cs int16 elements between columns; `a` is not read
     const short* a16 = nullptr;
     long long a16_cs = 0;
+    // glwe_automorphism_key_automorphism, fast form (keyauto_entries below): a plain key switch by phi_g(key) - the row-sliced copy is read
+    // through ka_perm - whose carry chains run between the signs of X -> X^ka_p
+    bool keyauto = false;
+    unsigned ka_p = 0;
+    KeyPerm ka_perm;
     int cols_in() const { return s.cols_in; }
     int64_t* res_at(size_t b0) const { return res + (long long)b0 * res_bs; }
 };
@@ -234,6 +239,8 @@ static int wave_input(const GlweCall& c, size_t b0, int nb, int64_t* a_conv, DV*
 // the permuted copy of the key a pipeline reads: the pinned / mirrored one if the caller declared the key immutable, else built now
 static int wave_key(const GlweCall& c, cplx* scratch, bool small_ring, const cplx** out) {
     const size_t bytes = (size_t)c.nrows * c.ncols * (size_t)c.M->n * 8;
+    // (key composition: the slices of phi_g(key), built per call in the call's own scratch - never a pinned key's cached copy, and never into it)
+    if (c.keyauto) { PZ_TRY(launch_permute_pmat_gal(c.M, c.pmat, scratch, c.nrows * c.ncols, c.ka_perm)); *out = scratch; return PZ_OK; }
     for (auto& pk : c.M->pinned)
         if (pk.key == (const void*)c.pmat && pk.sliced && pk.bytes == bytes) { *out = pk.sliced; return PZ_OK; }
     // the key arrives in the standard device layout; its row-sliced copy is rebuilt per call (2 x 128 MiB of traffic at the metric
@@ -459,6 +466,20 @@ static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int
     return PZ_OK;
 }
 
+// Key composition, fast form.  For one entry the reference computes phi_g(normalize(KS_K(phi_p(a)))), g = p^-1 (gglwe_atk.rs:77-107).  phi is a
+// ring automorphism, so with the limbs of `a` entering the product as they are (dsize 1, one base2k)
+//   phi_g(sum_j phi_p(a_j) K_j + phi_p(a_0)) = sum_j a_j phi_g(K_j) + a_0 :
+// the big value at the NATURAL index is a plain key switch of the unpermuted `a` by phi_g(K) (wave_key / KeyPerm), body operand a_0 as it is.
+// The carry chain does not commute with phi's signs (normalize(-x) != -normalize(x) on the tie 2^(base2k-1)): the reference normalizes
+// phi_p(B) and permutes back, i.e. s .* normalize(s .* B) per coefficient with s(i) the sign phi_p gives source index i - auto_mul = p in
+// front of the chain, post_neg behind it, no index map anywhere.
+static int wave_keyauto_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av) {
+    TailCall t = wave_tail(c, nb, f.T2, b0);
+    tail_operand(t, av, false);
+    t.auto_mul = c.ka_p; t.post_neg = true; t.keyauto = true;
+    return launch_inv_tail(c.M, t);
+}
+
 static int glwe_fused(const GlweCall& c) {
     pz_module* M = c.M;
     FusedBufs f;
@@ -499,7 +520,8 @@ static int glwe_fused(const GlweCall& c) {
             mc.perm = sp; mc.digits = c.digits ? &dg : nullptr;
             PZ_TRY(launch_mid(M, nb, mc));
         }
-        if (sp.on) PZ_TRY(wave_spectral_tail(c, f, b0, nb, av));
+        if (c.keyauto) PZ_TRY(wave_keyauto_tail(c, f, b0, nb, av));
+        else if (sp.on) PZ_TRY(wave_spectral_tail(c, f, b0, nb, av));
         else if (c.cross_out) PZ_TRY(wave_cross_base_tail(c, f, b0, nb, av));
         else PZ_TRY(wave_plain_tail(c, f, b0, nb, av));
     }
@@ -749,6 +771,7 @@ int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const d
     if (batch == 0) return PZ_OK;
     // dsize > 1 (digit-selected product inside the middle kernel) and res_base2k != key_base2k (the tail normalizes into the key's base,
     // one cross-base pass follows) ride on the fused pipeline too; both need the 128-point-row plans and no automorphism (fused_applies)
+    // (keyauto_entries below enters glwe_fused directly, with GlweCall::keyauto set, where keyauto_fast_applies says this line would take it)
     if (fused_applies(M, p, c.s, kind)) return glwe_fused(c);
     if (small_ring_applies(M, p, c.s, kind, lay == nullptr)) return glwe_small_ring(c);
     return glwe_unfused(c);
@@ -986,6 +1009,143 @@ int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64
     for (size_t s = 0; s < nsteps && gals && key_pmats; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
     graph_key_module(M, k);
     return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch); });
+}
+}  // extern "C"
+
+// ------------------------------------------------------------------------------
+// glwe_automorphism_key_automorphism (automorphism/gglwe_atk.rs:42-155), ggsw_keyswitch (keyswitching/ggsw.rs:37-85), ggsw_automorphism
+// (automorphism/ggsw_ct.rs:32-82)
+// ------------------------------------------------------------------------------
+// the spectrum of phi_g(K) read from the spectrum of K (evaluation points w^(4q+1)): index q' holds K[g q' + (g-1)/4] for g = 1 mod 4,
+// the conjugate of K[-g q' - (g+1)/4] for g = 3 mod 4 - the map spectral_perm applies on the middle kernel's stores, here on the key
+static KeyPerm key_perm(unsigned g, unsigned mm) {
+    KeyPerm kp;
+    if ((g & 3u) == 1u) {
+        kp.mul = g & (mm - 1u);
+        kp.add = ((g - 1u) >> 2) & (mm - 1u);
+    } else {
+        kp.conj = true;
+        kp.mul = (mm - (g & (mm - 1u))) & (mm - 1u);
+        kp.add = (mm - (((g + 1u) >> 2) & (mm - 1u))) & (mm - 1u);
+    }
+    return kp;
+}
+// Route table: the fast form where the limbs of `a` reach the forward transform as they are and the three-kernel pipeline of
+// a 128-point-row plan runs the key switch - dsize 1, one base2k, not the N = 4096 two-kernel path, every stage on
+// Off by default: no rate of the fast form against the composition has been measured yet - POULPY_DBG_KEYAUTO_SPECTRAL=1 selects it
+constexpr int kKeyautoSpectralDefault = 0;
+static bool keyauto_fast_applies(const GlweCall& c) {
+    const bool env_on = (rt_knob("POULPY_DBG_KEYAUTO_SPECTRAL", kKeyautoSpectralDefault) != 0);   // (read per call: once per GGLWE batch, and tests flip it)
+    const pz_module* M = c.M;
+    return env_on && M->plan.m2 == 128 && M->dbg_stages == 7 && !c.digits && !c.cross_out && !c.s.convert &&
+           fused_applies(M, c.p, c.s, GlweKind::KeySwitch) && !n4096_two_kernel(c);
+}
+// `batch` packed entries: res[e] = phi_g(glwe_keyswitch(phi_p(a[e]), key)), p = a_gal, g = p^-1 mod 2N
+static int keyauto_entries(pz_module* M, int64_t* res, const int64_t* a, const double* key, const pz_glwe_op_params* p, size_t batch, int64_t a_gal) {
+    GlweCall c;
+    PZ_TRY(glwe_call_init(c, M, GlweKind::KeySwitch, res, a, key, p, batch, nullptr, nullptr, nullptr));
+    if (batch == 0) return PZ_OK;
+    const unsigned g = inv_mod_2n((long long)a_gal, c.n);
+    if (keyauto_fast_applies(c)) {
+        c.keyauto = true;
+        c.ka_p = (unsigned)((unsigned long long)a_gal & (2ull * (unsigned long long)c.n - 1ull));
+        c.ka_perm = key_perm(g, (unsigned)M->m);
+        dispatch_note(M, "key composition: key switch by the permuted key (spectral form)");
+        return glwe_fused(c);
+    }
+    // composition: phi_p of every entry into the second workspace (before anything is written: in-place calls included), then the
+    // automorphism family in mode 0 with the inverse element
+    dispatch_note(M, "key composition: automorphism + glwe_automorphism (composition)");
+    PZ_TRY(ws2_reserve(M, batch * (size_t)c.a_ct * 8));
+    int64_t* tmp = (int64_t*)M->ws2;
+    const int polys = c.s.cols_a * (int)p->a_size;
+    PolyMap pm{1, polys, c.a_ct, 0, c.n, 0};
+    PZ_TRY(launch_automorphism(M, (int)batch * polys, (const long long*)a, pm, (long long*)tmp, pm, g, AUTO_SIGN));
+    AutoSpec au{(long long)g, 0};
+    return glwe_op(M, GlweKind::Automorphism, res, tmp, key, p, batch, &au);
+}
+
+extern "C" {
+int pz_glwe_automorphism_key_automorphism_batched(pz_module* M, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, int64_t a_gal,
+                                                  const double* key_pmat, const pz_glwe_op_params* p, size_t count) {
+    // (the argument checks that need no module come first)
+    PZ_REQUIRE(p != nullptr, "null params");
+    PZ_REQUIRE((a_gal & 1) != 0, "glwe_automorphism_key_automorphism: the Galois element of the input key must be odd");
+    PZ_REQUIRE(res_dnum >= 1 && res_dnum <= a_dnum, "glwe_automorphism_key_automorphism: res has more rows than a (or none)");
+    PZ_REQUIRE(p->res_base2k == p->a_base2k, "glwe_automorphism_key_automorphism: res and a share one base2k");
+    PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_automorphism_key_automorphism: the keys map rank -> rank");
+    PZ_ENTER(M);
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
+    if ((const void*)res == (const void*)a)
+        PZ_REQUIRE(res_dnum == a_dnum && p->res_size == p->a_size, "in-place call with different layouts for a and res");
+    const size_t rank = p->rank, cols = rank + 1;
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, key_pmat, (size_t)M->n * 8 * p->dnum * rank * cols * p->key_size, &key));
+    const long long a_ct = (long long)M->n * (long long)cols * (long long)p->a_size, res_ct = (long long)M->n * (long long)cols * (long long)p->res_size;
+    // rows of `a` beyond res_dnum are not computed: one call over everything when the row counts agree, else one per GGLWE
+    if (res_dnum == a_dnum || count <= 1) PZ_TRY(keyauto_entries(M, res, a, key, p, count * res_dnum * rank, a_gal));
+    else
+        for (size_t i = 0; i < count; ++i)
+            PZ_TRY(keyauto_entries(M, res + (long long)(i * res_dnum * rank) * res_ct, a + (long long)(i * a_dnum * rank) * a_ct, key, p,
+                                   res_dnum * rank, a_gal));
+    return finish_call(M, false);
+}
+
+// entries (row, 0) of `count` GGSWs through glwe_keyswitch (ggsw.rs:52-54, :80-82), then ggsw_expand_row on res
+int pz_ggsw_keyswitch_batched(pz_module* M, int64_t* res, const int64_t* a, size_t dnum, const double* key_pmat, const double* const* tsk_pmat,
+                              const pz_glwe_op_params* kp, const pz_glwe_op_params* tp, size_t count) {
+    PZ_REQUIRE(kp != nullptr && tp != nullptr && tsk_pmat != nullptr, "null params");
+    PZ_REQUIRE(dnum >= 1, "ggsw_keyswitch: empty GGSW");
+    PZ_REQUIRE(tp->rank == kp->rank_out && tp->res_size == kp->res_size && tp->res_base2k == kp->res_base2k,
+               "ggsw_keyswitch: the expansion's parameters describe res");
+    PZ_ENTER(M);
+    PZ_REQUIRE(kp->a_size >= 1 && kp->res_size >= 1 && kp->key_size >= 1 && kp->dnum >= 1, "glwe op: empty shape");
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
+    const long long n = (long long)M->n;
+    const long long a_row = n * (long long)(kp->rank + 1) * (long long)(kp->rank + 1) * (long long)kp->a_size;
+    const long long res_row = n * (long long)(kp->rank_out + 1) * (long long)(kp->rank_out + 1) * (long long)kp->res_size;
+    if ((const void*)res == (const void*)a) PZ_REQUIRE(a_row == res_row, "in-place call with different layouts for a and res");
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, key_pmat, (size_t)n * 8 * kp->dnum * kp->rank * (kp->rank_out + 1) * kp->key_size, &key));
+    OpLayout lay{a_row, res_row, 0};
+    PZ_TRY(glwe_op(M, GlweKind::KeySwitch, res, a, key, kp, count * dnum, nullptr, &lay));
+    PZ_TRY(ggsw_expand_row(M, res, dnum, tsk_pmat, tp, count));   // (the module lock is not recursive)
+    return finish_call(M, false);
+}
+
+// entries (row, 0), row < res_dnum, of `count` GGSWs through glwe_automorphism (ggsw_ct.rs:54-56, :77-79), then ggsw_expand_row on res.  The
+// automorphism family takes packed ciphertexts: the entries are staged through a packed copy in the second workspace.
+int pz_ggsw_automorphism_batched(pz_module* M, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, const double* key_pmat, int64_t gal,
+                                 const double* const* tsk_pmat, const pz_glwe_op_params* kp, const pz_glwe_op_params* tp, size_t count) {
+    PZ_REQUIRE(kp != nullptr && tp != nullptr && tsk_pmat != nullptr, "null params");
+    PZ_REQUIRE((gal & 1) != 0, "ggsw_automorphism: the Galois element must be odd");
+    PZ_REQUIRE(res_dnum >= 1 && res_dnum <= a_dnum, "ggsw_automorphism: res has more rows than a (or none)");
+    PZ_REQUIRE(kp->rank_out == kp->rank && tp->rank == kp->rank && tp->res_size == kp->res_size && tp->res_base2k == kp->res_base2k,
+               "ggsw_automorphism: rank -> rank, and the expansion's parameters describe res");
+    PZ_ENTER(M);
+    PZ_REQUIRE(kp->a_size >= 1 && kp->res_size >= 1 && kp->key_size >= 1 && kp->dnum >= 1, "glwe op: empty shape");
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
+    if ((const void*)res == (const void*)a)
+        PZ_REQUIRE(res_dnum == a_dnum && kp->res_size == kp->a_size, "in-place call with different layouts for a and res");
+    if (count == 0) return finish_call(M, false);
+    const long long n = (long long)M->n;
+    const size_t cols = kp->rank + 1;
+    const long long a_ct = n * (long long)cols * (long long)kp->a_size, res_ct = n * (long long)cols * (long long)kp->res_size;
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, key_pmat, (size_t)n * 8 * kp->dnum * kp->rank * cols * kp->key_size, &key));
+    const size_t ent = count * res_dnum;
+    PZ_TRY(ws2_reserve(M, align256(ent * (size_t)a_ct * 8) + ent * (size_t)res_ct * 8));
+    int64_t* pa = (int64_t*)M->ws2;
+    int64_t* pr = (int64_t*)((char*)M->ws2 + align256(ent * (size_t)a_ct * 8));
+    for (size_t i = 0; i < count; ++i)
+        PZ_TRY(launch_ew(M, EW_COPY, pa + (long long)(i * res_dnum) * a_ct, a_ct, n, a + (long long)(i * a_dnum) * (long long)cols * a_ct,
+                         (long long)cols * a_ct, n, nullptr, 0, 0, (int)(cols * kp->a_size), (int)res_dnum));
+    AutoSpec au{(long long)gal, 0};
+    PZ_TRY(glwe_op(M, GlweKind::Automorphism, pr, pa, key, kp, ent, &au));
+    PZ_TRY(launch_ew(M, EW_COPY, res, (long long)cols * res_ct, n, pr, res_ct, n, nullptr, 0, 0, (int)(cols * kp->res_size), (int)ent));
+    PZ_TRY(ggsw_expand_row(M, res, res_dnum, tsk_pmat, tp, count));
+    return finish_call(M, false);
 }
 }  // extern "C"
 

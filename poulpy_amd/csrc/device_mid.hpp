@@ -1412,4 +1412,37 @@ k_permute_pmat(const cplx* __restrict__ P, cplx* __restrict__ Pp, int npolys, in
     Pp[((long long)(tq1 * 16 + ty) * npolys + p) * m2 + tq2 * 16 + tx] = tile[tx][ty];
 }
 
+// The same re-slicing of phi_g(key), g odd (m2 = 128 plans): the spectrum of X -> X^g is an affine map of the spectrum index,
+//   P'[q1'][p][q2'] = P[p][(mul q' + add) mod m],  q' = q1' + m1 q2'     (conjugated, CONJ, for g = 3 mod 4; KeyPerm in internal.hpp)
+// and since m1 divides m the map sends frequency rows to frequency rows: q1 = (mul q1' + add) mod m1.  A workgroup takes 16 source rows
+// q1 of one polynomial (256-byte runs of the standard layout) through LDS and writes their 16 destination rows, 2 KiB runs each - both
+// sides coalesced, no pass over the ciphertexts.  mul_inv = mul^-1 mod m1.
+template <bool CONJ>
+__global__ void __launch_bounds__(256)
+k_permute_pmat_gal(const cplx* __restrict__ P, cplx* __restrict__ Pp, int npolys, int m1, unsigned mul, unsigned add, unsigned mul_inv) {
+    constexpr int M2 = 128;
+    __shared__ cplx tile[M2][17];
+    const int tiles_q1 = m1 / 16;
+    const int tq1 = blockIdx.x % tiles_q1, p = blockIdx.x / tiles_q1;
+    const unsigned m = (unsigned)m1 * M2;
+    const cplx* src = P + (long long)p * m + tq1 * 16;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = threadIdx.x + 256 * i;
+        tile[e >> 4][e & 15] = src[(long long)(e >> 4) * m1 + (e & 15)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = threadIdx.x + 256 * i;
+        const int q2d = e & (M2 - 1), ql = e >> 7;
+        const unsigned q1 = (unsigned)(tq1 * 16 + ql);
+        const unsigned q1d = (mul_inv * (q1 - add)) & (unsigned)(m1 - 1);
+        const unsigned q = (mul * (q1d + (unsigned)m1 * (unsigned)q2d) + add) & (m - 1u);   // (q mod m1 == q1)
+        cplx v = tile[q / (unsigned)m1][ql];
+        if (CONJ) v.y = -v.y;
+        Pp[((long long)q1d * npolys + p) * M2 + q2d] = v;
+    }
+}
+
 }  // namespace pz

@@ -106,6 +106,7 @@ struct TailCall {
     unsigned auto_mul = 0;            // != 0: the value enters the chain as s(n) (big + small), s(n) = -1 iff (n auto_mul) mod 2N >= N
     bool auto_neg = false;            // flips every s(n)
     bool post_neg = false;            // put s(n) back on the digits (plain form: phi acts on the normalized value)
+    bool keyauto = false;             // key switch by a permuted key (wave_keyauto_tail): every column's chain between the signs of auto_mul, body operand as it is
     unsigned gather_mul = 0;          // != 0: the operand is -+phi^-1(small), gathered inside the tail (older, non-spectral scheme)
     bool gather_neg = false;
     // ---- blind rotation's accumulator between two blocks: 32-bit digits at the same element strides, or 16-bit digits in the tail's tile order ----
@@ -166,6 +167,10 @@ int launch_inv_tail_nz(pz_module* M, int batch, const NzTailCall& c);
 constexpr size_t kMidDummyBytes = (size_t)256 * 64 * 128 * sizeof(cplx) + (1 << 20);
 bool mid_supported(const pz_module* M, int npi, int npo);
 int launch_permute_pmat(pz_module* M, const double* P, cplx* Pp, int npolys);
+// the row-sliced copy of phi_g(key), g odd: spectrum index q' of the copy reads index (mul q' + add) mod m of the key, conjugated if conj
+// (m2 = 128 plans; key_perm in api_glwe.hip derives the map from g)
+struct KeyPerm { unsigned mul = 1, add = 0; bool conj = false; };
+int launch_permute_pmat_gal(pz_module* M, const double* P, cplx* Pp, int npolys, const KeyPerm& kp);
 // mul != 0: spectrum permutation of X -> X^p folded into the middle kernel (m2 = 128 plans only; see MidArgs and spectral_perm in api_glwe.hip);
 // conj: the spectrum of phi(a) is the conjugate of the permuted one (p = 3 mod 4)
 struct SpectralPerm { bool on = false; unsigned mul = 0, add = 0; bool conj = false; };

@@ -21,6 +21,21 @@ int launch_permute_pmat(pz_module* M, const double* P, cplx* Pp, int npolys) {
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }
+// the row-sliced copy of phi_g(key) (k_permute_pmat_gal; 128-point-row plans)
+int launch_permute_pmat_gal(pz_module* M, const double* P, cplx* Pp, int npolys, const KeyPerm& kp) {
+    const FftPlan& pl = M->plan;
+    if (pl.m2 != 128 || (pl.m1 % 16) != 0) return fail(PZ_ERR_UNSUPPORTED, "permuted key slicing: 128-point-row plans only");
+    const unsigned m = (unsigned)pl.m1 * 128u;
+    if (!(kp.mul & 1u) || kp.mul >= m || kp.add >= m) return fail(PZ_ERR_INVALID, "permuted key slicing: not an index map of this ring");
+    unsigned inv = kp.mul;   // Newton steps for mul^-1 mod 2^32 (mul odd: 3 correct bits to start with)
+    for (int i = 0; i < 5; ++i) inv *= 2u - kp.mul * inv;
+    const int blocks = npolys * (pl.m1 / 16);
+    KTimer kt(M, PZ_K_ELEMENTWISE);
+    if (kp.conj) hipLaunchKernelGGL(k_permute_pmat_gal<true>, dim3(blocks), dim3(256), 0, M->stream, reinterpret_cast<const cplx*>(P), Pp, npolys, pl.m1, kp.mul, kp.add, inv);
+    else hipLaunchKernelGGL(k_permute_pmat_gal<false>, dim3(blocks), dim3(256), 0, M->stream, reinterpret_cast<const cplx*>(P), Pp, npolys, pl.m1, kp.mul, kp.add, inv);
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
 // m2 = 256 plans: k_mid, two ciphertexts per tile (one ciphertext per tile, two workgroups per CU, measured slower: NOTEBOOK.md section 4)
 static int launch_mid256(pz_module* M, MidArgs g, int batch) {
     constexpr int CT = 2;

@@ -116,6 +116,21 @@ static int launch_inv_tail_cols(pz_module* M, const TailCall& c, int col_base, i
 // variant that prefetches it (more registers, one workgroup less per CU), the other columns the plain one.
 int launch_inv_tail(pz_module* M, const TailCall& c) {
     if (c.post_rsh && !(c.small != nullptr && c.small_all)) return fail(PZ_ERR_UNSUPPORTED, "fused tail: shifted store needs an operand per column");
+    // key switch by a permuted key (glwe_automorphism_key_automorphism, wave_keyauto_tail in api_glwe.hip): the carry chain of every column runs
+    // between the signs of X -> X^p, s .* normalize(s .* big) - the body column on the operand variant (a0 at the natural index), the others
+    // on the sign-only variant of the f64 chain
+    if (c.keyauto) {
+        if (!(c.small != nullptr && !c.small_all && c.auto_mul != 0 && c.post_neg && c.ncols > 1 && c.rowmajor && !c.post_rsh && c.gather_mul == 0 &&
+              c.body_src == nullptr && !c.body16))
+            return fail(PZ_ERR_INVALID, "fused tail: the permuted-key form takes the plain key switch's operand and the signs of auto_mul, nothing else");
+        // (N = 4096 has no sign-only instantiation: every column on the operand variant, which only finds an operand on the body column)
+        if (!tail_rsh_supported(M)) return launch_inv_tail_cols(M, c, 0, c.ncols);
+        PZ_TRY(launch_inv_tail_cols(M, c, c.body_col, 1));
+        TailCall rest = c;
+        rest.small = nullptr; rest.small_bs = 0; rest.small_size = 0;
+        if (c.body_col > 0) PZ_TRY(launch_inv_tail_cols(M, rest, 0, c.body_col));
+        return launch_inv_tail_cols(M, rest, c.body_col + 1, c.ncols - 1 - c.body_col);
+    }
     if (c.small != nullptr && !c.small_all && c.ncols > 1) {
         TailCall body = c;       // the body column: operand, and the signs that go with it
         body.gather_mul = 0; body.gather_neg = false; body.body_src = nullptr; body.body_bs = body.body_ls = 0;

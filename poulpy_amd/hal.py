@@ -443,6 +443,26 @@ class Module:
         arr = _ptrs(tsk_pmats)
         self._ck(self.lib.pz_ggsw_expand_row_batched(self.handle, ggsw, dnum, arr, C.byref(params), count))
 
+    def glwe_automorphism_key_automorphism_batched(self, res: c_void_p, res_dnum: int, a: c_void_p, a_dnum: int, a_gal: int, key_pmat: c_void_p,
+                                                   key_gal: int, params: GlweOpParams, count: int = 1) -> int:
+        """automorphism/gglwe_atk.rs:42-155 on `count` contiguous device GGLWEs of Galois element a_gal (res == a: the _assign form); returns
+        the Galois element of the result, a_gal * key_gal mod 2N (res.set_p, :110)."""
+        self._ck(self.lib.pz_glwe_automorphism_key_automorphism_batched(self.handle, res, res_dnum, a, a_dnum, a_gal, key_pmat, C.byref(params), count))
+        return (int(a_gal) * int(key_gal)) % (2 * self.n())
+
+    def ggsw_keyswitch_batched(self, res: c_void_p, a: c_void_p, dnum: int, key_pmat: c_void_p, tsk_pmats, ks_params: GlweOpParams,
+                               tsk_params: GlweOpParams, count: int = 1):
+        """keyswitching/ggsw.rs:37-85 on `count` contiguous device GGSWs: glwe_keyswitch on the entries (row, 0), then ggsw_expand_row."""
+        arr = _ptrs(tsk_pmats)
+        self._ck(self.lib.pz_ggsw_keyswitch_batched(self.handle, res, a, dnum, key_pmat, arr, C.byref(ks_params), C.byref(tsk_params), count))
+
+    def ggsw_automorphism_batched(self, res: c_void_p, res_dnum: int, a: c_void_p, a_dnum: int, key_pmat: c_void_p, gal: int, tsk_pmats,
+                                  ks_params: GlweOpParams, tsk_params: GlweOpParams, count: int = 1):
+        """automorphism/ggsw_ct.rs:32-82 on `count` contiguous device GGSWs: glwe_automorphism on the entries (row, 0), then ggsw_expand_row."""
+        arr = _ptrs(tsk_pmats)
+        self._ck(self.lib.pz_ggsw_automorphism_batched(self.handle, res, res_dnum, a, a_dnum, key_pmat, gal, arr, C.byref(ks_params),
+                                                       C.byref(tsk_params), count))
+
     def glwe_external_product_batched(self, res: c_void_p, a: c_void_p, ggsw_pmat: c_void_p, params: GlweOpParams, batch: int):
         self._ck(self.lib.pz_glwe_external_product_batched(self.handle, res, a, ggsw_pmat, C.byref(params), batch))
 
