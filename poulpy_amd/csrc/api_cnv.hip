@@ -466,6 +466,7 @@ int pz_glwe_tensor_mul_relinearize_batched(pz_module* M, int64_t* res, const int
     static constexpr long long t16_phase = 768 * 1024 / 2;
     const long long t16_cs = (long long)chunk * t.res_size * w.n + t16_phase;
     PZ_TRY(ws2_reserve(M, compact ? (size_t)t16_cs * t.tcols * 2 : chunk * (size_t)tensor_ct * 8));
+    if (compact) dispatch_note(M, "glwe_tensor_mul_relinearize: 16-bit tensor in tile order");
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = std::min(chunk, batch - b0);
         int64_t* r0 = res + (long long)b0 * res_ct;

@@ -1,7 +1,11 @@
 """Cases for the encrypt / operate / decrypt tests (tests/ only): poulpy-core's core_backend_test_suite! procedures
 (poulpy-core/src/test_suite/mod.rs:26-88) as case builders, their negative controls, and the oracle runner and noise check that
 tests/test_core_semantics.py (oracle) and tests/test_gpu_core_semantics.py (device) share.  The builders call neither the oracle nor the
-device: keys and ciphertexts come from tests/fhe_sk.py, and each case carries what every output must decrypt to and the reference's bound."""
+device: keys and ciphertexts come from tests/fhe_sk.py, and each case carries what every output must decrypt to and the reference's bound.
+
+The other families built the same way: tests/key_ops_cases.py (automorphism-key composition, the GGSW forms), tests/tensor_cases.py
+(tensoring, relinearization, the one-call multiply, the plaintext and constant products) and tests/trace_cases.py (trace, packing).  LWE
+conversions and blind rotation remain."""
 from __future__ import annotations
 
 import math

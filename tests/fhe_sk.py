@@ -256,3 +256,119 @@ def keyswitch_bound(n, k_ksk, dnum, dsize, key_base2k, rank_in) -> float:
 def external_product_bound(n, base2k, rank, k_in, k_ggsw) -> float:
     """The bound of external_product/glwe_ct.rs:133-152 (message X^k, var_msg = 1/n); base2k = key_base2k * max_dsize there."""
     return noise_ggsw_product(n, base2k, 0.5, 1.0 / n, SIGMA * SIGMA, 1.0 / 12.0, SIGMA * SIGMA, 0.0, rank, k_in, k_ggsw) + 1.0
+
+
+def var_noise_gglwe_product(n, base2k, var_xs, var_msg, var_a_err, var_gct_err_lhs, var_gct_err_rhs, rank_in, a_logq, b_logq):
+    """noise/mod.rs:18-46 (the form trace.rs:133-147 calls)"""
+    a_logq = min(a_logq, b_logq)
+    a_cols = -(-a_logq // base2k)
+    b_scale = 2.0 ** b_logq
+    a_scale = 2.0 ** (b_logq - a_logq)
+    var_base = (2.0 ** base2k) ** 2 / 12.0
+    noise = a_cols * n * var_base * (var_gct_err_lhs + var_xs * var_gct_err_rhs)
+    noise += var_msg * var_a_err * a_scale * a_scale * n
+    noise *= rank_in
+    return noise / (b_scale * b_scale)
+
+
+# ---- messages and their exact products ----
+def encode(data: np.ndarray, base2k: int, k_pt: int, size: int) -> np.ndarray:
+    """encode_vec_i64 (poulpy-hal/src/layouts/encoding.rs:17-57): data 2^-k_pt as (size, n) normalized limbs at base2k; the data sit in
+    limb ceil(k_pt / base2k) - 1, shifted up by the bits that limb has below 2^-k_pt."""
+    data = np.asarray(data, dtype=np.int64)
+    used = limbs_for(k_pt, base2k)
+    assert used <= size
+    pt = np.zeros((size, data.shape[-1]), dtype=np.int64)
+    pt[used - 1] = data << (used * base2k - k_pt)
+    return normalize(pt, base2k)
+
+
+def mul_exact(a, b_int: np.ndarray) -> np.ndarray:
+    """The schoolbook negacyclic product on Python ints: a any integers ((n,) object array or int64), b int64; (n,) object array."""
+    ao = np.asarray(a).astype(object)
+    b = np.asarray(b_int, dtype=np.int64)
+    n = ao.shape[-1]
+    assert ao.shape == (n,) and b.shape == (n,) and n <= SCHOOLBOOK_MAX_N
+    out = np.zeros(n, dtype=object)
+    for k in np.flatnonzero(b):
+        r = np.roll(ao, int(k))
+        r[:k] *= -1
+        out += r * int(b[k])
+    return out
+
+
+def mul_msg(a_int: np.ndarray, b_int: np.ndarray) -> np.ndarray:
+    """The exact negacyclic product of two small integer message polynomials, (n,) x (n,) -> (n,) int64."""
+    a = np.asarray(a_int, dtype=np.int64)
+    b = np.asarray(b_int, dtype=np.int64)
+    n = a.shape[-1]
+    assert a.shape == (n,) and b.shape == (n,)
+    if n <= SCHOOLBOOK_MAX_N:
+        return mul_exact(a, b).astype(np.int64)
+    assert n * int(np.abs(a).max(initial=0)) * int(np.abs(b).max(initial=0)) < (1 << 50)
+    w = np.exp(1j * np.pi * np.arange(n) / n)
+    c = np.fft.ifft(np.fft.fft(a * w) * np.fft.fft(b * w)) / w
+    r = np.rint(c.real)
+    assert np.abs(c.real - r).max(initial=0) < 0.25 and np.abs(c.imag).max(initial=0) < 0.25
+    return r.astype(np.int64)
+
+
+def torus_from_int(values: np.ndarray, bits: int, base2k: int = 16) -> np.ndarray:
+    """values 2^-bits mod 1 as ((size, n), base2k) normalized limbs covering at least `bits` bits (bits <= 0: an integer, the zero
+    torus element), for torus_diff."""
+    v = np.asarray(values).astype(object)
+    if bits <= 0:
+        return np.zeros((1, v.shape[-1]), dtype=np.int64)
+    size = limbs_for(bits, base2k)
+    q = 1 << bits
+    v = (v % q) << (size * base2k - bits)
+    pt = np.zeros((size, v.shape[-1]), dtype=np.int64)
+    mask = (1 << base2k) - 1
+    for j in reversed(range(size)):
+        pt[j] = (v & mask).astype(np.int64)
+        v = v >> base2k
+    return normalize(pt, base2k)
+
+
+# ---- the tensor product of two GLWE (poulpy-core layouts/glwe_secret_tensor.rs, encryption/glwe_tensor_key.rs, decryption/glwe_tensor.rs) ----
+def pair_index(i: int, j: int, rank: int) -> int:
+    """glwe_secret_tensor.rs:204: the column of s_i s_j, i <= j."""
+    assert 0 <= i <= j < rank
+    return i * rank + j - i * (i + 1) // 2
+
+
+def secret_tensor(sk: np.ndarray) -> np.ndarray:
+    """glwe_secret_tensor.rs:200-218: (pairs, n) exact integers s_i s_j, i <= j, in the reference's order (s0^2, s0 s1, s1^2 at rank 2).
+    The coefficients reach N in magnitude; they stay plain integers."""
+    rank, n = sk.shape
+    out = np.zeros((rank * (rank + 1) // 2, n), dtype=np.int64)
+    for i in range(rank):
+        for j in range(i, rank):
+            out[pair_index(i, j, rank)] = mul_small(sk[i], sk[j])
+    return out
+
+
+def tensor_key(sk: np.ndarray, base2k: int, k: int, dnum: int, dsize: int, rng, order=None, limb_shift: int = 0) -> np.ndarray:
+    """encryption/glwe_tensor_key.rs:92-96: the GGLWE of secret_tensor(sk) under sk, (dnum, pairs, size, rank + 1, n).  order permutes
+    the pair columns and limb_shift moves every row's message (negative controls)."""
+    msgs = secret_tensor(sk)
+    if order is not None:
+        msgs = msgs[list(order)]
+    return gglwe_encrypt(sk, msgs, base2k, k, dnum, dsize, rng, limb_shift=limb_shift)
+
+
+def glwe_tensor_phase(ct: np.ndarray, sk: np.ndarray, base2k: int, reverse_pairs: bool = False) -> np.ndarray:
+    """decryption/glwe_tensor.rs:54-66: c_0 + sum_i c_i s_i + sum_{i<=j} c_ij s_i s_j over the columns [0, 1..rank, pairs] of a
+    (size, (rank + 1)(rank + 2) / 2, n) tensor at base2k, per limb (un-normalized): (size, n).  c_ij s_i is normalized at base2k
+    before it meets s_j (the torus is mod 1: the carry dropped off the top is an integer), which keeps mul_small's digits small.
+    reverse_pairs reads the pair columns in reversed order (s1^2 for s0^2 at rank 2: a negative control of this checker)."""
+    rank, n = sk.shape
+    assert ct.shape[1] == (rank + 1) * (rank + 2) // 2
+    body = glwe_phase(ct[:, :rank + 1], sk)
+    for i in range(rank):
+        for j in range(i, rank):
+            col = pair_index(i, j, rank)
+            if reverse_pairs:
+                col = rank * (rank + 1) // 2 - 1 - col
+            body += mul_small(normalize(mul_small(ct[:, rank + 1 + col], sk[i]), base2k), sk[j])
+    return body
