@@ -313,6 +313,17 @@ int pz_glwe_keyswitch_batched(pz_module* m, int64_t* res, const int64_t* a, cons
 enum { PZ_AUTO = 0, PZ_AUTO_ADD = 1, PZ_AUTO_SUB = 2, PZ_AUTO_SUB_NEGATE = 3 };
 int pz_glwe_automorphism_batched(pz_module* m, int64_t* res, const int64_t* a, const double* key_pmat,
                                  const pz_glwe_op_params* p, int64_t gal, int mode, size_t batch);
+/* res[r][b] = glwe_automorphism(a[b], key_pmats[r], gals[r])  (PZ_AUTO, glwe_ct.rs:51-72) for r < nrot, b < batch.
+ * gals / key_pmats: HOST arrays of nrot entries (as for pz_glwe_trace_batched); every key_pmats[r], a and res are device pointers.
+ * Rotation-major result: ciphertext b of rotation r at res + (r*batch + b) * n*(rank+1)*res_size, so each rotation is a
+ * contiguous batch for the next call.  res must not overlap a.  Bit-identical to nrot calls of pz_glwe_automorphism_batched.
+ * Where the three-kernel pipeline serves the shape, the forward column pass and the read of the body column - the work that does
+ * not depend on the Galois element - run once per wave for all rotations ("hoisted rotations"); every other shape, and nrot == 1, takes one
+ * pz_glwe_automorphism_batched per rotation.  nrot == 0, an even Galois element, a null key or an overlap: PZ_ERR_INVALID, nothing
+ * is launched.  The workspace query covers nrot row-sliced key copies (keys pinned with pz_module_pin_key use their cached ones). */
+int pz_glwe_automorphism_many_batched(pz_module* m, int64_t* res, const int64_t* a, size_t nrot, const int64_t* gals,
+                                      const double* const* key_pmats, const pz_glwe_op_params* p, size_t batch);
+size_t pz_glwe_automorphism_many_workspace_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t nrot, size_t batch);
 /* CoreImpl glwe_trace_assign (poulpy-core/src/glwe_trace.rs:129-176) on `batch` ciphertexts:
  * for s < nsteps:  res = rsh(res, 1 bit);  res = glwe_automorphism_add_assign(res, key_s)   (:164-174).
  * The caller resolves the steps skip..log_n into Galois elements (i = 0: -1, else galois_element(2^(i-1)),
@@ -752,6 +763,9 @@ int pz_module_dispatch_notes(pz_module* m, char* buf, size_t len, int reset);
  * graphs are not used in this mode).  pz_debug_workspace_overrun carves two segments of `bytes` and writes `overrun` bytes past the
  * end of the first one: the self-test of that mechanism (returns PZ_OK when the mode is off: nothing is checked then). */
 int pz_debug_workspace_overrun(pz_module* m, size_t bytes, size_t overrun);
+/* Bytes of the module's grow-only device workspace as allocated now (0 before the first call that needs one): what the
+ * *_workspace_bytes queries bound.  Read it between calls. */
+size_t pz_module_workspace_bytes(const pz_module* m);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,15 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
     void glwe_automorphism_batched(int64_t* res, const int64_t* a, const double* key, const pz_glwe_op_params& p, int64_t gal, int mode, size_t batch) {
         check(pz_glwe_automorphism_batched(m_, res, a, key, &p, gal, mode, batch), "glwe_automorphism_batched");
     }
+    // one batch rotated by nrot Galois elements (PZ_AUTO per element): gals / keys are nrot host arrays, rotation r of ciphertext b is
+    // ciphertext r * batch + b of res; res must not overlap a
+    void glwe_automorphism_many_batched(int64_t* res, const int64_t* a, size_t nrot, const int64_t* gals, const double* const* keys,
+                                        const pz_glwe_op_params& p, size_t batch) {
+        check(pz_glwe_automorphism_many_batched(m_, res, a, nrot, gals, keys, &p, batch), "glwe_automorphism_many_batched");
+    }
+    size_t glwe_automorphism_many_workspace_bytes(const pz_glwe_op_params& p, size_t nrot, size_t batch) const {
+        return pz_glwe_automorphism_many_workspace_bytes(m_, &p, nrot, batch);
+    }
     void blind_rotation_execute_batched(int64_t* res, const int64_t* lwe_2n, const int64_t* lut, const double* brk, const pz_blind_rotation_params& p, size_t batch) {
         check(pz_blind_rotation_execute_batched(m_, res, lwe_2n, lut, brk, &p, batch), "blind_rotation_execute_batched");
     }

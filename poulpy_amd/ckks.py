@@ -1,4 +1,5 @@
-"""The linear CKKS operations of poulpy-ckks (src/leveled/default/{add,sub,neg,pow2,rescale,pt_znx}.rs), each as ONE device call.
+"""The linear CKKS operations of poulpy-ckks (src/leveled/default/{add,sub,neg,pow2,rescale,pt_znx}.rs), each as ONE device call, and its
+rotations (rotate.rs, conjugate.rs) - one ciphertext batch by many Galois elements in one call (plan_rotate_many).
 
 Every operation there is one overwriting poulpy-core GLWE primitive, at most one accumulating one, and optionally a final
 glwe_normalize_assign.  Each primitive adds (or subtracts) a digit stream of its own operand, so an operation is one
@@ -232,3 +233,53 @@ def plan_add_pt_assign(dst: Ct, pt: Pt, sub=False, normalize=True) -> Plan:
     pt_shift = ensure_plaintext_alignment("ckks_" + name[:-7] + "_vec_znx_into", dst.log_budget, pt.log_delta, pt.max_k)
     return Plan(name, [Term("dst", RAW), Term("pt", RSH, pt_shift, -1 if sub else 1)], normalize, dst.log_delta, dst.log_budget,
                 pt_shift=pt_shift)
+
+
+@dataclass
+class RotatePlan:
+    """rotate.rs:23-56 for one source and one destination per Galois element: the metadata every destination takes, and the offset by which
+    the reference shifts the source first (glwe_lsh into dst, then glwe_automorphism_assign: :46-48)."""
+    name: str
+    offset: int
+    log_delta: int
+    log_budget: int
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dsts, src: Ct, gals, key_ptrs, params, batch: int, tmp=None):
+        """One pz_glwe_automorphism_many_batched over `batch` ciphertexts: dsts[0].data = the rotation-major device result (rotation r at
+        r * batch ciphertexts), src.data the device source; gals[r] / key_ptrs[r] per destination (conjugation: the element 2N - 1).
+        offset != 0: src is shifted first by one pz_glwe_combine_batched into `tmp` (a device pointer to `batch` ciphertexts of the
+        destinations' layout), and params.a_size is the destinations' size as in the reference's assign form."""
+        if len(gals) != len(dsts) or len(key_ptrs) != len(dsts):
+            raise CKKSError(f"{self.name}: one Galois element and one key per destination")
+        a = src.data
+        if self.offset != 0:
+            if tmp is None:
+                raise CKKSError(f"{self.name}: offset {self.offset} needs a temporary of the destinations' layout")
+            d0 = dsts[0]
+            module.glwe_combine_batched(tmp, d0.cols, d0.size, d0.base2k, [dict(a=src.data, a_size=src.size, kind=LSH, k=self.offset)], False, batch)
+            a = tmp
+        module.glwe_automorphism_many_batched(dsts[0].data, a, gals, key_ptrs, params, batch)
+        for d in dsts:
+            self.apply_meta(d)
+
+
+def plan_rotate_many(dsts, src: Ct) -> RotatePlan:
+    """rotate.rs:44-55 (conjugate.rs alike) for several destinations of one layout rotated from the same source."""
+    if not dsts:
+        raise CKKSError("rotate: no destination")
+    d0 = dsts[0]
+    for d in dsts:
+        _same_layout("rotate", d, src)
+        if (d.size, d.base2k) != (d0.size, d0.base2k):
+            raise CKKSError("rotate: the destinations of one call share one layout")
+    offset = offset_unary(d0, src)
+    return RotatePlan("rotate_many" if len(dsts) > 1 else "rotate_into", offset, src.log_delta,
+                      checked_log_budget_sub("rotate", src.log_budget, offset))
+
+
+def plan_rotate_into(dst: Ct, src: Ct) -> RotatePlan:
+    """rotate.rs:23-56."""
+    return plan_rotate_many([dst], src)

@@ -463,6 +463,7 @@ int pz_debug_workspace_overrun(pz_module* M, size_t bytes, size_t overrun) {
     PZ_HIP(hipMemsetAsync(s1, 0x22, seg, M->stream));
     return PZ_OK;   // the scope object of PZ_ENTER verifies the guards on the way out
 }
+size_t pz_module_workspace_bytes(const pz_module* M) { return M ? M->ws_bytes : 0; }
 int pz_module_get_kernel_stats(pz_module* M, int kclass, uint64_t* launches, double* total_ms) {
     PZ_ENTER(M);
     PZ_REQUIRE(kclass >= 0 && kclass < PZ_KCLASS_COUNT, "kernel class out of range");

@@ -237,12 +237,17 @@ static int wave_input(const GlweCall& c, size_t b0, int nb, int64_t* a_conv, DV*
     return PZ_OK;
 }
 // the permuted copy of the key a pipeline reads: the pinned / mirrored one if the caller declared the key immutable, else built now
-static int wave_key(const GlweCall& c, cplx* scratch, bool small_ring, const cplx** out) {
+// the cached row-sliced copy of `key` if the caller pinned it with this call's key shape, else null
+static const cplx* pinned_slices(const GlweCall& c, const double* key) {
     const size_t bytes = (size_t)c.nrows * c.ncols * (size_t)c.M->n * 8;
+    for (auto& pk : c.M->pinned)
+        if (pk.key == (const void*)key && pk.sliced && pk.bytes == bytes) return pk.sliced;
+    return nullptr;
+}
+static int wave_key(const GlweCall& c, cplx* scratch, bool small_ring, const cplx** out) {
     // (key composition: the slices of phi_g(key), built per call in the call's own scratch - never a pinned key's cached copy, and never into it)
     if (c.keyauto) { PZ_TRY(launch_permute_pmat_gal(c.M, c.pmat, scratch, c.nrows * c.ncols, c.ka_perm)); *out = scratch; return PZ_OK; }
-    for (auto& pk : c.M->pinned)
-        if (pk.key == (const void*)c.pmat && pk.sliced && pk.bytes == bytes) { *out = pk.sliced; return PZ_OK; }
+    if (const cplx* pinned = pinned_slices(c, c.pmat)) { *out = pinned; return PZ_OK; }
     // the key arrives in the standard device layout; its row-sliced copy is rebuilt per call (2 x 128 MiB of traffic at the metric
     // shape, ~4 % of a 128-ciphertext call) so that no stale copy can ever be used
     if (small_ring) PZ_TRY(launch_small_permute(c.M, c.pmat, scratch, c.nrows * c.ncols));
@@ -310,6 +315,7 @@ struct FusedBufs {
     cplx* key_scratch; int64_t* a_conv; cplx* T; cplx* T2; int64_t* res_tmp; int64_t* key_digits; cplx* mid_dummy;
     const cplx* Pp;
     short* side16 = nullptr;   // this wave's 16-bit side copy of pass 1's input (add / sub automorphism forms at rank 1: wave_spectral_tail), or null
+    const short* body16_pre = nullptr;   // plain form, hoisted rotations (glwe_rotations_hoisted): this rotation's 16-bit body operand, already written
 };
 static int fused_carve(const GlweCall& c, FusedBufs* f) {
     pz_module* M = c.M;
@@ -401,7 +407,9 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     //  the operand always fits and the flag-up launches of the shifted-store forms stay what they are there: never taken)
     const bool body16 = spectral_body16(c);   // (glwe_fused zeroed the flag word in front of pass 1: that kernel may raise it too, f.side16)
     if (body16) dispatch_note(M, "spectral tail: 16-bit body operand (%s form)", c.au_big ? "add / sub" : "plain");
-    short* b16 = body16 ? (short*)f.res_tmp : nullptr;
+    // (hoisted rotations: the copy of this Galois element was made from the one read of the body column all rotations share - the i64 fallback keeps
+    //  its own segment, res_tmp, so that it never lands on the copy of a rotation whose tail has not run yet)
+    short* b16 = body16 ? (f.body16_pre ? const_cast<short*>(f.body16_pre) : (short*)f.res_tmp) : nullptr;
     if (body16) {
         t.body16 = b16; t.body16_limbs = bl; t.body16_wide = M->wide16();
         if (f.side16 && c.au_big) t.other16 = f.side16;
@@ -411,7 +419,7 @@ static int wave_spectral_tail(const GlweCall& c, const FusedBufs& f, size_t b0, 
     if (!c.au_big) {
         // plain form, res = phi(normalize(big)) (glwe_ct.rs:65-71): the inverse transform is phi(big) with phi's signs; the tail undoes
         // them in front of the carry chain (auto_mul) and puts them back on the digits (post_neg); only the body column has an operand
-        if (body16) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, AUTO_SIGN, nullptr, PolyMap{1, 1, 0, 0, 0, 0}, b16));
+        if (body16 && !f.body16_pre) PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, nullptr, bdm, c.au_g, AUTO_SIGN, nullptr, PolyMap{1, 1, 0, 0, 0, 0}, b16));
         PZ_TRY(launch_automorphism(M, nb * bl, (const long long*)av.p, bsm, (long long*)f.res_tmp, bdm, c.au_g, AUTO_SIGN | cond));
         t.auto_mul = c.au_g; t.post_neg = true; t.body_only = true;
         return launch_inv_tail(M, t);
@@ -726,6 +734,12 @@ static int glwe_unfused(const GlweCall& c) {
 //  (profiles/r02_cu_mask_scaling.txt), so chunk c+1's pass 1, chunk c's middle kernel and chunk c-1's tail were run concurrently on
 //  disjoint CU sets, chained by events.  Bit-exact, but slower in every split tried (best 73 500/s against 88 700/s back to back,
 //  profiles/r02_overlap_sweep.txt): under concurrency the three kernels share HBM at ~4.7 TB/s aggregate.)
+// the Galois element of a call: au, p mod 2N and its inverse (glwe_call_init; glwe_rotations_hoisted per rotation)
+static void call_set_galois(GlweCall& c, const AutoSpec* au) {
+    c.au = au;
+    c.au_p = (unsigned)((unsigned long long)au->p & (2ull * (unsigned long long)c.n - 1ull));
+    c.au_g = inv_mod_2n(au->p, c.n);
+}
 static int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
                           size_t batch, const AutoSpec* au, const OpLayout* lay, bool* post_rsh) {
     const bool ks = kind_ks(kind), tensor = kind == GlweKind::TensorRelin;
@@ -747,8 +761,8 @@ static int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res
     c.npi = c.s.cols_in * c.s.a_size_eff; c.npo = c.s.cols_out * c.ksz;
     c.nrows = c.dnum * c.s.cols_in; c.ncols = c.s.cols_out * c.ksz;
     c.au_big = au && au->mode != 0;
-    c.au_p = au ? (unsigned)((unsigned long long)au->p & (2ull * (unsigned long long)c.n - 1ull)) : 0u;
-    c.au_g = au ? inv_mod_2n(au->p, c.n) : 0u;
+    c.au_p = c.au_g = 0u;
+    if (au) call_set_galois(c, au);
     c.a_bs = lay ? lay->a_stride : c.a_ct; c.res_bs = lay ? lay->res_stride : c.res_ct;
     c.body_col = lay ? lay->body_col : 0;
     c.digits = c.dsize > 1; c.cross_out = p->res_base2k != p->key_base2k;
@@ -1009,6 +1023,148 @@ int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64
     for (size_t s = 0; s < nsteps && gals && key_pmats; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
     graph_key_module(M, k);
     return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch); });
+}
+}  // extern "C"
+
+// ------------------------------------------------------------------------------
+// One ciphertext batch rotated by many Galois elements (pz_glwe_automorphism_many_batched).  res[r] = phi_r(normalize(KS_{K_r}(a))):
+// the key switch decomposes the unpermuted `a`, and in the spectral form phi_r only reaches the middle kernel's store position and the tail's
+// signs - so pass 1's output T and the body column's 16-bit image are the same for every rotation ("hoisted rotations").  Per wave:
+//   wave_input, pass 1                      once
+//   k_automorphism_t16_many                 once per kAutoManyCap rotations: one read of the body column, one 16-bit copy per rotation
+//   middle kernel (key r, perm r), tail r   per rotation - the launches of the single call, on copy r
+// Workspace: [row-sliced keys that are not pinned][a_conv][T][T2'][res_tmp: the i64 fallback's operand, one rotation at a time][copies, nrot x]
+// [middle kernel's scratch].  Each rotation's arithmetic is the single call's: the result is bit-identical to nrot calls.
+// ------------------------------------------------------------------------------
+static size_t rot_copy_bytes(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, size_t chunk) {
+    return align256(chunk * std::min<size_t>((size_t)s.a_size_eff, p->key_size) * (size_t)M->n * sizeof(short));
+}
+// why a call takes one glwe_op per rotation instead of the hoisted route; null: it takes the hoisted route
+static const char* rot_loop_reason(const GlweCall& c, size_t nrot) {
+    const pz_module* M = c.M;
+    // (measured at N = 2^16, 16 limbs, 512 ciphertexts: 49 850 against 50 235 rotations/s - nothing is shared, and the copy in a segment of its own costs 0.7 %)
+    if (nrot == 1) return "one rotation: nothing to share";
+    if (rt_knob("POULPY_DBG_ROT_HOIST", 1) == 0) return "POULPY_DBG_ROT_HOIST=0";   // (read per call: tests flip it)
+    if (c.digits) return "dsize > 1";
+    if (c.cross_out) return "res_base2k != key_base2k";
+    if (!fused_applies(M, c.p, c.s, GlweKind::Automorphism)) return "no three-kernel pipeline for this shape";
+    if (!spectral_perm(c).on) return "no spectral form on this plan";
+    if (n4096_two_kernel(c)) return "N = 4096 two-kernel path";
+    if (M->probe) return "rounding-margin probe";
+    if ((int)c.p->key_base2k > 16) return "digits beyond the 16-bit copies";   // (res_base2k == key_base2k here)
+    return nullptr;
+}
+static int glwe_rotations_hoisted(const GlweCall& c0, size_t nrot, const int64_t* gals, const double* const* keys) {
+    pz_module* M = c0.M;
+    const long long n = c0.n;
+    const bool copies = spectral_body16(c0);   // (false: the plans without the 16-bit-operand tail, N = 4096 - pass 1 is shared, the i64 pre-pass runs per rotation)
+    std::vector<const cplx*> Pp(nrot);
+    size_t nslice = 0;
+    for (size_t r = 0; r < nrot; ++r) { Pp[r] = pinned_slices(c0, keys[r]); nslice += Pp[r] == nullptr; }
+    const FusedWs fw = fused_ws(M, c0.p, c0.s, c0.chunk, true);
+    const size_t copy_bytes = copies ? rot_copy_bytes(M, c0.p, c0.s, c0.chunk) : 0;
+    PZ_TRY(ws_reserve(M, fw.total - fw.key + nslice * fw.key + nrot * copy_bytes));
+    char* base = (char*)M->ws;
+    FusedBufs f;
+    char* key_area; char* copy_area;
+    PZ_TRY(ws_take(M, base, nslice * fw.key, &key_area));
+    PZ_TRY(ws_take(M, base, fw.conv, &f.a_conv));
+    PZ_TRY(ws_take(M, base, fw.t, &f.T));
+    base += (kT2Phase - (size_t)(((uintptr_t)base - (uintptr_t)c0.res) & kT2PhaseMask)) & kT2PhaseMask;   // see kT2Phase
+    PZ_TRY(ws_take(M, base, fw.t2, &f.T2));
+    PZ_TRY(ws_take(M, base, fw.rtmp, &f.res_tmp));
+    PZ_TRY(ws_take(M, base, nrot * copy_bytes, &copy_area));
+    PZ_TRY(ws_take(M, base, kMidDummyBytes, &f.mid_dummy));
+    f.key_scratch = nullptr; f.key_digits = nullptr;
+    // every key row-sliced at most once per call
+    for (size_t r = 0, k = 0; r < nrot; ++r) {
+        if (Pp[r]) continue;
+        cplx* dst = (cplx*)(key_area + (k++) * fw.key);
+        PZ_TRY(launch_permute_pmat(M, keys[r], dst, c0.nrows * c0.ncols));
+        Pp[r] = dst;
+    }
+    std::vector<unsigned> muls(nrot);
+    for (size_t r = 0; r < nrot; ++r) muls[r] = inv_mod_2n((long long)gals[r], n);
+    dispatch_note(M, "rotations: hoisted, %d per forward pass%s", (int)nrot, copies ? "" : " (i64 body operand per rotation)");
+    for (size_t b0 = 0; b0 < c0.batch; b0 += c0.chunk) {
+        const int nb = (int)std::min(c0.chunk, c0.batch - b0);
+        DV av;
+        PZ_TRY(wave_input(c0, b0, nb, f.a_conv, &av));
+        PolyMap sm{av.size, c0.s.cols_in, av.bs, (long long)av.cols * n, n, n * c0.s.a_col0};
+        if (copies) PZ_TRY(launch_zero_bytes(M, M->margin + 1, 8));   // the wide flag: one for all rotations, it depends on the body's digits alone
+        PZ_TRY(launch_fwd_pass1(M, nb * c0.npi, (const long long*)av.p, sm, f.T, true));
+        if (copies) {
+            const int bl = std::min(av.size, c0.ksz);
+            PolyMap bsm{bl, 1, av.bs, (long long)av.cols * n, 0, 0}, bdm{bl, 1, (long long)bl * n, n, 0, 0};
+            PZ_TRY(launch_automorphism_t16_many(M, nb * bl, (const long long*)av.p, bsm, (short*)copy_area, bdm, (long long)(copy_bytes / sizeof(short)),
+                                                muls.data(), (int)nrot));
+        }
+        for (size_t r = 0; r < nrot; ++r) {
+            AutoSpec au{(long long)gals[r], 0};
+            GlweCall c = c0;
+            call_set_galois(c, &au);   // (c.au_g == muls[r]: the pre-pass's gather multiplier is the tail's)
+            c.pmat = keys[r];
+            c.res = c0.res + (long long)r * (long long)c0.batch * c0.res_ct;   // rotation-major
+            MidCall mc;
+            mc.T = f.T; mc.T2 = f.T2; mc.Pp = Pp[r]; mc.dummy = f.mid_dummy; mc.npi = c.npi; mc.npo = c.npo; mc.nrows = c.nrows; mc.ncols = c.ncols;
+            mc.perm = spectral_perm(c);
+            PZ_TRY(launch_mid(M, nb, mc));
+            f.body16_pre = copies ? (const short*)(copy_area + r * copy_bytes) : nullptr;
+            PZ_TRY(wave_spectral_tail(c, f, b0, nb, av));
+        }
+    }
+    return PZ_OK;
+}
+
+extern "C" {
+size_t pz_glwe_automorphism_many_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t nrot, size_t batch) {
+    if (!M || !p || p->key_size == 0 || p->a_size == 0 || nrot == 0) return 0;
+    // the per-rotation calls' reservation; where the three-kernel pipeline serves the shape, the hoisted layout on top of it: a row-sliced copy
+    // per key (none of them pinned) and a 16-bit copy of the body operand per rotation
+    // (+ the room ws_reserve adds for the guards of POULPY_DBG_CANARY: the figure bounds the allocation itself, pz_module_workspace_bytes)
+    const size_t loop = pz_glwe_op_workspace_bytes(M, p, batch, (int)GlweKind::Automorphism) + kGuardSlack + (kGuardSlack >> 3);
+    const OpShape s = op_shape(p, GlweKind::Automorphism);
+    if (!fused_applies(M, p, s, GlweKind::Automorphism) || M->plan.m2 != 128) return loop;
+    const size_t chunk = pick_chunk(M, p, s, std::max<size_t>(batch, 1));
+    const FusedWs fw = fused_ws(M, p, s, chunk, true);
+    const size_t bytes = fw.total + (nrot - 1) * fw.key + nrot * rot_copy_bytes(M, p, s, chunk) + kGuardSlack;
+    return std::max(loop, bytes + (bytes >> 3));
+}
+
+int pz_glwe_automorphism_many_batched(pz_module* M, int64_t* res, const int64_t* a, size_t nrot, const int64_t* gals, const double* const* key_pmats,
+                                      const pz_glwe_op_params* p, size_t batch) {
+    // (the argument checks that need no module come first; nothing is launched when one fails)
+    PZ_REQUIRE(p != nullptr, "null params");
+    PZ_REQUIRE(nrot >= 1, "glwe_automorphism_many: no rotation asked for");
+    PZ_REQUIRE(res != nullptr && a != nullptr && gals != nullptr && key_pmats != nullptr, "glwe_automorphism_many: null argument");
+    for (size_t r = 0; r < nrot; ++r) {
+        PZ_REQUIRE((gals[r] & 1) != 0, "glwe_automorphism_many: Galois element %zu is even", r);
+        PZ_REQUIRE(key_pmats[r] != nullptr, "glwe_automorphism_many: key %zu is null", r);
+    }
+    PZ_ENTER(M);
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_automorphism_many: the keys map rank -> rank");
+    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
+    const size_t a_bytes = batch * n8 * cols * p->a_size, res_bytes = nrot * batch * n8 * cols * p->res_size;
+    // every rotation reads `a` after the first one has written: no in-place form
+    PZ_REQUIRE(!((const char*)res < (const char*)a + a_bytes && (const char*)a < (const char*)res + res_bytes) && (const void*)res != (const void*)a,
+               "glwe_automorphism_many: res overlaps a");
+    for (size_t r = 0; r < nrot; ++r) PZ_REQUIRE(is_device_ptr(key_pmats[r]), "batched entry points take device pointers");
+    AutoSpec au0{(long long)gals[0], 0};
+    GlweCall c;
+    PZ_TRY(glwe_call_init(c, M, GlweKind::Automorphism, res, a, key_pmats[0], p, batch, &au0, nullptr, nullptr));
+    if (batch == 0) return PZ_OK;
+    const char* why = rot_loop_reason(c, nrot);
+    if (!why) {
+        PZ_TRY(glwe_rotations_hoisted(c, nrot, gals, key_pmats));
+        return finish_call(M, false);
+    }
+    dispatch_note(M, "rotations: per-rotation calls (%s)", why);
+    for (size_t r = 0; r < nrot; ++r) {
+        AutoSpec au{(long long)gals[r], 0};
+        PZ_TRY(glwe_op(M, GlweKind::Automorphism, res + (long long)(r * batch) * c.res_ct, a, key_pmats[r], p, batch, &au));
+    }
+    return finish_call(M, false);
 }
 }  // extern "C"
 

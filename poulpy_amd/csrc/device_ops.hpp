@@ -427,6 +427,68 @@ __global__ void __launch_bounds__(1024) k_automorphism_t16(AutoArgs g) {
     if (wide2) atomicOr(g.wide, 1u);
 }
 
+// The same pre-pass for SEVERAL Galois elements at once (pz_glwe_automorphism_many_batched: one ciphertext batch rotated by many elements).  The
+// source polynomial is read and narrowed once; the output phase runs once per element, reading the same LDS image at that element's permuted
+// index, and writes copy r at dst16 + r * stride + map_off(dm).  Plain form only: phi's signs, no `add` operand - so a value fits its copy exactly
+// when it fits the LDS image, and the input phase's check (the one of k_automorphism_t16, -32768 included) is the only one.  One flag for all
+// elements: it depends on the source digits alone.  The multipliers arrive in the argument struct, kAutoManyCap per launch (the launcher splits).
+constexpr int kAutoManyCap = 8;
+struct AutoManyArgs {
+    const long long* src;
+    short* dst16;
+    PolyMap sm, dm;
+    long long stride;               // int16 elements between the copies of two consecutive elements
+    unsigned* wide;
+    int n, nrot;
+    int t16_m1, t16_cb, t16_m2sh;   // tile: m1 rows, cb columns per block, log2 m2 (as AutoArgs)
+    unsigned mul[kAutoManyCap];     // gather multipliers g_r (odd, < 2n)
+};
+__global__ void __launch_bounds__(1024) k_automorphism_t16_many(AutoManyArgs g) {
+    extern __shared__ short a16[];   // the source polynomial, natural order
+    const int poly = blockIdx.x;
+    const long long* src = g.src + map_off(g.sm, poly);
+    const int tid = threadIdx.x;
+    bool wide = false;
+    for (int i = tid * 2; i < g.n; i += 2048 * 4) {   // 4 x 16 B in flight per thread
+        typedef unsigned long long pz_u64x2 __attribute__((ext_vector_type(2)));
+        pz_u64x2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u * 2048 < g.n) v[u] = __builtin_nontemporal_load(reinterpret_cast<const pz_u64x2*>(src + i + u * 2048));
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u * 2048 < g.n) {
+                wide = wide || (v[u].x + 32767ull) >= 65535ull || (v[u].y + 32767ull) >= 65535ull;
+                short2 s2;
+                s2.x = (short)v[u].x; s2.y = (short)v[u].y;
+                *reinterpret_cast<short2*>(a16 + i + u * 2048) = s2;
+            }
+    }
+    if (wide) atomicOr(g.wide, 1u);
+    __syncthreads();
+    short* dst0 = g.dst16 + map_off(g.dm, poly);
+    const unsigned mask2 = 2u * (unsigned)g.n - 1u, nn = (unsigned)g.n;
+    const unsigned m2 = 1u << g.t16_m2sh, tile = 2u * (unsigned)g.t16_m1 * (unsigned)g.t16_cb;
+    for (unsigned t = (unsigned)tid * 4u; t < nn; t += 4096u) {
+        // tile-order position t -> coefficient j (as k_automorphism_t16); the same j for every element
+        const unsigned blk = t / tile, rem = t % tile;
+        const unsigned j = (rem / (unsigned)g.t16_cb) * m2 + blk * (unsigned)g.t16_cb + (rem % (unsigned)g.t16_cb);
+        for (int r = 0; r < g.nrot; ++r) {
+            const unsigned mul = g.mul[r];
+            short o[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const unsigned i0 = ((j + (unsigned)x) * mul) & mask2;
+                const int v = (int)a16[i0 & (nn - 1u)];
+                o[x] = (short)(i0 >= nn ? -v : v);
+            }
+            short4 s4;
+            s4.x = o[0]; s4.y = o[1]; s4.z = o[2]; s4.w = o[3];
+            *reinterpret_cast<short4*>(dst0 + (long long)r * g.stride + t) = s4;
+        }
+    }
+}
+
 // =================================================================================
 // vec_znx_rotate family with a per-ciphertext exponent (reference/znx/rotate.rs:3-27: res = X^k * src), gather form:
 //   res[j] = +-src[(j - k) mod 2n]   (negated when that index is >= n).

@@ -277,6 +277,10 @@ enum AutoFlags : int {
 };
 int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, unsigned mul,
                         int flags, const long long* add = nullptr, PolyMap am = PolyMap{1, 1, 0, 0, 0, 0}, short* dst16 = nullptr);
+// the 16-bit tile-order pre-pass for `nrot` Galois elements from one read of the source (k_automorphism_t16_many): copy r, made with the
+// gather multiplier muls[r] and phi's signs, lands at dst16 + r * stride + map_off(dm); raises the module's wide flag like launch_automorphism
+int launch_automorphism_t16_many(pz_module* M, int npolys, const long long* src, PolyMap sm, short* dst16, PolyMap dm, long long stride,
+                                 const unsigned* muls, int nrot);
 // per-ciphertext shift: polynomial i turns by shift[(i / polys_per_batch) * shift_bs + shift_idx] (mode: see k_rotate)
 int launch_rotate(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, int mode,
                   int polys_per_batch, const long long* shift, long long shift_bs, long long shift_idx, long long shift_const);

@@ -82,6 +82,29 @@ int launch_automorphism(pz_module* M, int npolys, const long long* src, PolyMap 
     return PZ_OK;
 }
 
+// copy r of every polynomial = the signed X^p-gather with multiplier muls[r], 16-bit tile order, at dst16 + r * stride + map_off(dm); see
+// k_automorphism_t16_many.  More elements than one launch takes: several launches, each reading the source again.
+int launch_automorphism_t16_many(pz_module* M, int npolys, const long long* src, PolyMap sm, short* dst16, PolyMap dm, long long stride,
+                                 const unsigned* muls, int nrot) {
+    if (npolys <= 0 || nrot <= 0) return PZ_OK;
+    if (M->n < 4096 || M->n > 65536 || (M->plan.m2 % M->plan.cb) != 0 || M->plan.cb % 4 != 0)
+        return fail(PZ_ERR_UNSUPPORTED, "automorphism pre-pass: no 16-bit tile-order output on this plan");
+    AutoManyArgs g;
+    g.src = src; g.sm = sm; g.dm = dm; g.stride = stride; g.wide = M->wide16(); g.n = (int)M->n;
+    g.t16_m1 = M->plan.f1a * M->plan.f1b; g.t16_cb = M->plan.cb; g.t16_m2sh = 0;
+    while ((1 << g.t16_m2sh) < M->plan.m2) ++g.t16_m2sh;
+    const size_t lds = (size_t)M->n * sizeof(short);
+    for (int r0 = 0; r0 < nrot; r0 += kAutoManyCap) {
+        g.nrot = std::min(kAutoManyCap, nrot - r0);
+        g.dst16 = dst16 + (long long)r0 * stride;
+        for (int r = 0; r < kAutoManyCap; ++r) g.mul[r] = r < g.nrot ? muls[r0 + r] : 1u;
+        KTimer kt(M, PZ_K_ELEMENTWISE);
+        PZ_TRY(launch_k(k_automorphism_t16_many, dim3(npolys), dim3(1024), lds, M->stream, g));
+        PZ_HIP(hipGetLastError());
+    }
+    return PZ_OK;
+}
+
 int launch_rotate(pz_module* M, int npolys, const long long* src, PolyMap sm, long long* dst, PolyMap dm, int mode,
                          int polys_per_batch, const long long* shift, long long shift_bs, long long shift_idx, long long shift_const) {
     if (npolys <= 0) return PZ_OK;

@@ -429,6 +429,17 @@ class Module:
         mode = self.AUTO_MODES[mode] if isinstance(mode, str) else int(mode)
         self._ck(self.lib.pz_glwe_automorphism_batched(self.handle, res, a, key_pmat, C.byref(params), gal, mode, batch))
 
+    def glwe_automorphism_many_batched(self, res: c_void_p, a: c_void_p, gals, key_ptrs, params: GlweOpParams, batch: int):
+        """One batch rotated by many Galois elements (glwe_automorphism, glwe_ct.rs:51-72, per element): gals[r] / key_ptrs[r] (device
+        pointers) per rotation; rotation r of ciphertext b is ciphertext r * batch + b of res.  res must not overlap a."""
+        nr = len(gals)
+        g = (c_int64 * max(nr, 1))(*[int(x) for x in gals])
+        ptrs = _ptrs(key_ptrs) if len(key_ptrs) else (c_void_p * 1)()
+        self._ck(self.lib.pz_glwe_automorphism_many_batched(self.handle, res, a, nr, g, ptrs, C.byref(params), batch))
+
+    def glwe_automorphism_many_workspace_bytes(self, params: GlweOpParams, nrot: int, batch: int) -> int:
+        return self.lib.pz_glwe_automorphism_many_workspace_bytes(self.handle, C.byref(params), nrot, batch)
+
     def ggsw_external_product(self, res: c_void_p, a: c_void_p, a_dnum: int, ggsw_pmat: c_void_p, params: GlweOpParams):
         """poulpy-core external_product/ggsw.rs:54-58 on a device-resident GGSW (MatZnx layout)."""
         self._ck(self.lib.pz_ggsw_external_product(self.handle, res, a, a_dnum, ggsw_pmat, C.byref(params)))
@@ -747,6 +758,10 @@ class Module:
 
     def unpin_key(self, pmat: c_void_p):
         self._ck(self.lib.pz_module_unpin_key(self.handle, pmat))
+
+    def workspace_bytes(self) -> int:
+        """bytes of the module's grow-only device workspace as allocated now (pz_module_workspace_bytes)"""
+        return self.lib.pz_module_workspace_bytes(self.handle)
 
     def glwe_op_workspace_bytes(self, params: GlweOpParams, batch: int, keyswitch: bool) -> int:
         return self.lib.pz_glwe_op_workspace_bytes(self.handle, C.byref(params), batch, int(keyswitch))
