@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from poulpy_amd.layouts import MatZnx, ScalarZnx, SvpPPol, VecZnx, VecZnxBig
+from tests.device import on_device
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -127,14 +128,11 @@ def run_fixture(path: str, module_factory) -> None:
             from poulpy_amd.hal import GlweOpParams
             p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=a_size, a_base2k=base2k,
                              res_size=res_size, res_base2k=base2k, rank_out=rank)
-            d_a = mod.device_alloc(a_np.nbytes).upload(np.ascontiguousarray(a_np))
-            d_k = mod.device_alloc(pm.data.nbytes).upload(pm.data)
-            d_r = mod.device_alloc(want.nbytes)
-            (mod.glwe_keyswitch_batched if ks else mod.glwe_external_product_batched)(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
-            mod.sync()
-            got = d_r.download(np.int64, want.size).reshape(want.shape)
-            for buf in (d_a, d_k, d_r):
-                buf.free()
+            with on_device(mod) as dev:
+                d_a, d_k, d_r = dev.upload(a_np), dev.key(pm), dev.alloc(want.nbytes, poison=False)
+                (mod.glwe_keyswitch_batched if ks else mod.glwe_external_product_batched)(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
+                mod.sync()
+                got = d_r.download(np.int64, want.size).reshape(want.shape)
         else:                                                # the oracle: the reference's per-ciphertext op
             got = np.empty_like(want)
             for b in range(batch):
@@ -155,17 +153,14 @@ def run_fixture(path: str, module_factory) -> None:
             from poulpy_amd.hal import GlweOpParams
             p = GlweOpParams(rank=1, dnum=dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,
                              res_base2k=base2k, rank_out=1)
-            d_l = mod.device_alloc(lwe.nbytes).upload(np.ascontiguousarray(lwe))
-            d_k = mod.device_alloc(pm.data.nbytes).upload(pm.data)
-            d_r = mod.device_alloc(want.nbytes)
-            d_m = mod.device_alloc(want_ms.nbytes)
-            mod.lwe_keyswitch_batched(d_r.ptr, n_out, d_l.ptr, len_in - 1, d_k.ptr, p, batch)
-            mod.lwe_mod_switch_2n_batched(d_m.ptr, d_l.ptr, len_in - 1, size, base2k, n2, False, batch)
-            mod.sync()
-            got = d_r.download(np.int64, want.size).reshape(want.shape)
-            got_ms = d_m.download(np.int64, want_ms.size).reshape(want_ms.shape)
-            for buf in (d_l, d_k, d_r, d_m):
-                buf.free()
+            with on_device(mod) as dev:
+                d_l, d_k = dev.upload(lwe), dev.key(pm)
+                d_r, d_m = dev.alloc(want.nbytes, poison=False), dev.alloc(want_ms.nbytes, poison=False)
+                mod.lwe_keyswitch_batched(d_r.ptr, n_out, d_l.ptr, len_in - 1, d_k.ptr, p, batch)
+                mod.lwe_mod_switch_2n_batched(d_m.ptr, d_l.ptr, len_in - 1, size, base2k, n2, False, batch)
+                mod.sync()
+                got = d_r.download(np.int64, want.size).reshape(want.shape)
+                got_ms = d_m.download(np.int64, want_ms.size).reshape(want_ms.shape)
         else:
             got = np.stack([mod.lwe_keyswitch(n_out, size, base2k, lwe[b], base2k, pm, 1, base2k) for b in range(batch)])
             got_ms = np.stack([mod.mod_switch_2n(n2, lwe[b], base2k, False) for b in range(batch)])

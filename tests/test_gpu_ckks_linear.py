@@ -8,27 +8,10 @@ from poulpy_amd import ckks
 from poulpy_amd.ckks import Ct, Pt
 from poulpy_amd.layouts import VecZnx
 from tests import shift_oracle as so
+from tests.device import mods, on_device  # noqa: F401
 from tests.helpers import seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
-
-
-def _up(hip, arr):
-    arr = np.ascontiguousarray(arr)
-    return hip.device_alloc(arr.nbytes).upload(arr)
 
 
 def _down(buf, shape):
@@ -58,18 +41,19 @@ def test_accumulating_shifts_batched(mods, base2k, k, res_size, a_size, wide):
     rng = seeded(base2k * 7919 + k * 31 + res_size * 3 + a_size + int(wide))
     a = _fill(rng, (batch, a_size, cols, n), base2k, wide)
     r0 = _fill(rng, (batch, res_size, cols, n), base2k, wide)
-    d_a = _up(hip, a)
-    for name, (fn, sub) in SHIFT_OPS.items():
-        want = r0.copy()
-        for t in range(batch):
-            rv = VecZnx(n, cols, res_size, want[t])
-            fn(base2k, k, rv, 1, VecZnx(n, cols, a_size, a[t].copy()), 0, sub=sub)
-        d_r = _up(hip, r0)
-        getattr(hip, f"vec_znx_{name}_batched")(batch, base2k, k, d_r.ptr, cols, res_size, 1, d_a.ptr, cols, a_size, 0)
-        hip.sync()
-        got = _down(d_r, r0.shape)
-        d_r.free()
-        assert np.array_equal(got, want), name
+    with on_device(hip) as dev:
+        d_a = dev.upload(a)
+        for name, (fn, sub) in SHIFT_OPS.items():
+            want = r0.copy()
+            for t in range(batch):
+                rv = VecZnx(n, cols, res_size, want[t])
+                fn(base2k, k, rv, 1, VecZnx(n, cols, a_size, a[t].copy()), 0, sub=sub)
+            d_r = dev.upload(r0)
+            getattr(hip, f"vec_znx_{name}_batched")(batch, base2k, k, d_r.ptr, cols, res_size, 1, d_a.ptr, cols, a_size, 0)
+            hip.sync()
+            got = _down(d_r, r0.shape)
+            dev.free(d_r)
+            assert np.array_equal(got, want), name
 
 
 @pytest.mark.parametrize("base2k,k", [(12, 0), (12, 5), (12, 12), (12, 29), (19, 40), (50, 101)])
@@ -79,17 +63,18 @@ def test_accumulating_shifts_on_res_itself(mods, base2k, k):
     ref, hip = mods(n)
     rng = seeded(base2k + k)
     r0 = _fill(rng, (batch, size, cols, n), base2k, True)
-    for name, (fn, sub) in SHIFT_OPS.items():
-        for a_col in (1, 0):
-            want = r0.copy()
-            for t in range(batch):
-                fn(base2k, k, VecZnx(n, cols, size, want[t]), 1, VecZnx(n, cols, size, r0[t].copy()), a_col, sub=sub)
-            d_r = _up(hip, r0)
-            getattr(hip, f"vec_znx_{name}_batched")(batch, base2k, k, d_r.ptr, cols, size, 1, d_r.ptr, cols, size, a_col)
-            hip.sync()
-            got = _down(d_r, r0.shape)
-            d_r.free()
-            assert np.array_equal(got, want), (name, a_col)
+    with on_device(hip) as dev:
+        for name, (fn, sub) in SHIFT_OPS.items():
+            for a_col in (1, 0):
+                want = r0.copy()
+                for t in range(batch):
+                    fn(base2k, k, VecZnx(n, cols, size, want[t]), 1, VecZnx(n, cols, size, r0[t].copy()), a_col, sub=sub)
+                d_r = dev.upload(r0)
+                getattr(hip, f"vec_znx_{name}_batched")(batch, base2k, k, d_r.ptr, cols, size, 1, d_r.ptr, cols, size, a_col)
+                hip.sync()
+                got = _down(d_r, r0.shape)
+                dev.free(d_r)
+                assert np.array_equal(got, want), (name, a_col)
 
 
 # ---- the CKKS operations -----------------------------------------------------------------------------------------------------------
@@ -153,19 +138,18 @@ def _run_ckks(ref, hip, n, rank, B, label, build, dst, ops, shared, batch, seed,
         kw = {k: obj(k, o) for k, o in ops.items()}
         so.run(ref, plan, d, kw.get("a"), kw.get("b"), kw.get("pt"))
         want[t] = d.data.data
-    dev = {}
-    for name, arr in host.items():
-        full = arr if name in shared else arr[idx]
-        dev[name] = _up(hip, full)
-    args = {}
-    for k, o in ops.items():
-        args[k] = (Pt if isinstance(o, Pt) else Ct)(**{**o.__dict__, "data": dev[k].ptr})
-    d_dst = Ct(**{**dst.__dict__, "data": dev["dst"].ptr})
-    plan.launch(hip, d_dst, batch, args.get("a"), args.get("b"), args.get("pt"), shared=shared)
-    hip.sync()
-    got = _down(dev["dst"], (batch, dst.size, cols, n))
-    for b in dev.values():
-        b.free()
+    with on_device(hip) as scope:
+        dev = {}
+        for name, arr in host.items():
+            full = arr if name in shared else arr[idx]
+            dev[name] = scope.upload(full)
+        args = {}
+        for k, o in ops.items():
+            args[k] = (Pt if isinstance(o, Pt) else Ct)(**{**o.__dict__, "data": dev[k].ptr})
+        d_dst = Ct(**{**dst.__dict__, "data": dev["dst"].ptr})
+        plan.launch(hip, d_dst, batch, args.get("a"), args.get("b"), args.get("pt"), shared=shared)
+        hip.sync()
+        got = _down(dev["dst"], (batch, dst.size, cols, n))
     assert (d_dst.log_delta, d_dst.log_budget) == (plan.log_delta, plan.log_budget)
     return got, want[idx]
 
@@ -202,28 +186,28 @@ def test_combine_refusals_launch_nothing(mods):
     n, cols, size = 256, 2, 3
     ref, hip = mods(n)
     r0 = np.arange(size * cols * n, dtype=np.int64).reshape(1, size, cols, n)
-    d_r, d_a = _up(hip, r0), _up(hip, r0 + 1)
-    t = dict(a=d_a.ptr, a_size=size, kind="raw")
-    bad = [([dict(t, base2k=13)], {}),                         # mixed base2k
-           ([t] * 5, {}),                                      # too many terms
-           ([], {}),                                           # no term
-           ([dict(t, a_size=0)], {}),                          # bad sizes
-           ([t], {"res_size": 0}),
-           ([dict(t, kind="lsh", k=1 << 41)], {}),             # shift out of range
-           ([dict(t, k=3)], {}),                               # RAW takes no shift
-           ([dict(t, sign=2)], {}),
-           ([dict(t, a=d_r.at(8 * n))], {}),                   # overlaps res without being res
-           ([t], {"base2k": 64})]
-    for terms, kw in bad:
-        with pytest.raises(PoulpyHipError):
-            hip.glwe_combine_batched(d_r.ptr, cols, kw.get("res_size", size), kw.get("base2k", 12), terms, False, 1)
-    hip.sync()
-    assert np.array_equal(_down(d_r, r0.shape), r0)
-    # four terms is the limit, and it runs
-    hip.glwe_combine_batched(d_r.ptr, cols, size, 12, [t] * 4, False, 1)
-    hip.sync()
-    assert np.array_equal(_down(d_r, r0.shape), 4 * (r0 + 1))
-    d_r.free(); d_a.free()
+    with on_device(hip) as dev:
+        d_r, d_a = dev.upload(r0), dev.upload(r0 + 1)
+        t = dict(a=d_a.ptr, a_size=size, kind="raw")
+        bad = [([dict(t, base2k=13)], {}),                         # mixed base2k
+               ([t] * 5, {}),                                      # too many terms
+               ([], {}),                                           # no term
+               ([dict(t, a_size=0)], {}),                          # bad sizes
+               ([t], {"res_size": 0}),
+               ([dict(t, kind="lsh", k=1 << 41)], {}),             # shift out of range
+               ([dict(t, k=3)], {}),                               # RAW takes no shift
+               ([dict(t, sign=2)], {}),
+               ([dict(t, a=d_r.at(8 * n))], {}),                   # overlaps res without being res
+               ([t], {"base2k": 64})]
+        for terms, kw in bad:
+            with pytest.raises(PoulpyHipError):
+                hip.glwe_combine_batched(d_r.ptr, cols, kw.get("res_size", size), kw.get("base2k", 12), terms, False, 1)
+        hip.sync()
+        assert np.array_equal(_down(d_r, r0.shape), r0)
+        # four terms is the limit, and it runs
+        hip.glwe_combine_batched(d_r.ptr, cols, size, 12, [t] * 4, False, 1)
+        hip.sync()
+        assert np.array_equal(_down(d_r, r0.shape), 4 * (r0 + 1))
 
 
 @pytest.mark.parametrize("rank", [1, 2])
@@ -270,23 +254,22 @@ def test_ckks_chain_multiply_rescale_add_add_pt_on_device(mods, rank):
         so.run(ref, p_pt, Ct(B, size, 20, 18, cols, d.data), pt=Pt(B, 2, 20, VecZnx(n, 1, 2, pt_h[0].copy())))
         want[t] = d.data.data
 
-    d_a, d_b, d_o, d_pt = _up(hip, a_all), _up(hip, b_all), _up(hip, o_all), _up(hip, pt_h)
-    d_k = _up(hip, ph.data)
-    d_m = hip.device_alloc(want.nbytes)
-    d_d = hip.device_alloc(want.nbytes)
-    tp = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=B, a_effective_k=B * a_size, b_effective_k=B * b_size, res_size=t_size,
-                          res_base2k=B, cnv_offset=off)
-    rp = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=B, a_size=t_size, a_base2k=B, res_size=size, res_base2k=B,
-                      rank_out=rank)
-    hip.glwe_tensor_mul_relinearize_batched(d_m.ptr, d_a.ptr, d_b.ptr, d_k.ptr, tp, rp, "apply", batch)
-    m_dev = Ct(B, size, 20, 28, cols, d_m.ptr)
-    p_rs.launch(hip, m_dev, batch)
-    dd = Ct(B, size, 0, 0, cols, d_d.ptr)
-    p_add.launch(hip, dd, batch, m_dev, Ct(B, size, 20, 25, cols, d_o.ptr))
-    p_pt.launch(hip, dd, batch, pt=Pt(B, 2, 20, d_pt.ptr), shared=("pt",))
-    hip.sync()
-    got = _down(d_d, want.shape)
-    for buf in (d_a, d_b, d_o, d_pt, d_k, d_m, d_d):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a, d_b, d_o, d_pt = dev.upload(a_all), dev.upload(b_all), dev.upload(o_all), dev.upload(pt_h)
+        d_k = dev.key(ph)
+        d_m = dev.alloc(want.nbytes, poison=False)
+        d_d = dev.alloc(want.nbytes, poison=False)
+        tp = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=B, a_effective_k=B * a_size, b_effective_k=B * b_size, res_size=t_size,
+                              res_base2k=B, cnv_offset=off)
+        rp = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=B, a_size=t_size, a_base2k=B, res_size=size, res_base2k=B,
+                          rank_out=rank)
+        hip.glwe_tensor_mul_relinearize_batched(d_m.ptr, d_a.ptr, d_b.ptr, d_k.ptr, tp, rp, "apply", batch)
+        m_dev = Ct(B, size, 20, 28, cols, d_m.ptr)
+        p_rs.launch(hip, m_dev, batch)
+        dd = Ct(B, size, 0, 0, cols, d_d.ptr)
+        p_add.launch(hip, dd, batch, m_dev, Ct(B, size, 20, 25, cols, d_o.ptr))
+        p_pt.launch(hip, dd, batch, pt=Pt(B, 2, 20, d_pt.ptr), shared=("pt",))
+        hip.sync()
+        got = _down(d_d, want.shape)
     assert (dd.log_delta, dd.log_budget) == (20, 18)
     assert np.array_equal(got, want)

@@ -11,22 +11,10 @@ import numpy as np
 import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx, VecZnxBig, VecZnxDft
+from tests.device import mods, on_device, prepared_key  # noqa: F401
 from tests.helpers import seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _finish(mod, d, base2k, res_size):
@@ -152,18 +140,13 @@ def _run_tensor(hip, ref, n, rank, a_size, b_size, res_size, ab_base2k, res_base
         else:
             ref.glwe_tensor_apply(cnv_offset, r, res_base2k, a, a_k, b, b_k, ab_base2k, add_assign=(mode == "add_assign"))
         want[t] = r.data
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_b = hip.device_alloc(b_all.nbytes).upload(b_all)
-    d_r = hip.device_alloc(prev.nbytes).upload(prev)
     p = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=ab_base2k, a_effective_k=a_k, b_effective_k=b_k,
                          res_size=res_size, res_base2k=res_base2k, cnv_offset=cnv_offset)
-    hip.set_chunk(chunk)
-    hip.glwe_tensor_apply_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, p, mode, batch)
-    hip.sync()
-    hip.set_chunk(0)
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_a, d_b, d_r):
-        buf.free()
+    with on_device(hip, chunk=chunk) as dev:
+        d_a, d_b, d_r = dev.upload(a_all), dev.upload(b_all), dev.upload(prev)
+        hip.glwe_tensor_apply_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, p, mode, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     return got, want
 
 
@@ -218,9 +201,7 @@ def _run_relinearize(hip, ref, n, rank, a_size, a_base2k, key_size, key_base2k, 
     rng = seeded(seed)
     cols, pairs = rank + 1, rank * (rank + 1) // 2
     mat = MatZnx(n, dnum, pairs, cols, key_size).fill_uniform(key_base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, pairs, cols, key_size), hip.vmp_pmat_alloc(dnum, pairs, cols, key_size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, mat)
     a_all = np.empty((batch, a_size, cols + pairs, n), dtype=np.int64)
     want = np.empty((batch, res_size, cols, n), dtype=np.int64)
     for t in range(batch):
@@ -231,25 +212,15 @@ def _run_relinearize(hip, ref, n, rank, a_size, a_base2k, key_size, key_base2k, 
         r = VecZnx(n, cols, res_size)
         ref.glwe_tensor_relinearize(r, res_base2k, a, a_base2k, pr, dsize, key_base2k)
         want[t] = r.data
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, want.nbytes)
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_base2k, a_size=a_size, a_base2k=a_base2k,
                      res_size=res_size, res_base2k=res_base2k, rank_out=rank)
-    hip.set_chunk(chunk)
-    hip.set_fusion(*fuse)
-    if pin:
-        hip.pin_key(d_k.ptr, dnum, pairs, cols, key_size)
-    hip.glwe_tensor_relinearize_batched(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
-    hip.sync()
-    if pin:
-        hip.unpin_key(d_k.ptr)
-    hip.set_chunk(0)
-    hip.set_fusion(True, True)
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_a, d_k, d_r):
-        buf.free()
+    with on_device(hip, chunk=chunk, fuse=fuse) as dev:
+        d_a, d_k, d_r = dev.upload(a_all), dev.key(ph), dev.alloc(want.nbytes)
+        if pin:
+            dev.pin(d_k, dnum, pairs, cols, key_size)
+        hip.glwe_tensor_relinearize_batched(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     return got, want
 
 
@@ -290,9 +261,7 @@ def _run_mul_relinearize(hip, ref, n, rank, a_size, b_size, t_size, base2k, cnv_
     a_k = base2k * a_size - a_bits_off
     b_k = a_k if square else base2k * b_size
     mat = MatZnx(n, dnum, pairs, cols, key_size).fill_uniform(key_base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, pairs, cols, key_size), hip.vmp_pmat_alloc(dnum, pairs, cols, key_size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, mat)
     a_all = np.empty((batch, a_size, cols, n), dtype=np.int64)
     b_all = np.empty((batch, (a_size if square else b_size), cols, n), dtype=np.int64)
     want = np.empty((batch, res_size, cols, n), dtype=np.int64)
@@ -312,26 +281,17 @@ def _run_mul_relinearize(hip, ref, n, rank, a_size, b_size, t_size, base2k, cnv_
         r = VecZnx(n, cols, res_size)
         ref.glwe_tensor_relinearize(r, res_base2k, tmp, base2k, pr, dsize, key_base2k)
         want[t] = r.data
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_b = hip.device_alloc(b_all.nbytes).upload(b_all)
-    d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, want.nbytes)
     tp = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=base2k, a_effective_k=a_k, b_effective_k=b_k, res_size=t_size,
                           res_base2k=base2k, cnv_offset=cnv_offset)
     rp = GlweOpParams(rank=rank, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_base2k, a_size=t_size, a_base2k=base2k,
                       res_size=res_size, res_base2k=res_base2k, rank_out=rank)
-    hip.set_chunk(chunk)
-    if pin:
-        hip.pin_key(d_k.ptr, dnum, pairs, cols, key_size)
-    hip.glwe_tensor_mul_relinearize_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, d_k.ptr, tp, rp, mode, batch)
-    hip.sync()
-    if pin:
-        hip.unpin_key(d_k.ptr)
-    hip.set_chunk(0)
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_a, d_b, d_k, d_r):
-        buf.free()
+    with on_device(hip, chunk=chunk) as dev:
+        d_a, d_b, d_k, d_r = dev.upload(a_all), dev.upload(b_all), dev.key(ph), dev.alloc(want.nbytes)
+        if pin:
+            dev.pin(d_k, dnum, pairs, cols, key_size)
+        hip.glwe_tensor_mul_relinearize_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, d_k.ptr, tp, rp, mode, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     return got, want
 
 
@@ -380,51 +340,49 @@ def test_vec_znx_family_batched(mods, n):
         a = rng.integers(-(1 << 40), 1 << 40, (batch, as_, ac, n), dtype=np.int64)
         b = rng.integers(-(1 << 40), 1 << 40, (batch, bs, bc, n), dtype=np.int64)
         r0 = rng.integers(-(1 << 40), 1 << 40, (batch, rs, rc, n), dtype=np.int64)
-        d_a, d_b = hip.device_alloc(a.nbytes).upload(a), hip.device_alloc(b.nbytes).upload(b)
-        d_r = hip.device_alloc(r0.nbytes)
-        rcol, acol, bcol = rc - 1, ac - 1, 0
+        with on_device(hip) as dev:
+            d_a, d_b, d_r = dev.upload(a), dev.upload(b), dev.alloc(r0.nbytes, poison=False)
+            rcol, acol, bcol = rc - 1, ac - 1, 0
 
-        def oracle(fn):
-            out = r0.copy()
-            for t in range(batch):
-                fn(VecZnx(n, rc, rs, out[t]), VecZnx(n, ac, as_, a[t].copy()), VecZnx(n, bc, bs, b[t].copy()))
-            return out
+            def oracle(fn):
+                out = r0.copy()
+                for t in range(batch):
+                    fn(VecZnx(n, rc, rs, out[t]), VecZnx(n, ac, as_, a[t].copy()), VecZnx(n, bc, bs, b[t].copy()))
+                return out
 
-        def device(call):
-            d_r.upload(r0)
-            hip._ck(call())
-            hip.sync()
-            return d_r.download(np.int64, r0.size).reshape(r0.shape)
+            def device(call):
+                d_r.upload(r0)
+                hip._ck(call())
+                hip.sync()
+                return d_r.download(np.int64, r0.size).reshape(r0.shape)
 
-        L = hip.lib
-        cases = {
-            "add_into": (lambda r, x, y: ref.vec_znx_add_into(r, rcol, x, acol, y, bcol),
-                         lambda: L.pz_vec_znx_add_into_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol), d_b.ptr, *sz(bc, bs, bcol))),
-            "sub": (lambda r, x, y: ref.vec_znx_sub(r, rcol, x, acol, y, bcol),
-                    lambda: L.pz_vec_znx_sub_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol), d_b.ptr, *sz(bc, bs, bcol))),
-            "add_assign": (lambda r, x, y: ref.vec_znx_add_assign(r, rcol, x, acol),
-                           lambda: L.pz_vec_znx_add_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "sub_assign": (lambda r, x, y: ref.vec_znx_sub_assign(r, rcol, x, acol),
-                           lambda: L.pz_vec_znx_sub_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "sub_negate_assign": (lambda r, x, y: ref.vec_znx_sub_negate_assign(r, rcol, x, acol),
-                                  lambda: L.pz_vec_znx_sub_negate_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "negate": (lambda r, x, y: ref.vec_znx_negate(r, rcol, x, acol),
-                       lambda: L.pz_vec_znx_negate_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "copy": (lambda r, x, y: ref.vec_znx_copy(r, rcol, x, acol),
-                     lambda: L.pz_vec_znx_copy_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "rotate": (lambda r, x, y: ref.vec_znx_rotate(-7 - n, r, rcol, x, acol),
-                       lambda: L.pz_vec_znx_rotate_batched(hip.handle, C.c_size_t(batch), C.c_int64(-7 - n), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "normalize": (lambda r, x, y: ref.vec_znx_normalize(r, 13, -5, rcol, x, 17, acol),
-                          lambda: L.pz_vec_znx_normalize_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, 13), C.c_int64(-5), C.c_size_t(rcol), d_a.ptr, *sz(ac, as_, 17, acol))),
-            "lsh": (lambda r, x, y: ref.vec_znx_lsh(14, 19, r, rcol, x, acol),
-                    lambda: L.pz_vec_znx_lsh_batched(hip.handle, C.c_size_t(batch), *sz(14, 19), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-            "rsh": (lambda r, x, y: ref.vec_znx_rsh(14, 23, r, rcol, x, acol),
-                    lambda: L.pz_vec_znx_rsh_batched(hip.handle, C.c_size_t(batch), *sz(14, 23), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
-        }
-        for name, (of, df) in cases.items():
-            assert np.array_equal(device(df), oracle(of)), (n, name, rc, rs, ac, as_)
-        want = r0.copy()
-        want[:, :, rcol] = 0
-        assert np.array_equal(device(lambda: L.pz_vec_znx_zero_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol))), want)
-        for buf in (d_a, d_b, d_r):
-            buf.free()
+            L = hip.lib
+            cases = {
+                "add_into": (lambda r, x, y: ref.vec_znx_add_into(r, rcol, x, acol, y, bcol),
+                             lambda: L.pz_vec_znx_add_into_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol), d_b.ptr, *sz(bc, bs, bcol))),
+                "sub": (lambda r, x, y: ref.vec_znx_sub(r, rcol, x, acol, y, bcol),
+                        lambda: L.pz_vec_znx_sub_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol), d_b.ptr, *sz(bc, bs, bcol))),
+                "add_assign": (lambda r, x, y: ref.vec_znx_add_assign(r, rcol, x, acol),
+                               lambda: L.pz_vec_znx_add_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "sub_assign": (lambda r, x, y: ref.vec_znx_sub_assign(r, rcol, x, acol),
+                               lambda: L.pz_vec_znx_sub_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "sub_negate_assign": (lambda r, x, y: ref.vec_znx_sub_negate_assign(r, rcol, x, acol),
+                                      lambda: L.pz_vec_znx_sub_negate_assign_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "negate": (lambda r, x, y: ref.vec_znx_negate(r, rcol, x, acol),
+                           lambda: L.pz_vec_znx_negate_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "copy": (lambda r, x, y: ref.vec_znx_copy(r, rcol, x, acol),
+                         lambda: L.pz_vec_znx_copy_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "rotate": (lambda r, x, y: ref.vec_znx_rotate(-7 - n, r, rcol, x, acol),
+                           lambda: L.pz_vec_znx_rotate_batched(hip.handle, C.c_size_t(batch), C.c_int64(-7 - n), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "normalize": (lambda r, x, y: ref.vec_znx_normalize(r, 13, -5, rcol, x, 17, acol),
+                              lambda: L.pz_vec_znx_normalize_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, 13), C.c_int64(-5), C.c_size_t(rcol), d_a.ptr, *sz(ac, as_, 17, acol))),
+                "lsh": (lambda r, x, y: ref.vec_znx_lsh(14, 19, r, rcol, x, acol),
+                        lambda: L.pz_vec_znx_lsh_batched(hip.handle, C.c_size_t(batch), *sz(14, 19), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+                "rsh": (lambda r, x, y: ref.vec_znx_rsh(14, 23, r, rcol, x, acol),
+                        lambda: L.pz_vec_znx_rsh_batched(hip.handle, C.c_size_t(batch), *sz(14, 23), d_r.ptr, *sz(rc, rs, rcol), d_a.ptr, *sz(ac, as_, acol))),
+            }
+            for name, (of, df) in cases.items():
+                assert np.array_equal(device(df), oracle(of)), (n, name, rc, rs, ac, as_)
+            want = r0.copy()
+            want[:, :, rcol] = 0
+            assert np.array_equal(device(lambda: L.pz_vec_znx_zero_batched(hip.handle, C.c_size_t(batch), d_r.ptr, *sz(rc, rs, rcol))), want)

@@ -11,23 +11,11 @@ import pytest
 
 from tests import core_cases as cs
 from tests import fhe_sk as fs
+from tests.device import mods, on_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 3
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _device(hip, c, in_place=False, fuse=(True, True), chunk=0):
@@ -38,19 +26,15 @@ def _device(hip, c, in_place=False, fuse=(True, True), chunk=0):
     a_all = np.ascontiguousarray(c.a)
     shape = (a_all.shape[0], c.res_size, cols_out, n)
     nbytes = int(np.prod(shape)) * 8
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    if in_place:
-        assert a_all.shape == shape
-        d_res = d_a
-    else:
-        d_res = hip.device_alloc(nbytes)
-        hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, nbytes)
     p = GlweOpParams(rank=c.rank, dnum=rows, dsize=c.dsize, key_size=ksz, key_base2k=c.key_base2k, a_size=a_all.shape[1],
                      a_base2k=c.a_base2k, res_size=c.res_size, res_base2k=c.res_base2k, rank_out=c.rank_out)
-    try:
-        hip.set_chunk(chunk)
-        hip.set_fusion(*fuse)
+    with on_device(hip, chunk=chunk, fuse=fuse) as dev:
+        d_a, d_key = dev.upload(a_all), dev.key(ph)
+        if in_place:
+            assert a_all.shape == shape
+            d_res = d_a
+        else:
+            d_res = dev.alloc(nbytes)
         hip.dispatch_notes(reset=True)
         if c.op == "auto":
             hip.glwe_automorphism_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, c.p % (2 * n), c.mode, len(a_all))
@@ -61,11 +45,6 @@ def _device(hip, c, in_place=False, fuse=(True, True), chunk=0):
         hip.sync()
         got = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
         notes = hip.dispatch_notes()
-    finally:
-        hip.set_chunk(0)
-        hip.set_fusion(True, True)
-        for buf in ((d_a, d_key) if in_place else (d_a, d_key, d_res)):
-            buf.free()
     return got, notes
 
 
@@ -118,8 +97,7 @@ def test_routes_decrypt(mods, shape, op, mode):
     # the spectral automorphism from N = 4096 on the fused pipeline; its 16-bit body operand where the tail's plan has that form (N >= 8192 here)
     perm = op == "auto" and knob not in ("unfused", "small-on") and n >= 4096
     body16 = perm and n >= 8192
-    try:
-        hip.set_small_path(knob != "small-off")
+    with on_device(hip, small_path=knob != "small-off"):
         for in_place in (False, True):
             c = _shape_case(op, n, 1, limbs, base2k, seed=n + limbs + int(in_place) + 7 * len(mode or op), mode=mode or "automorphism",
                             p=P_SPECTRAL)
@@ -132,8 +110,6 @@ def test_routes_decrypt(mods, shape, op, mode):
             if knob == "unfused" or (knob == "small-on" and op != "auto"):
                 assert "k_mid128" not in notes, (label, notes)
             assert ("PERM=1" in notes) == perm and (BODY16 in notes) == body16, (label, notes)
-    finally:
-        hip.set_small_path(True)
 
 
 @pytest.mark.parametrize("mode", ["automorphism", "add"])

@@ -17,6 +17,7 @@ import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx
 from tests import unnormalized as un
+from tests.device import prepared_key
 from tests.helpers import MARGIN_MAX, seeded
 
 pytestmark = pytest.mark.gpu
@@ -95,10 +96,7 @@ def _after_change(mod, case, label, note=None):
 
 
 def _prepared(hip, ref, n, rows, cols_in, cols_out, size, base2k, rng):
-    mat = MatZnx(n, rows, cols_in, cols_out, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(rows, cols_in, cols_out, size), hip.vmp_pmat_alloc(rows, cols_in, cols_out, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, MatZnx(n, rows, cols_in, cols_out, size).fill_uniform(base2k, rng))
     hip.sync()
     return pr, ph
 

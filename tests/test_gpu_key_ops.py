@@ -14,6 +14,7 @@ import pytest
 from tests import fhe_sk as fs
 from tests import key_ops_cases as kc
 from tests import unnormalized as un
+from tests.device import mods, on_device  # noqa: F401
 from tests.helpers import MARGIN_MAX, seeded
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +22,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAST = "key composition: key switch by the permuted key"
 COMPOSED = "key composition: automorphism + glwe_automorphism"
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 @pytest.fixture(autouse=True)
@@ -81,23 +69,21 @@ def device(hip, s, a_gal, res_dnum=None, res_size=None, in_place=False, key="dev
     res_dnum, res_size = res_dnum or s.a_dnum, res_size or s.a_size
     ph = kc.prepare(hip, s.key)
     shape = (s.count, res_dnum, s.rank, res_size, s.rank + 1, s.n)
-    d_a = hip.device_alloc(s.a.nbytes).upload(s.a)
-    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    key_ptr = d_key.ptr if key == "device" else ph.data.ctypes.data
-    if in_place:
-        assert shape == s.a.shape
-        d_res = d_a
-    else:
-        d_res = hip.device_alloc(int(np.prod(shape)) * 8)
-        hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, int(np.prod(shape)) * 8)
-    try:
+    with on_device(hip) as dev:
+        d_a, d_key = dev.upload(s.a), dev.key(ph)
+        key_ptr = d_key.ptr if key == "device" else ph.data.ctypes.data
+        if in_place:
+            assert shape == s.a.shape
+            d_res = d_a
+        else:
+            d_res = dev.alloc(int(np.prod(shape)) * 8)
         if pin:   # ... and one plain key switch by the pinned key first, so that its cached row slices exist when the composition runs
-            hip.pin_key(d_key.ptr, s.key_dnum, s.rank, s.rank + 1, s.key_size)
-            d_warm = hip.device_alloc(int(np.prod(shape)) * 8)
+            dev.pin(d_key, s.key_dnum, s.rank, s.rank + 1, s.key_size)
+            d_warm = dev.alloc(int(np.prod(shape)) * 8, poison=False)
             hip.glwe_keyswitch_batched(d_warm.ptr, d_a.ptr, d_key.ptr, s.params(res_size), s.count * res_dnum * s.rank)
             hip.sync()
             warm = d_warm.download(np.int64, int(np.prod(shape))).reshape(shape)
-            d_warm.free()
+            dev.free(d_warm)
         hip.dispatch_notes(reset=True)
         gal = hip.glwe_automorphism_key_automorphism_batched(d_res.ptr, res_dnum, d_a.ptr, s.a_dnum, a_gal, key_ptr, -5, s.params(res_size), s.count)
         assert gal == (a_gal * -5) % (2 * s.n)
@@ -110,11 +96,6 @@ def device(hip, s, a_gal, res_dnum=None, res_size=None, in_place=False, key="dev
             hip.sync()
             extra = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
             assert np.array_equal(extra, warm), "the pinned key's cached slices changed across the composition call"
-    finally:
-        if pin:
-            hip.unpin_key(d_key.ptr)
-        for buf in ((d_a, d_key) if in_place else (d_a, d_key, d_res)):
-            buf.free()
     return (got, notes, extra) if pin else (got, notes)
 
 
@@ -189,13 +170,11 @@ def test_identity_element_is_a_plain_key_switch(mods, name):
     assert np.array_equal(got, want)
     # ... and the device's own key switch says the same
     ph = kc.prepare(hip, s.key)
-    d_a, d_key = hip.device_alloc(s.a.nbytes).upload(s.a), hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_res = hip.device_alloc(s.a.nbytes)
-    hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, s.params(s.a_size), s.count * s.a_dnum * s.rank)
-    hip.sync()
-    assert np.array_equal(d_res.download(np.int64, s.a.size).reshape(got.shape), got)
-    for b in (d_a, d_key, d_res):
-        b.free()
+    with on_device(hip) as dev:
+        d_a, d_key, d_res = dev.upload(s.a), dev.key(ph), dev.alloc(s.a.nbytes, poison=False)
+        hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, s.params(s.a_size), s.count * s.a_dnum * s.rank)
+        hip.sync()
+        assert np.array_equal(d_res.download(np.int64, s.a.size).reshape(got.shape), got)
 
 
 def _digest(x):
@@ -314,25 +293,19 @@ def ggsw_device(hip, s, op, gal=None, res_dnum=None, in_place=False):
     shape = (s.count, res_dnum, cols, s.res_size, cols, s.n)
     ph = kc.prepare(hip, s.key)
     pts = [kc.prepare(hip, t) for t in s.tsk]
-    d_a = hip.device_alloc(s.a.nbytes).upload(s.a)
-    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_tsk = [hip.device_alloc(p.data.nbytes).upload(p.data) for p in pts]
-    if in_place:
-        assert shape == s.a.shape
-        d_res = d_a
-    else:
-        d_res = hip.device_alloc(int(np.prod(shape)) * 8)
-        hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, int(np.prod(shape)) * 8)
-    try:
+    with on_device(hip) as dev:
+        d_a, d_key, d_tsk = dev.upload(s.a), dev.key(ph), [dev.key(p) for p in pts]
+        if in_place:
+            assert shape == s.a.shape
+            d_res = d_a
+        else:
+            d_res = dev.alloc(int(np.prod(shape)) * 8)
         if op == "ks":
             hip.ggsw_keyswitch_batched(d_res.ptr, d_a.ptr, s.a_dnum, d_key.ptr, [t.ptr for t in d_tsk], s.params(), s.params(expand=True), s.count)
         else:
             hip.ggsw_automorphism_batched(d_res.ptr, res_dnum, d_a.ptr, s.a_dnum, d_key.ptr, gal, [t.ptr for t in d_tsk], s.params(), s.params(expand=True), s.count)
         hip.sync()
         return d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
-    finally:
-        for buf in [d_a, d_key] + d_tsk + ([] if in_place else [d_res]):
-            buf.free()
 
 
 def ggsw_oracle(ref, s, op, gal=None, res_dnum=None):

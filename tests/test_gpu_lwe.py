@@ -5,22 +5,10 @@ import numpy as np
 import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx
+from tests.device import mods, on_device, prepared_key  # noqa: F401
 from tests.helpers import seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def rand_lwe(rng, batch, size, n_lwe, base2k):
@@ -28,11 +16,7 @@ def rand_lwe(rng, batch, size, n_lwe, base2k):
 
 
 def prepared(ref, hip, rng, n, dnum, cols_in, cols_out, size, base2k):
-    mat = MatZnx(n, dnum, cols_in, cols_out, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, cols_in, cols_out, size), hip.vmp_pmat_alloc(dnum, cols_in, cols_out, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
-    return pr, ph
+    return prepared_key(ref, hip, MatZnx(n, dnum, cols_in, cols_out, size).fill_uniform(base2k, rng))
 
 
 @pytest.mark.parametrize("n2,base2k,size", [(2048, 17, 2), (2048, 12, 2), (2048, 5, 4), (1 << 15, 13, 3), (64, 7, 1), (4096, 13, 1), (1024, 11, 2)])
@@ -45,22 +29,22 @@ def test_mod_switch_2n(mods, n2, base2k, size, negate):
     batch, n_lwe = 37, 101
     lwe = rand_lwe(rng, batch, size, n_lwe, base2k)
     want = np.stack([ref.mod_switch_2n(n2, lwe[b], base2k, negate) for b in range(batch)])
-    d_l = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.lwe_mod_switch_2n_batched(d_r.ptr, d_l.ptr, n_lwe, size, base2k, n2, negate, batch)
-    hip.sync()
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    d_l.free(); d_r.free()
+    with on_device(hip) as dev:
+        d_l = dev.upload(lwe)
+        d_r = dev.alloc(want.nbytes, poison=False)
+        hip.lwe_mod_switch_2n_batched(d_r.ptr, d_l.ptr, n_lwe, size, base2k, n2, negate, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
 def test_mod_switch_2n_rejects_short_lwes(mods):
     from poulpy_amd.hal import PoulpyHipError
     _, hip = mods(256)
-    d = hip.device_alloc(1 << 16)
-    with pytest.raises(PoulpyHipError):
-        hip.lwe_mod_switch_2n_batched(d.ptr, d.ptr, 10, 1, 5, 2048, False, 1)   # 12 bits wanted, one limb of 5
-    d.free()
+    with on_device(hip) as dev:
+        d = dev.alloc(1 << 16, poison=False)
+        with pytest.raises(PoulpyHipError):
+            hip.lwe_mod_switch_2n_batched(d.ptr, d.ptr, 10, 1, 5, 2048, False, 1)   # 12 bits wanted, one limb of 5
 
 
 @pytest.mark.parametrize("n,n_lwe", [(256, 100), (1024, 1024), (4096, 77)])
@@ -70,13 +54,13 @@ def test_sample_extract(mods, n, n_lwe):
     for cols, a_size, res_size, batch in ((2, 3, 3, 5), (2, 4, 2, 3), (3, 2, 4, 2)):
         a = rng.integers(-2048, 2048, (batch, a_size, cols, n), dtype=np.int64)
         want = np.stack([ref.lwe_sample_extract(n_lwe, res_size, VecZnx(n, cols, a_size, a[b].copy())) for b in range(batch)])
-        d_a = hip.device_alloc(a.nbytes).upload(a)
-        d_r = hip.device_alloc(want.nbytes)
-        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
-        hip.lwe_sample_extract_batched(d_r.ptr, n_lwe, res_size, d_a.ptr, cols, a_size, batch)
-        hip.sync()
-        got = d_r.download(np.int64, want.size).reshape(want.shape)
-        d_a.free(); d_r.free()
+        with on_device(hip) as dev:
+            d_a = dev.upload(a)
+            d_r = dev.alloc(want.nbytes, poison=False)
+            hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
+            hip.lwe_sample_extract_batched(d_r.ptr, n_lwe, res_size, d_a.ptr, cols, a_size, batch)
+            hip.sync()
+            got = d_r.download(np.int64, want.size).reshape(want.shape)
         assert np.array_equal(got, want)
 
 
@@ -99,15 +83,14 @@ def test_lwe_keyswitch(mods, n, n_in, n_out, a_size, res_size, a_b, key_b, res_b
     want = np.stack([ref.lwe_keyswitch(n_out, res_size, res_b, lwe[b], a_b, pr, dsize, key_b) for b in range(batch)])
     p = GlweOpParams(rank=1, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_b, a_size=a_size, a_base2k=a_b, res_size=res_size,
                      res_base2k=res_b, rank_out=1)
-    d_l = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
-    hip.lwe_keyswitch_batched(d_r.ptr, n_out, d_l.ptr, n_in, d_k.ptr, p, batch)
-    hip.sync()
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_l, d_k, d_r):
-        buf.free()
+    with on_device(hip) as dev:
+        d_l = dev.upload(lwe)
+        d_k = dev.key(ph)
+        d_r = dev.alloc(want.nbytes, poison=False)
+        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
+        hip.lwe_keyswitch_batched(d_r.ptr, n_out, d_l.ptr, n_in, d_k.ptr, p, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -132,14 +115,13 @@ def test_glwe_from_lwe(mods, n, n_lwe, lwe_size, lwe_b, key_b, rank_out, fill=No
         want[b] = r.data
     p = GlweOpParams(rank=1, dnum=dnum, dsize=1, key_size=key_size, key_base2k=key_b, a_size=glwe_size, a_base2k=key_b, res_size=res_size,
                      res_base2k=key_b, rank_out=rank_out)
-    d_l = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.glwe_from_lwe_batched(d_r.ptr, d_l.ptr, n_lwe, lwe_size, lwe_b, d_k.ptr, p, batch)
-    hip.sync()
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_l, d_k, d_r):
-        buf.free()
+    with on_device(hip) as dev:
+        d_l = dev.upload(lwe)
+        d_k = dev.key(ph)
+        d_r = dev.alloc(want.nbytes, poison=False)
+        hip.glwe_from_lwe_batched(d_r.ptr, d_l.ptr, n_lwe, lwe_size, lwe_b, d_k.ptr, p, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -159,15 +141,14 @@ def test_lwe_from_glwe(mods, n, rank, a_idx, n_lwe, fill=None):
                      for b in range(batch)])
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,
                      res_base2k=base2k, rank_out=1)
-    d_a = hip.device_alloc(a.nbytes).upload(a)
-    d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_r = hip.device_alloc(want.nbytes)
-    hip.lwe_from_glwe_batched(d_r.ptr, n_lwe, d_a.ptr, a_idx, d_k.ptr, p, batch)
-    hip.sync()
-    got = d_r.download(np.int64, want.size).reshape(want.shape)
-    a_after = d_a.download(np.int64, a.size).reshape(a.shape)
-    for buf in (d_a, d_k, d_r):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a = dev.upload(a)
+        d_k = dev.key(ph)
+        d_r = dev.alloc(want.nbytes, poison=False)
+        hip.lwe_from_glwe_batched(d_r.ptr, n_lwe, d_a.ptr, a_idx, d_k.ptr, p, batch)
+        hip.sync()
+        got = d_r.download(np.int64, want.size).reshape(want.shape)
+        a_after = d_a.download(np.int64, a.size).reshape(a.shape)
     assert np.array_equal(got, want) and np.array_equal(a_after, a)
 
 
@@ -200,24 +181,23 @@ def test_gate_bootstrap_chain(mods, block_size):
         want_acc[b] = acc.data
         want_out[b] = ref.lwe_from_glwe(n_lwe, rsz, k, acc, k, 0, ksk_r, 1, k)
     # device chain
-    d_lwe = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_2n = hip.device_alloc(want_2n.nbytes)
-    d_lut = hip.device_alloc(lut.data.nbytes).upload(lut.data)
-    d_brk = hip.device_alloc(brk_h.nbytes).upload(brk_h)
-    d_ksk = hip.device_alloc(ksk_h.data.nbytes).upload(ksk_h.data)
-    d_acc = hip.device_alloc(want_acc.nbytes)
-    d_out = hip.device_alloc(want_out.nbytes)
-    hip.lwe_mod_switch_2n_batched(d_2n.ptr, d_lwe.ptr, n_lwe, 2, k, 2 * n, False, batch)
-    bp = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
-    hip.blind_rotation_execute_batched(d_acc.ptr, d_2n.ptr, d_lut.ptr, d_brk.ptr, bp, batch)
-    kp = GlweOpParams(rank=rank, dnum=rsz, dsize=1, key_size=rsz + 1, key_base2k=k, a_size=rsz, a_base2k=k, res_size=rsz, res_base2k=k, rank_out=1)
-    hip.lwe_from_glwe_batched(d_out.ptr, n_lwe, d_acc.ptr, 0, d_ksk.ptr, kp, batch)
-    hip.sync()
-    got_2n = d_2n.download(np.int64, want_2n.size).reshape(want_2n.shape)
-    got_acc = d_acc.download(np.int64, want_acc.size).reshape(want_acc.shape)
-    got_out = d_out.download(np.int64, want_out.size).reshape(want_out.shape)
-    for buf in (d_lwe, d_2n, d_lut, d_brk, d_ksk, d_acc, d_out):
-        buf.free()
+    with on_device(hip) as dev:
+        d_lwe = dev.upload(lwe)
+        d_2n = dev.alloc(want_2n.nbytes, poison=False)
+        d_lut = dev.upload(lut.data)
+        d_brk = dev.upload(brk_h)
+        d_ksk = dev.key(ksk_h)
+        d_acc = dev.alloc(want_acc.nbytes, poison=False)
+        d_out = dev.alloc(want_out.nbytes, poison=False)
+        hip.lwe_mod_switch_2n_batched(d_2n.ptr, d_lwe.ptr, n_lwe, 2, k, 2 * n, False, batch)
+        bp = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
+        hip.blind_rotation_execute_batched(d_acc.ptr, d_2n.ptr, d_lut.ptr, d_brk.ptr, bp, batch)
+        kp = GlweOpParams(rank=rank, dnum=rsz, dsize=1, key_size=rsz + 1, key_base2k=k, a_size=rsz, a_base2k=k, res_size=rsz, res_base2k=k, rank_out=1)
+        hip.lwe_from_glwe_batched(d_out.ptr, n_lwe, d_acc.ptr, 0, d_ksk.ptr, kp, batch)
+        hip.sync()
+        got_2n = d_2n.download(np.int64, want_2n.size).reshape(want_2n.shape)
+        got_acc = d_acc.download(np.int64, want_acc.size).reshape(want_acc.shape)
+        got_out = d_out.download(np.int64, want_out.size).reshape(want_out.shape)
     assert np.array_equal(got_2n, want_2n)
     assert np.array_equal(got_acc, want_acc)
     assert np.array_equal(got_out, want_out)

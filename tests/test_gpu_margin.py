@@ -6,45 +6,27 @@ instantiations in their own translation units for every form of the fused tail, 
 launch_br_probe.hip; a run-time wave-uniform test in k_small_inv and k_small_idft): the results must stay bit-identical
 to the oracle's, and the margin max |x - round(x)| must be (a) non-zero - the probe really ran on this path, (b) far from 0.5 at the
 reference's parameters, (c) growing with base2k the way the error model says (about x4 per bit)."""
+from contextlib import contextmanager
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
+from tests.device import mods, on_device  # noqa: F401
 from tests.helpers import MARGIN_MAX
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
-
-
-class probing:
+@contextmanager
+def probing(hip):
     """with probing(hip) as box: ...   -> box.margin after the block"""
-
-    def __init__(self, hip):
-        self.hip, self.margin = hip, None
-
-    def __enter__(self):
-        self.hip.sync()
-        self.hip.set_margin_probe(True)
-        return self
-
-    def __exit__(self, *exc):
-        try:
-            self.hip.sync()
-            self.margin = self.hip.get_margin()
-        finally:
-            self.hip.set_margin_probe(False)
-        return False
+    box = SimpleNamespace(margin=None)
+    hip.sync()
+    with on_device(hip, probe=True):
+        yield box
+        hip.sync()
+        box.margin = hip.get_margin()
 
 
 GLWE_CASES = [
@@ -131,7 +113,7 @@ def test_probe_off_leaves_no_margin(mods):
     from tests.test_gpu_parity import _run_glwe_op
     n = 1024
     ref, hip = mods(n)
-    hip.set_margin_probe(True)
-    hip.set_margin_probe(False)
+    with on_device(hip, probe=True):
+        pass
     _run_glwe_op(hip, ref, False, n, 1, 1, 2, 17, 2, 17, 2, 1, 2, 17, batch=2, seed=5)
     assert hip.get_margin() == 0.0

@@ -9,22 +9,10 @@ import pytest
 
 from poulpy_amd.layouts import VecZnx
 from tests import plain_oracle as po
+from tests.device import mods, on_device  # noqa: F401
 from tests.helpers import seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _run_plain(hip, ref, n, rank, a_size, b_size, res_size, ab, rb, off, mode, shared, batch, seed, chunk=0, abo=0, bbo=0, pool=None, a_fill=None,
@@ -59,25 +47,20 @@ def _run_plain(hip, ref, n, rank, a_size, b_size, res_size, ab, rb, off, mode, s
     idx = np.arange(batch) % pool
     a_all = np.ascontiguousarray(a_p[idx])
     pt_all = np.ascontiguousarray(pt_p if shared else pt_p[idx])
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_pt = hip.device_alloc(pt_all.nbytes).upload(pt_all)
-    if assign:
-        d_r = d_a
-    else:
-        d_r = hip.device_alloc(batch * res_size * cols * n * 8)
-        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, batch * res_size * cols * n * 8)
-    p = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=ab, a_effective_k=a_k, b_effective_k=b_k, res_size=res_size,
-                         res_base2k=rb if not assign else ab, cnv_offset=off)
-    assert hip.glwe_mul_plain_workspace_bytes(p, mode, shared, batch) > 0
-    hip.set_chunk(chunk)
-    try:
-        hip.glwe_mul_plain_batched(d_r.ptr, None if assign else d_a.ptr, d_pt.ptr, shared, p, mode, batch)
-        hip.sync()
-    finally:
-        hip.set_chunk(0)
-    got = d_r.download(np.int64, batch * res_size * cols * n).reshape(batch, res_size, cols, n)
-    for buf in {id(x): x for x in (d_a, d_pt, d_r)}.values():
-        buf.free()
+    with on_device(hip) as dev:
+        d_a = dev.upload(a_all)
+        d_pt = dev.upload(pt_all)
+        if assign:
+            d_r = d_a
+        else:
+            d_r = dev.alloc(batch * res_size * cols * n * 8)
+        p = GlweTensorParams(rank=rank, a_size=a_size, b_size=b_size, ab_base2k=ab, a_effective_k=a_k, b_effective_k=b_k, res_size=res_size,
+                             res_base2k=rb if not assign else ab, cnv_offset=off)
+        assert hip.glwe_mul_plain_workspace_bytes(p, mode, shared, batch) > 0
+        with on_device(hip, chunk=chunk):
+            hip.glwe_mul_plain_batched(d_r.ptr, None if assign else d_a.ptr, d_pt.ptr, shared, p, mode, batch)
+            hip.sync()
+        got = d_r.download(np.int64, batch * res_size * cols * n).reshape(batch, res_size, cols, n)
     return got, want_p[idx]
 
 
@@ -125,26 +108,22 @@ def _run_plain_pool(hip, ref, n, b_size, off, shared, batch, pool, chunk, seed):
         po.glwe_mul_plain(ref, off, r, k, a_p[t].copy(), size * k, pt_p[0 if shared else t].copy(), b_size * k, k)
         want.append(r.data)
     ct, pb = size * cols * n * 8, b_size * n * 8
-    d_a, d_r = hip.device_alloc(batch * ct), hip.device_alloc(batch * ct)
-    d_pt = hip.device_alloc((1 if shared else batch) * pb)
-    for t in range(batch):
-        hip._ck(hip.lib.pz_memcpy_h2d(hip.handle, d_a.at(t * ct), a_p[t % pool].data.ctypes.data_as(C.c_void_p), C.c_size_t(ct)))
-        if not shared:
-            hip._ck(hip.lib.pz_memcpy_h2d(hip.handle, d_pt.at(t * pb), pt_p[t % pool].data.ctypes.data_as(C.c_void_p), C.c_size_t(pb)))
-    if shared:
-        d_pt.upload(pt_p[0].data)
-    hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, C.c_size_t(batch * ct))
-    p = GlweTensorParams(rank=1, a_size=size, b_size=b_size, ab_base2k=k, a_effective_k=size * k, b_effective_k=b_size * k, res_size=size, res_base2k=k,
-                         cnv_offset=off)
-    hip.set_chunk(chunk)
-    try:
-        hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, shared, p, "into", batch)
-        hip.sync()
-    finally:
-        hip.set_chunk(0)
-    bad = [t for t in range(batch) if not np.array_equal(d_r.download(np.int64, ct // 8, t * ct).reshape(size, cols, n), want[t % pool])]
-    for buf in (d_a, d_r, d_pt):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a, d_r = dev.alloc(batch * ct, poison=False), dev.alloc(batch * ct, poison=False)
+        d_pt = dev.alloc((1 if shared else batch) * pb, poison=False)
+        for t in range(batch):
+            hip._ck(hip.lib.pz_memcpy_h2d(hip.handle, d_a.at(t * ct), a_p[t % pool].data.ctypes.data_as(C.c_void_p), C.c_size_t(ct)))
+            if not shared:
+                hip._ck(hip.lib.pz_memcpy_h2d(hip.handle, d_pt.at(t * pb), pt_p[t % pool].data.ctypes.data_as(C.c_void_p), C.c_size_t(pb)))
+        if shared:
+            d_pt.upload(pt_p[0].data)
+        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, C.c_size_t(batch * ct))
+        p = GlweTensorParams(rank=1, a_size=size, b_size=b_size, ab_base2k=k, a_effective_k=size * k, b_effective_k=b_size * k, res_size=size, res_base2k=k,
+                             cnv_offset=off)
+        with on_device(hip, chunk=chunk):
+            hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, shared, p, "into", batch)
+            hip.sync()
+        bad = [t for t in range(batch) if not np.array_equal(d_r.download(np.int64, ct // 8, t * ct).reshape(size, cols, n), want[t % pool])]
     assert not bad, bad[:8]
     return batch
 
@@ -264,23 +243,18 @@ def _run_const(hip, ref, n, rank, a_size, res_size, ab, rb, off, mode, re, im, b
         want_p[t] = r.data
     idx = np.arange(batch) % pool
     a_all = np.ascontiguousarray(a_p[idx])
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    if assign:
-        d_r = d_a
-    else:
-        d_r = hip.device_alloc(batch * res_size * cols * n * 8)
-        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, batch * res_size * cols * n * 8)
-    p = GlweMulConstParams(rank=rank, a_size=a_size, a_base2k=ab, res_size=res_size, res_base2k=rb, cnv_offset=off)
-    hip.set_chunk(chunk)
-    try:
-        b_size = len(re) if re is not None else (len(im) if im is not None else 0)
-        hip.glwe_mul_const_batched(d_r.ptr, None if assign else d_a.ptr, re, im, p, mode, batch, b_size=b_size)
-        hip.sync()
-    finally:
-        hip.set_chunk(0)
-    got = d_r.download(np.int64, batch * res_size * cols * n).reshape(batch, res_size, cols, n)
-    for buf in {id(x): x for x in (d_a, d_r)}.values():
-        buf.free()
+    with on_device(hip) as dev:
+        d_a = dev.upload(a_all)
+        if assign:
+            d_r = d_a
+        else:
+            d_r = dev.alloc(batch * res_size * cols * n * 8)
+        p = GlweMulConstParams(rank=rank, a_size=a_size, a_base2k=ab, res_size=res_size, res_base2k=rb, cnv_offset=off)
+        with on_device(hip, chunk=chunk):
+            b_size = len(re) if re is not None else (len(im) if im is not None else 0)
+            hip.glwe_mul_const_batched(d_r.ptr, None if assign else d_a.ptr, re, im, p, mode, batch, b_size=b_size)
+            hip.sync()
+        got = d_r.download(np.int64, batch * res_size * cols * n).reshape(batch, res_size, cols, n)
     return got, want_p[idx]
 
 
@@ -330,35 +304,34 @@ def test_refusals(mods):
     n = 256
     _, hip = mods(n)
     cols, size = 2, 3
-    d_a = hip.device_alloc(n * cols * size * 8)
-    d_r = hip.device_alloc(n * cols * size * 8)
-    d_pt = hip.device_alloc(n * size * 8)
-    host = np.zeros((size, cols, n), dtype=np.int64)
-    good = dict(rank=1, a_size=size, b_size=size, ab_base2k=12, a_effective_k=36, b_effective_k=36, res_size=size, res_base2k=12, cnv_offset=12)
-    bad = [dict(rank=0), dict(a_size=0), dict(ab_base2k=0), dict(res_base2k=64), dict(a_effective_k=40), dict(b_effective_k=20),
-           dict(cnv_offset=12 * 12)]
-    for d in bad:
-        with pytest.raises(PoulpyHipError):
-            hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, False, GlweTensorParams(**{**good, **d}), "into", 1)
-    p = GlweTensorParams(**good)
-    for (r, a, pt, mode) in ((host.ctypes.data, d_a.ptr, d_pt.ptr, "into"), (d_r.ptr, host.ctypes.data, d_pt.ptr, "into"),
-                             (d_r.ptr, d_a.ptr, host.ctypes.data, "into"), (d_r.ptr, d_r.ptr, d_pt.ptr, "into"), (d_r.ptr, None, d_r.ptr, "assign"),
-                             (d_r.ptr, d_a.ptr, d_pt.ptr, "assign")):
-        with pytest.raises(PoulpyHipError):
-            hip.glwe_mul_plain_batched(r, a, pt, False, p, mode, 1)
-    hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, False, p, "into", 0)   # batch 0: a no-op
-    cgood = dict(rank=1, a_size=size, a_base2k=12, res_size=size, res_base2k=12, cnv_offset=12)
-    b = np.array([3, -2], dtype=np.int64)
-    for d in (dict(rank=0), dict(res_size=0), dict(a_base2k=64), dict(cnv_offset=12 * 10)):
-        with pytest.raises(PoulpyHipError):
-            hip.glwe_mul_const_batched(d_r.ptr, d_a.ptr, b, None, GlweMulConstParams(**{**cgood, **d}), "into", 1)
-    cp = GlweMulConstParams(**cgood)
-    for (r, a, mode) in ((host.ctypes.data, d_a.ptr, "into"), (d_r.ptr, host.ctypes.data, "into"), (d_r.ptr, d_r.ptr, "into"),
-                         (d_r.ptr, d_a.ptr, "assign")):
-        with pytest.raises(PoulpyHipError):
-            hip.glwe_mul_const_batched(r, a, b, None, cp, mode, 1)
-    for buf in (d_a, d_r, d_pt):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a = dev.alloc(n * cols * size * 8, poison=False)
+        d_r = dev.alloc(n * cols * size * 8, poison=False)
+        d_pt = dev.alloc(n * size * 8, poison=False)
+        host = np.zeros((size, cols, n), dtype=np.int64)
+        good = dict(rank=1, a_size=size, b_size=size, ab_base2k=12, a_effective_k=36, b_effective_k=36, res_size=size, res_base2k=12, cnv_offset=12)
+        bad = [dict(rank=0), dict(a_size=0), dict(ab_base2k=0), dict(res_base2k=64), dict(a_effective_k=40), dict(b_effective_k=20),
+               dict(cnv_offset=12 * 12)]
+        for d in bad:
+            with pytest.raises(PoulpyHipError):
+                hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, False, GlweTensorParams(**{**good, **d}), "into", 1)
+        p = GlweTensorParams(**good)
+        for (r, a, pt, mode) in ((host.ctypes.data, d_a.ptr, d_pt.ptr, "into"), (d_r.ptr, host.ctypes.data, d_pt.ptr, "into"),
+                                 (d_r.ptr, d_a.ptr, host.ctypes.data, "into"), (d_r.ptr, d_r.ptr, d_pt.ptr, "into"), (d_r.ptr, None, d_r.ptr, "assign"),
+                                 (d_r.ptr, d_a.ptr, d_pt.ptr, "assign")):
+            with pytest.raises(PoulpyHipError):
+                hip.glwe_mul_plain_batched(r, a, pt, False, p, mode, 1)
+        hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, False, p, "into", 0)   # batch 0: a no-op
+        cgood = dict(rank=1, a_size=size, a_base2k=12, res_size=size, res_base2k=12, cnv_offset=12)
+        b = np.array([3, -2], dtype=np.int64)
+        for d in (dict(rank=0), dict(res_size=0), dict(a_base2k=64), dict(cnv_offset=12 * 10)):
+            with pytest.raises(PoulpyHipError):
+                hip.glwe_mul_const_batched(d_r.ptr, d_a.ptr, b, None, GlweMulConstParams(**{**cgood, **d}), "into", 1)
+        cp = GlweMulConstParams(**cgood)
+        for (r, a, mode) in ((host.ctypes.data, d_a.ptr, "into"), (d_r.ptr, host.ctypes.data, "into"), (d_r.ptr, d_r.ptr, "into"),
+                             (d_r.ptr, d_a.ptr, "assign")):
+            with pytest.raises(PoulpyHipError):
+                hip.glwe_mul_const_batched(r, a, b, None, cp, mode, 1)
 
 
 @pytest.mark.parametrize("n,b_size,off", [(65536, 3, 36), (4096, 8, 0), (1024, 3, 31)])
@@ -370,12 +343,11 @@ def test_rounding_margin_of_the_plaintext_paths(mods, n, b_size, off):
     cols, size, k, batch = 2, 16 if n == 65536 else 8, 12, 4
     a = np.stack([VecZnx(n, cols, size).fill_uniform(k, rng).data for _ in range(batch)])
     pt = VecZnx(n, 1, b_size).fill_uniform(k, rng).data
-    d_a = hip.device_alloc(a.nbytes).upload(a)
-    d_pt = hip.device_alloc(pt.nbytes).upload(np.ascontiguousarray(pt))
-    d_r = hip.device_alloc(a.nbytes)
-    p = GlweTensorParams(rank=1, a_size=size, b_size=b_size, ab_base2k=k, a_effective_k=size * k, b_effective_k=b_size * k, res_size=size,
-                         res_base2k=k, cnv_offset=off)
-    margin = hip.rounding_margin_of(lambda: hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, True, p, "into", batch))
-    for buf in (d_a, d_pt, d_r):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a = dev.upload(a)
+        d_pt = dev.alloc(pt.nbytes, poison=False).upload(np.ascontiguousarray(pt))
+        d_r = dev.alloc(a.nbytes, poison=False)
+        p = GlweTensorParams(rank=1, a_size=size, b_size=b_size, ab_base2k=k, a_effective_k=size * k, b_effective_k=b_size * k, res_size=size,
+                             res_base2k=k, cnv_offset=off)
+        margin = hip.rounding_margin_of(lambda: hip.glwe_mul_plain_batched(d_r.ptr, d_a.ptr, d_pt.ptr, True, p, "into", batch))
     assert 0.0 < margin < 0.05, margin

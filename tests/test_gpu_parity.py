@@ -10,22 +10,10 @@ import numpy as np
 import pytest
 
 from poulpy_amd.layouts import MatZnx, ScalarZnx, SvpPPol, VecZnx, VecZnxBig, VecZnxDft, VmpPMat
+from tests.device import mods, on_device, prepared_key  # noqa: F401
 from tests.helpers import garbage_dft, normalize_all, seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 @pytest.mark.parametrize("n", [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072])
@@ -259,9 +247,7 @@ def _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, a_base2k, key_size, ke
     cols_in = rank if ks else rank + 1
     cols_out = (rank_out if ks else rank) + 1
     mat = MatZnx(n, dnum, cols_in, cols_out, key_size).fill_uniform(key_base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, cols_in, cols_out, key_size), hip.vmp_pmat_alloc(dnum, cols_in, cols_out, key_size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, mat)
     a_all = np.empty((batch, a_size, cols_a, n), dtype=np.int64)
     want = np.empty((batch, res_size, cols_out, n), dtype=np.int64)
     for b in range(batch):
@@ -285,49 +271,38 @@ def _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, a_base2k, key_size, ke
         else:
             oracle_op()
         want[b] = res.data
-    d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    if in_place:
-        assert a_all.shape == want.shape
-        d_res = d_a
-    else:
-        d_res = hip.device_alloc(want.nbytes)
-        hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, want.nbytes)
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_base2k, a_size=a_size, a_base2k=a_base2k,
                      res_size=res_size, res_base2k=res_base2k, rank_out=rank_out)
-    hip.set_chunk(chunk)
-    hip.set_fusion(*fuse)
-    if pin:
-        hip.pin_key(d_key.ptr, dnum, cols_in, cols_out, key_size)
-        hip.glwe_external_product_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch) if not ks else None  # first call after pinning
-    if auto is not None:
-        hip.glwe_automorphism_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, auto[0], auto[1], batch)
-    elif ks:
-        hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch)
-    else:
-        hip.glwe_external_product_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    if pin:
-        hip.unpin_key(d_key.ptr)
-    if out is not None:
-        out["notes"] = hip.dispatch_notes()
-        # the same call once more under the margin probe, on fresh copies of the inputs (in place: the first call overwrote them)
-        d_a2, d_r2 = hip.device_alloc(a_all.nbytes).upload(a_all), hip.device_alloc(want.nbytes)
-        if auto is not None:
-            run = lambda: hip.glwe_automorphism_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, auto[0], auto[1], batch)   # noqa: E731
-        elif ks:
-            run = lambda: hip.glwe_keyswitch_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
+    with on_device(hip, chunk=chunk, fuse=fuse) as dev:
+        d_a, d_key = dev.upload(a_all), dev.key(ph)
+        if in_place:
+            assert a_all.shape == want.shape
+            d_res = d_a
         else:
-            run = lambda: hip.glwe_external_product_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
-        out["gpu_margin"] = hip.rounding_margin_of(run)
-        d_a2.free()
-        d_r2.free()
-        out["mat"], out["a"] = mat.data.copy(), a_all.copy()
-    hip.set_chunk(0)
-    hip.set_fusion(True, True)
-    for buf in ((d_a, d_key) if in_place else (d_a, d_key, d_res)):
-        buf.free()
+            d_res = dev.alloc(want.nbytes)
+        if pin:
+            dev.pin(d_key, dnum, cols_in, cols_out, key_size)
+            hip.glwe_external_product_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch) if not ks else None  # first call after pinning
+        if auto is not None:
+            hip.glwe_automorphism_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, auto[0], auto[1], batch)
+        elif ks:
+            hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch)
+        else:
+            hip.glwe_external_product_batched(d_res.ptr, d_a.ptr, d_key.ptr, p, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
+        if out is not None:
+            out["notes"] = hip.dispatch_notes()
+            # the same call once more under the margin probe, on fresh copies of the inputs (in place: the first call overwrote them)
+            d_a2, d_r2 = dev.upload(a_all), dev.alloc(want.nbytes, poison=False)
+            if auto is not None:
+                run = lambda: hip.glwe_automorphism_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, auto[0], auto[1], batch)   # noqa: E731
+            elif ks:
+                run = lambda: hip.glwe_keyswitch_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
+            else:
+                run = lambda: hip.glwe_external_product_batched(d_r2.ptr, d_a2.ptr, d_key.ptr, p, batch)   # noqa: E731
+            out["gpu_margin"] = hip.rounding_margin_of(run)
+            out["mat"], out["a"] = mat.data.copy(), a_all.copy()
     return got, want
 
 
@@ -398,12 +373,9 @@ def test_metric_config_external_product_n65536(mods):
     got, want = _run_glwe_op(hip, ref, False, n, 1, 1, 8, 12, 8, 12, 8, 1, 8, 12, batch=3, seed=65536)
     assert np.array_equal(got, want)
     # the same call on the probing instantiations of the same kernels: same bits, and the margin as a first-class output
-    hip.set_margin_probe(True)
-    try:
+    with on_device(hip, probe=True):
         got, want = _run_glwe_op(hip, ref, False, n, 1, 1, 8, 12, 8, 12, 8, 1, 8, 12, batch=3, seed=65536)
         margin = hip.get_margin()
-    finally:
-        hip.set_margin_probe(False)
     assert np.array_equal(got, want)
     assert 0.0 < margin < 1e-4, f"rounding margin at the metric shape: max |x-round(x)| = {margin} (4.8e-6 in round 1)"
 
@@ -418,14 +390,14 @@ def test_pinned_key_n65536(mods):
     assert np.array_equal(got, want)
     got, want = _run_glwe_op(hip, ref, True, n, 1, 1, 8, 12, 8, 12, 8, 1, 8, 12, batch=2, seed=12, pin=True)
     assert np.array_equal(got, want)
-    buf = hip.device_alloc(n * 8 * 4)
-    hip.pin_key(buf.ptr, 1, 1, 2, 2)
-    with pytest.raises(PoulpyHipError):
+    with on_device(hip) as dev:     # the pin and the unpin are what is tested: by hand
+        buf = dev.alloc(n * 8 * 4, poison=False)
         hip.pin_key(buf.ptr, 1, 1, 2, 2)
-    hip.unpin_key(buf.ptr)
-    with pytest.raises(PoulpyHipError):
+        with pytest.raises(PoulpyHipError):
+            hip.pin_key(buf.ptr, 1, 1, 2, 2)
         hip.unpin_key(buf.ptr)
-    buf.free()
+        with pytest.raises(PoulpyHipError):
+            hip.unpin_key(buf.ptr)
 
 
 @pytest.mark.parametrize("n", [1024, 2048])
@@ -437,12 +409,9 @@ def test_pinned_key_on_the_small_ring_pipeline(mods, n):
     for (ks, auto) in ((False, None), (True, None), (True, (5, "add"))):
         want_u, ref_u = _run_glwe_op(hip, ref, ks, n, 1, 1, 4, 14, 4, 14, 4, 1, 4, 14, batch=9, seed=n + int(ks), auto=auto)
         assert np.array_equal(want_u, ref_u)
-        hip.set_kernel_timing(True)
-        try:
+        with on_device(hip, timing=True):
             got, want = _run_glwe_op(hip, ref, ks, n, 1, 1, 4, 14, 4, 14, 4, 1, 4, 14, batch=9, seed=n + int(ks), auto=auto, pin=True)
             stats = hip.kernel_stats()
-        finally:
-            hip.set_kernel_timing(False)
         assert np.array_equal(got, want) and np.array_equal(got, want_u), (n, ks, auto)
         # one k_small_permute launch: pz_module_pin_key's own - none inside the one (key switch, automorphism) or two (external product) calls
         assert stats.get("elementwise", (0, 0.0))[0] == 1, stats
@@ -609,9 +578,7 @@ def test_ggsw_external_product(mods, fill=None):
     rng = seeded(77)
     cols = rank + 1
     mat = MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, size), hip.vmp_pmat_alloc(dnum, cols, cols, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, mat)
     a = MatZnx(n, dnum_a, cols, cols, size).fill_uniform(base2k, rng)   # the GGSW being multiplied
     if fill is not None:
         fill(0, a.data, rng)
@@ -624,16 +591,13 @@ def test_ggsw_external_product(mods, fill=None):
         res = VecZnx(n, cols, size)
         ref.glwe_external_product(res, base2k, ct, base2k, pr, 1, base2k)
         flat_w[e] = res.data
-    d_a = hip.device_alloc(a.data.nbytes).upload(a.data)
-    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-    d_res = hip.device_alloc(want.nbytes)
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,
                      res_base2k=base2k, rank_out=rank)
-    hip.ggsw_external_product(d_res.ptr, d_a.ptr, dnum_a, d_key.ptr, p)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_a, d_key, d_res):
-        buf.free()
+    with on_device(hip) as dev:
+        d_a, d_key, d_res = dev.upload(a.data), dev.key(ph), dev.alloc(want.nbytes, poison=False)
+        hip.ggsw_external_product(d_res.ptr, d_a.ptr, dnum_a, d_key.ptr, p)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -653,30 +617,26 @@ def test_ggsw_expand_row_batched(mods, n, rank, dnum, size, key_dnum, key_size, 
     ref, hip = mods(n)
     rng = seeded(900 + n + rank)
     cols = rank + 1
-    keys_r, keys_d = [], []
-    for c in range(rank):
-        mat = MatZnx(n, key_dnum, rank, cols, key_size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(key_dnum, rank, cols, key_size), hip.vmp_pmat_alloc(key_dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+    with on_device(hip) as dev:
+        keys_r, keys_d = [], []
+        for c in range(rank):
+            pr, ph = prepared_key(ref, hip, MatZnx(n, key_dnum, rank, cols, key_size).fill_uniform(base2k, rng))
+            hip.sync()
+            keys_r.append(pr)
+            keys_d.append(dev.key(ph))
+        ggsws = [MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
+        for i, g in enumerate(ggsws if fill is not None else ()):
+            fill(i, g.data, rng)
+        flat = np.stack([g.data for g in ggsws])
+        d = dev.upload(flat)
+        for g in ggsws:
+            ref.ggsw_expand_row(g, base2k, keys_r, dsize, base2k)
+        want = np.stack([g.data for g in ggsws])
+        p = GlweOpParams(rank=rank, dnum=key_dnum, dsize=dsize, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k,
+                         res_size=size, res_base2k=base2k, rank_out=rank)
+        hip.ggsw_expand_row_batched(d.ptr, dnum, [k.ptr for k in keys_d], p, count)
         hip.sync()
-        keys_r.append(pr)
-        keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    ggsws = [MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
-    for i, g in enumerate(ggsws if fill is not None else ()):
-        fill(i, g.data, rng)
-    flat = np.stack([g.data for g in ggsws])
-    d = hip.device_alloc(flat.nbytes).upload(flat)
-    for g in ggsws:
-        ref.ggsw_expand_row(g, base2k, keys_r, dsize, base2k)
-    want = np.stack([g.data for g in ggsws])
-    p = GlweOpParams(rank=rank, dnum=key_dnum, dsize=dsize, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k,
-                     res_size=size, res_base2k=base2k, rank_out=rank)
-    hip.ggsw_expand_row_batched(d.ptr, dnum, [k.ptr for k in keys_d], p, count)
-    hip.sync()
-    got = d.download(np.int64, want.size).reshape(want.shape)
-    for buf in keys_d + [d]:
-        buf.free()
+        got = d.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got[:, :, 0], flat[:, :, 0])
     assert np.array_equal(got, want)
 
@@ -690,34 +650,29 @@ def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in, fill=None):
     ref, hip = mods(n)
     rng = seeded(950 + n + rank)
     cols = rank + 1
-    keys_r, keys_d = [], []
-    for c in range(rank):
-        mat = MatZnx(n, key_dnum, rank, cols, key_size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(key_dnum, rank, cols, key_size), hip.vmp_pmat_alloc(key_dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+    with on_device(hip) as dev:
+        keys_r, keys_d = [], []
+        for c in range(rank):
+            pr, ph = prepared_key(ref, hip, MatZnx(n, key_dnum, rank, cols, key_size).fill_uniform(base2k, rng))
+            hip.sync()
+            keys_r.append(pr)
+            keys_d.append(dev.key(ph))
+        gglwes = [MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
+        for i, g in enumerate(gglwes if fill is not None else ()):
+            fill(i, g.data, rng)
+        want = []
+        for a in gglwes:
+            g = MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng)   # stale contents must be overwritten
+            ref.ggsw_from_gglwe(g, base2k, a, keys_r, 1, base2k)
+            want.append(g.data)
+        want = np.stack(want)
+        flat_a = np.stack([a.data for a in gglwes])
+        d_a, d_g = dev.upload(flat_a), dev.upload(rng.integers(-9, 9, want.shape, dtype=np.int64))
+        p = GlweOpParams(rank=rank, dnum=key_dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k,
+                         res_size=size, res_base2k=base2k, rank_out=rank)
+        hip.ggsw_from_gglwe_batched(d_g.ptr, d_a.ptr, cols_in, dnum, [k.ptr for k in keys_d], p, count)
         hip.sync()
-        keys_r.append(pr)
-        keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    gglwes = [MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng) for _ in range(count)]
-    for i, g in enumerate(gglwes if fill is not None else ()):
-        fill(i, g.data, rng)
-    want = []
-    for a in gglwes:
-        g = MatZnx(n, dnum, cols, cols, size).fill_uniform(base2k, rng)   # stale contents must be overwritten
-        ref.ggsw_from_gglwe(g, base2k, a, keys_r, 1, base2k)
-        want.append(g.data)
-    want = np.stack(want)
-    flat_a = np.stack([a.data for a in gglwes])
-    d_a = hip.device_alloc(flat_a.nbytes).upload(flat_a)
-    d_g = hip.device_alloc(want.nbytes).upload(rng.integers(-9, 9, want.shape, dtype=np.int64))
-    p = GlweOpParams(rank=rank, dnum=key_dnum, dsize=1, key_size=key_size, key_base2k=base2k, a_size=size, a_base2k=base2k,
-                     res_size=size, res_base2k=base2k, rank_out=rank)
-    hip.ggsw_from_gglwe_batched(d_g.ptr, d_a.ptr, cols_in, dnum, [k.ptr for k in keys_d], p, count)
-    hip.sync()
-    got = d_g.download(np.int64, want.size).reshape(want.shape)
-    for buf in keys_d + [d_a, d_g]:
-        buf.free()
+        got = d_g.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -738,10 +693,7 @@ def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, re
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * brk_size), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):
-        mat = MatZnx(n, dnum, cols, cols, brk_size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, brk_size), hip.vmp_pmat_alloc(dnum, cols, cols, brk_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols, cols, brk_size).fill_uniform(base2k, rng))
         brk_r[i] = pr.data.reshape(-1)
         brk_h[i] = ph.data.reshape(-1)
     lwe = rng.integers(-n, n, (batch, n_lwe + 1), dtype=np.int64)   # mod_switch_2n output range
@@ -759,25 +711,19 @@ def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, re
         else:
             oracle_op()
         want[b] = res.data
-    d_lwe = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_lut = hip.device_alloc(lut.data.nbytes).upload(lut.data)
-    d_brk = hip.device_alloc(brk_h.nbytes).upload(brk_h)
-    d_res = hip.device_alloc(want.nbytes)
-    hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x33, want.nbytes)
     p = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=dnum, brk_size=brk_size, base2k=base2k,
                             res_size=res_size, lut_size=lut_size)
-    hip.set_fusion(*fuse)
-    hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
-    hip.sync()
-    if out is not None:
-        out["notes"] = hip.dispatch_notes()
-        d_r2 = hip.device_alloc(want.nbytes)
-        out["gpu_margin"] = hip.rounding_margin_of(lambda: hip.blind_rotation_execute_batched(d_r2.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch))
-        d_r2.free()
-    hip.set_fusion(True, True)
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_lwe, d_lut, d_brk, d_res):
-        buf.free()
+    with on_device(hip, fuse=fuse) as dev:
+        d_lwe, d_lut, d_brk = dev.upload(lwe), dev.upload(lut.data), dev.upload(brk_h)
+        d_res = dev.alloc(want.nbytes, poison=False)
+        hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x33, want.nbytes)
+        hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
+        hip.sync()
+        if out is not None:
+            out["notes"] = hip.dispatch_notes()
+            d_r2 = dev.alloc(want.nbytes, poison=False)
+            out["gpu_margin"] = hip.rounding_margin_of(lambda: hip.blind_rotation_execute_batched(d_r2.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch))
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     return got, want
 
 
@@ -859,14 +805,11 @@ def test_small_ring_mixed_bases(mods, n, a_b, k_b, r_b):
         cases += [(True, 1, 1, 3, 4, 3, 3, 5, (5, "add")), (True, 1, 1, 4, 3, 3, 4, 3, (-1, "automorphism")), (True, 2, 2, 3, 3, 3, 3, 2, (3, "sub_negate"))]
     for (ks, rank, rank_out, a_size, key_size, dnum, res_size, batch, auto) in cases:
         args = (ks, n, rank, rank_out, a_size, a_b, key_size, k_b, dnum, 1, res_size, r_b, batch)
-        hip.set_small_path(True)
-        got, want = _run_glwe_op(hip, ref, *args, seed=500 + rank + a_size + batch, auto=auto)
+        with on_device(hip, small_path=True):
+            got, want = _run_glwe_op(hip, ref, *args, seed=500 + rank + a_size + batch, auto=auto)
         assert np.array_equal(got, want), (ks, rank, rank_out, a_size, key_size, res_size, auto)
-        hip.set_small_path(False)
-        try:
+        with on_device(hip, small_path=False):
             got2, _ = _run_glwe_op(hip, ref, *args, seed=500 + rank + a_size + batch, auto=auto)
-        finally:
-            hip.set_small_path(True)
         assert np.array_equal(got2, want)
 
 
@@ -883,16 +826,13 @@ def test_small_ring_automorphism_family(mods, n, mode, in_place):
     for (rank, gal, a_size, key_size, dnum, res_size, batch) in cases:
         if in_place and a_size != res_size:
             continue
-        hip.set_small_path(True)
-        got, want = _run_glwe_op(hip, ref, True, n, rank, rank, a_size, k, key_size, k, dnum, 1, res_size, k, batch, seed=300 + rank + a_size + batch,
-                                 auto=(gal, mode), in_place=in_place)
+        with on_device(hip, small_path=True):
+            got, want = _run_glwe_op(hip, ref, True, n, rank, rank, a_size, k, key_size, k, dnum, 1, res_size, k, batch, seed=300 + rank + a_size + batch,
+                                     auto=(gal, mode), in_place=in_place)
         assert np.array_equal(got, want), (rank, gal, a_size, key_size, res_size)
-        hip.set_small_path(False)
-        try:
+        with on_device(hip, small_path=False):
             got2, _ = _run_glwe_op(hip, ref, True, n, rank, rank, a_size, k, key_size, k, dnum, 1, res_size, k, batch,
                                    seed=300 + rank + a_size + batch, auto=(gal, mode), in_place=in_place)
-        finally:
-            hip.set_small_path(True)
         assert np.array_equal(got2, want)
 
 
@@ -912,14 +852,11 @@ def test_blind_rotation_small_ring_transforms(mods, n, rank, n_lwe, blk, dnum, b
     with the block's keys re-ordered | k_small_inv (no product: inverse transform + accumulator + carry chain) — against the oracle, and
     against the per-op composition bit for bit."""
     ref, hip = mods(n)
-    hip.set_small_path(True)
-    got, want = _run_blind_rotation(hip, ref, n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch=batch, seed=n + rank + blk + dnum)
+    with on_device(hip, small_path=True):
+        got, want = _run_blind_rotation(hip, ref, n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch=batch, seed=n + rank + blk + dnum)
     assert np.array_equal(got, want), (n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch)
-    hip.set_small_path(False)
-    try:
+    with on_device(hip, small_path=False):
         got2, _ = _run_blind_rotation(hip, ref, n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch=batch, seed=n + rank + blk + dnum)
-    finally:
-        hip.set_small_path(True)
     assert np.array_equal(got2, want)
 
 
@@ -940,16 +877,13 @@ def test_small_ring_two_kernel_pipeline(mods, n, ks, rank, rank_out, a_size, key
     the other pipeline (three kernels at N = 4096, five below) on the same inputs bit for bit."""
     k = 17
     ref, hip = mods(n)
-    hip.set_small_path(True)
-    got, want = _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, k, key_size, k, dnum, 1, res_size, k, batch, seed=900 + a_size + key_size + batch,
-                             in_place=in_place)
+    with on_device(hip, small_path=True):
+        got, want = _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, k, key_size, k, dnum, 1, res_size, k, batch, seed=900 + a_size + key_size + batch,
+                                 in_place=in_place)
     assert np.array_equal(got, want)
-    hip.set_small_path(False)
-    try:
+    with on_device(hip, small_path=False):
         got3, _ = _run_glwe_op(hip, ref, ks, n, rank, rank_out, a_size, k, key_size, k, dnum, 1, res_size, k, batch, seed=900 + a_size + key_size + batch,
                                in_place=in_place)
-    finally:
-        hip.set_small_path(True)
     assert np.array_equal(got3, want)
 
 
@@ -1393,10 +1327,7 @@ def test_batched_primitives_compose_an_external_product(mods, n):
     for (step, offset, limb_offset) in ((1, 0, 0), (2, 1, 1)):
         sel = len(range(offset, a_size, step))
         d_size = min(sel, dnum)
-        mat = MatZnx(n, dnum, cols, cols, size).fill_uniform(k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, size), hip.vmp_pmat_alloc(dnum, cols, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols, cols, size).fill_uniform(k, rng))
         a_all = np.empty((batch, a_size, cols, n), dtype=np.int64)
         want = np.empty((batch, size, cols, n), dtype=np.int64)
         for b in range(batch):
@@ -1412,22 +1343,21 @@ def test_batched_primitives_compose_an_external_product(mods, n):
             for c in range(cols):
                 ref.vec_znx_big_normalize(res, k, 0, c, big, k, c)
             want[b] = res.data
-        d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-        d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-        d_ad = hip.device_alloc(batch * d_size * cols * n * 8)
-        d_rd = hip.device_alloc(batch * size * cols * n * 8)
-        d_res = hip.device_alloc(want.nbytes)
-        hip.lib.pz_memset_d(hip.handle, d_rd.ptr, 0, batch * size * cols * n * 8)
-        for c in range(cols):
-            hip.vec_znx_dft_apply_batched(batch, step, offset, d_ad.ptr, cols, d_size, c, d_a.ptr, cols, a_size, c)
-        hip.vmp_apply_dft_to_dft_batched(batch, d_rd.ptr, cols, size, d_ad.ptr, cols, d_size, d_key.ptr, dnum, cols, cols, size, limb_offset)
-        hip.vec_znx_idft_apply_consume_batched(batch, d_rd.ptr, cols, size)
-        for c in range(cols):
-            hip.vec_znx_big_normalize_batched(batch, d_res.ptr, cols, size, k, 0, c, d_rd.ptr, cols, size, k, c)
-        hip.sync()
-        got = d_res.download(np.int64, want.size).reshape(want.shape)
-        for buf in (d_a, d_key, d_ad, d_rd, d_res):
-            buf.free()
+        with on_device(hip) as dev:
+            d_a = dev.upload(a_all)
+            d_key = dev.key(ph)
+            d_ad = dev.alloc(batch * d_size * cols * n * 8, poison=False)
+            d_rd = dev.alloc(batch * size * cols * n * 8, poison=False)
+            d_res = dev.alloc(want.nbytes, poison=False)
+            hip.lib.pz_memset_d(hip.handle, d_rd.ptr, 0, batch * size * cols * n * 8)
+            for c in range(cols):
+                hip.vec_znx_dft_apply_batched(batch, step, offset, d_ad.ptr, cols, d_size, c, d_a.ptr, cols, a_size, c)
+            hip.vmp_apply_dft_to_dft_batched(batch, d_rd.ptr, cols, size, d_ad.ptr, cols, d_size, d_key.ptr, dnum, cols, cols, size, limb_offset)
+            hip.vec_znx_idft_apply_consume_batched(batch, d_rd.ptr, cols, size)
+            for c in range(cols):
+                hip.vec_znx_big_normalize_batched(batch, d_res.ptr, cols, size, k, 0, c, d_rd.ptr, cols, size, k, c)
+            hip.sync()
+            got = d_res.download(np.int64, want.size).reshape(want.shape)
         assert np.array_equal(got, want), (n, step, offset, limb_offset)
 
 
@@ -1469,35 +1399,35 @@ def test_batched_entry_points_reject_bad_arguments(mods):
     n = 256
     _, hip = mods(n)
     good = GlweOpParams(rank=1, dnum=2, dsize=1, key_size=2, key_base2k=12, a_size=2, a_base2k=12, res_size=2, res_base2k=12, rank_out=1)
-    d = hip.device_alloc(n * 8 * 64)
-    host = np.zeros(n * 64, dtype=np.int64)
-    hp = host.ctypes.data_as(C.c_void_p)
-    hip.glwe_external_product_batched(d.ptr, d.ptr, d.ptr, good, 0)                      # batch 0: nothing to do
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_external_product_batched(None, d.ptr, d.ptr, good, 1)                   # null pointer
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_keyswitch_batched(d.ptr, d.ptr, None, good, 1)
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_pack_batched(hp, [0], [d.ptr], 0, [5] * 8, [d.ptr] * 8, good, d.ptr, 1 << 20, 1)   # host pointer where a device one is required
-    bad = GlweOpParams(rank=1, dnum=0, dsize=1, key_size=2, key_base2k=12, a_size=2, a_base2k=12, res_size=2, res_base2k=12, rank_out=1)
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_external_product_batched(d.ptr, d.ptr, d.ptr, bad, 1)                   # empty shape
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, good, 4, "automorphism", 1)   # even Galois element
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, good, 5, 9, 1)                # unknown mode
-    rk = GlweOpParams(rank=1, dnum=2, dsize=1, key_size=2, key_base2k=12, a_size=2, a_base2k=12, res_size=2, res_base2k=12, rank_out=2)
-    with pytest.raises(PoulpyHipError):
-        hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, rk, 5, "add", 1)              # key changes the rank
-    br = BlindRotationParams(rank=1, n_lwe=4, block_size=2, dnum=1, brk_size=1, base2k=70, res_size=1, lut_size=1)
-    with pytest.raises(PoulpyHipError):
-        hip.blind_rotation_execute_batched(d.ptr, d.ptr, d.ptr, d.ptr, br, 1)            # base2k out of range
-    br0 = BlindRotationParams(rank=1, n_lwe=0, block_size=2, dnum=1, brk_size=1, base2k=12, res_size=1, lut_size=1)
-    with pytest.raises(PoulpyHipError):
-        hip.blind_rotation_execute_batched(d.ptr, d.ptr, d.ptr, d.ptr, br0, 1)           # empty LWE
-    with pytest.raises(PoulpyHipError):
-        hip.vec_znx_big_normalize_batched(1, hp, 1, 1, 12, 0, 0, d.ptr, 1, 1, 12, 0)     # host pointer to a batched primitive
-    d.free()
+    with on_device(hip) as dev:
+        d = dev.alloc(n * 8 * 64, poison=False)
+        host = np.zeros(n * 64, dtype=np.int64)
+        hp = host.ctypes.data_as(C.c_void_p)
+        hip.glwe_external_product_batched(d.ptr, d.ptr, d.ptr, good, 0)                      # batch 0: nothing to do
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_external_product_batched(None, d.ptr, d.ptr, good, 1)                   # null pointer
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_keyswitch_batched(d.ptr, d.ptr, None, good, 1)
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_pack_batched(hp, [0], [d.ptr], 0, [5] * 8, [d.ptr] * 8, good, d.ptr, 1 << 20, 1)   # host pointer where a device one is required
+        bad = GlweOpParams(rank=1, dnum=0, dsize=1, key_size=2, key_base2k=12, a_size=2, a_base2k=12, res_size=2, res_base2k=12, rank_out=1)
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_external_product_batched(d.ptr, d.ptr, d.ptr, bad, 1)                   # empty shape
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, good, 4, "automorphism", 1)   # even Galois element
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, good, 5, 9, 1)                # unknown mode
+        rk = GlweOpParams(rank=1, dnum=2, dsize=1, key_size=2, key_base2k=12, a_size=2, a_base2k=12, res_size=2, res_base2k=12, rank_out=2)
+        with pytest.raises(PoulpyHipError):
+            hip.glwe_automorphism_batched(d.ptr, d.ptr, d.ptr, rk, 5, "add", 1)              # key changes the rank
+        br = BlindRotationParams(rank=1, n_lwe=4, block_size=2, dnum=1, brk_size=1, base2k=70, res_size=1, lut_size=1)
+        with pytest.raises(PoulpyHipError):
+            hip.blind_rotation_execute_batched(d.ptr, d.ptr, d.ptr, d.ptr, br, 1)            # base2k out of range
+        br0 = BlindRotationParams(rank=1, n_lwe=0, block_size=2, dnum=1, brk_size=1, base2k=12, res_size=1, lut_size=1)
+        with pytest.raises(PoulpyHipError):
+            hip.blind_rotation_execute_batched(d.ptr, d.ptr, d.ptr, d.ptr, br0, 1)           # empty LWE
+        with pytest.raises(PoulpyHipError):
+            hip.vec_znx_big_normalize_batched(1, hp, 1, 1, 12, 0, 0, d.ptr, 1, 1, 12, 0)     # host pointer to a batched primitive
 
 
 @pytest.mark.parametrize("n", [64, 2048, 65536])
@@ -1528,31 +1458,26 @@ def test_glwe_trace_batched(mods, fuse):
         rng = seeded(n + rank)
         cols = rank + 1
         gals = [-1] + [pow(5, 1 << i, 2 * n) for i in range(nsteps - 1)]
-        prs, d_keys = [], []
-        for _ in gals:
-            mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng)
-            pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, key_size), hip.vmp_pmat_alloc(dnum, rank, cols, key_size)
-            ref.vmp_prepare(pr, mat)
-            hip.vmp_prepare(ph, mat)
-            prs.append(pr)
-            d_keys.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-        cts = np.empty((batch, size, cols, n), dtype=np.int64)
-        want = np.empty_like(cts)
-        for b in range(batch):
-            ct = VecZnx(n, cols, size).fill_uniform(k, rng)
-            cts[b] = ct.data
-            ref.glwe_trace_assign(ct, k, gals, prs)
-            want[b] = ct.data
-        d_res = hip.device_alloc(cts.nbytes).upload(cts)
-        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size,
-                         res_base2k=k, rank_out=rank)
-        hip.set_fusion(*fuse)
-        hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
-        hip.sync()
-        hip.set_fusion(True, True)
-        got = d_res.download(np.int64, want.size).reshape(want.shape)
-        for d in d_keys + [d_res]:
-            d.free()
+        with on_device(hip) as dev:
+            prs, d_keys = [], []
+            for _ in gals:
+                pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng))
+                prs.append(pr)
+                d_keys.append(dev.key(ph))
+            cts = np.empty((batch, size, cols, n), dtype=np.int64)
+            want = np.empty_like(cts)
+            for b in range(batch):
+                ct = VecZnx(n, cols, size).fill_uniform(k, rng)
+                cts[b] = ct.data
+                ref.glwe_trace_assign(ct, k, gals, prs)
+                want[b] = ct.data
+            d_res = dev.upload(cts)
+            p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size,
+                             res_base2k=k, rank_out=rank)
+            with on_device(hip, fuse=fuse):
+                hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
+                hip.sync()
+            got = d_res.download(np.int64, want.size).reshape(want.shape)
         assert np.array_equal(got, want), (n, rank, size)
 
 
@@ -1583,30 +1508,26 @@ def _trace_shifted_stores(mods, n, size, key_size, res_gals, k):
     ref, hip = mods(n)
     rng = seeded(n + size)
     cols = rank + 1
-    prs, d_keys = [], []
-    for _ in res_gals:
-        mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, key_size), hip.vmp_pmat_alloc(dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
-        prs.append(pr)
-        d_keys.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    gals = [g % (2 * n) if g > 0 else g for g in res_gals]
-    cts = np.empty((batch, size, cols, n), dtype=np.int64)
-    want = np.empty_like(cts)
-    for b in range(batch):
-        ct = VecZnx(n, cols, size).fill_uniform(k, rng)
-        cts[b] = ct.data
-        ref.glwe_trace_assign(ct, k, gals, prs)
-        want[b] = ct.data
-    d_res = hip.device_alloc(cts.nbytes).upload(cts)
-    p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size, res_base2k=k,
-                     rank_out=rank)
-    hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for d in d_keys + [d_res]:
-        d.free()
+    with on_device(hip) as dev:
+        prs, d_keys = [], []
+        for _ in res_gals:
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng))
+            prs.append(pr)
+            d_keys.append(dev.key(ph))
+        gals = [g % (2 * n) if g > 0 else g for g in res_gals]
+        cts = np.empty((batch, size, cols, n), dtype=np.int64)
+        want = np.empty_like(cts)
+        for b in range(batch):
+            ct = VecZnx(n, cols, size).fill_uniform(k, rng)
+            cts[b] = ct.data
+            ref.glwe_trace_assign(ct, k, gals, prs)
+            want[b] = ct.data
+        d_res = dev.upload(cts)
+        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size, res_base2k=k,
+                         rank_out=rank)
+        hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -1626,32 +1547,28 @@ def test_glwe_trace_batched_result_in_another_base_than_the_keys(mods, n, rank, 
     dnum = conv_size
     log_n = n.bit_length() - 1
     gals = ([-1] + [pow(5, 1 << i, 2 * n) for i in range(log_n - 1)])[log_n - nsteps:]
-    prs, d_keys = [], []
-    for _ in gals:
-        mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(key_k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, key_size), hip.vmp_pmat_alloc(dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
-        prs.append(pr)
-        d_keys.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    cts = np.empty((batch, res_size, cols, n), dtype=np.int64)
-    want = np.empty_like(cts)
-    for b in range(batch):
-        ct = VecZnx(n, cols, res_size).fill_uniform(res_k, rng)
-        cts[b] = ct.data
-        ref.glwe_trace_assign_bases(ct, res_k, conv_size, key_k, gals, prs)
-        want[b] = ct.data
-    d_res = hip.device_alloc(cts.nbytes).upload(cts)
-    p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=key_k, a_size=conv_size, a_base2k=key_k, res_size=res_size,
-                     res_base2k=res_k, rank_out=rank)
-    for _ in range(3):    # second and third call: captured / replayed as a HIP graph, same contents restored each time
-        d_res.upload(cts)
-        hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
-        hip.sync()
-        got = d_res.download(np.int64, want.size).reshape(want.shape)
-        assert np.array_equal(got, want)
-    for d in d_keys + [d_res]:
-        d.free()
+    with on_device(hip) as dev:
+        prs, d_keys = [], []
+        for _ in gals:
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, key_size).fill_uniform(key_k, rng))
+            prs.append(pr)
+            d_keys.append(dev.key(ph))
+        cts = np.empty((batch, res_size, cols, n), dtype=np.int64)
+        want = np.empty_like(cts)
+        for b in range(batch):
+            ct = VecZnx(n, cols, res_size).fill_uniform(res_k, rng)
+            cts[b] = ct.data
+            ref.glwe_trace_assign_bases(ct, res_k, conv_size, key_k, gals, prs)
+            want[b] = ct.data
+        d_res = dev.upload(cts)
+        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=key_k, a_size=conv_size, a_base2k=key_k, res_size=res_size,
+                         res_base2k=res_k, rank_out=rank)
+        for _ in range(3):    # second and third call: captured / replayed as a HIP graph, same contents restored each time
+            d_res.upload(cts)
+            hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
+            hip.sync()
+            got = d_res.download(np.int64, want.size).reshape(want.shape)
+            assert np.array_equal(got, want)
 
 
 @pytest.mark.parametrize("n,rank,size,ct_k,key_k,log_gap_out,indices,batch", [
@@ -1672,37 +1589,33 @@ def test_glwe_pack_batched_keys_in_another_base(mods, n, rank, size, ct_k, key_k
     key_size = -(-(kbits + key_k) // key_k)
     dnum = trace_size
     gals = [-1] + [pow(5, 1 << i, 2 * n) for i in range(log_n - 1)]
-    keys_r, keys_d = [], []
-    for _ in gals:
-        mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(key_k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, key_size), hip.vmp_pmat_alloc(dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+    with on_device(hip) as dev:
+        keys_r, keys_d = [], []
+        for _ in gals:
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, key_size).fill_uniform(key_k, rng))
+            hip.sync()
+            keys_r.append(pr)
+            keys_d.append(dev.key(ph))
+        data = {j: rng.integers(-(1 << (ct_k - 1)), 1 << (ct_k - 1), (batch, size, cols, n), dtype=np.int64) for j in indices}
+        want = np.empty((batch, size, cols, n), dtype=np.int64)
+        for b in range(batch):
+            cts = {j: VecZnx(n, cols, size, data[j][b].copy()) for j in indices}
+            res = VecZnx(n, cols, size)
+            ref.glwe_pack_bases(res, ct_k, key_k, trace_size, cts, log_gap_out, gals, keys_r)
+            want[b] = res.data
+        d_cts = [dev.upload(data[j]) for j in indices]
+        d_res = dev.alloc(want.nbytes, poison=False)
+        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=key_k, a_size=size, a_base2k=ct_k, res_size=size,
+                         res_base2k=ct_k, rank_out=rank)
+        nbytes = hip.glwe_pack_bases_tmp_bytes(p, trace_size, batch)
+        d_tmp = dev.alloc(nbytes, poison=False)
+        from poulpy_amd.hal import PoulpyHipError
+        with pytest.raises(PoulpyHipError):     # the one-base entry point refuses keys in another base
+            hip.glwe_pack_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, d_tmp.ptr, nbytes, batch)
+        hip.glwe_pack_bases_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, trace_size,
+                                    d_tmp.ptr, nbytes, batch)
         hip.sync()
-        keys_r.append(pr)
-        keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    data = {j: rng.integers(-(1 << (ct_k - 1)), 1 << (ct_k - 1), (batch, size, cols, n), dtype=np.int64) for j in indices}
-    want = np.empty((batch, size, cols, n), dtype=np.int64)
-    for b in range(batch):
-        cts = {j: VecZnx(n, cols, size, data[j][b].copy()) for j in indices}
-        res = VecZnx(n, cols, size)
-        ref.glwe_pack_bases(res, ct_k, key_k, trace_size, cts, log_gap_out, gals, keys_r)
-        want[b] = res.data
-    d_cts = [hip.device_alloc(data[j].nbytes).upload(data[j]) for j in indices]
-    d_res = hip.device_alloc(want.nbytes)
-    p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=key_k, a_size=size, a_base2k=ct_k, res_size=size,
-                     res_base2k=ct_k, rank_out=rank)
-    nbytes = hip.glwe_pack_bases_tmp_bytes(p, trace_size, batch)
-    d_tmp = hip.device_alloc(nbytes)
-    from poulpy_amd.hal import PoulpyHipError
-    with pytest.raises(PoulpyHipError):     # the one-base entry point refuses keys in another base
-        hip.glwe_pack_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, d_tmp.ptr, nbytes, batch)
-    hip.glwe_pack_bases_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, trace_size,
-                                d_tmp.ptr, nbytes, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in keys_d + d_cts + [d_res, d_tmp]:
-        buf.free()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -1750,10 +1663,7 @@ def test_circuit_bootstrapping_to_constant(mods, n, rank, n_lwe, block_size, brk
     gap = 2 * int(rng.integers(1, n // 8))
 
     def prepared(rows, cols_in, size):
-        mat = MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(rows, cols_in, cols, size), hip.vmp_pmat_alloc(rows, cols_in, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng))
         hip.sync()
         return pr, ph
 
@@ -1776,34 +1686,26 @@ def test_circuit_bootstrapping_to_constant(mods, n, rank, n_lwe, block_size, brk
                                           xpa, gals, [a[0] for a in atk], [t[0] for t in tsk], gap)
         want[b] = g.data
 
-    bufs = []
-
-    def up(arr):
-        d = hip.device_alloc(arr.nbytes).upload(arr)
-        bufs.append(d)
-        return d
-
-    d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
-    d_atk = [up(a[1].data) for a in atk]
-    d_tsk = [up(t[1].data) for t in tsk]
-    d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))   # stale contents must be overwritten
-    p = CircuitBootstrappingParams(
-        br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=glwe_size, base2k=base2k,
-                               res_size=glwe_size, lut_size=glwe_size),
-        atk_dnum=atk_dnum, atk_size=tmp_size, tsk_dnum=tsk_dnum, tsk_size=res_size + 1, res_dnum=res_dnum, res_size=res_size, gap=gap)
-    nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
-    assert nbytes > 0
-    d_tmp = hip.device_alloc(nbytes)
-    bufs.append(d_tmp)
-    with pytest.raises(Exception):   # undersized scratch is refused, as the reference's scratch.available() assert
+    with on_device(hip) as dev:
+        up = dev.upload
+        d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
+        d_atk = [up(a[1].data) for a in atk]
+        d_tsk = [up(t[1].data) for t in tsk]
+        d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))   # stale contents must be overwritten
+        p = CircuitBootstrappingParams(
+            br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=glwe_size, base2k=base2k,
+                                   res_size=glwe_size, lut_size=glwe_size),
+            atk_dnum=atk_dnum, atk_size=tmp_size, tsk_dnum=tsk_dnum, tsk_size=res_size + 1, res_dnum=res_dnum, res_size=res_size, gap=gap)
+        nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
+        assert nbytes > 0
+        d_tmp = dev.alloc(nbytes, poison=False)
+        with pytest.raises(Exception):   # undersized scratch is refused, as the reference's scratch.available() assert
+            hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
+                                                                  [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes - 1, batch)
         hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                              [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes - 1, batch)
-    hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                          [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in bufs:
-        buf.free()
+                                                              [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got[:, :, 0], want[:, :, 0]), "trace rows differ"
     assert np.array_equal(got, want)
 
@@ -1821,42 +1723,36 @@ def test_composite_calls_replay_as_hip_graphs(mods):
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * bsz), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):
-        mat = MatZnx(n, dnum, cols, cols, bsz).fill_uniform(k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, bsz), hip.vmp_pmat_alloc(dnum, cols, cols, bsz)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols, cols, bsz).fill_uniform(k, rng))
         brk_r[i], brk_h[i] = pr.data.reshape(-1), ph.data.reshape(-1)
     xpa = ref.blind_rotation_x_pow_a()
-    d_lwe = hip.device_alloc(batch * (n_lwe + 1) * 8)
-    d_lut = hip.device_alloc(lut.data.nbytes).upload(lut.data)
-    d_brk = hip.device_alloc(brk_h.nbytes).upload(brk_h)
-    d_res = hip.device_alloc(batch * rsz * cols * n * 8)
-    p = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
-    hip.set_graphs(True)
-    before = hip.graph_launches()
-    for it in range(5):
-        lwe = rng.integers(-n, n, (batch, n_lwe + 1), dtype=np.int64)
-        d_lwe.upload(lwe)
-        hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
-        hip.sync()
-        got = d_res.download(np.int64, batch * rsz * cols * n).reshape(batch, rsz, cols, n)
-        for b in range(batch):
-            res = VecZnx(n, cols, rsz)
-            ref.blind_rotation_execute(res, k, np.ascontiguousarray(lwe[b]), lut, brk_r, dnum, bsz, blk, xpa)
-            assert np.array_equal(got[b], res.data), (it, b)
-    # (the workspace-guard mode runs every call plainly: a replay would not re-arm the guards; POULPY_DBG_GRAPHS=0 is the A/B knob for plain launches)
-    if os.environ.get("POULPY_DBG_CANARY") != "1" and os.environ.get("POULPY_DBG_GRAPHS") != "0":
-        assert hip.graph_launches() - before >= 2, "the repeated call was never served by a graph"
-    # switched off: plain launches again, same results
-    hip.set_graphs(False)
-    mid = hip.graph_launches()
-    hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
-    hip.sync()
-    assert hip.graph_launches() == mid
-    assert np.array_equal(d_res.download(np.int64, batch * rsz * cols * n).reshape(batch, rsz, cols, n), got)
-    hip.set_graphs(True)
-    for buf in (d_lwe, d_lut, d_brk, d_res):
-        buf.free()
+    with on_device(hip, graphs=True) as dev:
+        d_lwe = dev.alloc(batch * (n_lwe + 1) * 8, poison=False)
+        d_lut = dev.upload(lut.data)
+        d_brk = dev.upload(brk_h)
+        d_res = dev.alloc(batch * rsz * cols * n * 8, poison=False)
+        p = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
+        before = hip.graph_launches()
+        for it in range(5):
+            lwe = rng.integers(-n, n, (batch, n_lwe + 1), dtype=np.int64)
+            d_lwe.upload(lwe)
+            hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
+            hip.sync()
+            got = d_res.download(np.int64, batch * rsz * cols * n).reshape(batch, rsz, cols, n)
+            for b in range(batch):
+                res = VecZnx(n, cols, rsz)
+                ref.blind_rotation_execute(res, k, np.ascontiguousarray(lwe[b]), lut, brk_r, dnum, bsz, blk, xpa)
+                assert np.array_equal(got[b], res.data), (it, b)
+        # (the workspace-guard mode runs every call plainly: a replay would not re-arm the guards; POULPY_DBG_GRAPHS=0 is the A/B knob for plain launches)
+        if os.environ.get("POULPY_DBG_CANARY") != "1" and os.environ.get("POULPY_DBG_GRAPHS") != "0":
+            assert hip.graph_launches() - before >= 2, "the repeated call was never served by a graph"
+        # switched off: plain launches again, same results
+        with on_device(hip, graphs=False):
+            mid = hip.graph_launches()
+            hip.blind_rotation_execute_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, batch)
+            hip.sync()
+            assert hip.graph_launches() == mid
+            assert np.array_equal(d_res.download(np.int64, batch * rsz * cols * n).reshape(batch, rsz, cols, n), got)
 
 
 @pytest.mark.parametrize("n", [32, 1024, 65536])
@@ -1944,36 +1840,32 @@ def test_glwe_pack_batched(mods, n, rank, size, log_gap_out, indices, batch, fil
     cols = rank + 1
     log_n = n.bit_length() - 1
     gals = [-1] + [pow(5, 1 << i, 2 * n) for i in range(log_n - 1)]
-    keys_r, keys_d = [], []
-    for _ in gals:
-        mat = MatZnx(n, dnum, rank, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, size), hip.vmp_pmat_alloc(dnum, rank, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
-        hip.sync()
-        keys_r.append(pr)
-        keys_d.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    data = {j: rng.integers(-(1 << (base2k - 1)), 1 << (base2k - 1), (batch, size, cols, n), dtype=np.int64) for j in indices}
-    for j in (indices if fill is not None else ()):
+    with on_device(hip) as dev:
+        keys_r, keys_d = [], []
+        for _ in gals:
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, size).fill_uniform(base2k, rng))
+            hip.sync()
+            keys_r.append(pr)
+            keys_d.append(dev.key(ph))
+        data = {j: rng.integers(-(1 << (base2k - 1)), 1 << (base2k - 1), (batch, size, cols, n), dtype=np.int64) for j in indices}
+        for j in (indices if fill is not None else ()):
+            for b in range(batch):
+                fill(b, data[j][b], rng)
+        want = np.empty((batch, size, cols, n), dtype=np.int64)
         for b in range(batch):
-            fill(b, data[j][b], rng)
-    want = np.empty((batch, size, cols, n), dtype=np.int64)
-    for b in range(batch):
-        cts = {j: VecZnx(n, cols, size, data[j][b].copy()) for j in indices}
-        res = VecZnx(n, cols, size)
-        ref.glwe_pack(res, base2k, cts, log_gap_out, gals, keys_r)
-        want[b] = res.data
-    d_cts = [hip.device_alloc(data[j].nbytes).upload(data[j]) for j in indices]
-    d_res = hip.device_alloc(want.nbytes)
-    p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,
-                     res_base2k=base2k, rank_out=rank)
-    nbytes = hip.glwe_pack_tmp_bytes(p, batch)
-    d_tmp = hip.device_alloc(nbytes)
-    hip.glwe_pack_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, d_tmp.ptr, nbytes, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in keys_d + d_cts + [d_res, d_tmp]:
-        buf.free()
+            cts = {j: VecZnx(n, cols, size, data[j][b].copy()) for j in indices}
+            res = VecZnx(n, cols, size)
+            ref.glwe_pack(res, base2k, cts, log_gap_out, gals, keys_r)
+            want[b] = res.data
+        d_cts = [dev.upload(data[j]) for j in indices]
+        d_res = dev.alloc(want.nbytes, poison=False)
+        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k, res_size=size,
+                         res_base2k=base2k, rank_out=rank)
+        nbytes = hip.glwe_pack_tmp_bytes(p, batch)
+        d_tmp = dev.alloc(nbytes, poison=False)
+        hip.glwe_pack_batched(d_res.ptr, indices, [d.ptr for d in d_cts], log_gap_out, gals, [k.ptr for k in keys_d], p, d_tmp.ptr, nbytes, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -1995,10 +1887,7 @@ def test_circuit_bootstrapping_to_exponent(mods, n, rank, log_gap_in, log_gap_ou
     gap = 2 * int(rng.integers(1, n // 8))
 
     def prepared(rows, cols_in, size):
-        mat = MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(rows, cols_in, cols, size), hip.vmp_pmat_alloc(rows, cols_in, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng))
         hip.sync()
         return pr, ph
 
@@ -2019,31 +1908,23 @@ def test_circuit_bootstrapping_to_exponent(mods, n, rank, log_gap_in, log_gap_ou
         ref.circuit_bootstrap_to_exponent(g, base2k, np.ascontiguousarray(lwe[b]), lut, brk_r, brk_dnum, glwe_size, glwe_size, block_size,
                                           xpa, gals, [a[0] for a in atk], [t[0] for t in tsk], gap, log_gap_in, log_gap_out, log_domain)
         want[b] = g.data
-    bufs = []
-
-    def up(arr):
-        d = hip.device_alloc(arr.nbytes).upload(arr)
-        bufs.append(d)
-        return d
-
-    d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
-    d_atk = [up(a[1].data) for a in atk]
-    d_tsk = [up(t[1].data) for t in tsk]
-    d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))
-    p = CircuitBootstrappingParams(
-        br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=glwe_size, base2k=base2k,
-                               res_size=glwe_size, lut_size=glwe_size),
-        atk_dnum=atk_dnum, atk_size=glwe_size, tsk_dnum=tsk_dnum, tsk_size=res_size + 1, res_dnum=res_dnum, res_size=res_size, gap=gap)
-    nbytes = hip.circuit_bootstrapping_to_exponent_tmp_bytes(p, log_domain, batch)
-    d_tmp = hip.device_alloc(nbytes)
-    bufs.append(d_tmp)
-    hip.circuit_bootstrapping_execute_to_exponent_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                          [k.ptr for k in d_tsk], p, log_gap_in, log_gap_out, log_domain, d_tmp.ptr, nbytes,
-                                                          batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in bufs:
-        buf.free()
+    with on_device(hip) as dev:
+        up = dev.upload
+        d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
+        d_atk = [up(a[1].data) for a in atk]
+        d_tsk = [up(t[1].data) for t in tsk]
+        d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))
+        p = CircuitBootstrappingParams(
+            br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=glwe_size, base2k=base2k,
+                                   res_size=glwe_size, lut_size=glwe_size),
+            atk_dnum=atk_dnum, atk_size=glwe_size, tsk_dnum=tsk_dnum, tsk_size=res_size + 1, res_dnum=res_dnum, res_size=res_size, gap=gap)
+        nbytes = hip.circuit_bootstrapping_to_exponent_tmp_bytes(p, log_domain, batch)
+        d_tmp = dev.alloc(nbytes, poison=False)
+        hip.circuit_bootstrapping_execute_to_exponent_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
+                                                              [k.ptr for k in d_tsk], p, log_gap_in, log_gap_out, log_domain, d_tmp.ptr, nbytes,
+                                                              batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got[:, :, 0], want[:, :, 0]), "packed rows differ"
     assert np.array_equal(got, want)
 
@@ -2092,37 +1973,30 @@ def test_circuit_bootstrapping_one_base2k_per_object(mods, n, rank, bases, res_l
                                     sh["glwe_size"], sh["atk_glwe_size"], sh["trace_size"], block_size, xpa, gals, [a[0] for a in atk],
                                     [t[0] for t in tsk], gap, log_gap_in, log_gap_out, log_domain)
         want[b] = g.data
-    bufs = []
-
-    def up(arr):
-        d = hip.device_alloc(arr.nbytes).upload(arr)
-        bufs.append(d)
-        return d
-
-    d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
-    d_atk = [up(a[1].data) for a in atk]
-    d_tsk = [up(t[1].data) for t in tsk]
-    d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))
-    p = CircuitBootstrappingParams(
-        br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=sh["glwe_size"], base2k=k_brk,
-                               res_size=sh["glwe_size"], lut_size=sh["glwe_size"]),
-        atk_dnum=atk_dnum, atk_size=sh["atk_size"], tsk_dnum=tsk_dnum, tsk_size=sh["tsk_size"], res_dnum=res_dnum, res_size=sh["res_size"],
-        gap=gap, atk_base2k=k_atk, tsk_base2k=k_tsk, res_base2k=k_res, atk_glwe_size=sh["atk_glwe_size"], trace_size=sh["trace_size"])
-    if mode == "constant":
-        nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
-        d_tmp = up(np.zeros(nbytes // 8 + 1, dtype=np.int64))
-        hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                              [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
-    else:
-        nbytes = hip.circuit_bootstrapping_to_exponent_tmp_bytes(p, log_domain, batch)
-        d_tmp = up(np.zeros(nbytes // 8 + 1, dtype=np.int64))
-        hip.circuit_bootstrapping_execute_to_exponent_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                              [k.ptr for k in d_tsk], p, log_gap_in, log_gap_out, log_domain, d_tmp.ptr,
-                                                              nbytes, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in bufs:
-        buf.free()
+    with on_device(hip) as dev:
+        up = dev.upload
+        d_lwe, d_lut, d_brk = up(lwe), up(lut.data), up(brk_h)
+        d_atk = [up(a[1].data) for a in atk]
+        d_tsk = [up(t[1].data) for t in tsk]
+        d_res = up(rng.integers(-5, 5, want.shape, dtype=np.int64))
+        p = CircuitBootstrappingParams(
+            br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=block_size, dnum=brk_dnum, brk_size=sh["glwe_size"], base2k=k_brk,
+                                   res_size=sh["glwe_size"], lut_size=sh["glwe_size"]),
+            atk_dnum=atk_dnum, atk_size=sh["atk_size"], tsk_dnum=tsk_dnum, tsk_size=sh["tsk_size"], res_dnum=res_dnum, res_size=sh["res_size"],
+            gap=gap, atk_base2k=k_atk, tsk_base2k=k_tsk, res_base2k=k_res, atk_glwe_size=sh["atk_glwe_size"], trace_size=sh["trace_size"])
+        if mode == "constant":
+            nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
+            d_tmp = up(np.zeros(nbytes // 8 + 1, dtype=np.int64))
+            hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
+                                                                  [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
+        else:
+            nbytes = hip.circuit_bootstrapping_to_exponent_tmp_bytes(p, log_domain, batch)
+            d_tmp = up(np.zeros(nbytes // 8 + 1, dtype=np.int64))
+            hip.circuit_bootstrapping_execute_to_exponent_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
+                                                                  [k.ptr for k in d_tsk], p, log_gap_in, log_gap_out, log_domain, d_tmp.ptr,
+                                                                  nbytes, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got[:, :, 0], want[:, :, 0]), "rows before ggsw_expand_row differ"
     assert np.array_equal(got, want)
 
@@ -2152,10 +2026,7 @@ def test_blind_rotation_extended(mods, n, rank, ext, n_lwe, blk, dnum, bsz, rsz,
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * bsz), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):
-        mat = MatZnx(n, dnum, cols, cols, bsz).fill_uniform(k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, bsz), hip.vmp_pmat_alloc(dnum, cols, cols, bsz)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols, cols, bsz).fill_uniform(k, rng))
         brk_r[i], brk_h[i] = pr.data.reshape(-1), ph.data.reshape(-1)
     lwe = rng.integers(-n * ext, n * ext, (batch, n_lwe + 1), dtype=np.int64)   # mod_switch_2n(2 n ext) output range
     lwe[0, 1] = 0                       # contributes nothing
@@ -2169,20 +2040,18 @@ def test_blind_rotation_extended(mods, n, rank, ext, n_lwe, blk, dnum, bsz, rsz,
         res = VecZnx(n, cols, rsz)
         ref.blind_rotation_execute_extended(res, k, np.ascontiguousarray(lwe[b]), luts, brk_r, dnum, bsz, blk, xpa)
         want[b] = res.data
-    d_lwe = hip.device_alloc(lwe.nbytes).upload(lwe)
-    d_lut = hip.device_alloc(luts.nbytes).upload(luts)
-    d_brk = hip.device_alloc(brk_h.nbytes).upload(brk_h)
-    d_res = hip.device_alloc(want.nbytes)
-    p = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
-    nbytes = hip.blind_rotation_extended_tmp_bytes(p, ext, batch)
-    d_tmp = hip.device_alloc(nbytes)
-    hip.set_fusion(fuse, fuse)
-    hip.blind_rotation_execute_extended_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, ext, d_tmp.ptr, nbytes, batch)
-    hip.sync()
-    hip.set_fusion(True, True)
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in (d_lwe, d_lut, d_brk, d_res, d_tmp):
-        buf.free()
+    with on_device(hip) as dev:
+        d_lwe = dev.upload(lwe)
+        d_lut = dev.upload(luts)
+        d_brk = dev.upload(brk_h)
+        d_res = dev.alloc(want.nbytes, poison=False)
+        p = BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=dnum, brk_size=bsz, base2k=k, res_size=rsz, lut_size=rsz)
+        nbytes = hip.blind_rotation_extended_tmp_bytes(p, ext, batch)
+        d_tmp = dev.alloc(nbytes, poison=False)
+        with on_device(hip, fuse=(fuse, fuse)):
+            hip.blind_rotation_execute_extended_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, p, ext, d_tmp.ptr, nbytes, batch)
+            hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -2198,10 +2067,7 @@ def test_circuit_bootstrapping_with_extension_factor(mods):
     gap = 2 * int(rng.integers(1, n // 8))
 
     def prepared(rows, cols_in, size):
-        mat = MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(rows, cols_in, cols, size), hip.vmp_pmat_alloc(rows, cols_in, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, rows, cols_in, cols, size).fill_uniform(base2k, rng))
         hip.sync()
         return pr, ph
 
@@ -2232,29 +2098,21 @@ def test_circuit_bootstrapping_with_extension_factor(mods):
                 acc = nxt
         ref.ggsw_expand_row(g, base2k, [t[0] for t in tsk], 1, base2k)
         want[b] = g.data
-    bufs = []
-
-    def up(arr):
-        d = hip.device_alloc(arr.nbytes).upload(arr)
-        bufs.append(d)
-        return d
-
-    d_lwe, d_lut, d_brk = up(lwe), up(luts), up(brk_h)
-    d_atk = [up(a[1].data) for a in atk]
-    d_tsk = [up(t[1].data) for t in tsk]
-    d_res = up(np.zeros(want.shape, dtype=np.int64))
-    p = CircuitBootstrappingParams(
-        br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=brk_dnum, brk_size=gsz, base2k=base2k, res_size=gsz, lut_size=gsz),
-        atk_dnum=atk_dnum, atk_size=gsz, tsk_dnum=tsk_dnum, tsk_size=rsz + 1, res_dnum=res_dnum, res_size=rsz, gap=gap, extension_factor=ext)
-    nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
-    d_tmp = hip.device_alloc(nbytes)
-    bufs.append(d_tmp)
-    hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
-                                                          [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
-    hip.sync()
-    got = d_res.download(np.int64, want.size).reshape(want.shape)
-    for buf in bufs:
-        buf.free()
+    with on_device(hip) as dev:
+        up = dev.upload
+        d_lwe, d_lut, d_brk = up(lwe), up(luts), up(brk_h)
+        d_atk = [up(a[1].data) for a in atk]
+        d_tsk = [up(t[1].data) for t in tsk]
+        d_res = up(np.zeros(want.shape, dtype=np.int64))
+        p = CircuitBootstrappingParams(
+            br=BlindRotationParams(rank=rank, n_lwe=n_lwe, block_size=blk, dnum=brk_dnum, brk_size=gsz, base2k=base2k, res_size=gsz, lut_size=gsz),
+            atk_dnum=atk_dnum, atk_size=gsz, tsk_dnum=tsk_dnum, tsk_size=rsz + 1, res_dnum=res_dnum, res_size=rsz, gap=gap, extension_factor=ext)
+        nbytes = hip.circuit_bootstrapping_tmp_bytes(p, batch)
+        d_tmp = dev.alloc(nbytes, poison=False)
+        hip.circuit_bootstrapping_execute_to_constant_batched(d_res.ptr, d_lwe.ptr, d_lut.ptr, d_brk.ptr, gals, [k.ptr for k in d_atk],
+                                                              [k.ptr for k in d_tsk], p, d_tmp.ptr, nbytes, batch)
+        hip.sync()
+        got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
 
 
@@ -2368,9 +2226,7 @@ def test_glwe_ops_on_host_containers(mods, n):
         cols_in = rank if ks else cols
         a_cols = cols + 1 if kind == "relinearize" else cols
         mat = MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols_in, cols, size), hip.vmp_pmat_alloc(dnum, cols_in, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, mat)
         a_all = np.empty((batch, size, a_cols, n), dtype=np.int64)
         want = np.empty((batch, size, cols, n), dtype=np.int64)
 
@@ -2415,43 +2271,42 @@ def test_glwe_ops_on_host_containers(mods, n):
             run(inout, inout, hp(ph.data))
             assert np.array_equal(inout, want), kind
         # mixed: device ciphertexts, host key
-        d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-        d_r = hip.device_alloc(want.nbytes)
-        run(d_r.ptr, d_a.ptr, hp(ph.data))
-        hip.sync()
-        assert np.array_equal(d_r.download(np.int64, want.size).reshape(want.shape), want), kind
-        # the host key changes: re-prepared in place (mirror dropped by vmp_prepare) ...
-        mat2 = MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng)
-        ref.vmp_prepare(pr, mat2)
-        hip.vmp_prepare(ph, mat2)
-        oracle(pr)
-        run(got, a_all, hp(ph.data))
-        assert np.array_equal(got, want), kind
-        # ... or overwritten behind the backend's back (fingerprint mismatch -> refreshed), here with the first key again
-        ph1 = hip.vmp_pmat_alloc(dnum, cols_in, cols, size)
-        hip.vmp_prepare(ph1, mat)
-        ph.data[...] = ph1.data
-        ref.vmp_prepare(pr, mat)
-        oracle(pr)
-        run(got, a_all, hp(ph.data))
-        assert np.array_equal(got, want), kind
-        assert hip.lib.pz_module_forget_host_key(hip.handle, hp(ph.data)) == 0
-        run(got, a_all, hp(ph.data))
-        assert np.array_equal(got, want), kind
-        assert hip.lib.pz_module_forget_host_key(hip.handle, hp(ph.data)) == 0
-        # a key inside a pz_alloc_bytes block (Backend::OwnedBuf of the Rust shim): releasing the block drops its mirror
-        lib = hip.lib
-        before = lib.pz_module_host_key_mirrors(hip.handle)
-        blk = lib.pz_alloc_bytes(ph.data.nbytes + 4096)
-        inner = np.ctypeslib.as_array(C.cast(blk + 4096, C.POINTER(C.c_double)), shape=(ph.data.size,))
-        inner[...] = ph.data.reshape(-1)
-        run(got, a_all, C.c_void_p(blk + 4096))
-        assert np.array_equal(got, want), kind
-        assert lib.pz_module_host_key_mirrors(hip.handle) == before + 1
-        lib.pz_free_bytes(C.c_void_p(blk))
-        assert lib.pz_module_host_key_mirrors(hip.handle) == before
-        for buf in (d_a, d_r):
-            buf.free()
+        with on_device(hip) as dev:
+            d_a = dev.upload(a_all)
+            d_r = dev.alloc(want.nbytes, poison=False)
+            run(d_r.ptr, d_a.ptr, hp(ph.data))
+            hip.sync()
+            assert np.array_equal(d_r.download(np.int64, want.size).reshape(want.shape), want), kind
+            # the host key changes: re-prepared in place (mirror dropped by vmp_prepare) ...
+            mat2 = MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng)
+            ref.vmp_prepare(pr, mat2)
+            hip.vmp_prepare(ph, mat2)
+            oracle(pr)
+            run(got, a_all, hp(ph.data))
+            assert np.array_equal(got, want), kind
+            # ... or overwritten behind the backend's back (fingerprint mismatch -> refreshed), here with the first key again
+            ph1 = hip.vmp_pmat_alloc(dnum, cols_in, cols, size)
+            hip.vmp_prepare(ph1, mat)
+            ph.data[...] = ph1.data
+            ref.vmp_prepare(pr, mat)
+            oracle(pr)
+            run(got, a_all, hp(ph.data))
+            assert np.array_equal(got, want), kind
+            assert hip.lib.pz_module_forget_host_key(hip.handle, hp(ph.data)) == 0
+            run(got, a_all, hp(ph.data))
+            assert np.array_equal(got, want), kind
+            assert hip.lib.pz_module_forget_host_key(hip.handle, hp(ph.data)) == 0
+            # a key inside a pz_alloc_bytes block (Backend::OwnedBuf of the Rust shim): releasing the block drops its mirror
+            lib = hip.lib
+            before = lib.pz_module_host_key_mirrors(hip.handle)
+            blk = lib.pz_alloc_bytes(ph.data.nbytes + 4096)
+            inner = np.ctypeslib.as_array(C.cast(blk + 4096, C.POINTER(C.c_double)), shape=(ph.data.size,))
+            inner[...] = ph.data.reshape(-1)
+            run(got, a_all, C.c_void_p(blk + 4096))
+            assert np.array_equal(got, want), kind
+            assert lib.pz_module_host_key_mirrors(hip.handle) == before + 1
+            lib.pz_free_bytes(C.c_void_p(blk))
+            assert lib.pz_module_host_key_mirrors(hip.handle) == before
 
 
 @pytest.mark.parametrize("n,size", [(4096, 3), (65536, 8)])
@@ -2479,10 +2334,7 @@ def test_glwe_ops_on_pinned_host_containers_duplex(mods, n, size):
     try:
         for ks in (False, True):
             cols_in = rank if ks else cols
-            mat = MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng)
-            pr, ph = ref.vmp_pmat_alloc(dnum, cols_in, cols, size), hip.vmp_pmat_alloc(dnum, cols_in, cols, size)
-            ref.vmp_prepare(pr, mat)
-            hip.vmp_prepare(ph, mat)
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng))
             key_host, kp = pinned(ph.data.shape, np.float64)
             held.append(kp)
             key_host[...] = ph.data
@@ -2536,10 +2388,7 @@ def test_pinned_host_in_place_mismatch_and_partial_overlap(mods):
     hp = lambda arr: arr.ctypes.data_as(C.c_void_p)
     held = []
     try:
-        mat = MatZnx(n, size, cols, cols, size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(size, cols, cols, size), hip.vmp_pmat_alloc(size, cols, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, size, cols, cols, size).fill_uniform(base2k, rng))
         key_host, kp = pinned(ph.data.shape, np.float64)
         held.append(kp)
         key_host[...] = ph.data
@@ -2588,3 +2437,49 @@ def test_blind_rotation_block_counts_and_accumulator_forms(mods, n, rank, blk, d
     n_lwe = nblocks * blk + extra
     got, want = _run_blind_rotation(hip, ref, n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch=5, seed=n + 31 * nblocks + rank)
     assert np.array_equal(got, want)
+
+
+def test_a_refused_call_in_a_device_scope_leaves_the_module_as_it_was(mods):
+    """tests/device.py's on_device on the real module, N = 1024 (small-ring pipeline), rank 1, 2 limbs, base2k 12, batch 7: a call the ABI refuses
+    before it launches anything (dsize = 0: "glwe op: empty shape") inside a scope that chunks, unfuses and pins - afterwards the key can be
+    pinned again (a leaked pin says "key already pinned") and the default key switch runs the kernels it ran before, as often, bit-exact
+    (a leaked set_chunk(3) / set_fusion(False, False) changes both at this size)."""
+    from poulpy_amd.hal import GlweOpParams, PoulpyHipError
+    n, rank, size, k, batch = 1024, 1, 2, 12, 7
+    ref, hip = mods(n)
+    rng = seeded(10247)
+    cols = rank + 1
+    pr, ph = prepared_key(ref, hip, MatZnx(n, size, rank, cols, size).fill_uniform(k, rng))
+    a_all = np.empty((batch, size, cols, n), dtype=np.int64)
+    want = np.empty_like(a_all)
+    for b in range(batch):
+        a = VecZnx(n, cols, size).fill_uniform(k, rng)
+        a_all[b] = a.data
+        res = VecZnx(n, cols, size)
+        ref.glwe_keyswitch(res, k, a, k, pr, 1, k)
+        want[b] = res.data
+    shape = dict(rank=rank, dnum=size, key_size=size, key_base2k=k, a_size=size, a_base2k=k, res_size=size, res_base2k=k, rank_out=rank)
+
+    def default_keyswitch():
+        with on_device(hip, timing=True) as dev:
+            d_a, d_key, d_res = dev.upload(a_all), dev.key(ph), dev.alloc(want.nbytes)
+            hip.dispatch_notes(reset=True)
+            hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, GlweOpParams(dsize=1, **shape), batch)
+            hip.sync()
+            launches = {name: count for name, (count, _) in hip.kernel_stats().items()}
+            return d_res.download(np.int64, want.size).reshape(want.shape), hip.dispatch_notes(), launches
+
+    got, notes, launches = default_keyswitch()
+    assert np.array_equal(got, want) and sum(launches.values()) > 0
+    d_key = hip.device_alloc(ph.data.nbytes).upload(ph.data)      # outside any scope: it outlives the one that pins it
+    with pytest.raises(PoulpyHipError, match="empty shape"):
+        with on_device(hip, chunk=3, fuse=(False, False)) as dev:
+            dev.pin(d_key, size, rank, cols, size)
+            d_a, d_res = dev.upload(a_all), dev.alloc(want.nbytes)
+            hip.glwe_keyswitch_batched(d_res.ptr, d_a.ptr, d_key.ptr, GlweOpParams(dsize=0, **shape), batch)
+    hip.pin_key(d_key.ptr, size, rank, cols, size)
+    hip.unpin_key(d_key.ptr)
+    d_key.free()
+    got2, notes2, launches2 = default_keyswitch()
+    assert np.array_equal(got2, want)
+    assert notes2 == notes and launches2 == launches, (notes, notes2, launches, launches2)

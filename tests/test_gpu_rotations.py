@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx
+from tests.device import mods, on_device  # noqa: F401
 from tests.helpers import seeded
 
 pytestmark = pytest.mark.gpu
@@ -24,19 +25,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOISTED, LOOP = "rotations: hoisted", "rotations: per-rotation calls"
 CAP = 8   # k_automorphism_t16_many takes this many Galois elements per launch (device_ops.hpp kAutoManyCap)
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def inputs(n, rank, a_size, a_base2k, key_size, key_base2k, dnum, dsize, res_size, res_base2k, batch, gals, seed, wide=None):
@@ -87,44 +75,30 @@ def run_device(hip, c, chunk=0, fuse=(True, True), pin=(), probe=False, single=F
     nrot = len(c.gals)
     shape = (nrot, c.batch, c.res_size, c.cols, c.n)
     nbytes = int(np.prod(shape)) * 8
-    d_keys = []
-    for m in c.mats:
-        ph = hip.vmp_pmat_alloc(c.dnum, c.rank, c.cols, c.key_size)
-        hip.vmp_prepare(ph, m)
-        d_keys.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    d_a = hip.device_alloc(c.a.nbytes).upload(np.ascontiguousarray(c.a))
-    d_res = hip.device_alloc(nbytes)
-    hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, nbytes)
-    try:
-        hip.set_chunk(chunk)
-        hip.set_fusion(*fuse)
+    with on_device(hip, chunk=chunk, fuse=fuse) as dev:
+        d_keys = []
+        for m in c.mats:
+            ph = hip.vmp_pmat_alloc(c.dnum, c.rank, c.cols, c.key_size)
+            hip.vmp_prepare(ph, m)
+            d_keys.append(dev.key(ph))
+        d_a, d_res = dev.upload(c.a), dev.alloc(nbytes)
         for r in pin:
-            hip.pin_key(d_keys[r].ptr, c.dnum, c.rank, c.cols, c.key_size)
+            dev.pin(d_keys[r], c.dnum, c.rank, c.cols, c.key_size)
         query = hip.glwe_automorphism_many_workspace_bytes(p, nrot, c.batch)
         hip.sync()
         hip.dispatch_notes(reset=True)
-        hip.set_kernel_timing(True)
-        before = hip.kernel_stats()["fwd_pass1"][0]
-        hip.set_margin_probe(probe)
-        if single:
-            for r in range(nrot):
-                hip.glwe_automorphism_batched(d_res.at(r * nbytes // nrot), d_a.ptr, d_keys[r].ptr, p, c.gals[r], "automorphism", c.batch)
-        else:
-            hip.glwe_automorphism_many_batched(d_res.ptr, d_a.ptr, c.gals, [k.ptr for k in d_keys], p, c.batch)
-        hip.sync()
-        pass1 = hip.kernel_stats()["fwd_pass1"][0] - before
-        got = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
-        notes = hip.dispatch_notes()
-        used = hip.workspace_bytes()
-    finally:
-        hip.set_margin_probe(False)
-        hip.set_kernel_timing(False)
-        hip.set_chunk(0)
-        hip.set_fusion(True, True)
-        for r in pin:
-            hip.unpin_key(d_keys[r].ptr)
-        for buf in (d_a, d_res, *d_keys):
-            buf.free()
+        with on_device(hip, timing=True, probe=probe):
+            before = hip.kernel_stats()["fwd_pass1"][0]
+            if single:
+                for r in range(nrot):
+                    hip.glwe_automorphism_batched(d_res.at(r * nbytes // nrot), d_a.ptr, d_keys[r].ptr, p, c.gals[r], "automorphism", c.batch)
+            else:
+                hip.glwe_automorphism_many_batched(d_res.ptr, d_a.ptr, c.gals, [k.ptr for k in d_keys], p, c.batch)
+            hip.sync()
+            pass1 = hip.kernel_stats()["fwd_pass1"][0] - before
+            got = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
+            notes = hip.dispatch_notes()
+            used = hip.workspace_bytes()
     return got, notes, pass1, query, used
 
 
@@ -311,27 +285,25 @@ def test_argument_errors_launch_nothing(mods):
     c = simple(n, 1, 3, 12, 2, [5, 3], seed=9900)
     p = params(c)
     ct = c.n * c.cols * c.res_size * 8
-    d_a = hip.device_alloc(c.a.nbytes + ct).upload(np.ascontiguousarray(c.a))
-    d_res = hip.device_alloc(2 * c.batch * ct)
-    d_key = hip.device_alloc(c.n * 8 * c.dnum * c.rank * c.cols * c.key_size)
-    hip.lib.pz_memset_d(hip.handle, d_res.ptr, 0x5A, d_res.nbytes)
-    hip.sync()
+    with on_device(hip) as dev:
+        d_a = dev.alloc(c.a.nbytes + ct, poison=False).upload(np.ascontiguousarray(c.a))
+        d_res = dev.alloc(2 * c.batch * ct)
+        d_key = dev.alloc(c.n * 8 * c.dnum * c.rank * c.cols * c.key_size, poison=False)
+        hip.sync()
 
-    def call(res, gals, keys):
-        g = (C.c_int64 * max(len(gals), 1))(*gals)
-        k = (C.c_void_p * max(len(keys), 1))(*keys)
-        st = hip.lib.pz_glwe_automorphism_many_batched(hip.handle, res, d_a.ptr, len(gals), g, k, C.byref(p), c.batch)
-        return st, hip.lib.pz_last_error().decode()
+        def call(res, gals, keys):
+            g = (C.c_int64 * max(len(gals), 1))(*gals)
+            k = (C.c_void_p * max(len(keys), 1))(*keys)
+            st = hip.lib.pz_glwe_automorphism_many_batched(hip.handle, res, d_a.ptr, len(gals), g, k, C.byref(p), c.batch)
+            return st, hip.lib.pz_last_error().decode()
 
-    key = d_key.ptr.value
-    tail = C.c_void_p(d_a.ptr.value + c.a.nbytes - ct)     # the last ciphertext of `a`
-    for label, args in (("nrot = 0", (d_res.ptr, [], [])), ("even element", (d_res.ptr, [5, 4], [key, key])),
-                        ("null key", (d_res.ptr, [5, 3], [key, 0])), ("res == a", (d_a.ptr, [5, 3], [key, key])),
-                        ("res overlaps the tail of a", (tail, [5, 3], [key, key]))):
-        st, msg = call(*args)
-        assert st < 0 and msg, (label, st, msg)
-    hip.sync()
-    assert np.all(d_res.download(np.uint8, d_res.nbytes) == 0x5A)
-    assert np.array_equal(d_a.download(np.int64, c.a.size).reshape(c.a.shape), c.a)
-    for buf in (d_a, d_res, d_key):
-        buf.free()
+        key = d_key.ptr.value
+        tail = C.c_void_p(d_a.ptr.value + c.a.nbytes - ct)     # the last ciphertext of `a`
+        for label, args in (("nrot = 0", (d_res.ptr, [], [])), ("even element", (d_res.ptr, [5, 4], [key, key])),
+                            ("null key", (d_res.ptr, [5, 3], [key, 0])), ("res == a", (d_a.ptr, [5, 3], [key, key])),
+                            ("res overlaps the tail of a", (tail, [5, 3], [key, key]))):
+            st, msg = call(*args)
+            assert st < 0 and msg, (label, st, msg)
+        hip.sync()
+        assert np.all(d_res.download(np.uint8, d_res.nbytes) == 0x5A)
+        assert np.array_equal(d_a.download(np.int64, c.a.size).reshape(c.a.shape), c.a)

@@ -17,22 +17,10 @@ import numpy as np
 import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx
+from tests.device import mods, on_device, prepared_key  # noqa: F401
 from tests.helpers import MARGIN_MAX, probed_margin, seeded
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _pool_parity(hip, ref, ks, n, rank, size, base2k, dnum, batch, pool, seed, chunk=0, pin=False, in_chunks=64):
@@ -43,10 +31,7 @@ def _pool_parity(hip, ref, ks, n, rank, size, base2k, dnum, batch, pool, seed, c
     rng = seeded(seed)
     cols = rank + 1
     cols_in = rank if ks else cols
-    mat = MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, cols_in, cols, size), hip.vmp_pmat_alloc(dnum, cols_in, cols, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols_in, cols, size).fill_uniform(base2k, rng))
     a_pool = np.empty((pool, size, cols, n), dtype=np.int64)
     want_pool = np.empty((pool, size, cols, n), dtype=np.int64)
     for i in range(pool):
@@ -66,9 +51,6 @@ def _pool_parity(hip, ref, ks, n, rank, size, base2k, dnum, batch, pool, seed, c
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k,
                      res_size=size, res_base2k=base2k, rank_out=rank)
     ptr = lambda t: C.c_void_p(t.data_ptr())
-    hip.set_chunk(chunk)
-    if pin:
-        hip.pin_key(ptr(key), dnum, cols_in, cols, size)
     def count_bad():
         bad = 0
         for b0 in range(0, batch, in_chunks):             # compare on the device, a slab at a time
@@ -77,7 +59,9 @@ def _pool_parity(hip, ref, ks, n, rank, size, base2k, dnum, batch, pool, seed, c
             bad += int((~eq).sum().item())
         return bad
     run = lambda: (hip.glwe_keyswitch_batched if ks else hip.glwe_external_product_batched)(ptr(res), ptr(a_all), ptr(key), p, batch)
-    try:
+    with on_device(hip, chunk=chunk) as scope:
+        if pin:
+            scope.pin(ptr(key), dnum, cols_in, cols, size)
         run()
         hip.sync()
         bad = count_bad()
@@ -86,10 +70,6 @@ def _pool_parity(hip, ref, ks, n, rank, size, base2k, dnum, batch, pool, seed, c
         torch.cuda.synchronize()   # torch's stream and the module's stream are not ordered
         margin = probed_margin(hip, run)
         bad_probe = count_bad()
-    finally:
-        if pin:
-            hip.unpin_key(ptr(key))
-        hip.set_chunk(0)
     assert bad_probe == 0 or bad != 0, f"the probing instantiations changed {bad_probe} results (the product kernels were right)"
     bad += bad_probe
     assert margin < MARGIN_MAX, f"rounding margin too thin: max |x - round(x)| = {margin} (N = {n}, base2k {base2k}, {size} limbs)"
@@ -159,10 +139,7 @@ def _auto_pool_parity(hip, ref, n, rank, size, base2k, dnum, gal, mode, batch, p
     from poulpy_amd.hal import GlweOpParams
     rng = seeded(seed)
     cols = rank + 1
-    mat = MatZnx(n, dnum, rank, cols, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, size), hip.vmp_pmat_alloc(dnum, rank, cols, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, size).fill_uniform(base2k, rng))
     a_pool = np.empty((pool, size, cols, n), dtype=np.int64)
     want_pool = np.empty((pool, size, cols, n), dtype=np.int64)
     for i in range(pool):
@@ -190,9 +167,9 @@ def _auto_pool_parity(hip, ref, n, rank, size, base2k, dnum, gal, mode, batch, p
             bad += int((~eq).sum().item())
         return bad
     run = lambda: hip.glwe_automorphism_batched(ptr(res), ptr(a_all), ptr(key), p, gal, mode, batch)
-    if pin:
-        hip.pin_key(ptr(key), dnum, rank, cols, size)
-    try:
+    with on_device(hip) as scope:
+        if pin:
+            scope.pin(ptr(key), dnum, rank, cols, size)
         run()
         hip.sync()
         bad = count_bad()
@@ -203,9 +180,6 @@ def _auto_pool_parity(hip, ref, n, rank, size, base2k, dnum, gal, mode, batch, p
         torch.cuda.synchronize()   # torch's stream and the module's stream are not ordered
         margin = probed_margin(hip, run)
         bad_probe = count_bad()
-    finally:
-        if pin:
-            hip.unpin_key(ptr(key))
     assert bad_probe == 0 or bad != 0, f"the probing instantiations changed {bad_probe} results (the product kernels were right)"
     bad += bad_probe
     assert margin < MARGIN_MAX, f"rounding margin too thin: max |x - round(x)| = {margin} (N = {n}, base2k {base2k}, {size} limbs, automorphism {mode})"
@@ -345,10 +319,7 @@ def test_config5_relinearize_16_limbs_pool_parity_at_bench_batch(mods):
     ref, hip = mods(n)
     rng = seeded(6200)
     cols, pairs = rank + 1, rank * (rank + 1) // 2
-    mat = MatZnx(n, dnum, pairs, cols, size).fill_uniform(base2k, rng)
-    pr, ph = ref.vmp_pmat_alloc(dnum, pairs, cols, size), hip.vmp_pmat_alloc(dnum, pairs, cols, size)
-    ref.vmp_prepare(pr, mat)
-    hip.vmp_prepare(ph, mat)
+    pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, pairs, cols, size).fill_uniform(base2k, rng))
     a_pool = np.empty((pool, size, cols + pairs, n), dtype=np.int64)
     want_pool = np.empty((pool, size, cols, n), dtype=np.int64)
     for i in range(pool):
@@ -367,12 +338,10 @@ def test_config5_relinearize_16_limbs_pool_parity_at_bench_batch(mods):
     p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k,
                      res_size=size, res_base2k=base2k, rank_out=rank)
     ptr = lambda t: C.c_void_p(t.data_ptr())
-    hip.pin_key(ptr(key), dnum, pairs, cols, size)
-    try:
+    with on_device(hip) as scope:
+        scope.pin(ptr(key), dnum, pairs, cols, size)
         hip.glwe_tensor_relinearize_batched(ptr(d_r), ptr(d_a), ptr(key), p, batch)
         hip.sync()
-    finally:
-        hip.unpin_key(ptr(key))
     bad = int((d_r != d_want[idx]).flatten(1).any(dim=1).sum().item())
     del d_a, d_r, d_want, key
     torch.cuda.empty_cache()
@@ -407,10 +376,7 @@ def _br_pool_parity(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, res_si
     brk_r = np.empty((n_lwe, n * dnum * cols * cols * brk_size), dtype=np.float64)
     brk_h = np.empty_like(brk_r)
     for i in range(n_lwe):
-        mat = MatZnx(n, dnum, cols, cols, brk_size).fill_uniform(base2k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, brk_size), hip.vmp_pmat_alloc(dnum, cols, cols, brk_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, cols, cols, brk_size).fill_uniform(base2k, rng))
         brk_r[i], brk_h[i] = pr.data.reshape(-1), ph.data.reshape(-1)
     lwe_pool = rng.integers(-n, n, (pool, n_lwe + 1), dtype=np.int64)
     lwe_pool[0, 1] = 0
@@ -626,9 +592,7 @@ def test_fused_tail_large_and_saturating_values(mods, n):
         mat = MatZnx(n, dnum, cols, cols, size)
         mat.data[:, :, :, :, 0] = ck                       # every key entry = the constant ck
         mat.data[0, 0, 1, 1, 0] = ck + 1
-        pr, ph = ref.vmp_pmat_alloc(dnum, cols, cols, size), hip.vmp_pmat_alloc(dnum, cols, cols, size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
+        pr, ph = prepared_key(ref, hip, mat)
         batch = 5
         a_all = np.zeros((batch, size, cols, n), dtype=np.int64)
         want = np.empty_like(a_all)
@@ -638,22 +602,20 @@ def test_fused_tail_large_and_saturating_values(mods, n):
             r = VecZnx(n, cols, size)
             ref.glwe_external_product(r, base2k, a, base2k, pr, 1, base2k)
             want[b] = r.data
-        d_a = hip.device_alloc(a_all.nbytes).upload(a_all)
-        d_k = hip.device_alloc(ph.data.nbytes).upload(ph.data)
-        d_r = hip.device_alloc(want.nbytes)
-        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k,
-                         res_size=size, res_base2k=base2k, rank_out=rank)
-        for fuse in ((True, True), (False, False)):
-            hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x11, want.nbytes)
-            hip.set_fusion(*fuse)
-            hip.glwe_external_product_batched(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
-            hip.sync()
-            hip.set_fusion(True, True)
-            got = d_r.download(np.int64, want.size).reshape(want.shape)
-            assert np.array_equal(got, want), (n, ca, ck, fuse)
-        assert np.abs(want).max() > 0
-        for buf in (d_a, d_k, d_r):
-            buf.free()
+        with on_device(hip) as dev:
+            d_a = dev.upload(a_all)
+            d_k = dev.key(ph)
+            d_r = dev.alloc(want.nbytes, poison=False)
+            p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=size, key_base2k=base2k, a_size=size, a_base2k=base2k,
+                             res_size=size, res_base2k=base2k, rank_out=rank)
+            for fuse in ((True, True), (False, False)):
+                hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x11, want.nbytes)
+                with on_device(hip, fuse=fuse):
+                    hip.glwe_external_product_batched(d_r.ptr, d_a.ptr, d_k.ptr, p, batch)
+                    hip.sync()
+                got = d_r.download(np.int64, want.size).reshape(want.shape)
+                assert np.array_equal(got, want), (n, ca, ck, fuse)
+            assert np.abs(want).max() > 0
 
 
 # ------------------------------------------------------------------------------------------
@@ -668,28 +630,27 @@ def test_pz_bcast_key_single_rank_rccl(mods):
     n = 4096
     ref, hip = mods(n)
     assert hip.lib.pz_comm_world_size(hip.handle) == 0 and hip.lib.pz_comm_rank(hip.handle) == -1
-    buf = hip.device_alloc(1 << 20)
-    with pytest.raises(PoulpyHipError):
-        hip.bcast_key(buf.ptr, 1 << 20, 0)            # no communicator yet
-    uid = hip.comm_unique_id()
-    assert len(uid) == 128
-    hip.comm_init_rank(1, 0, uid)
-    assert hip.lib.pz_comm_world_size(hip.handle) == 1 and hip.lib.pz_comm_rank(hip.handle) == 0
-    with pytest.raises(PoulpyHipError):
-        hip.comm_init_rank(1, 0, uid)                 # one communicator per module
-    data = np.arange((200 << 20) // 8, dtype=np.float64)   # 200 MiB: four buckets
-    big = hip.device_alloc(data.nbytes).upload(data)
-    hip.bcast_key(big.ptr, data.nbytes, 0)
-    with pytest.raises(PoulpyHipError):
-        hip.bcast_key(big.ptr, data.nbytes, 3)        # root out of range
-    hip.sync()
-    assert np.array_equal(big.download(np.float64, data.size), data)
-    assert _pool_parity(hip, ref, False, n, 1, 4, 17, 4, batch=40, pool=5, seed=77) == 0
-    hip.comm_destroy()
-    hip.comm_destroy()                                # idempotent
-    assert hip.lib.pz_comm_world_size(hip.handle) == 0
-    for b in (buf, big):
-        b.free()
+    with on_device(hip) as dev:
+        buf = dev.alloc(1 << 20, poison=False)
+        with pytest.raises(PoulpyHipError):
+            hip.bcast_key(buf.ptr, 1 << 20, 0)            # no communicator yet
+        uid = hip.comm_unique_id()
+        assert len(uid) == 128
+        hip.comm_init_rank(1, 0, uid)
+        assert hip.lib.pz_comm_world_size(hip.handle) == 1 and hip.lib.pz_comm_rank(hip.handle) == 0
+        with pytest.raises(PoulpyHipError):
+            hip.comm_init_rank(1, 0, uid)                 # one communicator per module
+        data = np.arange((200 << 20) // 8, dtype=np.float64)   # 200 MiB: four buckets
+        big = dev.upload(data)
+        hip.bcast_key(big.ptr, data.nbytes, 0)
+        with pytest.raises(PoulpyHipError):
+            hip.bcast_key(big.ptr, data.nbytes, 3)        # root out of range
+        hip.sync()
+        assert np.array_equal(big.download(np.float64, data.size), data)
+        assert _pool_parity(hip, ref, False, n, 1, 4, 17, 4, batch=40, pool=5, seed=77) == 0
+        hip.comm_destroy()
+        hip.comm_destroy()                                # idempotent
+        assert hip.lib.pz_comm_world_size(hip.handle) == 0
 
 
 # ------------------------------------------------------------------------------------------

@@ -15,23 +15,11 @@ import pytest
 
 from tests import tensor_cases as tc
 from tests.core_cases import prepare
+from tests.device import mods, on_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 3
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _device(hip, c, kind, mode=None, chunk=0, fuse=(True, True), pin=False):
@@ -44,22 +32,11 @@ def _device(hip, c, kind, mode=None, chunk=0, fuse=(True, True), pin=False):
     tcols = cols + pairs
     batch, a_size = c.a.shape[0], c.a.shape[1]
     b_all = c.a if c.b is None else c.b
-    bufs = []
-
-    def dev(x=None, nbytes=None):
-        if x is not None:
-            d = hip.device_alloc(x.nbytes).upload(np.ascontiguousarray(x))
-        else:
-            d = hip.device_alloc(nbytes)
-            hip.lib.pz_memset_d(hip.handle, d.ptr, 0x5A, nbytes)
-        bufs.append(d)
-        return d
-
     out = {}
     d_key = None
-    try:
-        d_a = dev(c.a)
-        d_b = d_a if c.b is None else dev(c.b)
+    with on_device(hip) as dev:
+        d_a = dev.upload(c.a)
+        d_b = d_a if c.b is None else dev.upload(c.b)
         t_shape = (batch, c.res_size, tcols, n)
         tp = GlweTensorParams(rank=c.rank, a_size=a_size, b_size=b_all.shape[1], ab_base2k=c.in_base2k, a_effective_k=c.a_k,
                               b_effective_k=c.b_k, res_size=c.res_size, res_base2k=c.res_base2k, cnv_offset=c.cnv_offset)
@@ -67,36 +44,28 @@ def _device(hip, c, kind, mode=None, chunk=0, fuse=(True, True), pin=False):
             rows, pr, ksz, _, _ = c.key.shape
             assert pr == pairs
             ph = prepare(hip, c.key)
-            d_key = dev(ph.data)
+            d_key = dev.key(ph)
             rp = GlweOpParams(rank=c.rank, dnum=rows, dsize=c.dsize, key_size=ksz, key_base2k=c.key_base2k, a_size=c.res_size,
                               a_base2k=c.res_base2k, res_size=c.relin[0], res_base2k=c.relin[1], rank_out=c.rank)
             r_shape = (batch, c.relin[0], cols, n)
-            d_r = dev(nbytes=int(np.prod(r_shape)) * 8)
-        hip.set_chunk(chunk)
-        hip.set_fusion(*fuse)
-        hip.dispatch_notes(reset=True)
-        if pin:
-            hip.pin_key(d_key.ptr, rows, pairs, cols, ksz)
-        if kind == "one_call":
-            hip.glwe_tensor_mul_relinearize_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, d_key.ptr, tp, rp, mode, batch)
-        else:
-            d_t = dev(c.acc) if mode == "add_assign" else dev(nbytes=int(np.prod(t_shape)) * 8)
-            hip.glwe_tensor_apply_batched(d_t.ptr, d_a.ptr, None if square else d_b.ptr, tp, mode, batch)
-            if kind == "two_calls" and d_key is not None:
-                hip.glwe_tensor_relinearize_batched(d_r.ptr, d_t.ptr, d_key.ptr, rp, batch)
+            d_r = dev.alloc(int(np.prod(r_shape)) * 8)
+        with on_device(hip, chunk=chunk, fuse=fuse) as pinned:
+            hip.dispatch_notes(reset=True)
+            if pin:
+                pinned.pin(d_key, rows, pairs, cols, ksz)
+            if kind == "one_call":
+                hip.glwe_tensor_mul_relinearize_batched(d_r.ptr, d_a.ptr, None if square else d_b.ptr, d_key.ptr, tp, rp, mode, batch)
+            else:
+                d_t = dev.upload(c.acc) if mode == "add_assign" else dev.alloc(int(np.prod(t_shape)) * 8)
+                hip.glwe_tensor_apply_batched(d_t.ptr, d_a.ptr, None if square else d_b.ptr, tp, mode, batch)
+                if kind == "two_calls" and d_key is not None:
+                    hip.glwe_tensor_relinearize_batched(d_r.ptr, d_t.ptr, d_key.ptr, rp, batch)
+                hip.sync()
+                out["tensor"] = d_t.download(np.int64, int(np.prod(t_shape))).reshape(t_shape)
             hip.sync()
-            out["tensor"] = d_t.download(np.int64, int(np.prod(t_shape))).reshape(t_shape)
-        hip.sync()
-        if d_key is not None:
-            out["relin"] = d_r.download(np.int64, int(np.prod(r_shape))).reshape(r_shape)
-        notes = hip.dispatch_notes()
-    finally:
-        if pin and d_key is not None:
-            hip.unpin_key(d_key.ptr)
-        hip.set_chunk(0)
-        hip.set_fusion(True, True)
-        for d in bufs:
-            d.free()
+            if d_key is not None:
+                out["relin"] = d_r.download(np.int64, int(np.prod(r_shape))).reshape(r_shape)
+            notes = hip.dispatch_notes()
     return out, notes
 
 
@@ -163,35 +132,27 @@ def _device_plain(hip, c, chunk=2):
     assign = c.mode == "assign"
     shape = (batch, c.res_size, cols, n)
     nbytes = int(np.prod(shape)) * 8
-    bufs = [hip.device_alloc(c.a.nbytes).upload(np.ascontiguousarray(c.a))]
-    d_a = bufs[0]
-    try:
+    with on_device(hip) as dev:
+        d_a = dev.upload(c.a)
         if assign:
             assert c.a.shape == shape
             d_r = d_a
         else:
-            d_r = hip.device_alloc(nbytes)
-            bufs.append(d_r)
-            hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x5A, nbytes)
-        hip.set_chunk(chunk)
-        hip.dispatch_notes(reset=True)
-        if c.op == "plain":
-            pt = np.ascontiguousarray(c.pt)
-            d_pt = hip.device_alloc(pt.nbytes).upload(pt)
-            bufs.append(d_pt)
-            p = GlweTensorParams(rank=c.rank, a_size=a_size, b_size=pt.shape[1], ab_base2k=c.ab, a_effective_k=c.a_k, b_effective_k=c.b_k,
-                                 res_size=c.res_size, res_base2k=c.rb, cnv_offset=c.cnv_offset)
-            hip.glwe_mul_plain_batched(d_r.ptr, None if assign else d_a.ptr, d_pt.ptr, c.shared, p, c.mode, batch)
-        else:
-            p = GlweMulConstParams(rank=c.rank, a_size=a_size, a_base2k=c.ab, res_size=c.res_size, res_base2k=c.rb, cnv_offset=c.cnv_offset)
-            hip.glwe_mul_const_batched(d_r.ptr, None if assign else d_a.ptr, c.re, c.im, p, c.mode, batch, b_size=3)
-        hip.sync()
-        got = d_r.download(np.int64, int(np.prod(shape))).reshape(shape)
-        notes = hip.dispatch_notes()
-    finally:
-        hip.set_chunk(0)
-        for d in bufs:
-            d.free()
+            d_r = dev.alloc(nbytes)
+        with on_device(hip, chunk=chunk):
+            hip.dispatch_notes(reset=True)
+            if c.op == "plain":
+                pt = np.ascontiguousarray(c.pt)
+                d_pt = dev.upload(pt)
+                p = GlweTensorParams(rank=c.rank, a_size=a_size, b_size=pt.shape[1], ab_base2k=c.ab, a_effective_k=c.a_k, b_effective_k=c.b_k,
+                                     res_size=c.res_size, res_base2k=c.rb, cnv_offset=c.cnv_offset)
+                hip.glwe_mul_plain_batched(d_r.ptr, None if assign else d_a.ptr, d_pt.ptr, c.shared, p, c.mode, batch)
+            else:
+                p = GlweMulConstParams(rank=c.rank, a_size=a_size, a_base2k=c.ab, res_size=c.res_size, res_base2k=c.rb, cnv_offset=c.cnv_offset)
+                hip.glwe_mul_const_batched(d_r.ptr, None if assign else d_a.ptr, c.re, c.im, p, c.mode, batch, b_size=3)
+            hip.sync()
+            got = d_r.download(np.int64, int(np.prod(shape))).reshape(shape)
+            notes = hip.dispatch_notes()
     return got, notes
 
 

@@ -13,23 +13,11 @@ import pytest
 
 from tests import trace_cases as tc
 from tests.core_cases import prepare
+from tests.device import mods, on_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 3
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _device(hip, c, fuse=(True, True)):
@@ -38,52 +26,37 @@ def _device(hip, c, fuse=(True, True)):
     n, cols = c.n, c.rank + 1
     rows, _, ksz, _, _ = c.keys[0].shape
     gals = [tc._gal(g, n) for g in c.gals]
-    bufs = []
-
-    def dev(x=None, nbytes=None):
-        if x is not None:
-            d = hip.device_alloc(x.nbytes).upload(np.ascontiguousarray(x))
-        else:
-            d = hip.device_alloc(nbytes)
-            hip.lib.pz_memset_d(hip.handle, d.ptr, 0x5A, nbytes)
-        bufs.append(d)
-        return d
-
-    try:
-        d_keys = [dev(prepare(hip, key).data) for key in c.keys]
+    with on_device(hip) as dev:
+        d_keys = [dev.key(prepare(hip, key)) for key in c.keys]
         hip.sync()
         one_base = c.base2k == c.key_base2k
-        hip.set_fusion(*fuse)
-        hip.dispatch_notes(reset=True)
-        if c.op == "trace":
-            batch, size = c.a.shape[0], c.a.shape[1]
-            p = GlweOpParams(rank=c.rank, dnum=rows, dsize=1, key_size=ksz, key_base2k=c.key_base2k, a_size=size if one_base else c.conv_size,
-                             a_base2k=c.key_base2k, res_size=size, res_base2k=c.base2k, rank_out=c.rank)
-            d_res = dev(c.a)
-            hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
-            shape = c.a.shape
-        else:
-            batch, size = len(c.want), c.size
-            p = GlweOpParams(rank=c.rank, dnum=rows, dsize=1, key_size=ksz, key_base2k=c.key_base2k, a_size=size, a_base2k=c.base2k, res_size=size,
-                             res_base2k=c.base2k, rank_out=c.rank)
-            shape = (batch, size, cols, n)
-            d_cts = [dev(c.a[j]) for j in c.indices]
-            d_res = dev(nbytes=int(np.prod(shape)) * 8)
-            nbytes = hip.glwe_pack_tmp_bytes(p, batch) if one_base else hip.glwe_pack_bases_tmp_bytes(p, c.conv_size, batch)
-            d_tmp = dev(nbytes=nbytes)
-            if one_base:
-                hip.glwe_pack_batched(d_res.ptr, c.indices, [d.ptr for d in d_cts], c.log_gap_out, gals, [k.ptr for k in d_keys], p, d_tmp.ptr,
-                                      nbytes, batch)
+        with on_device(hip, fuse=fuse):
+            hip.dispatch_notes(reset=True)
+            if c.op == "trace":
+                batch, size = c.a.shape[0], c.a.shape[1]
+                p = GlweOpParams(rank=c.rank, dnum=rows, dsize=1, key_size=ksz, key_base2k=c.key_base2k, a_size=size if one_base else c.conv_size,
+                                 a_base2k=c.key_base2k, res_size=size, res_base2k=c.base2k, rank_out=c.rank)
+                d_res = dev.upload(c.a)
+                hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
+                shape = c.a.shape
             else:
-                hip.glwe_pack_bases_batched(d_res.ptr, c.indices, [d.ptr for d in d_cts], c.log_gap_out, gals, [k.ptr for k in d_keys], p,
-                                            c.conv_size, d_tmp.ptr, nbytes, batch)
-        hip.sync()
-        got = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
-        notes = hip.dispatch_notes()
-    finally:
-        hip.set_fusion(True, True)
-        for d in bufs:
-            d.free()
+                batch, size = len(c.want), c.size
+                p = GlweOpParams(rank=c.rank, dnum=rows, dsize=1, key_size=ksz, key_base2k=c.key_base2k, a_size=size, a_base2k=c.base2k, res_size=size,
+                                 res_base2k=c.base2k, rank_out=c.rank)
+                shape = (batch, size, cols, n)
+                d_cts = [dev.upload(c.a[j]) for j in c.indices]
+                d_res = dev.alloc(int(np.prod(shape)) * 8)
+                nbytes = hip.glwe_pack_tmp_bytes(p, batch) if one_base else hip.glwe_pack_bases_tmp_bytes(p, c.conv_size, batch)
+                d_tmp = dev.alloc(nbytes)
+                if one_base:
+                    hip.glwe_pack_batched(d_res.ptr, c.indices, [d.ptr for d in d_cts], c.log_gap_out, gals, [k.ptr for k in d_keys], p, d_tmp.ptr,
+                                          nbytes, batch)
+                else:
+                    hip.glwe_pack_bases_batched(d_res.ptr, c.indices, [d.ptr for d in d_cts], c.log_gap_out, gals, [k.ptr for k in d_keys], p,
+                                                c.conv_size, d_tmp.ptr, nbytes, batch)
+            hip.sync()
+            got = d_res.download(np.int64, int(np.prod(shape))).reshape(shape)
+            notes = hip.dispatch_notes()
     return got, notes
 
 

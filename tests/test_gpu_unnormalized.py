@@ -17,6 +17,7 @@ import pytest
 
 from poulpy_amd.layouts import MatZnx, VecZnx
 from tests import unnormalized as un
+from tests.device import mods, on_device, prepared_key  # noqa: F401
 from tests.helpers import seeded
 from tests.test_gpu_cnv import _run_mul_relinearize, _run_relinearize, _run_tensor
 from tests.test_gpu_mul_plain import _run_const, _run_plain
@@ -28,19 +29,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 pytestmark = pytest.mark.gpu
 
 STRUCTURED_MARGIN_MAX = 0.25
-
-
-@pytest.fixture(scope="module")
-def mods():
-    from oracle.ref import RefModule
-    from poulpy_amd.hal import Module
-    cache = {}
-
-    def get(n):
-        if n not in cache:
-            cache[n] = (RefModule(n), Module(n))
-        return cache[n]
-    return get
 
 
 def _check_margins(label, gpu_margin, oracle_margin):
@@ -102,8 +90,7 @@ def test_external_product_and_keyswitch_on_unnormalized_input(mods, shape, ks):
     variants = _variants(base2k, smax, 2, batch)
     fuse = (False, False) if knob == "unfused" else (True, True)
     case = 0
-    try:
-        hip.set_small_path(knob != "small-off")
+    with on_device(hip, small_path=knob != "small-off"):
         for j, (rank, dsize) in enumerate(((1, 1), (2, 1), (1, 2), (2, 2))):
             # rank 1, dsize 1: every input variant (N = 2^16: every third); the other pairs: every third one, in turn
             for i in (range(len(variants)) if j == 0 and n < 65536 else range(j % 3, len(variants), 3)):
@@ -129,8 +116,6 @@ def test_external_product_and_keyswitch_on_unnormalized_input(mods, shape, ks):
                         exact = _exact_glwe(ks, out["a"][b], out["mat"], base2k, limbs)
                         assert np.array_equal(want[b], exact), (label, b, "oracle != exact")
                     print(f"[exact] {label}: gpu == oracle == exact product")
-    finally:
-        hip.set_small_path(True)
 
 
 @pytest.mark.parametrize("mode", ["automorphism", "add", "sub", "sub_negate"])
@@ -162,37 +147,30 @@ def _run_trace(hip, ref, n, rank, size, k, nsteps, batch, seed, fill, chunk=0):
     rng = seeded(seed)
     cols, dnum, key_size = rank + 1, size, size
     gals = [-1] + [pow(5, 1 << i, 2 * n) for i in range(nsteps - 1)]
-    prs, d_keys = [], []
-    for _ in gals:
-        mat = MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng)
-        pr, ph = ref.vmp_pmat_alloc(dnum, rank, cols, key_size), hip.vmp_pmat_alloc(dnum, rank, cols, key_size)
-        ref.vmp_prepare(pr, mat)
-        hip.vmp_prepare(ph, mat)
-        prs.append(pr)
-        d_keys.append(hip.device_alloc(ph.data.nbytes).upload(ph.data))
-    cts = np.empty((batch, size, cols, n), dtype=np.int64)
-    want = np.empty_like(cts)
-    oracle_margin = 0.0
-    for b in range(batch):
-        ct = VecZnx(n, cols, size).fill_uniform(k, rng)
-        fill(b, ct.data, rng)
-        cts[b] = ct.data
-        oracle_margin = max(oracle_margin, ref.rounding_margin_of(lambda: ref.glwe_trace_assign(ct, k, gals, prs)))
-        want[b] = ct.data
-    p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size, res_base2k=k,
-                     rank_out=rank)
-    d_res = hip.device_alloc(cts.nbytes).upload(cts)
-    hip.set_chunk(chunk)
-    try:
-        hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
-        hip.sync()
-        got = d_res.download(np.int64, want.size).reshape(want.shape)
-        d_res.upload(cts)
-        gpu_margin = hip.rounding_margin_of(lambda: hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch))
-    finally:
-        hip.set_chunk(0)
-    for d in d_keys + [d_res]:
-        d.free()
+    with on_device(hip) as dev:
+        prs, d_keys = [], []
+        for _ in gals:
+            pr, ph = prepared_key(ref, hip, MatZnx(n, dnum, rank, cols, key_size).fill_uniform(k, rng))
+            prs.append(pr)
+            d_keys.append(dev.key(ph))
+        cts = np.empty((batch, size, cols, n), dtype=np.int64)
+        want = np.empty_like(cts)
+        oracle_margin = 0.0
+        for b in range(batch):
+            ct = VecZnx(n, cols, size).fill_uniform(k, rng)
+            fill(b, ct.data, rng)
+            cts[b] = ct.data
+            oracle_margin = max(oracle_margin, ref.rounding_margin_of(lambda: ref.glwe_trace_assign(ct, k, gals, prs)))
+            want[b] = ct.data
+        p = GlweOpParams(rank=rank, dnum=dnum, dsize=1, key_size=key_size, key_base2k=k, a_size=size, a_base2k=k, res_size=size, res_base2k=k,
+                         rank_out=rank)
+        d_res = dev.upload(cts)
+        with on_device(hip, chunk=chunk):
+            hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch)
+            hip.sync()
+            got = d_res.download(np.int64, want.size).reshape(want.shape)
+            d_res.upload(cts)
+            gpu_margin = hip.rounding_margin_of(lambda: hip.glwe_trace_batched(d_res.ptr, gals, [d.ptr for d in d_keys], p, batch))
     return got, want, gpu_margin, oracle_margin
 
 
@@ -323,13 +301,12 @@ def test_mod_switch_2n_on_full_range_limbs(mods, negate):
         batch, n_lwe = 5, 101
         lwe = un.full_range(rng, (batch, size, n_lwe + 1))
         want = np.stack([ref.mod_switch_2n(n2, lwe[b], base2k, negate) for b in range(batch)])
-        d_l = hip.device_alloc(lwe.nbytes).upload(lwe)
-        d_r = hip.device_alloc(want.nbytes)
-        hip.lwe_mod_switch_2n_batched(d_r.ptr, d_l.ptr, n_lwe, size, base2k, n2, negate, batch)
-        hip.sync()
-        got = d_r.download(np.int64, want.size).reshape(want.shape)
-        d_l.free()
-        d_r.free()
+        with on_device(hip) as dev:
+            d_l = dev.upload(lwe)
+            d_r = dev.alloc(want.nbytes, poison=False)
+            hip.lwe_mod_switch_2n_batched(d_r.ptr, d_l.ptr, n_lwe, size, base2k, n2, negate, batch)
+            hip.sync()
+            got = d_r.download(np.int64, want.size).reshape(want.shape)
         assert np.array_equal(got, want), (n2, base2k, size, negate)
 
 
@@ -340,14 +317,13 @@ def test_sample_extract_on_full_range_limbs(mods, n, n_lwe):
     for cols, a_size, res_size, batch in ((2, 3, 3, 5), (3, 2, 4, 2)):
         a = un.full_range(rng, (batch, a_size, cols, n))
         want = np.stack([ref.lwe_sample_extract(n_lwe, res_size, VecZnx(n, cols, a_size, a[b].copy())) for b in range(batch)])
-        d_a = hip.device_alloc(a.nbytes).upload(a)
-        d_r = hip.device_alloc(want.nbytes)
-        hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
-        hip.lwe_sample_extract_batched(d_r.ptr, n_lwe, res_size, d_a.ptr, cols, a_size, batch)
-        hip.sync()
-        got = d_r.download(np.int64, want.size).reshape(want.shape)
-        d_a.free()
-        d_r.free()
+        with on_device(hip) as dev:
+            d_a = dev.upload(a)
+            d_r = dev.alloc(want.nbytes, poison=False)
+            hip.lib.pz_memset_d(hip.handle, d_r.ptr, 0x33, want.nbytes)
+            hip.lwe_sample_extract_batched(d_r.ptr, n_lwe, res_size, d_a.ptr, cols, a_size, batch)
+            hip.sync()
+            got = d_r.download(np.int64, want.size).reshape(want.shape)
         assert np.array_equal(got, want), (n, cols, a_size, res_size)
 
 
