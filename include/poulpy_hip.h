@@ -353,6 +353,48 @@ size_t pz_glwe_pack_bases_tmp_bytes(const pz_module* m, const pz_glwe_op_params*
 int pz_glwe_pack_bases_batched(pz_module* m, int64_t* res, size_t nslots, const uint64_t* indices, int64_t* const* cts,
                                size_t log_gap_out, const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p,
                                size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch);
+/* CMUX, the gate of poulpy-bin-fhe's bdd_arithmetic (poulpy-bin-fhe/src/bdd_arithmetic/eval.rs:524-626), on `batch` ciphertexts sharing
+ * one prepared GGSW:   res = normalize((t - f) (x) GGSW(bit) + f)   - res = t when bit = 1, f when bit = 0.
+ *   D[l]  = t[l] - f[l] on the p->a_size limbs of the difference container, missing limbs of either side zero, NOT normalized
+ *           (glwe_sub / glwe_sub_assign, poulpy-core/src/api/operations.rs:330-394)
+ *   big   = glwe_external_product_internal(D, ggsw)   (external_product/glwe.rs:197-271; key_size limbs, any dsize >= 1)
+ *   big  += f on every column, min(key_size, f_size) limbs (vec_znx_big_add_small_assign), IN FRONT of the carry chain - which is why the
+ *           gate is not pz_glwe_external_product_batched followed by an addition
+ *   res   = vec_znx_big_normalize(big) on every column
+ * The three forms of the reference are this call with different aliasing:
+ *   cmux            (eval.rs:550-572)  t, f, res distinct                      p->a_size = res_size (the difference is written into res)
+ *   cmux_assign     (:606-625)         res == t, f = a                         p->a_size = res_size
+ *   cmux_assign_neg (:575-603)         res == f, t = a                         p->a_size = ceil(max(res.k, a.k) / base2k)
+ * p: rank, the GGSW (dnum, dsize, key_size, key_base2k), a_size = limbs of D, res_size; t, f, res and the GGSW share ONE base2k
+ * (external_product/glwe.rs:213): anything else is PZ_ERR_INVALID, nothing launched.  t_size / f_size: limbs of t and of f.
+ * res == t and res == f (equal layouts) are allowed: every ciphertext is consumed before its result is written.  Any other overlap of
+ * res with t or f: PZ_ERR_ALIAS.
+ * Rotated source: t == NULL means t = X^{t_rot} f (negacyclic, t_rot taken mod 2N and read in this form only; t_size == f_size) - glwe_rotate followed by cmux_assign,
+ * one step of glwe_blind_rotation_assign (bdd_arithmetic/blind_rotation.rs:225-232); res must not overlap f then (PZ_ERR_ALIAS).
+ * t, f, res: device pointers; the prepared GGSW resolves as for every GLWE call (pinned, host with a device mirror, device).
+ * N = 1024 / 2048 / 4096 on the small-ring kernels form the difference inside the forward stage (D never reaches memory); every other
+ * shape writes D to the module's second workspace first (POULPY_DBG_CMUX_FUSED=0 sends every shape that way). */
+int pz_glwe_cmux_batched(pz_module* m, int64_t* res, const int64_t* t, size_t t_size, int64_t t_rot, const int64_t* f, size_t f_size,
+                         const double* ggsw_pmat, const pz_glwe_op_params* p, size_t batch);
+/* what the call reserves in the module's grow-only workspace: the external product's figure with a_size = limbs of D.  NOT counted: on the
+ * materialised route (N >= 8192, N < 1024, dsize > 1, N = 4096 with the small path off, POULPY_DBG_CMUX_FUSED=0) D itself goes to the module's
+ * second grow-only workspace, batch * N * (rank + 1) * a_size * 8 bytes - for the WHOLE batch, not per wave of ciphertexts */
+size_t pz_glwe_cmux_workspace_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t batch);
+/* GLWEBlindRotation::glwe_blind_rotation / _assign (poulpy-bin-fhe/src/bdd_arithmetic/blind_rotation.rs:196-264) on `batch` ciphertexts:
+ *   res = a X^{+-((k >> bit_rsh) mod 2^bit_mask) << bit_lsh}   by nbits = bit_mask CMUX steps; step i is the rotated-source CMUX by
+ * +-2^(i + bit_lsh) (sign != 0: +) with the GGSW of bit i + bit_rsh.  The steps ping-pong between res and tmp (:218-236); in place an odd
+ * step count ends with a copy into res (:238-241); out of place with one layout for a and res, step 0 reads a itself and the last step lands
+ * in res.  Bit-identical to nbits calls of pz_glwe_cmux_batched.
+ *   bits   HOST array of nbits device pointers to prepared GGSWs: bits[i] = the GGSW of bit i + bit_rsh (the caller resolves get_bit, as it
+ *          resolves the keys of pz_glwe_trace_batched)
+ *   p      rank, the GGSWs' layout, a_size = limbs of a, res_size; one base2k.  Every step works on the layout of res
+ *   tmp    device scratch of pz_glwe_blind_rotation_tmp_bytes (one batch in the layout of res)
+ * res == a (equal layouts) is glwe_blind_rotation_assign; nbits == 0 copies a.  ggsw_blind_rotation / _assign (:45-106) is the same call
+ * on the dnum (rank + 1) GLWE entries of `count` contiguous GGSWs (MatZnx layout: the entries are contiguous): batch = count dnum (rank + 1).
+ * A call repeated with the same arguments is replayed as one HIP graph (pz_module_set_graphs). */
+size_t pz_glwe_blind_rotation_tmp_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t batch);
+int pz_glwe_blind_rotation_batched(pz_module* m, int64_t* res, const int64_t* a, size_t nbits, const double* const* bits, int sign,
+                                   size_t bit_lsh, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
 /* CoreImpl ggsw_external_product (poulpy-core/src/external_product/ggsw.rs:54-58): res[row][col] = a[row][col] (x) ggsw
  * for the a_dnum * (rank+1) GLWE entries of the GGSW `a` (MatZnx layout: entries are contiguous), device pointers. */
 int pz_ggsw_external_product(pz_module* m, int64_t* res, const int64_t* a, size_t a_dnum, const double* ggsw_pmat,

@@ -160,6 +160,19 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
     size_t glwe_automorphism_many_workspace_bytes(const pz_glwe_op_params& p, size_t nrot, size_t batch) const {
         return pz_glwe_automorphism_many_workspace_bytes(m_, &p, nrot, batch);
     }
+    // CMUX (bdd_arithmetic/eval.rs:524-626): res = normalize((t - f) (x) ggsw + f); p.a_size = limbs of the difference; res may be t or f.
+    // t == nullptr: t = X^t_rot f (one step of glwe_blind_rotation_assign), t_size == f_size
+    void glwe_cmux_batched(int64_t* res, const int64_t* t, size_t t_size, int64_t t_rot, const int64_t* f, size_t f_size, const double* ggsw,
+                           const pz_glwe_op_params& p, size_t batch) {
+        check(pz_glwe_cmux_batched(m_, res, t, t_size, t_rot, f, f_size, ggsw, &p, batch), "glwe_cmux_batched");
+    }
+    size_t glwe_cmux_workspace_bytes(const pz_glwe_op_params& p, size_t batch) const { return pz_glwe_cmux_workspace_bytes(m_, &p, batch); }
+    // glwe_blind_rotation / _assign (bdd_arithmetic/blind_rotation.rs:196-264): bits = nbits host entries, the prepared GGSW of bit i + bit_rsh each
+    size_t glwe_blind_rotation_tmp_bytes(const pz_glwe_op_params& p, size_t batch) const { return pz_glwe_blind_rotation_tmp_bytes(m_, &p, batch); }
+    void glwe_blind_rotation_batched(int64_t* res, const int64_t* a, size_t nbits, const double* const* bits, bool sign, size_t bit_lsh,
+                                     const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_glwe_blind_rotation_batched(m_, res, a, nbits, bits, sign ? 1 : 0, bit_lsh, &p, tmp, tmp_bytes, batch), "glwe_blind_rotation_batched");
+    }
     void blind_rotation_execute_batched(int64_t* res, const int64_t* lwe_2n, const int64_t* lut, const double* brk, const pz_blind_rotation_params& p, size_t batch) {
         check(pz_blind_rotation_execute_batched(m_, res, lwe_2n, lut, brk, &p, batch), "blind_rotation_execute_batched");
     }

@@ -201,6 +201,13 @@ struct GlweCall {
     bool keyauto = false;
     unsigned ka_p = 0;
     KeyPerm ka_perm;
+    // CMUX (glwe_cmux below; eval.rs:565-571): every column of `add` - add_size limbs, add_bs elements between ciphertexts - joins the big value in
+    // front of the carry chain (vec_znx_big_add_small_assign on every column).  diff != null, the fused routes: `a` = t - f is not in memory, the
+    // small-ring forward stage forms it from the two sources (SmallDiff; its maps address the whole call, wave_diff moves them to a wave)
+    const int64_t* add = nullptr;
+    long long add_bs = 0;
+    int add_size = 0;
+    const SmallDiff* diff = nullptr;
     int cols_in() const { return s.cols_in; }
     int64_t* res_at(size_t b0) const { return res + (long long)b0 * res_bs; }
 };
@@ -228,6 +235,7 @@ size_t pz_glwe_op_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p
 // ------------------------------------------------------------------------------
 // the wave's input in the key's base: `a` itself, or glwe_normalize into a_conv (external_product/glwe.rs:124-132)
 static int wave_input(const GlweCall& c, size_t b0, int nb, int64_t* a_conv, DV* av) {
+    if (c.diff) { *av = DV{nullptr, c.a_bs, c.s.cols_a, (int)c.p->a_size}; return PZ_OK; }   // (CMUX, fused routes: the forward stage reads c.diff)
     *av = DV{(void*)(c.a + (long long)b0 * c.a_bs), c.a_bs, c.s.cols_a, (int)c.p->a_size};
     if (!c.s.convert) return PZ_OK;
     DV cv{a_conv, c.n * c.s.cols_a * c.s.a_size_eff, c.s.cols_a, c.s.a_size_eff};
@@ -272,8 +280,17 @@ static SmallKey small_key(const GlweCall& c, const cplx* Pp) { return SmallKey{P
 static SmallRes small_res(const GlweCall& c, size_t b0) {
     return SmallRes{(long long*)c.res_at(b0), c.res_bs, c.s.cols_out, (int)c.p->res_size, (int)c.p->res_base2k};
 }
-static SmallOperand small_operand(const GlweCall& c, const DV& av) {
+static SmallOperand small_operand(const GlweCall& c, const DV& av, size_t b0) {
+    if (c.add) return SmallOperand{(const long long*)(c.add + (long long)b0 * c.add_bs), c.add_bs, c.s.cols_out, c.add_size, -1};   // CMUX: + f on every column
     return SmallOperand{c.ks ? (const long long*)av.p : nullptr, av.bs, c.s.cols_a, av.size, c.body_col};
+}
+// CMUX: the wave's part of the every-column operand f, and of the two sources of the fused forward stage
+static DV wave_add(const GlweCall& c, size_t b0) { return DV{(void*)(c.add + (long long)b0 * c.add_bs), c.add_bs, c.s.cols_out, c.add_size}; }
+static SmallDiff wave_diff(const GlweCall& c, size_t b0) {
+    SmallDiff d = *c.diff;
+    if (d.t) d.t += (long long)b0 * d.tmap.sb;
+    d.f += (long long)b0 * d.fmap.sb;
+    return d;
 }
 // ... and the automorphism form of the inverse kernel, with glwe_trace's shifted store where asked for
 static void small_inv_auto(SmallInvCall& sc, const GlweCall& c, bool rsh) {
@@ -338,15 +355,20 @@ static int fused_carve(const GlweCall& c, FusedBufs* f) {
 // limbs, BASELINE configs[1] - beats the two-kernel form, 3.25 vs 3.16 M/s, profiles/r03_ab_small_vs_pipeline.txt)
 static bool n4096_two_kernel(const GlweCall& c) {
     const pz_module* M = c.M;
-    const bool mid8 = !c.ks && !c.au && c.npi == 8 && c.npo == 8 && std::min(c.nrows, c.npi) == 8;
+    // (CMUX at that shape stays on the two kernels: their forward stage forms the difference itself, where the pipeline needs it written out first
+    //  and its tail takes the every-column operand - 2.51 against 2.05 M gates / s at batch 4096, profiles/cmux_lines.txt)
+    const bool mid8 = !c.ks && !c.au && !c.add && c.npi == 8 && c.npo == 8 && std::min(c.nrows, c.npi) == 8;
     return M->small_path && (!c.au || (c.ks && !c.lay)) && !c.tensor && !c.digits && !c.cross_out &&
            M->dbg_stages == 7 && small_supported(M, c.npi, c.ksz) && !mid8;
 }
 static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av, const PolyMap& sm) {
     const bool rsh = c.want_rsh && c.au && c.au->mode != 0 && c.p->res_base2k <= 29;
-    PZ_TRY(launch_small_fwd(c.M, nb * c.npi, (const long long*)av.p, sm, f.T));
+    if (c.diff) {
+        dispatch_note(c.M, "cmux: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)");
+        PZ_TRY(launch_small_fwd_diff(c.M, nb * c.npi, wave_diff(c, b0), f.T));
+    } else PZ_TRY(launch_small_fwd(c.M, nb * c.npi, (const long long*)av.p, sm, f.T));
     SmallInvCall sc;
-    sc.S = f.T; sc.key = small_key(c, f.Pp); sc.res = small_res(c, b0); sc.small = small_operand(c, av);
+    sc.S = f.T; sc.key = small_key(c, f.Pp); sc.res = small_res(c, b0); sc.small = small_operand(c, av, b0);
     small_inv_auto(sc, c, rsh);
     PZ_TRY(launch_small_inv(c.M, nb, sc));
     if (rsh) *c.post_rsh = true;
@@ -461,6 +483,7 @@ static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int
         TailCall t = wave_tail(c, nb, f.T2, b0);
         if (c.au) { t.res = (long long*)f.res_tmp; t.res_bs = c.res_ct; }
         if (c.ks) tail_operand(t, av, c.au_big || c.tensor);
+        else if (c.add) tail_operand(t, wave_add(c, b0), true);   // CMUX: + f on every column
         if (c.a16) { t.small16 = c.a16 + (long long)b0 * av.size * c.n; t.small16_cs = c.a16_cs; t.small_bs = 0; }
         if (c.au_big) { t.auto_mul = c.au_p; t.gather_mul = c.au_p; t.gather_neg = c.au->mode != 1; }
         t.auto_neg = c.au && c.au->mode == 3;
@@ -561,13 +584,18 @@ static int glwe_small_ring(const GlweCall& c) {
         PZ_TRY(wave_input(c, b0, nb, a_conv, &av));
         PolyMap sm{av.size, c.s.cols_in, av.bs, (long long)av.cols * c.n, c.n, c.n * c.s.a_col0};
         const SmallKey key = small_key(c, Pp);
-        const SmallOperand body = small_operand(c, av);
+        const SmallOperand body = small_operand(c, av, b0);
+        const SmallDiff wd = c.diff ? wave_diff(c, b0) : SmallDiff{};
         // plain product / key switch of a rank-1 ciphertext: one kernel, the spectra never leave the CU (round 6, device_small_one.hpp)
         if (!c.au && !c.cross_out && small_one_supported(M, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, nb)) {
-            PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body}));
+            if (c.diff) dispatch_note(M, "cmux: fused small-one (k_small_one<.., difference>)");
+            PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body, c.diff ? &wd : nullptr}));
             continue;
         }
-        PZ_TRY(launch_small_fwd(M, nb * c.npi, (const long long*)av.p, sm, S));
+        if (c.diff) {
+            dispatch_note(M, "cmux: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)");
+            PZ_TRY(launch_small_fwd_diff(M, nb * c.npi, wd, S));
+        } else PZ_TRY(launch_small_fwd(M, nb * c.npi, (const long long*)av.p, sm, S));
         SmallInvCall sc;
         sc.S = S; sc.key = key; sc.res = small_res(c, b0); sc.small = body;
         if (c.cross_out) {
@@ -699,6 +727,7 @@ static int glwe_unfused(const GlweCall& c) {
             t.res = (long long*)rv.p; t.res_bs = rv.bs; t.res_cols = rv.cols; t.res_size = rv.size; t.base2k = (int)c.p->res_base2k;
             t.body_col = c.body_col;
             if (c.ks) tail_operand(t, c.tensor ? raw_av : av, c.tensor);
+            else if (c.add) tail_operand(t, wave_add(c, b0), true);
             PZ_TRY(launch_inv_tail(M, t));
         } else {
             PZ_TRY(dev_idft(M, nb, rb, 0, rb, 0, c.s.cols_out, res_dft_size, u.T));
@@ -708,6 +737,11 @@ static int glwe_unfused(const GlweCall& c) {
                 for (int col = 0; col < c.s.cols_out; ++col)
                     PZ_TRY(launch_ew(M, EW_ADD_I64, u.res_dft + (long long)col * n, rb.bs, big_ls, u.res_dft + (long long)col * n, rb.bs, big_ls,
                                      (const int64_t*)sv.p + (long long)col * n, sv.bs, (long long)sv.cols * n, std::min(res_dft_size, sv.size), nb));
+            } else if (c.add) {  // CMUX, eval.rs:568-569: + f[col] on every column
+                const DV fv = wave_add(c, b0);
+                for (int col = 0; col < c.s.cols_out; ++col)
+                    PZ_TRY(launch_ew(M, EW_ADD_I64, u.res_dft + (long long)col * n, rb.bs, big_ls, u.res_dft + (long long)col * n, rb.bs, big_ls,
+                                     (const int64_t*)fv.p + (long long)col * n, fv.bs, (long long)fv.cols * n, std::min(res_dft_size, fv.size), nb));
             } else if (c.ks) {  // body column added after the inverse transform (keyswitching/glwe.rs:237)
                 PZ_TRY(launch_ew(M, EW_ADD_I64, u.res_dft + (long long)c.body_col * n, rb.bs, big_ls, u.res_dft + (long long)c.body_col * n, rb.bs,
                                  big_ls, av.p, av.bs, (long long)av.cols * n, std::min(res_dft_size, av.size), nb));
@@ -1023,6 +1057,201 @@ int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64
     for (size_t s = 0; s < nsteps && gals && key_pmats; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
     graph_key_module(M, k);
     return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch); });
+}
+}  // extern "C"
+
+// ------------------------------------------------------------------------------
+// CMUX, the gate of poulpy-bin-fhe's bdd_arithmetic (eval.rs:524-626): res = normalize((t - f) (x) GGSW + f), f added to the big
+// value on every column BEFORE the carry chain - which is why the gate is not an external product followed by an addition.  Routes:
+//   fused         N = 1024 / 2048 / 4096 on the small-ring kernels: the forward stage reads t and f (or f twice through the monomial map of
+//                 X^rot) and forms the difference in registers; the inverse stage adds f as its every-column operand
+//   materialised  every other shape the external product serves: D = t - f written to the second workspace by the element-wise / rotate kernels,
+//                 then the shape's pipeline on D with f as the tail's every-column operand.  POULPY_DBG_CMUX_FUSED=0 sends every shape here.
+// In place (res == t, res == f): every kernel that reads t or f of a ciphertext runs before the one that writes its result, and the inverse
+// stages read f at the positions they then write - as for the automorphism family's add forms.
+// ------------------------------------------------------------------------------
+struct CmuxOperands { uint64_t t_size, f_size; int64_t t_rot; };   // limbs of t and of f; t null: t = X^t_rot f
+struct CmuxShape {
+    long long cols, t_ct, f_ct, d_ct, res_ct;   // i64 elements of one ciphertext of t / f / D / res
+    size_t t_bytes, f_bytes, res_bytes;         // bytes of the whole batch
+};
+static CmuxShape cmux_shape(const pz_module* M, const pz_glwe_op_params* p, const CmuxOperands* o, size_t batch) {
+    CmuxShape s;
+    const long long n = (long long)M->n;
+    s.cols = (long long)p->rank + 1;
+    s.t_ct = n * s.cols * (long long)o->t_size; s.f_ct = n * s.cols * (long long)o->f_size;
+    s.d_ct = n * s.cols * (long long)p->a_size; s.res_ct = n * s.cols * (long long)p->res_size;
+    s.t_bytes = batch * (size_t)s.t_ct * 8; s.f_bytes = batch * (size_t)s.f_ct * 8; s.res_bytes = batch * (size_t)s.res_ct * 8;
+    return s;
+}
+// the argument checks that need no module (nothing is launched when one fails)
+static int cmux_check_args(const int64_t* res, const int64_t* t, const int64_t* f, const double* pmat, const pz_glwe_op_params* p,
+                           const CmuxOperands* o) {
+    PZ_REQUIRE(p != nullptr, "glwe_cmux: null params");
+    PZ_REQUIRE(res != nullptr && f != nullptr && pmat != nullptr, "glwe_cmux: null argument");
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1 && o->f_size >= 1, "glwe_cmux: empty shape");
+    // external_product/glwe.rs:213 (and glwe_sub, operations.rs:343-344): t, f, res and the GGSW share one base2k
+    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_cmux: t, f, res and the GGSW share one base2k (%llu / %llu / %llu)",
+               (unsigned long long)p->a_base2k, (unsigned long long)p->res_base2k, (unsigned long long)p->key_base2k);
+    if (t == nullptr) {
+        PZ_REQUIRE(o->t_size == o->f_size, "glwe_cmux: the rotated source t = X^t_rot f has the layout of f (t_size == f_size)");
+        if ((const void*)res == (const void*)f) return fail(PZ_ERR_ALIAS, "glwe_cmux: with the rotated source res must not overlap f");
+    } else {
+        PZ_REQUIRE(o->t_size >= 1, "glwe_cmux: empty shape");
+        if ((const void*)res == (const void*)t) PZ_REQUIRE(p->res_size == o->t_size, "in-place call with different layouts for t and res");
+    }
+    if ((const void*)res == (const void*)f && t != nullptr) PZ_REQUIRE(p->res_size == o->f_size, "in-place call with different layouts for f and res");
+    return PZ_OK;
+}
+static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+// the checks that need the ring degree: res may BE t or f (the assign forms), any other overlap is refused
+static int cmux_check_overlap(const CmuxShape& s, const int64_t* res, const int64_t* t, const int64_t* f) {
+    if (t != nullptr && (const void*)res != (const void*)t && ranges_overlap(res, s.res_bytes, t, s.t_bytes))
+        return fail(PZ_ERR_ALIAS, "glwe_cmux: res overlaps t without being t");
+    if (((const void*)res != (const void*)f || t == nullptr) && ranges_overlap(res, s.res_bytes, f, s.f_bytes))
+        return fail(PZ_ERR_ALIAS, t ? "glwe_cmux: res overlaps f without being f" : "glwe_cmux: with the rotated source res must not overlap f");
+    return PZ_OK;
+}
+// which pipeline serves the product of a CMUX, and whether its forward stage can take the two sources
+static bool cmux_fused_route(const GlweCall& c) {
+    if (fused_applies(c.M, c.p, c.s, c.kind)) return n4096_two_kernel(c);
+    return small_ring_applies(c.M, c.p, c.s, c.kind, true);
+}
+// D = t - f (t null: X^rot f - f) on the limbs of D, missing limbs of either side zero (vec_znx_sub, sub.rs:6-58; vec_znx_sub_assign :60-84)
+static int cmux_materialise(pz_module* M, int64_t* D, const CmuxShape& s, const int64_t* t, const int64_t* f, const pz_glwe_op_params* p,
+                            const CmuxOperands* o, size_t batch) {
+    const long long n = (long long)M->n;
+    const int cols = (int)s.cols, B = (int)batch, d_size = (int)p->a_size;
+    const int f_sz = std::min((int)o->f_size, d_size), t_sz = t ? std::min((int)o->t_size, d_size) : f_sz;
+    const int common = std::min(t_sz, f_sz), top = std::max(t_sz, f_sz);
+    auto limb = [&](const int64_t* v, int l) { return v + (long long)l * cols * n; };
+    if (t == nullptr) {   // glwe_rotate + glwe_sub_assign in one pass (k_rotate mode 1)
+        PolyMap sm{common * cols, 1, s.f_ct, n, 0, 0}, dm{common * cols, 1, s.d_ct, n, 0, 0};
+        PZ_TRY(launch_rotate(M, B * common * cols, (const long long*)f, sm, (long long*)D, dm, 1, B * common * cols, nullptr, 0, 0, (long long)o->t_rot));
+    } else {
+        PZ_TRY(launch_ew(M, EW_SUB_I64, D, s.d_ct, n, t, s.t_ct, n, f, s.f_ct, n, common * cols, B));
+        if (t_sz > common) PZ_TRY(launch_ew(M, EW_COPY, (void*)limb(D, common), s.d_ct, n, limb(t, common), s.t_ct, n, nullptr, 0, 0, (t_sz - common) * cols, B));
+        else if (f_sz > common) PZ_TRY(launch_ew(M, EW_NEG_I64, (void*)limb(D, common), s.d_ct, n, limb(f, common), s.f_ct, n, nullptr, 0, 0, (f_sz - common) * cols, B));
+    }
+    return launch_ew(M, EW_ZERO, (void*)limb(D, top), s.d_ct, n, nullptr, 0, 0, nullptr, 0, 0, (d_size - top) * cols, B);
+}
+// device pointers, the key resolved, the module lock held (pz_glwe_cmux_batched and the ladder of pz_glwe_blind_rotation_batched)
+static int glwe_cmux(pz_module* M, int64_t* res, const int64_t* t, const int64_t* f, const double* key, const pz_glwe_op_params* p,
+                     const CmuxOperands* o, size_t batch) {
+    GlweCall c;
+    PZ_TRY(glwe_call_init(c, M, GlweKind::ExternalProduct, res, f, key, p, batch, nullptr, nullptr, nullptr));   // (`a` is set below: D, or nothing)
+    if (batch == 0) return PZ_OK;
+    const CmuxShape s = cmux_shape(M, p, o, batch);
+    c.add = f; c.add_bs = s.f_ct; c.add_size = (int)o->f_size;
+    const bool pipeline = fused_applies(M, p, c.s, c.kind), small_ring = !pipeline && small_ring_applies(M, p, c.s, c.kind, true);
+    const int knob = rt_knob("POULPY_DBG_CMUX_FUSED", 1);   // (read per call: tests flip it)
+    SmallDiff d;
+    if (knob != 0 && cmux_fused_route(c)) {
+        const long long n = c.n;
+        const int d_size = (int)p->a_size, cols = (int)s.cols;
+        d.t = (const long long*)t; d.f = (const long long*)f;
+        d.tmap = PolyMap{d_size, cols, s.t_ct, (long long)cols * n, n, 0};
+        d.fmap = PolyMap{d_size, cols, s.f_ct, (long long)cols * n, n, 0};
+        d.t_size = t ? (int)o->t_size : (int)o->f_size; d.f_size = (int)o->f_size;
+        d.rot = (unsigned)((unsigned long long)o->t_rot & (2ull * (unsigned long long)n - 1ull));
+        c.diff = &d; c.a = nullptr;
+        return pipeline ? glwe_fused(c) : glwe_small_ring(c);
+    }
+    dispatch_note(M, "cmux: materialised difference (%s)", knob == 0 ? "POULPY_DBG_CMUX_FUSED=0" : (pipeline ? "three-kernel pipeline" : (small_ring ? "small ring" : "five-kernel path")));
+    PZ_TRY(ws2_reserve(M, batch * (size_t)s.d_ct * 8));
+    int64_t* D = (int64_t*)M->ws2;
+    PZ_TRY(cmux_materialise(M, D, s, t, f, p, o, batch));
+    c.a = D;
+    if (pipeline) return glwe_fused(c);
+    if (small_ring) return glwe_small_ring(c);
+    return glwe_unfused(c);
+}
+
+extern "C" {
+size_t pz_glwe_cmux_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
+    // the external product's reservation (D has a_size limbs); the materialised route keeps D in the module's second workspace on top of it
+    return pz_glwe_op_workspace_bytes(M, p, batch, (int)GlweKind::ExternalProduct);
+}
+int pz_glwe_cmux_batched(pz_module* M, int64_t* res, const int64_t* t, size_t t_size, int64_t t_rot, const int64_t* f, size_t f_size,
+                         const double* ggsw_pmat, const pz_glwe_op_params* p, size_t batch) {
+    const CmuxOperands ops{t_size, f_size, t ? 0 : t_rot};
+    const CmuxOperands* o = &ops;
+    PZ_TRY(cmux_check_args(res, t, f, ggsw_pmat, p, o));
+    PZ_ENTER(M);
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(f) && (t == nullptr || is_device_ptr(t)), "batched entry points take device pointers");
+    PZ_TRY(cmux_check_overlap(cmux_shape(M, p, o, batch), res, t, f));
+    const size_t cols = p->rank + 1;
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, ggsw_pmat, (size_t)M->n * 8 * p->dnum * cols * cols * p->key_size, &key));
+    PZ_TRY(glwe_cmux(M, res, t, f, key, p, o, batch));
+    return finish_call(M, false);
+}
+
+// GLWEBlindRotation::glwe_blind_rotation / _assign (bdd_arithmetic/blind_rotation.rs:196-264) on `batch` ciphertexts: nbits rotated-source CMUX
+// steps that ping-pong between res and tmp (:218-236), the final copy when the step count is odd (:238-241)
+size_t pz_glwe_blind_rotation_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
+    if (!M || !p) return 0;
+    return batch * (size_t)M->n * 8 * (p->rank + 1) * p->res_size;
+}
+static int glwe_blind_rotation_steps(pz_module* M, int64_t* res, const int64_t* a, size_t nbits, const double* const* keys, int sign, size_t bit_lsh,
+                                     const pz_glwe_op_params* p, int64_t* tmp, size_t batch) {
+    const long long n = (long long)M->n;
+    const int cols = (int)p->rank + 1, B = (int)batch;
+    const long long res_ct = n * cols * (long long)p->res_size, a_ct = n * cols * (long long)p->a_size;
+    // glwe_copy (:262): the common limbs, zero beyond.  With one layout for a and res the copy only feeds step 0, which then reads `a` itself:
+    // the same digits, one pass over the batch less (res is first written by step 1, or by the final copy)
+    const int64_t* first = (p->a_size == p->res_size && nbits > 0) ? a : res;
+    if ((const void*)res != (const void*)a && first == res) {
+        const int mn = (int)std::min(p->a_size, p->res_size);
+        PZ_TRY(launch_ew(M, EW_COPY, res, res_ct, n, a, a_ct, n, nullptr, 0, 0, mn * cols, B));
+        PZ_TRY(launch_ew(M, EW_ZERO, res + (long long)mn * cols * n, res_ct, n, nullptr, 0, 0, nullptr, 0, 0, ((int)p->res_size - mn) * cols, B));
+    }
+    pz_glwe_op_params q = *p;
+    q.a_size = p->res_size;   // every step works on the layout of res (:212)
+    CmuxOperands o;
+    o.t_size = o.f_size = p->res_size;
+    int64_t *cur = res, *other = tmp;
+    if (first != res && (nbits & 1)) std::swap(cur, other);   // step 0 does not read res: an odd count starts INTO res and ends there, no final copy
+    for (size_t i = 0; i < nbits; ++i) {
+        const int64_t* src = i == 0 ? first : cur;
+        const size_t sh = i + bit_lsh;
+        const long long pw = sh < 62 ? (1ll << sh) : 0;   // (X^(2^sh) = 1 once 2^sh is a multiple of 2n)
+        o.t_rot = sign ? pw : -pw;   // :226-229
+        PZ_TRY(glwe_cmux(M, other, nullptr, src, keys[i], &q, &o, batch));   // :232, b <- (X^rot a - a) GGSW(bit) + a
+        std::swap(cur, other);
+    }
+    if (cur != res) PZ_TRY(launch_ew(M, EW_COPY, res, res_ct, n, tmp, res_ct, n, nullptr, 0, 0, (int)p->res_size * cols, B));   // :238-241
+    return PZ_OK;
+}
+int pz_glwe_blind_rotation_batched(pz_module* M, int64_t* res, const int64_t* a, size_t nbits, const double* const* bits, int sign, size_t bit_lsh,
+                                   const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_REQUIRE(p != nullptr, "null params");
+    PZ_REQUIRE(res != nullptr && a != nullptr && (nbits == 0 || bits != nullptr), "glwe_blind_rotation: null argument");
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_blind_rotation: a, res and the GGSWs share one base2k");
+    for (size_t i = 0; i < nbits; ++i) PZ_REQUIRE(bits[i] != nullptr, "glwe_blind_rotation: GGSW %zu is null", i);
+    if ((const void*)res == (const void*)a) PZ_REQUIRE(p->res_size == p->a_size, "in-place call with different layouts for a and res");
+    PZ_ENTER(M);
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a), "batched entry points take device pointers");
+    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
+    const size_t res_bytes = batch * n8 * cols * p->res_size, a_bytes = batch * n8 * cols * p->a_size;
+    if ((const void*)res != (const void*)a && ranges_overlap(res, res_bytes, a, a_bytes)) return fail(PZ_ERR_ALIAS, "glwe_blind_rotation: res overlaps a without being a");
+    if (nbits > 0 && batch > 0) {
+        PZ_REQUIRE(tmp != nullptr && is_device_ptr(tmp) && tmp_bytes >= pz_glwe_blind_rotation_tmp_bytes(M, p, batch), "glwe_blind_rotation: tmp too small (%zu bytes)", tmp_bytes);
+        if (ranges_overlap(tmp, res_bytes, res, res_bytes) || ranges_overlap(tmp, res_bytes, a, a_bytes)) return fail(PZ_ERR_ALIAS, "glwe_blind_rotation: tmp overlaps res or a");
+    }
+    std::vector<const double*> keys(nbits);
+    for (size_t i = 0; i < nbits; ++i) PZ_TRY(resolve_key(M, bits[i], n8 * p->dnum * cols * cols * p->key_size, &keys[i]));
+    if (batch == 0) return PZ_OK;
+    KeyHash k;
+    k.add((int)7); k.add(res); k.add(a); k.add(tmp); k.add(nbits); k.add(sign != 0); k.add(bit_lsh); k.add(batch); k.add(*p);
+    k.add(rt_knob("POULPY_DBG_CMUX_FUSED", 1));
+    for (size_t i = 0; i < nbits; ++i) k.add(keys[i]);
+    graph_key_module(M, k);
+    PZ_TRY(with_graph(M, k.h, [&]() { return glwe_blind_rotation_steps(M, res, a, nbits, keys.data(), sign, bit_lsh, p, (int64_t*)tmp, batch); }));
+    return finish_call(M, false);
 }
 }  // extern "C"
 

@@ -164,6 +164,17 @@ __device__ __forceinline__ long long map_off(const PolyMap& mp, int p) {
     return (long long)b * mp.sb + (long long)j * mp.sj + (long long)i * mp.si + mp.s0;
 }
 
+// CMUX (pz_glwe_cmux_batched, eval.rs:524-626): the polynomial that enters the forward transform is the difference D = t - f, formed in
+// registers from the two sources by the small-ring forward stages (device_small.hpp: small_diff_load) - D never exists in HBM.  Rotated
+// form (one step of glwe_blind_rotation_assign, blind_rotation.rs:225-232): t = X^rot f, read from f through the monomial's index and sign map.
+struct SmallDiff {
+    const long long* t;   // minuend; null: the rotated form
+    const long long* f;   // subtrahend
+    PolyMap tmap, fmap;   // polynomial p of the launch -> its limb of t / of f (nj limbs of D, ni columns)
+    int t_size, f_size;   // limbs beyond a source's size are zero (vec_znx_sub / vec_znx_sub_assign, sub.rs:6-112)
+    unsigned rot;         // rotated form, mod 2n: coefficient i of t is f[(i - rot) mod 2n], negated where that index is >= n
+};
+
 // Rust `(x).round() as i64`: half away from zero, saturating, NaN -> 0 (reim/conversion.rs:43-60).
 // Branch-free: round = trunc(x) +- 1 when the (exactly computed) fraction reaches one half.
 __device__ __forceinline__ double round_half_away(double x) {

@@ -31,6 +31,49 @@ constexpr int small_inv_rs(int m1, bool noprod) { return noprod ? kSmallRS + (m1
 #ifndef PZ_SMALL_PROBE
 #define PZ_SMALL_PROBE 1   // (A/B: -DPZ_SMALL_PROBE=0 compiles the run-time rounding-margin probe out of the small-ring kernels)
 #endif
+// the 2 M1 coefficients thread t of a polynomial owns in the forward column pass (i = j1 128 + t and m + i), as wrapping i64 differences.
+// SRC 1: t - f; 2: X^rot f - f.  Digits of D span one bit more than a normalized source (more on un-normalized input): they stay 64-bit
+// integers up to the conversion to f64, like every input of this kernel.
+template <int M1, int SRC>
+__device__ __forceinline__ void small_diff_load(const SmallDiff& d, int p, int t, long long (&re)[M1], long long (&im)[M1]) {
+    constexpr int M2 = 128;
+    constexpr unsigned m = (unsigned)M1 * M2, n = 2 * m;
+    const int limb = (p / d.fmap.ni) % d.fmap.nj;
+    const bool hf = limb < d.f_size, ht = SRC == 1 && limb < d.t_size;
+    const long long* fa = d.f + map_off(d.fmap, p);
+    unsigned long long fr[M1], fi[M1], tr[M1], ti[M1];
+#pragma unroll
+    for (int j1 = 0; j1 < M1; ++j1) { fr[j1] = fi[j1] = tr[j1] = ti[j1] = 0ull; }
+    if (hf) {
+#pragma unroll
+        for (int j1 = 0; j1 < M1; ++j1) {
+            fr[j1] = (unsigned long long)fa[j1 * M2 + t];
+            fi[j1] = (unsigned long long)fa[m + j1 * M2 + t];
+        }
+        if constexpr (SRC == 2) {
+#pragma unroll
+            for (int j1 = 0; j1 < M1; ++j1) {
+                const unsigned s0 = ((unsigned)(j1 * M2 + t) - d.rot) & (2 * n - 1), s1 = (m + (unsigned)(j1 * M2 + t) - d.rot) & (2 * n - 1);
+                const unsigned long long v0 = (unsigned long long)fa[s0 & (n - 1)], v1 = (unsigned long long)fa[s1 & (n - 1)];
+                tr[j1] = s0 >= n ? 0ull - v0 : v0;
+                ti[j1] = s1 >= n ? 0ull - v1 : v1;
+            }
+        }
+    }
+    if constexpr (SRC == 1) {
+        if (ht) {
+            const long long* ta = d.t + map_off(d.tmap, p);
+#pragma unroll
+            for (int j1 = 0; j1 < M1; ++j1) {
+                tr[j1] = (unsigned long long)ld_stream(ta + j1 * M2 + t);
+                ti[j1] = (unsigned long long)ld_stream(ta + m + j1 * M2 + t);
+            }
+        }
+    }
+#pragma unroll
+    for (int j1 = 0; j1 < M1; ++j1) { re[j1] = (long long)(tr[j1] - fr[j1]); im[j1] = (long long)(ti[j1] - fi[j1]); }
+}
+
 struct SmallFwdArgs {
     const long long* src;
     PolyMap smap;
@@ -46,10 +89,11 @@ struct SmallFwdArgs {
     int use_dmap;
     PolyMap dmap;
     const cplx* mul;
+    SmallDiff diff;      // SRC != 0: the two sources of the difference (src / smap are not read)
 };
 
-// 256 threads = 2 polynomials x 128 threads; LDS 2 x M1 rows x 144 points + wL2
-template <int M1>
+// 256 threads = 2 polynomials x 128 threads; LDS 2 x M1 rows x 144 points + wL2.  SRC: 0 the limbs of `src`, 1 / 2 the CMUX forms (SmallDiff)
+template <int M1, int SRC = 0>
 __global__ void __launch_bounds__(256, 2) k_small_fwd(SmallFwdArgs g) {
     constexpr int M2 = kSmallM2, RS = kSmallRS;
     constexpr long long m = (long long)M1 * kSmallM2;
@@ -59,15 +103,19 @@ __global__ void __launch_bounds__(256, 2) k_small_fwd(SmallFwdArgs g) {
     if (tid < M2) wl[tid] = g.wL2[tid];
     const int p = blockIdx.x * 2 + pl;
     const bool active = p < g.npolys;
-    const long long* a = g.src + map_off(g.smap, active ? p : g.npolys - 1);
     cplx* buf = lds + pl * M1 * RS;
     // ---- column pass: thread t owns column j2 = t, M1 points over j1 (k_fwd_pass1 with one radix-M1 butterfly)
     {
         long long re[M1], im[M1];
+        if constexpr (SRC == 0) {
+            const long long* a = g.src + map_off(g.smap, active ? p : g.npolys - 1);
 #pragma unroll
-        for (int j1 = 0; j1 < M1; ++j1) {
-            re[j1] = ld_stream(a + j1 * M2 + t);
-            im[j1] = ld_stream(a + m + j1 * M2 + t);
+            for (int j1 = 0; j1 < M1; ++j1) {
+                re[j1] = ld_stream(a + j1 * M2 + t);
+                im[j1] = ld_stream(a + m + j1 * M2 + t);
+            }
+        } else {
+            small_diff_load<M1, SRC>(g.diff, active ? p : g.npolys - 1, t, re, im);
         }
         cplx v[M1];
 #pragma unroll

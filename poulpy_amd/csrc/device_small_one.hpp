@@ -43,6 +43,7 @@ struct SmallOneArgs {
     const cplx* wL2;             // exp(2 pi i t / 128)
     const cplx* tw1inv;          // [M1] untwist with 1/m folded in
     unsigned long long* margin;  // rounding-margin probe (margin_note); null = off
+    SmallDiff diff;              // SRC != 0 (CMUX): the input polynomials are differences of two sources (device_small.hpp; src / smap are not read)
 };
 
 // (Measured and dropped, round 6: input groups of 4 polynomials through a 32-row tile at N = 2048 - 73.7 KiB, two workgroups per CU, the product's sums
@@ -51,7 +52,7 @@ struct SmallOneArgs {
 // (Also measured and dropped: the i64 loads of both column-pass sweeps requested before the first butterfly, and the key values of the product's first row
 //  requested in front of the forward row pass - N = 1024: 16.55 -> 16.5 M external products/s, key switch 20.7 -> 19.9 M/s, 2 limbs 30.9 -> 29.5 M/s; N = 2048
 //  7.9 -> 7.8 M/s: with two workgroups per CU the other workgroup already fills those waits, and the extra live registers cost; profiles/r06_ab_small_one.txt)
-template <int M1, int KS>
+template <int M1, int KS, int SRC = 0>
 __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneArgs g) {   // (waves per SIMD: two workgroups per CU at N = 1024, one at 2048)
     constexpr int NT = 512, M2 = kSmallM2, RS = kSmallRS, CO = 2, NPO = CO * KS, PP = M1 / 4;
     constexpr long long m = (long long)M1 * M2, n = 2 * m;
@@ -77,12 +78,16 @@ __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneAr
     {
         const int t = tid & 127;
         for (int p = tid >> 7; p < g.npi; p += NT / 128) {
-            const long long* a = g.src + map_off(g.smap, b * g.npi + p);
             long long re[M1], im[M1];
+            if constexpr (SRC == 0) {
+                const long long* a = g.src + map_off(g.smap, b * g.npi + p);
 #pragma unroll
-            for (int j1 = 0; j1 < M1; ++j1) {
-                re[j1] = ld_stream(a + j1 * M2 + t);
-                im[j1] = ld_stream(a + m + j1 * M2 + t);
+                for (int j1 = 0; j1 < M1; ++j1) {
+                    re[j1] = ld_stream(a + j1 * M2 + t);
+                    im[j1] = ld_stream(a + m + j1 * M2 + t);
+                }
+            } else {
+                small_diff_load<M1, SRC>(g.diff, b * g.npi + p, t, re, im);
             }
             cplx v[M1];
 #pragma unroll

@@ -210,6 +210,8 @@ bool small_supported(const pz_module* M, int npi, int key_limbs);
 int launch_small_permute(pz_module* M, const double* P, cplx* Pp, int npolys);
 int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* S, bool natural_order = false,
                      const PolyMap* dmap = nullptr, const cplx* mul = nullptr);
+// the CMUX forms of the forward stage: polynomial p = diff.t - diff.f (diff.t null: X^rot f - f), in the launch order of diff.fmap
+int launch_small_fwd_diff(pz_module* M, int npolys, const SmallDiff& diff, cplx* S);
 bool small_transform_supported(const pz_module* M);   // N = 1024 / 2048 / 4096: per-op transforms in one kernel (launch_small.hip)
 int launch_small_idft(pz_module* M, int npolys, const double* a, PolyMap smap, long long* res, PolyMap dmap);
 // the groups both small-ring product launchers share; glwe_small_ring fills them once per wave
@@ -257,6 +259,7 @@ struct SmallOneCall {
     SmallKey key;
     SmallRes res;
     SmallOperand small;
+    const SmallDiff* diff = nullptr;  // CMUX: the input polynomials are differences of two sources (src / smap are not read)
 };
 int launch_small_one(pz_module* M, int batch, const SmallOneCall& c);
 

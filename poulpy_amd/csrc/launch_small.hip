@@ -87,27 +87,38 @@ int launch_small_idft(pz_module* M, int npolys, const double* a, PolyMap smap, l
 #undef X
     return fail(PZ_ERR_UNSUPPORTED, "small-ring transform: unsupported ring degree");
 }
-int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* S, bool natural_order, const PolyMap* dmap,
-                     const cplx* mul) {
+static int small_fwd_launch(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* S, bool natural_order, const PolyMap* dmap,
+                            const cplx* mul, const SmallDiff* diff) {
     if (npolys <= 0) return PZ_OK;
     PZ_TRY(ensure_small_tables(M));
     SmallFwdArgs g;
     g.src = src; g.smap = smap; g.S = S; g.npolys = npolys; g.tw1 = M->s_tw1; g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.natural = natural_order ? 1 : 0;
     g.use_dmap = dmap ? 1 : 0; g.dmap = dmap ? *dmap : smap; g.mul = mul;
+    g.diff = diff ? *diff : SmallDiff{nullptr, nullptr, smap, smap, 0, 0, 0u};
     if ((dmap || mul) && !natural_order) return fail(PZ_ERR_INVALID, "small-ring forward transform: a destination map / factor needs the standard order");
     const int m1 = small_m1(M);
     const size_t lds = ((size_t)2 * m1 * kSmallRS + kSmallM2) * sizeof(cplx);
     KTimer kt(M, PZ_K_FWD_PASS1);
     const dim3 grid((unsigned)((npolys + 1) / 2));
+    const int src_form = !diff ? 0 : (diff->t ? 1 : 2);
 #define X(M1_)                                                                                      \
     if (m1 == M1_) {                                                                                \
-        PZ_TRY(launch_k(k_small_fwd<M1_>, grid, dim3(256), lds, M->stream, g));                     \
+        if (src_form == 0) PZ_TRY(launch_k((k_small_fwd<M1_, 0>), grid, dim3(256), lds, M->stream, g));          \
+        else if (src_form == 1) PZ_TRY(launch_k((k_small_fwd<M1_, 1>), grid, dim3(256), lds, M->stream, g));     \
+        else PZ_TRY(launch_k((k_small_fwd<M1_, 2>), grid, dim3(256), lds, M->stream, g));                       \
         PZ_HIP(hipGetLastError());                                                                  \
         return PZ_OK;                                                                               \
     }
     X(4) X(8) X(16)
 #undef X
     return fail(PZ_ERR_UNSUPPORTED, "small-ring pipeline: m1 = %d", m1);
+}
+int launch_small_fwd(pz_module* M, int npolys, const long long* src, PolyMap smap, cplx* S, bool natural_order, const PolyMap* dmap,
+                     const cplx* mul) {
+    return small_fwd_launch(M, npolys, src, smap, S, natural_order, dmap, mul, nullptr);
+}
+int launch_small_fwd_diff(pz_module* M, int npolys, const SmallDiff& diff, cplx* S) {
+    return small_fwd_launch(M, npolys, nullptr, diff.fmap, S, false, nullptr, nullptr, &diff);
 }
 
 int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c) {
@@ -192,12 +203,16 @@ int launch_small_one(pz_module* M, int batch, const SmallOneCall& c) {
     g.batch = batch; g.npi = npi; g.nrows = c.key.nrows; g.ncols = c.key.ncols; g.ksz = ksz;
     g.res_cols = c.res.cols; g.res_size = c.res.size; g.small_cols = c.small.cols; g.small_size = c.small.size; g.base2k = c.res.base2k; g.body_col = c.small.body_col;
     g.tw1 = M->s_tw1; g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv; g.margin = M->probe ? M->margin : nullptr;
+    g.diff = c.diff ? *c.diff : SmallDiff{nullptr, nullptr, c.smap, c.smap, 0, 0, 0u};
+    const int src_form = !c.diff ? 0 : (c.diff->t ? 1 : 2);
     const int m1 = small_m1(M);
     const size_t lds = ((size_t)8 * m1 * kSmallRS + kSmallM2 + m1) * sizeof(cplx);   // tile of 8 polynomials + wL2 + tw1inv
     KTimer kt(M, PZ_K_FUSED_TAIL);
 #define X(M1_, KS_)                                                                                           \
     if (m1 == M1_ && ksz == KS_) {                                                                            \
-        PZ_TRY(launch_k((k_small_one<M1_, KS_>), dim3(batch), dim3(512), lds, M->stream, g));                 \
+        if (src_form == 0) PZ_TRY(launch_k((k_small_one<M1_, KS_, 0>), dim3(batch), dim3(512), lds, M->stream, g));        \
+        else if (src_form == 1) PZ_TRY(launch_k((k_small_one<M1_, KS_, 1>), dim3(batch), dim3(512), lds, M->stream, g));   \
+        else PZ_TRY(launch_k((k_small_one<M1_, KS_, 2>), dim3(batch), dim3(512), lds, M->stream, g));                     \
         dispatch_note(M, "k_small_one<M1=%d,KS=%d> (one kernel per ciphertext, %d input polynomials)", M1_, KS_, npi); \
         PZ_HIP(hipGetLastError());                                                                            \
         return PZ_OK;                                                                                         \

@@ -21,8 +21,8 @@
 
 namespace pz {
 
-// Run-time switches: the eleven a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
-// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST;
+// Run-time switches: the twelve a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
+// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST, _CMUX_FUSED;
 // DESIGN.md section 9).
 inline int rt_knob(const char* name, int dflt) {
     const char* e = getenv(name);

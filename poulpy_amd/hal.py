@@ -440,6 +440,27 @@ class Module:
     def glwe_automorphism_many_workspace_bytes(self, params: GlweOpParams, nrot: int, batch: int) -> int:
         return self.lib.pz_glwe_automorphism_many_workspace_bytes(self.handle, C.byref(params), nrot, batch)
 
+    def glwe_cmux_batched(self, res: c_void_p, t, f: c_void_p, ggsw_pmat: c_void_p, params: GlweOpParams, batch: int, *,
+                          t_size: int, f_size: int, t_rot: int = 0):
+        """poulpy-bin-fhe bdd_arithmetic/eval.rs:524-626: res = normalize((t - f) (x) GGSW + f); params.a_size = limbs of the difference.
+        res may be t (cmux_assign) or f (cmux_assign_neg).  t = None: t = X^t_rot f, the step of glwe_blind_rotation_assign."""
+        self._ck(self.lib.pz_glwe_cmux_batched(self.handle, res, t, t_size, t_rot, f, f_size, ggsw_pmat, C.byref(params), batch))
+
+    def glwe_cmux_workspace_bytes(self, params: GlweOpParams, batch: int) -> int:
+        return self.lib.pz_glwe_cmux_workspace_bytes(self.handle, C.byref(params), batch)
+
+    def glwe_blind_rotation_tmp_bytes(self, params: GlweOpParams, batch: int) -> int:
+        return self.lib.pz_glwe_blind_rotation_tmp_bytes(self.handle, C.byref(params), batch)
+
+    def glwe_blind_rotation_batched(self, res: c_void_p, a: c_void_p, bit_ptrs, sign: bool, bit_lsh: int, params: GlweOpParams, tmp: c_void_p,
+                                    tmp_bytes: int, batch: int):
+        """bdd_arithmetic/blind_rotation.rs:196-264: res = a X^{+-(bits) << bit_lsh} by len(bit_ptrs) CMUX steps; bit_ptrs[i]: the device
+        pointer of the prepared GGSW of bit i + bit_rsh.  res may be a.  The GLWE entries of GGSWs are a batch like any other (:45-106)."""
+        nb = len(bit_ptrs)
+        ptrs = _ptrs(bit_ptrs) if nb else (c_void_p * 1)()
+        self._ck(self.lib.pz_glwe_blind_rotation_batched(self.handle, res, a, nb, ptrs, 1 if sign else 0, bit_lsh, C.byref(params), tmp, tmp_bytes,
+                                                         batch))
+
     def ggsw_external_product(self, res: c_void_p, a: c_void_p, a_dnum: int, ggsw_pmat: c_void_p, params: GlweOpParams):
         """poulpy-core external_product/ggsw.rs:54-58 on a device-resident GGSW (MatZnx layout)."""
         self._ck(self.lib.pz_ggsw_external_product(self.handle, res, a, a_dnum, ggsw_pmat, C.byref(params)))
