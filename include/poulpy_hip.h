@@ -395,6 +395,45 @@ size_t pz_glwe_cmux_workspace_bytes(const pz_module* m, const pz_glwe_op_params*
 size_t pz_glwe_blind_rotation_tmp_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t batch);
 int pz_glwe_blind_rotation_batched(pz_module* m, int64_t* res, const int64_t* a, size_t nbits, const double* const* bits, int sign,
                                    size_t bit_lsh, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
+/* Conditional swap, the other gate of bdd_arithmetic: Cswap::cswap (poulpy-bin-fhe/src/bdd_arithmetic/eval.rs:417-461, the equal-base
+ * branch) on `batch` pairs sharing one prepared GGSW; IN PLACE on a and b - (a, b) stays when bit = 0 and becomes (b, a) when bit = 1:
+ *   D     = b - a  on p->a_size limbs (glwe_sub, missing limbs zero, NOT normalized)
+ *   big   = glwe_external_product_internal(D, ggsw)                (key_size limbs)
+ *   a'[j] = vec_znx_big_normalize(big[j] + a[j])    (vec_znx_big_add_small_into: min(key_size, a_size) limbs of a)
+ *   b'[j] = vec_znx_big_normalize(b[j] - big[j])    (vec_znx_big_sub_small_a: limbs of big beyond b_size enter negated)
+ * for every column j; a' has a_size limbs, b' has b_size limbs.  ONE external product, both results from its one big value - which is why
+ * the gate is not two calls of pz_glwe_cmux_batched (two products of +-D, other digits).
+ * p: rank, the GGSW (dnum, any dsize >= 1, key_size, key_base2k), a_size = limbs of D = max(a_size, b_size) (tmp_c, eval.rs:437-442),
+ * res_size = a_size.  a, b and the GGSW share ONE base2k (eval.rs:427, external_product/glwe.rs:213): anything else is PZ_ERR_INVALID,
+ * nothing launched - the reference's other branch, res_base2k != s_base2k (:462-511), is not provided.
+ * a, b: device pointers to `batch` packed ciphertexts each; ANY overlap of the two ranges, a == b included, is PZ_ERR_ALIAS and nothing
+ * is launched.  The prepared GGSW resolves as for every GLWE call (pinned, host with a device mirror, device).
+ * N = 1024 / 2048 / 4096 on the small-ring kernels form D inside the forward stage and run both carry chains behind one inverse
+ * transform; every other shape writes D to the module's second workspace and leaves the two results from the one big value of its
+ * pipeline (POULPY_DBG_CMUX_FUSED=0 sends every shape that way). */
+int    pz_glwe_cswap_batched(pz_module* m, int64_t* a, size_t a_size, int64_t* b, size_t b_size,
+                             const double* ggsw_pmat, const pz_glwe_op_params* p, size_t batch);
+/* what the call reserves in the module's grow-only workspace: the external product's figure with a_size = limbs of D.  NOT counted: on the
+ * materialised route D itself goes to the module's second grow-only workspace, batch * N * (rank + 1) * a_size * 8 bytes */
+size_t pz_glwe_cswap_workspace_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t batch);
+
+/* GLWEBlindRetrieval::glwe_blind_retrieval_statefull (reverse == 0, blind_retrieval.rs:214-236) / _rev (reverse != 0, :243-265)
+ * on `batch` independent vectors of nslots ciphertexts of one layout: afterwards slot 0 holds the element at the encrypted index
+ * (bits >> bit_rsh) mod 2^nbits; the reverse call undoes the permutation.
+ *   slots  dense slot-major device buffer [nslots][batch]: slot s of every vector at slots + s * batch * n * (rank + 1) * size;
+ *          p->a_size == p->res_size = size, one base2k
+ *   bits   HOST array of nbits device pointers to prepared GGSWs: bits[i] = the GGSW of bit bit_rsh + i (the caller resolves get_bit,
+ *          as for pz_glwe_blind_rotation_batched); a null entry is PZ_ERR_INVALID
+ * Level i uses t = 2^(nbits - 1 - i) and bits[nbits - 1 - i]; the reference's loop `for j in 0..t { if j + t < len { cswap(res[j],
+ * res[j + t]) } }` is ONE pz_glwe_cswap_batched on cnt * batch contiguous pairs, cnt = t < nslots ? min(t, nslots - t) : 0, a = slot 0,
+ * b = slot t (disjoint: cnt <= t); a level with cnt == 0 launches nothing.  Forward: levels 0 .. nbits - 1; reverse: the same levels in
+ * the opposite order.  nslots == 0 or nbits == 0: PZ_OK, nothing launched.  Bit-identical to the per-level pz_glwe_cswap_batched calls.
+ * A call repeated with the same arguments is replayed as one HIP graph (pz_module_set_graphs).
+ * Not provided: GLWEBlindRetriever (blind_retrieval.rs:31-179) - glwe_copy + cmux_assign_neg, i.e. pz_glwe_cmux_batched as it is. */
+int    pz_glwe_blind_retrieval_batched(pz_module* m, int64_t* slots, size_t nslots, size_t nbits, const double* const* bits,
+                                       int reverse, const pz_glwe_op_params* p, size_t batch);
+/* the swap's figure at the largest level */
+size_t pz_glwe_blind_retrieval_workspace_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t nslots, size_t nbits, size_t batch);
 /* CoreImpl ggsw_external_product (poulpy-core/src/external_product/ggsw.rs:54-58): res[row][col] = a[row][col] (x) ggsw
  * for the a_dnum * (rank+1) GLWE entries of the GGSW `a` (MatZnx layout: entries are contiguous), device pointers. */
 int pz_ggsw_external_product(pz_module* m, int64_t* res, const int64_t* a, size_t a_dnum, const double* ggsw_pmat,

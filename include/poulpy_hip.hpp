@@ -173,6 +173,20 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                                      const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
         check(pz_glwe_blind_rotation_batched(m_, res, a, nbits, bits, sign ? 1 : 0, bit_lsh, &p, tmp, tmp_bytes, batch), "glwe_blind_rotation_batched");
     }
+    // Cswap::cswap (bdd_arithmetic/eval.rs:417-461, one base2k) in place on a and b: one external product of b - a, both results from its big value;
+    // p.a_size = max(a_size, b_size), p.res_size = a_size; a and b must not overlap
+    void glwe_cswap_batched(int64_t* a, size_t a_size, int64_t* b, size_t b_size, const double* ggsw, const pz_glwe_op_params& p, size_t batch) {
+        check(pz_glwe_cswap_batched(m_, a, a_size, b, b_size, ggsw, &p, batch), "glwe_cswap_batched");
+    }
+    size_t glwe_cswap_workspace_bytes(const pz_glwe_op_params& p, size_t batch) const { return pz_glwe_cswap_workspace_bytes(m_, &p, batch); }
+    // glwe_blind_retrieval_statefull / _rev (bdd_arithmetic/blind_retrieval.rs:195-266): slots = dense [nslots][batch], bits = nbits host entries
+    void glwe_blind_retrieval_batched(int64_t* slots, size_t nslots, size_t nbits, const double* const* bits, bool reverse, const pz_glwe_op_params& p,
+                                      size_t batch) {
+        check(pz_glwe_blind_retrieval_batched(m_, slots, nslots, nbits, bits, reverse ? 1 : 0, &p, batch), "glwe_blind_retrieval_batched");
+    }
+    size_t glwe_blind_retrieval_workspace_bytes(const pz_glwe_op_params& p, size_t nslots, size_t nbits, size_t batch) const {
+        return pz_glwe_blind_retrieval_workspace_bytes(m_, &p, nslots, nbits, batch);
+    }
     void blind_rotation_execute_batched(int64_t* res, const int64_t* lwe_2n, const int64_t* lut, const double* brk, const pz_blind_rotation_params& p, size_t batch) {
         check(pz_blind_rotation_execute_batched(m_, res, lwe_2n, lut, brk, &p, batch), "blind_rotation_execute_batched");
     }

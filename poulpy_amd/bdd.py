@@ -1,4 +1,4 @@
-"""Helpers on top of the CMUX entry point (pz_glwe_cmux_batched) for poulpy-bin-fhe's bdd_arithmetic."""
+"""Helpers on top of the gate entry points (pz_glwe_cmux_batched, pz_glwe_cswap_batched) for poulpy-bin-fhe's bdd_arithmetic."""
 from __future__ import annotations
 
 from ctypes import c_void_p
@@ -30,3 +30,19 @@ def glwe_blind_selection(mod, buf, bit_ptrs, params, batch: int) -> c_void_p:
         hi = c_void_p(base + (slots - 2 * t) * slot_bytes)
         mod.glwe_cmux_batched(lo, lo, hi, bit_ptrs[bit_mask - 1 - i], params, t * batch, t_size=size, f_size=size)
     return c_void_p(base + (slots - 1) * slot_bytes)
+
+
+def glwe_blind_retrieval(mod, buf, nslots: int, bit_ptrs, params, batch: int, reverse: bool = False) -> c_void_p:
+    """GLWEBlindRetrieval::glwe_blind_retrieval_statefull / _rev (bdd_arithmetic/blind_retrieval.rs:195-266) on `batch` independent vectors.
+
+    buf: device pointer to a dense slot-major buffer [nslots][batch] of GLWE ciphertexts (one layout: params.a_size == params.res_size limbs),
+    slot s holding element s of every vector.  bit_ptrs[i]: the prepared GGSW of bit bit_rsh + i (device pointers), bit_mask = len(bit_ptrs).
+    The buffer is permuted IN PLACE, as the reference's Vec is: afterwards slot 0 holds the element at the encrypted index; reverse=True applies
+    the same network backwards and restores the order.
+
+    Level i (bit bit_rsh + bit_mask - 1 - i, :222-223) pairs element j with element j + t, t = 2^(bit_mask - 1 - i), for every j < t with
+    j + t < nslots (:224-230): one conditional swap on min(t, nslots - t) * batch contiguous pairs.  All levels are ONE call of
+    pz_glwe_blind_retrieval_batched.  Returns the device pointer of slot 0."""
+    assert params.a_size == params.res_size
+    mod.glwe_blind_retrieval_batched(buf, nslots, bit_ptrs, reverse, params, batch)
+    return c_void_p(_addr(buf))

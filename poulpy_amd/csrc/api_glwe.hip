@@ -208,6 +208,12 @@ struct GlweCall {
     long long add_bs = 0;
     int add_size = 0;
     const SmallDiff* diff = nullptr;
+    // conditional swap (glwe_cswap below; eval.rs:444-461): a SECOND result from the same big value, res2 = normalize(res2 - big) on every column
+    // (vec_znx_big_sub_small_a), in place on its own operand; res2_size limbs, res2_bs elements between ciphertexts.  `add` is the first one's operand
+    int64_t* res2 = nullptr;
+    long long res2_bs = 0;
+    int res2_size = 0;
+    int64_t* res2_at(size_t b0) const { return res2 + (long long)b0 * res2_bs; }
     int cols_in() const { return s.cols_in; }
     int64_t* res_at(size_t b0) const { return res + (long long)b0 * res_bs; }
 };
@@ -284,6 +290,16 @@ static SmallOperand small_operand(const GlweCall& c, const DV& av, size_t b0) {
     if (c.add) return SmallOperand{(const long long*)(c.add + (long long)b0 * c.add_bs), c.add_bs, c.s.cols_out, c.add_size, -1};   // CMUX: + f on every column
     return SmallOperand{c.ks ? (const long long*)av.p : nullptr, av.bs, c.s.cols_a, av.size, c.body_col};
 }
+// conditional swap: the wave's part of the second result, which is its own operand
+static SmallRes small_res2(const GlweCall& c, size_t b0) {
+    if (!c.res2) return SmallRes{};
+    return SmallRes{(long long*)c.res2_at(b0), c.res2_bs, c.s.cols_out, c.res2_size, (int)c.p->res_base2k};
+}
+static SmallOperand small_operand2(const GlweCall& c, size_t b0) {
+    if (!c.res2) return SmallOperand{};
+    return SmallOperand{(const long long*)c.res2_at(b0), c.res2_bs, c.s.cols_out, c.res2_size, -1};
+}
+static const char* gate_name(const GlweCall& c) { return c.res2 ? "cswap" : "cmux"; }
 // CMUX: the wave's part of the every-column operand f, and of the two sources of the fused forward stage
 static DV wave_add(const GlweCall& c, size_t b0) { return DV{(void*)(c.add + (long long)b0 * c.add_bs), c.add_bs, c.s.cols_out, c.add_size}; }
 static SmallDiff wave_diff(const GlweCall& c, size_t b0) {
@@ -364,11 +380,12 @@ static bool n4096_two_kernel(const GlweCall& c) {
 static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av, const PolyMap& sm) {
     const bool rsh = c.want_rsh && c.au && c.au->mode != 0 && c.p->res_base2k <= 29;
     if (c.diff) {
-        dispatch_note(c.M, "cmux: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)");
+        dispatch_note(c.M, "%s: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)", gate_name(c));
         PZ_TRY(launch_small_fwd_diff(c.M, nb * c.npi, wave_diff(c, b0), f.T));
     } else PZ_TRY(launch_small_fwd(c.M, nb * c.npi, (const long long*)av.p, sm, f.T));
     SmallInvCall sc;
     sc.S = f.T; sc.key = small_key(c, f.Pp); sc.res = small_res(c, b0); sc.small = small_operand(c, av, b0);
+    sc.res2 = small_res2(c, b0); sc.small2 = small_operand2(c, b0);
     small_inv_auto(sc, c, rsh);
     PZ_TRY(launch_small_inv(c.M, nb, sc));
     if (rsh) *c.post_rsh = true;
@@ -488,6 +505,13 @@ static int wave_plain_tail(const GlweCall& c, const FusedBufs& f, size_t b0, int
         if (c.au_big) { t.auto_mul = c.au_p; t.gather_mul = c.au_p; t.gather_neg = c.au->mode != 1; }
         t.auto_neg = c.au && c.au->mode == 3;
         PZ_TRY(launch_inv_tail(M, t));
+        if (c.res2) {   // conditional swap: the big value in T2' (the tail only reads it) once more - negated in front of the chain, operand res2
+            TailCall t2 = wave_tail(c, nb, f.T2, b0);
+            t2.res = (long long*)c.res2_at(b0); t2.res_bs = c.res2_bs; t2.res_size = c.res2_size;
+            tail_operand(t2, DV{(void*)c.res2_at(b0), c.res2_bs, c.s.cols_out, c.res2_size}, true);
+            t2.big_neg = true;
+            PZ_TRY(launch_inv_tail(M, t2));
+        }
     }
     if (c.au) {
         PolyMap tm{(int)c.p->res_size, c.s.cols_out, c.res_ct, (long long)c.s.cols_out * c.n, c.n, 0};
@@ -588,16 +612,18 @@ static int glwe_small_ring(const GlweCall& c) {
         const SmallDiff wd = c.diff ? wave_diff(c, b0) : SmallDiff{};
         // plain product / key switch of a rank-1 ciphertext: one kernel, the spectra never leave the CU (round 6, device_small_one.hpp)
         if (!c.au && !c.cross_out && small_one_supported(M, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, nb)) {
-            if (c.diff) dispatch_note(M, "cmux: fused small-one (k_small_one<.., difference>)");
-            PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body, c.diff ? &wd : nullptr}));
+            if (c.diff) dispatch_note(M, "%s: fused small-one (k_small_one<.., difference>)", gate_name(c));
+            PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body, c.diff ? &wd : nullptr,
+                                                        small_res2(c, b0), small_operand2(c, b0)}));
             continue;
         }
         if (c.diff) {
-            dispatch_note(M, "cmux: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)");
+            dispatch_note(M, "%s: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)", gate_name(c));
             PZ_TRY(launch_small_fwd_diff(M, nb * c.npi, wd, S));
         } else PZ_TRY(launch_small_fwd(M, nb * c.npi, (const long long*)av.p, sm, S));
         SmallInvCall sc;
         sc.S = S; sc.key = key; sc.res = small_res(c, b0); sc.small = body;
+        sc.res2 = small_res2(c, b0); sc.small2 = small_operand2(c, b0);
         if (c.cross_out) {
             const long long tmp_ct = c.n * c.s.cols_out * (long long)c.ksz;
             sc.res = SmallRes{(long long*)key_digits, tmp_ct, c.s.cols_out, c.ksz, (int)c.p->key_base2k};
@@ -716,7 +742,7 @@ static int glwe_unfused(const GlweCall& c) {
         DV rv{(void*)c.res_at(b0), c.res_bs, c.s.cols_out, (int)c.p->res_size};
         if (c.au) {
             PZ_TRY(wave_unfused_auto(c, u, nb, av, rb, rv));
-        } else if (c.p->res_base2k == c.p->key_base2k && M->fuse_tail && tail_supported(M)) {
+        } else if (!c.res2 && c.p->res_base2k == c.p->key_base2k && M->fuse_tail && tail_supported(M)) {
             // inverse pass 2, then the fused tail: inverse pass 1 + body add + carry chain, no VecZnxBig in HBM
             PolyMap sm{res_dft_size, c.s.cols_out, rb.bs, (long long)c.s.cols_out * n, n, 0};
             PZ_TRY(launch_inv_pass2(M, nb * res_dft_size * c.s.cols_out, u.res_dft, sm, u.T));
@@ -732,6 +758,22 @@ static int glwe_unfused(const GlweCall& c) {
         } else {
             PZ_TRY(dev_idft(M, nb, rb, 0, rb, 0, c.s.cols_out, res_dft_size, u.T));
             const long long big_ls = (long long)c.s.cols_out * n;
+            if (c.res2) {   // conditional swap, eval.rs:455-459: the i64 big value feeds both normalizations - first b - big (limbs of big beyond b:
+                            // negated, vec_znx_big_sub_small_a) into the transform scratch (free again: the bytes of the big value) and from there into res2
+                int64_t* big2 = (int64_t*)u.T;
+                const int sum = std::min(res_dft_size, c.res2_size);
+                for (int col = 0; col < c.s.cols_out; ++col) {
+                    int64_t* bc = big2 + (long long)col * n;
+                    const int64_t* xc = (const int64_t*)u.res_dft + (long long)col * n;
+                    const int64_t* oc = c.res2_at(b0) + (long long)col * n;
+                    PZ_TRY(launch_ew(M, EW_SUB_I64, bc, rb.bs, big_ls, oc, c.res2_bs, big_ls, xc, rb.bs, big_ls, sum, nb));
+                    PZ_TRY(launch_ew(M, EW_NEG_I64, bc + (long long)sum * big_ls, rb.bs, big_ls, xc + (long long)sum * big_ls, rb.bs, big_ls, nullptr, 0, 0,
+                                     res_dft_size - sum, nb));
+                }
+                DV r2{(void*)c.res2_at(b0), c.res2_bs, c.s.cols_out, c.res2_size}, b2{big2, rb.bs, c.s.cols_out, res_dft_size};
+                for (int col = 0; col < c.s.cols_out; ++col)
+                    PZ_TRY(dev_normalize(M, nb, r2, (int)c.p->res_base2k, 0, col, b2, (int)c.p->key_base2k, col));
+            }
             if (c.tensor) {  // operations/glwe.rs:588-598: + a[col] on every column (raw a when res_base2k == key_base2k, else the converted one)
                 const DV& sv = c.p->res_base2k == c.p->key_base2k ? raw_av : av;
                 for (int col = 0; col < c.s.cols_out; ++col)
@@ -1137,14 +1179,16 @@ static int cmux_materialise(pz_module* M, int64_t* D, const CmuxShape& s, const 
     }
     return launch_ew(M, EW_ZERO, (void*)limb(D, top), s.d_ct, n, nullptr, 0, 0, nullptr, 0, 0, (d_size - top) * cols, B);
 }
-// device pointers, the key resolved, the module lock held (pz_glwe_cmux_batched and the ladder of pz_glwe_blind_rotation_batched)
+// device pointers, the key resolved, the module lock held (pz_glwe_cmux_batched and the ladder of pz_glwe_blind_rotation_batched).
+// res2 != null: the conditional swap (glwe_cswap below) - res == f, res2 == t, and t takes the second result normalize(t - big) in place
 static int glwe_cmux(pz_module* M, int64_t* res, const int64_t* t, const int64_t* f, const double* key, const pz_glwe_op_params* p,
-                     const CmuxOperands* o, size_t batch) {
+                     const CmuxOperands* o, size_t batch, int64_t* res2 = nullptr) {
     GlweCall c;
     PZ_TRY(glwe_call_init(c, M, GlweKind::ExternalProduct, res, f, key, p, batch, nullptr, nullptr, nullptr));   // (`a` is set below: D, or nothing)
     if (batch == 0) return PZ_OK;
     const CmuxShape s = cmux_shape(M, p, o, batch);
     c.add = f; c.add_bs = s.f_ct; c.add_size = (int)o->f_size;
+    c.res2 = res2; c.res2_bs = s.t_ct; c.res2_size = (int)o->t_size;
     const bool pipeline = fused_applies(M, p, c.s, c.kind), small_ring = !pipeline && small_ring_applies(M, p, c.s, c.kind, true);
     const int knob = rt_knob("POULPY_DBG_CMUX_FUSED", 1);   // (read per call: tests flip it)
     SmallDiff d;
@@ -1159,7 +1203,7 @@ static int glwe_cmux(pz_module* M, int64_t* res, const int64_t* t, const int64_t
         c.diff = &d; c.a = nullptr;
         return pipeline ? glwe_fused(c) : glwe_small_ring(c);
     }
-    dispatch_note(M, "cmux: materialised difference (%s)", knob == 0 ? "POULPY_DBG_CMUX_FUSED=0" : (pipeline ? "three-kernel pipeline" : (small_ring ? "small ring" : "five-kernel path")));
+    dispatch_note(M, "%s: materialised difference (%s)", gate_name(c), knob == 0 ? "POULPY_DBG_CMUX_FUSED=0" : (pipeline ? "three-kernel pipeline" : (small_ring ? "small ring" : "five-kernel path")));
     PZ_TRY(ws2_reserve(M, batch * (size_t)s.d_ct * 8));
     int64_t* D = (int64_t*)M->ws2;
     PZ_TRY(cmux_materialise(M, D, s, t, f, p, o, batch));
@@ -1251,6 +1295,106 @@ int pz_glwe_blind_rotation_batched(pz_module* M, int64_t* res, const int64_t* a,
     for (size_t i = 0; i < nbits; ++i) k.add(keys[i]);
     graph_key_module(M, k);
     PZ_TRY(with_graph(M, k.h, [&]() { return glwe_blind_rotation_steps(M, res, a, nbits, keys.data(), sign, bit_lsh, p, (int64_t*)tmp, batch); }));
+    return finish_call(M, false);
+}
+}  // extern "C"
+
+// ------------------------------------------------------------------------------
+// Conditional swap, the other gate of bdd_arithmetic (Cswap::cswap, eval.rs:417-461, the equal-base branch), IN PLACE on a and b:
+//   D = b - a (glwe_sub into tmp_c of max(a, b) limbs, not normalized);  big = D (x) GGSW - ONE external product;
+//   a' = normalize(big + a) (vec_znx_big_add_small_into),  b' = normalize(b - big) (vec_znx_big_sub_small_a) on every column.
+// The forward half is the CMUX's with t = b, f = a (fused: SmallDiff; materialised: cmux_materialise into the second workspace).  The inverse half leaves
+// two results from the one big value:
+//   small-ring kernels  the dual forms k_small_inv<.., DUAL> / k_small_one<.., DUAL>: two carry chains behind one inverse transform
+//   pipeline            two tails over the same T2' (the tail only reads it), the second with the big value negated (TailCall::big_neg)
+//   five-kernel path    the i64 big value in the workspace feeds both normalizations
+// In place: every kernel that reads a or b of a ciphertext as a SOURCE runs before the one that writes its results (or, in the one-kernel form, four
+// barriers earlier in the same workgroup), and the chains read their operands at the positions they then write.
+// ------------------------------------------------------------------------------
+static int cswap_check_args(const int64_t* a, size_t a_size, const int64_t* b, size_t b_size, const double* pmat, const pz_glwe_op_params* p, size_t batch) {
+    PZ_REQUIRE(p != nullptr, "glwe_cswap: null params");
+    PZ_REQUIRE(a != nullptr && b != nullptr && pmat != nullptr, "glwe_cswap: null argument");
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1 && a_size >= 1 && b_size >= 1, "glwe_cswap: empty shape");
+    // eval.rs:427 (this branch) and external_product/glwe.rs:213
+    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_cswap: a, b and the GGSW share one base2k (%llu / %llu / %llu)",
+               (unsigned long long)p->a_base2k, (unsigned long long)p->res_base2k, (unsigned long long)p->key_base2k);
+    PZ_REQUIRE(p->a_size == std::max(a_size, b_size), "glwe_cswap: p->a_size is the limb count of the difference, max(a_size, b_size) = %zu, not %llu",
+               std::max(a_size, b_size), (unsigned long long)p->a_size);   // tmp_c: k = max(res_a.max_k, res_b.max_k), eval.rs:437-442
+    PZ_REQUIRE(p->res_size == a_size, "glwe_cswap: p->res_size is a_size = %zu, not %llu", a_size, (unsigned long long)p->res_size);
+    // what the pointers alone tell: the same buffer, or two ranges that overlap at the smallest ring degree a module can have (n = 2)
+    const size_t cols = p->rank + 1;
+    if ((const void*)a == (const void*)b || (batch > 0 && ranges_overlap(a, batch * cols * a_size * 16, b, batch * cols * b_size * 16)))
+        return fail(PZ_ERR_ALIAS, "glwe_cswap: a and b overlap");
+    return PZ_OK;
+}
+// device pointers, the key resolved, the module lock held (pz_glwe_cswap_batched and the levels of pz_glwe_blind_retrieval_batched): the CMUX with
+// t = b, f = a, res = a, and b taking the second result
+static int glwe_cswap(pz_module* M, int64_t* a, size_t a_size, int64_t* b, size_t b_size, const double* key, const pz_glwe_op_params* p, size_t batch) {
+    const CmuxOperands ops{b_size, a_size, 0};
+    return glwe_cmux(M, a, b, a, key, p, &ops, batch, b);
+}
+// the levels of the retrieval network in its dense form: level i pairs slot j with slot j + t, t = 2^(nbits - 1 - i), for j < cnt (blind_retrieval.rs:222-233)
+static size_t retrieval_cnt(size_t nslots, size_t t) { return t < nslots ? std::min(t, nslots - t) : 0; }
+static int glwe_blind_retrieval_levels(pz_module* M, int64_t* slots, size_t nslots, size_t nbits, const double* const* keys, int reverse,
+                                       const pz_glwe_op_params* p, size_t batch) {
+    const size_t slot_elems = batch * (size_t)M->n * (p->rank + 1) * p->res_size;
+    for (size_t s = 0; s < nbits; ++s) {
+        const size_t i = reverse ? nbits - 1 - s : s;
+        if (nbits - 1 - i >= 63) continue;   // (t beyond any slot count)
+        const size_t t = (size_t)1 << (nbits - 1 - i), cnt = retrieval_cnt(nslots, t);
+        if (cnt == 0) continue;
+        PZ_TRY(glwe_cswap(M, slots, p->res_size, slots + t * slot_elems, p->res_size, keys[nbits - 1 - i], p, cnt * batch));
+    }
+    return PZ_OK;
+}
+
+extern "C" {
+size_t pz_glwe_cswap_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
+    // the external product's reservation (D has p->a_size limbs); the materialised route keeps D in the module's second workspace on top of it
+    return pz_glwe_op_workspace_bytes(M, p, batch, (int)GlweKind::ExternalProduct);
+}
+int pz_glwe_cswap_batched(pz_module* M, int64_t* a, size_t a_size, int64_t* b, size_t b_size, const double* ggsw_pmat, const pz_glwe_op_params* p,
+                          size_t batch) {
+    PZ_TRY(cswap_check_args(a, a_size, b, b_size, ggsw_pmat, p, batch));
+    PZ_ENTER(M);
+    PZ_REQUIRE(is_device_ptr(a) && is_device_ptr(b), "batched entry points take device pointers");
+    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
+    if (ranges_overlap(a, batch * n8 * cols * a_size, b, batch * n8 * cols * b_size)) return fail(PZ_ERR_ALIAS, "glwe_cswap: a and b overlap");
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, ggsw_pmat, n8 * p->dnum * cols * cols * p->key_size, &key));
+    PZ_TRY(glwe_cswap(M, a, a_size, b, b_size, key, p, batch));
+    return finish_call(M, false);
+}
+
+// GLWEBlindRetrieval::glwe_blind_retrieval_statefull / _rev (bdd_arithmetic/blind_retrieval.rs:195-266) on `batch` vectors of nslots ciphertexts in
+// a dense slot-major buffer: every level of the butterfly network is one conditional swap on cnt * batch contiguous pairs
+size_t pz_glwe_blind_retrieval_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t nslots, size_t nbits, size_t batch) {
+    if (!M || !p) return 0;
+    size_t most = 0;   // the swap's figure at the largest level
+    for (size_t i = 0; i < nbits && i < 63; ++i) most = std::max(most, retrieval_cnt(nslots, (size_t)1 << i));
+    return most == 0 ? 0 : pz_glwe_cswap_workspace_bytes(M, p, most * batch);
+}
+int pz_glwe_blind_retrieval_batched(pz_module* M, int64_t* slots, size_t nslots, size_t nbits, const double* const* bits, int reverse,
+                                    const pz_glwe_op_params* p, size_t batch) {
+    PZ_REQUIRE(p != nullptr, "glwe_blind_retrieval: null params");
+    if (nslots == 0 || nbits == 0) return PZ_OK;
+    PZ_REQUIRE(slots != nullptr && bits != nullptr, "glwe_blind_retrieval: null argument");
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe_blind_retrieval: empty shape");
+    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_blind_retrieval: the slots and the GGSWs share one base2k");
+    PZ_REQUIRE(p->a_size == p->res_size, "glwe_blind_retrieval: all slots share one layout (p->a_size == p->res_size)");
+    for (size_t i = 0; i < nbits; ++i) PZ_REQUIRE(bits[i] != nullptr, "glwe_blind_retrieval: GGSW %zu is null", i);
+    PZ_ENTER(M);
+    PZ_REQUIRE(is_device_ptr(slots), "batched entry points take device pointers");
+    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
+    std::vector<const double*> keys(nbits);
+    for (size_t i = 0; i < nbits; ++i) PZ_TRY(resolve_key(M, bits[i], n8 * p->dnum * cols * cols * p->key_size, &keys[i]));
+    if (batch == 0) return PZ_OK;
+    KeyHash k;
+    k.add((int)8); k.add(slots); k.add(nslots); k.add(nbits); k.add(reverse != 0); k.add(batch); k.add(*p);
+    k.add(rt_knob("POULPY_DBG_CMUX_FUSED", 1));
+    for (size_t i = 0; i < nbits; ++i) k.add(keys[i]);
+    graph_key_module(M, k);
+    PZ_TRY(with_graph(M, k.h, [&]() { return glwe_blind_retrieval_levels(M, slots, nslots, nbits, keys.data(), reverse, p, batch); }));
     return finish_call(M, false);
 }
 }  // extern "C"

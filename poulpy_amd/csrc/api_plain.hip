@@ -228,6 +228,9 @@ int pz_glwe_mul_plain_batched(pz_module* M, int64_t* res, const int64_t* a, cons
     if (t.mid && !t.fused) dispatch_note(M, "glwe_mul_plain: pass 1 + k_mid_cnv per column + normalizing tail");
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = (int)std::min(chunk, batch - b0);
+        // every wave carves the workspace again, and a shorter last wave puts its segments over the guards of the waves before it: those are
+        // verified now, before their bytes become someone else's segment (as ws_reserve does for a composite call)
+        if (canary_mode() && b0 > 0) canary_verify(M, "a workspace segment carved by an earlier wave of this call", M->ws, (char*)M->ws + M->ws_bytes);
         PZ_TRY(mul_plain_wave(M, t, p, nb, res + (long long)b0 * r_ct, a + (long long)b0 * a_ct, pt + (long long)b0 * pt_ct, shared, pb_once,
                               b0 > 0));
     }

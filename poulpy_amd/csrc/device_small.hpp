@@ -323,6 +323,12 @@ struct SmallInvArgs {
     int acc32;                   // NOPROD (blind rotation's tail): bit 0 `small` holds 32-bit digits, bit 1 `res` takes 32-bit digits (bits 2 / 3: 16-bit digits) - same
                                  // element strides, half the bytes: between the blocks of a rotation the accumulator only ever holds normalized
                                  // digits (base2k <= 31), and this kernel moves them at HBM rate (api_br.hip)
+    // DUAL (conditional swap, pz_glwe_cswap_batched): a second result from the same big value, res2 = normalize(small2 - big) on every column
+    // (vec_znx_big_sub_small_a: limbs of big beyond small2_size enter negated); both containers have res_cols columns
+    long long* res2;
+    const long long* small2;
+    long long res2_bs, small2_bs;
+    int res2_size, small2_size;
 };
 
 // 64 M1 threads (1024 at N = 4096: 16 waves, the product phase is latency-bound with fewer); LDS holds the KS output polynomials of one
@@ -349,8 +355,12 @@ struct SmallInvArgs {
 // stores; round 3: glwe_trace at N = 4096 +24 %).  The key-switch body is added at the source positions by the column pass (coalesced
 // loads).  In place (res == a): those loads happen before the barrier in front of the carry phase, i.e. before any thread stores; the
 // operand at a thread's own positions is loaded before its first store.
-template <int M1, int KS, bool NOPROD = false, bool FWD = false, bool AU = false>
+// DUAL (Cswap::cswap, eval.rs:417-461): ONE product and ONE inverse transform, two carry chains - the coefficient's big value x enters the first
+// as x + small (stored to res) and the second as small2 - x (stored to res2).  In place on both (res == small, res2 == small2): a thread loads
+// both operands at exactly the positions it later stores, before the barrier in front of the carry phase; no other thread touches them.
+template <int M1, int KS, bool NOPROD = false, bool FWD = false, bool AU = false, bool DUAL = false>
 __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
+    static_assert(!DUAL || (!NOPROD && !FWD && !AU), "two results: the plain product form");
     constexpr int NT = 64 * M1;          // 2 product positions per thread (m = 128 M1 points)
     constexpr int M2 = kSmallM2, RS = small_inv_rs(M1, NOPROD), L = KS;
     constexpr long long m = (long long)M1 * kSmallM2, n = 2 * m;
@@ -598,6 +608,17 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
 #undef PZ_SMALL_ROUND
         }
     }
+    // DUAL: the second operand of this thread's coefficients, requested behind the column pass (its registers are free again) and in front of
+    // the barrier; limbs beyond its size: the last one is read again, masked below
+    long long smv2[DUAL ? KS : 1][4];
+    if constexpr (DUAL) {
+        const long long* small2_col = g.small2 + (long long)b * g.small2_bs + (long long)col * n + (ch ? m : 0) + cj2 + (long long)jq * M2;
+        const long long small2_ls = (long long)g.res_cols * n;
+#pragma unroll
+        for (int j = 0; j < KS; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) smv2[j][e] = small2_col[(long long)min(j, g.small2_size - 1) * small2_ls + JG * e * M2];
+    }
     PZ_SSTAMP(4)
     __syncthreads();
     PZ_SSTAMP(7)
@@ -674,6 +695,21 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
         }
     const unsigned long long half = 1ull << (k - 1), mask = (1ull << k) - 1;
     const long long* xin = reinterpret_cast<const long long*>(lds);
+    long long carry2[DUAL ? 4 : 1];
+    long long* res2_col = nullptr;
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) carry2[u] = 0;
+#pragma unroll
+        for (int j = 0; j < KS; ++j)
+            if (j >= g.small2_size)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) smv2[j][e] = 0;
+        res2_col = g.res2 + (long long)b * g.res2_bs + (long long)col * n + (ch ? m : 0) + cj2 + (long long)jq * M2;
+        for (int j = L; j < g.res2_size; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) res2_col[(long long)j * res_ls + opos[e]] = 0;
+    }
     // One limb at a time: the chain steps of the thread's four coefficients in straight-line code, then the stores / the FWD tile writes
     // behind ONE uniform test each.  (Rounds 1 - 3 tested "carry only" - a last limb that is not stored - and `writes` per coefficient:
     // a branch per (limb, coefficient) in the unrolled chain; the carry-only case needs no test at all, the chain starts from carry 0, for
@@ -682,9 +718,20 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
     for (int j = L - 1; j >= 0; --j) {
         const bool writes = j < g.res_size;
         long long x1v[4];
+        long long x2v[DUAL ? 4 : 1];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             long long x = xin[lsrc[e] + 2 * j * M1 * RS];
+            if constexpr (DUAL) {   // the second chain: small2 - big
+                const long long xb = (long long)((unsigned long long)smv2[j][e] - (unsigned long long)x);
+                long long& cy = carry2[e];
+                const unsigned long long y = (unsigned long long)xb + half;
+                const long long d = (long long)(y & mask) - (long long)half;
+                const long long cr = (long long)y >> k;
+                const unsigned long long y2 = (unsigned long long)d + (unsigned long long)cy + half;
+                x2v[e] = (long long)(y2 & mask) - (long long)half;
+                cy = (long long)((unsigned long long)cr + (unsigned long long)((long long)y2 >> k));
+            }
             if constexpr (AU) {
                 unsigned long long ux = (unsigned long long)x;   // (the body was added at the source position, in the column pass)
                 if (g.au_mode != 0) {   // phi on the big value, then +- a over the common limbs (limbs beyond a: + 0, - 0, 0 - big)
@@ -728,6 +775,12 @@ __global__ void __launch_bounds__(64 * M1) k_small_inv(SmallInvArgs g) {
                     else if (res32) res_col32[(long long)j * res_ls + opos[e]] = (int)xs;
                     else st_stream(res_col + (long long)j * res_ls + opos[e], xs);
                 }
+            }
+        }
+        if constexpr (DUAL) {
+            if (j < g.res2_size) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) st_stream(res2_col + (long long)j * res_ls + opos[e], x2v[e]);
             }
         }
         if constexpr (FWD) {   // this thread's own slots (read above): component ch of z[limb j][j1][j2]

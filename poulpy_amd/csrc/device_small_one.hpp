@@ -44,6 +44,11 @@ struct SmallOneArgs {
     const cplx* tw1inv;          // [M1] untwist with 1/m folded in
     unsigned long long* margin;  // rounding-margin probe (margin_note); null = off
     SmallDiff diff;              // SRC != 0 (CMUX): the input polynomials are differences of two sources (device_small.hpp; src / smap are not read)
+    // DUAL (conditional swap): a second result from the same big value, res2 = normalize(small2 - big) on every column (k_small_inv<.., DUAL>)
+    long long* res2;
+    const long long* small2;
+    long long res2_bs, small2_bs;
+    int res2_size, small2_size;
 };
 
 // (Measured and dropped, round 6: input groups of 4 polynomials through a 32-row tile at N = 2048 - 73.7 KiB, two workgroups per CU, the product's sums
@@ -52,7 +57,10 @@ struct SmallOneArgs {
 // (Also measured and dropped: the i64 loads of both column-pass sweeps requested before the first butterfly, and the key values of the product's first row
 //  requested in front of the forward row pass - N = 1024: 16.55 -> 16.5 M external products/s, key switch 20.7 -> 19.9 M/s, 2 limbs 30.9 -> 29.5 M/s; N = 2048
 //  7.9 -> 7.8 M/s: with two workgroups per CU the other workgroup already fills those waits, and the extra live registers cost; profiles/r06_ab_small_one.txt)
-template <int M1, int KS, int SRC = 0>
+// DUAL (Cswap::cswap): stage F runs two carry chains on the coefficient's big value x - x + small into res, small2 - x into res2; both operands are
+// loaded at the positions the thread then stores, before its first store (in place on both: nobody else touches them; stage A read both sources
+// of the whole ciphertext four barriers earlier).
+template <int M1, int KS, int SRC = 0, bool DUAL = false>
 __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneArgs g) {   // (waves per SIMD: two workgroups per CU at N = 1024, one at 2048)
     constexpr int NT = 512, M2 = kSmallM2, RS = kSmallRS, CO = 2, NPO = CO * KS, PP = M1 / 4;
     constexpr long long m = (long long)M1 * M2, n = 2 * m;
@@ -304,10 +312,29 @@ __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneAr
 #pragma unroll
                     for (int e = 0; e < 4; ++e) smv[j][e] = small_col[(long long)min(j, g.small_size - 1) * small_ls + JG * e * M2];
             }
+            long long smv2[DUAL ? KS : 1][4];
+            if constexpr (DUAL) {   // the second operand, in the same batch of loads (limbs beyond its size: the last one read again, masked in the chain)
+                const long long* small2_col = g.small2 + (long long)b * g.small2_bs + (long long)col * n + (ch ? m : 0) + cj2 + (long long)jq * M2;
+                const long long small2_ls = (long long)g.res_cols * n;
+#pragma unroll
+                for (int j = 0; j < KS; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) smv2[j][e] = small2_col[(long long)min(j, g.small2_size - 1) * small2_ls + JG * e * M2];
+            }
             __builtin_amdgcn_sched_barrier(0);
             long long carry[4] = {0, 0, 0, 0};
             long long* res_col = g.res + (long long)b * g.res_bs + (long long)col * n + (ch ? m : 0) + cj2 + (long long)jq * M2;
             const long long res_ls = (long long)g.res_cols * n;
+            long long carry2[DUAL ? 4 : 1];
+            long long* res2_col = nullptr;
+            if constexpr (DUAL) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) carry2[u] = 0;
+                res2_col = g.res2 + (long long)b * g.res2_bs + (long long)col * n + (ch ? m : 0) + cj2 + (long long)jq * M2;
+                for (int j = KS; j < g.res2_size; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) res2_col[(long long)j * res_ls + JG * e * M2] = 0;
+            }
             // limbs of res beyond the precision of the big value are zero (normalize.rs:118-120)
             for (int j = KS; j < g.res_size; ++j)
 #pragma unroll
@@ -316,9 +343,21 @@ __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneAr
             for (int j = KS - 1; j >= 0; --j) {
                 const bool has_body = small_col && j < g.small_size;
                 long long x1v[4];
+                long long x2v[DUAL ? 4 : 1];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     long long x = xin[2 * (((col * KS + j) * M1 + JG * e + jq) * RS + cj2) + ch];
+                    if constexpr (DUAL) {   // the second chain: small2 - big (limbs beyond small2: 0 - big)
+                        const unsigned long long s2 = j < g.small2_size ? (unsigned long long)smv2[j][e] : 0ull;
+                        const long long xb = (long long)(s2 - (unsigned long long)x);
+                        long long& cy = carry2[e];
+                        const unsigned long long y = (unsigned long long)xb + half;
+                        const long long d = (long long)(y & mask) - (long long)half;
+                        const long long cr = (long long)y >> k;
+                        const unsigned long long y2 = (unsigned long long)d + (unsigned long long)cy + half;
+                        x2v[e] = (long long)(y2 & mask) - (long long)half;
+                        cy = (long long)((unsigned long long)cr + (unsigned long long)((long long)y2 >> k));
+                    }
                     if (has_body) x = (long long)((unsigned long long)x + (unsigned long long)smv[j][e]);
                     long long& cy = carry[e];
                     const unsigned long long y = (unsigned long long)x + half;
@@ -331,6 +370,12 @@ __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneAr
                 if (j < g.res_size) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) st_stream(res_col + (long long)j * res_ls + JG * e * M2, x1v[e]);
+                }
+                if constexpr (DUAL) {
+                    if (j < g.res2_size) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) st_stream(res2_col + (long long)j * res_ls + JG * e * M2, x2v[e]);
+                    }
                 }
             }
         }

@@ -106,6 +106,9 @@ struct TailCall {
     unsigned auto_mul = 0;            // != 0: the value enters the chain as s(n) (big + small), s(n) = -1 iff (n auto_mul) mod 2N >= N
     bool auto_neg = false;            // flips every s(n)
     bool post_neg = false;            // put s(n) back on the digits (plain form: phi acts on the normalized value)
+    bool big_neg = false;             // the value enters the chain as small - big on every column (vec_znx_big_sub_small_a: limbs of big beyond the operand
+                                      // enter negated) - the second result of a conditional swap.  Needs small_all; on its own, not with auto_mul /
+                                      // post_neg / the gathered or prepared operands (launch_tail.hip expresses it through the kernel's sign and operand forms)
     bool keyauto = false;             // key switch by a permuted key (wave_keyauto_tail): every column's chain between the signs of auto_mul, body operand as it is
     unsigned gather_mul = 0;          // != 0: the operand is -+phi^-1(small), gathered inside the tail (older, non-spectral scheme)
     bool gather_neg = false;
@@ -248,6 +251,10 @@ struct SmallInvCall {
     bool post_rsh = false;
     // ---- blind rotation's accumulator between two blocks (product-free form) ----
     Digits small_digits = Digits::I64, res_digits = Digits::I64;
+    // ---- conditional swap (pz_glwe_cswap_batched): res2.p != null - a second result from the same big value, res2 = normalize(small2 - big) on
+    //      every column beside res = normalize(big + small); plain product form only, both containers with the columns of res ----
+    SmallRes res2;
+    SmallOperand small2;
 };
 int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c);
 // ONE kernel per call for N = 1024 / 2048 (device_small_one.hpp): forward transforms, product, inverse transforms and carry chains of a ciphertext in
@@ -260,6 +267,8 @@ struct SmallOneCall {
     SmallRes res;
     SmallOperand small;
     const SmallDiff* diff = nullptr;  // CMUX: the input polynomials are differences of two sources (src / smap are not read)
+    SmallRes res2;                    // conditional swap: res2.p != null - res2 = normalize(small2 - big) beside res (SmallInvCall)
+    SmallOperand small2;
 };
 int launch_small_one(pz_module* M, int batch, const SmallOneCall& c);
 

@@ -139,6 +139,11 @@ int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c) {
     const bool narrow = c.small_digits != Digits::I64 || c.res_digits != Digits::I64;
     if (narrow && !(noprod && base2k <= 31)) return fail(PZ_ERR_INVALID, "small-ring pipeline: 32-bit accumulator digits need the product-free form and base2k <= 31");
     g.S_out = c.fwd_S; g.tw1 = M->s_tw1; g.fwd_limbs = c.fwd_S ? fwd_limbs : 0;
+    const bool dual = c.res2.p != nullptr;
+    g.res2 = c.res2.p; g.small2 = c.small2.p; g.res2_bs = c.res2.bs; g.small2_bs = c.small2.bs; g.res2_size = c.res2.size; g.small2_size = c.small2.size;
+    if (dual && (noprod || au || c.fwd_S || narrow || c.small.p == nullptr || c.small.body_col >= 0 || c.small2.p == nullptr || c.small2.size < 1 ||
+                 c.res2.cols != c.res.cols || c.small2.cols != c.res.cols || c.small.cols != c.res.cols || c.res2.base2k != base2k))
+        return fail(PZ_ERR_INVALID, "small-ring pipeline: two results need the plain product form, an operand per column for each and one layout of columns");
     g.au_p = au_p; g.au_mode = au_mode; g.post_rsh = (post_rsh && au) ? 1 : 0;
     {   // p^-1 mod 2^32 by Newton steps (p odd), reduced mod 2n in the kernel
         unsigned x = au_p | 1u;
@@ -167,6 +172,7 @@ int launch_small_inv(pz_module* M, int batch, const SmallInvCall& c) {
         if (noprod && g.fwd_limbs) XFWD_##M1_(KS_)                                                            \
         else if (noprod) XL((k_small_inv<M1_, KS_, true>))                                                    \
         else if (au) XL((k_small_inv<M1_, KS_, false, false, true>))                                          \
+        else if (dual) XL((k_small_inv<M1_, KS_, false, false, false, true>))                                 \
         else XL((k_small_inv<M1_, KS_>))                                                                      \
         PZ_HIP(hipGetLastError());                                                                            \
         return PZ_OK;                                                                                         \
@@ -205,12 +211,19 @@ int launch_small_one(pz_module* M, int batch, const SmallOneCall& c) {
     g.tw1 = M->s_tw1; g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv; g.margin = M->probe ? M->margin : nullptr;
     g.diff = c.diff ? *c.diff : SmallDiff{nullptr, nullptr, c.smap, c.smap, 0, 0, 0u};
     const int src_form = !c.diff ? 0 : (c.diff->t ? 1 : 2);
+    const bool dual = c.res2.p != nullptr;
+    g.res2 = c.res2.p; g.small2 = c.small2.p; g.res2_bs = c.res2.bs; g.small2_bs = c.small2.bs; g.res2_size = c.res2.size; g.small2_size = c.small2.size;
+    if (dual && (src_form == 2 || c.small.p == nullptr || c.small.body_col >= 0 || c.small2.p == nullptr || c.small2.size < 1 || c.res2.cols != c.res.cols ||
+                 c.small2.cols != c.res.cols || c.small.cols != c.res.cols || c.res2.base2k != c.res.base2k))
+        return fail(PZ_ERR_INVALID, "one-kernel product: two results need an operand per column for each, one layout of columns, and no rotated source");
     const int m1 = small_m1(M);
     const size_t lds = ((size_t)8 * m1 * kSmallRS + kSmallM2 + m1) * sizeof(cplx);   // tile of 8 polynomials + wL2 + tw1inv
     KTimer kt(M, PZ_K_FUSED_TAIL);
 #define X(M1_, KS_)                                                                                           \
     if (m1 == M1_ && ksz == KS_) {                                                                            \
-        if (src_form == 0) PZ_TRY(launch_k((k_small_one<M1_, KS_, 0>), dim3(batch), dim3(512), lds, M->stream, g));        \
+        if (dual && src_form == 0) PZ_TRY(launch_k((k_small_one<M1_, KS_, 0, true>), dim3(batch), dim3(512), lds, M->stream, g));   \
+        else if (dual) PZ_TRY(launch_k((k_small_one<M1_, KS_, 1, true>), dim3(batch), dim3(512), lds, M->stream, g));              \
+        else if (src_form == 0) PZ_TRY(launch_k((k_small_one<M1_, KS_, 0>), dim3(batch), dim3(512), lds, M->stream, g));   \
         else if (src_form == 1) PZ_TRY(launch_k((k_small_one<M1_, KS_, 1>), dim3(batch), dim3(512), lds, M->stream, g));   \
         else PZ_TRY(launch_k((k_small_one<M1_, KS_, 2>), dim3(batch), dim3(512), lds, M->stream, g));                     \
         dispatch_note(M, "k_small_one<M1=%d,KS=%d> (one kernel per ciphertext, %d input polynomials)", M1_, KS_, npi); \

@@ -50,6 +50,12 @@ static TailArgs tail_args(const pz_module* M, const TailCall& c, int col_base, i
     g.xcd_map = 0;
     g.d16w = nz ? nz->d16.w : nullptr; g.d16a = nz ? nz->d16.ra : nullptr; g.d16b = nz ? nz->d16.rb : nullptr;
     if (c.small16) { g.d16a = c.small16; g.body_bs = c.small16_cs; }
+    if (c.big_neg) {
+        // small - big = -(big + (-small)): every sign flipped (auto_mul = 2N gives s(n) = +1 everywhere, auto_neg flips it) on the sum with the negated
+        // operand.  small_neg acts on the prepared-operand path: the body column's stream is column body_col of `small` itself, at the strides of `small`
+        g.auto_mul = 2u * (unsigned)M->n; g.auto_neg = 1; g.small_neg = 1; g.pre_body = 1;
+        g.body_src = c.small + (long long)c.body_col * (long long)M->n; g.body_bs = c.small_bs; g.body_ls = (long long)c.small_cols * (long long)M->n;
+    }
     g.body16_wide = nullptr;
     if (c.body16) { g.d16a = c.body16; g.body_bs = (long long)c.body16_limbs * (long long)M->n; g.body16_wide = c.body16_wide; }
     return g;
@@ -115,6 +121,10 @@ static int launch_inv_tail_cols(pz_module* M, const TailCall& c, int col_base, i
 // The body operand of a key switch only exists for one column (0; `body_col` for ggsw_expand_row): that column runs the
 // variant that prefetches it (more registers, one workgroup less per CU), the other columns the plain one.
 int launch_inv_tail(pz_module* M, const TailCall& c) {
+    if (c.big_neg && !(c.small != nullptr && c.small_all && c.auto_mul == 0 && !c.auto_neg && !c.post_neg && !c.small_neg && !c.post_rsh && !c.keyauto &&
+                       c.gather_mul == 0 && c.body_src == nullptr && !c.body16 && !c.small16 && !c.body_only && c.small_digits == Digits::I64 &&
+                       c.res_digits == Digits::I64))
+        return fail(PZ_ERR_INVALID, "fused tail: the negated big value takes an i64 operand per column and nothing else");
     if (c.post_rsh && !(c.small != nullptr && c.small_all)) return fail(PZ_ERR_UNSUPPORTED, "fused tail: shifted store needs an operand per column");
     // key switch by a permuted key (glwe_automorphism_key_automorphism, wave_keyauto_tail in api_glwe.hip): the carry chain of every column runs
     // between the signs of X -> X^p, s .* normalize(s .* big) - the body column on the operand variant (a0 at the natural index), the others

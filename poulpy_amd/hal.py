@@ -461,6 +461,24 @@ class Module:
         self._ck(self.lib.pz_glwe_blind_rotation_batched(self.handle, res, a, nb, ptrs, 1 if sign else 0, bit_lsh, C.byref(params), tmp, tmp_bytes,
                                                          batch))
 
+    def glwe_cswap_batched(self, a: c_void_p, b: c_void_p, ggsw_pmat: c_void_p, params: GlweOpParams, batch: int, *, a_size: int, b_size: int):
+        """poulpy-bin-fhe bdd_arithmetic/eval.rs:417-461 (one base2k), in place: (a, b) stays under a GGSW of 0 and becomes (b, a) under 1 - one
+        external product of b - a, both results from its one big value.  params.a_size = max(a_size, b_size), params.res_size = a_size."""
+        self._ck(self.lib.pz_glwe_cswap_batched(self.handle, a, a_size, b, b_size, ggsw_pmat, C.byref(params), batch))
+
+    def glwe_cswap_workspace_bytes(self, params: GlweOpParams, batch: int) -> int:
+        return self.lib.pz_glwe_cswap_workspace_bytes(self.handle, C.byref(params), batch)
+
+    def glwe_blind_retrieval_batched(self, slots: c_void_p, nslots: int, bit_ptrs, reverse: bool, params: GlweOpParams, batch: int):
+        """bdd_arithmetic/blind_retrieval.rs:195-266 on `batch` vectors of nslots ciphertexts, slot-major [nslots][batch]: slot 0 ends up holding the
+        element at the encrypted index (reverse: the network undone); bit_ptrs[i]: the device pointer of the prepared GGSW of bit i + bit_rsh."""
+        nb = len(bit_ptrs)
+        ptrs = _ptrs(bit_ptrs) if nb else (c_void_p * 1)()
+        self._ck(self.lib.pz_glwe_blind_retrieval_batched(self.handle, slots, nslots, nb, ptrs, 1 if reverse else 0, C.byref(params), batch))
+
+    def glwe_blind_retrieval_workspace_bytes(self, params: GlweOpParams, nslots: int, nbits: int, batch: int) -> int:
+        return self.lib.pz_glwe_blind_retrieval_workspace_bytes(self.handle, C.byref(params), nslots, nbits, batch)
+
     def ggsw_external_product(self, res: c_void_p, a: c_void_p, a_dnum: int, ggsw_pmat: c_void_p, params: GlweOpParams):
         """poulpy-core external_product/ggsw.rs:54-58 on a device-resident GGSW (MatZnx layout)."""
         self._ck(self.lib.pz_ggsw_external_product(self.handle, res, a, a_dnum, ggsw_pmat, C.byref(params)))
