@@ -6,13 +6,18 @@ LIB   := poulpy_amd/libpoulpy_hip.so
 all: $(LIB) oracle
 
 UNITS := $(wildcard $(CSRC)/*.hip)
-OBJS  := $(patsubst $(CSRC)/%.hip,$(CSRC)/_obj/%.o,$(UNITS))
+HOST_UNITS := $(wildcard $(CSRC)/*.cpp)   # plain C++, no HIP (the BDD schedule compiler)
+OBJS  := $(patsubst $(CSRC)/%.hip,$(CSRC)/_obj/%.o,$(UNITS)) $(patsubst $(CSRC)/%.cpp,$(CSRC)/_obj/%.o,$(HOST_UNITS))
 RCCL  := -ldl   # RCCL itself is dlopen-ed at the first pz_comm_* call (api_dist.hip)
 
 # one object per translation unit (make -j8 compiles them in parallel; launch_br.hip is the long pole, ~75 s)
 $(CSRC)/_obj/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/poulpy_hip.h
 	@mkdir -p $(CSRC)/_obj
 	cd $(CSRC) && $(HIPCC) -O3 -std=c++17 --offload-arch=gfx950 -fPIC -c $(notdir $<) -o _obj/$(notdir $@)
+
+$(CSRC)/_obj/%.o: $(CSRC)/%.cpp $(wildcard $(CSRC)/*.hpp)
+	@mkdir -p $(CSRC)/_obj
+	$(CXX) -O2 -std=c++17 -fPIC -c $< -o $@
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=gfx950 -fPIC -shared -o $@ $(OBJS) $(RCCL)
@@ -39,9 +44,14 @@ test-gpu:
 bench:
 	python bench.py
 
+# host-only check of the BDD schedule compiler under the host sanitizers (tests/test_bdd_host.py builds and runs the same program)
+cpp-test-bdd:
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_bdd_schedule.cpp $(CSRC)/bdd_schedule.cpp -o tests/cpp/test_bdd_schedule
+	tests/cpp/test_bdd_schedule
+
 clean:
-	rm -f $(LIB) tests/cpp/test_abi
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 
-.PHONY: all oracle cpp-test kres test-cpu test-gpu bench clean
+.PHONY: all oracle cpp-test cpp-test-bdd kres test-cpu test-gpu bench clean

@@ -434,6 +434,76 @@ int    pz_glwe_blind_retrieval_batched(pz_module* m, int64_t* slots, size_t nslo
                                        int reverse, const pz_glwe_op_params* p, size_t batch);
 /* the swap's figure at the largest level */
 size_t pz_glwe_blind_retrieval_workspace_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t nslots, size_t nbits, size_t batch);
+
+/* ---- BDD circuits: ExecuteBDDCircuit (poulpy-bin-fhe/src/bdd_arithmetic/eval.rs:104-305) --------------------------------------
+ * A circuit is one node list per output bit, in chunks of state_size nodes, one chunk per level (eval_level, :241-305).  The state is two banks
+ * of state_size GLWEs in the layout of the result, all zero but slot 1 of the 2 state_size, which is encode_coeff_i64(base2k, col 0, k = 2,
+ * idx 0, 1): the value 2^-2 at coefficient 0.  Per level, node j of the chunk:
+ *   PZ_BDD_CMUX(sel, hi, lo)   next[j] = cmux(prev[hi], prev[lo], GGSW(sel)) - pz_glwe_cmux_batched out of place, t = prev[hi], f = prev[lo]
+ *   PZ_BDD_COPY                next[j] = prev[j]
+ *   PZ_BDD_NONE                next[j] stays what it was
+ * then the banks are swapped.  The last chunk is [cmux, none, ...]: its gate writes the output bit.  An output with state_size 0 has no nodes
+ * and is zero. */
+typedef enum { PZ_BDD_NONE = 0, PZ_BDD_COPY = 1, PZ_BDD_CMUX = 2 } pz_bdd_kind;
+/* (declared WITH its tag, unlike the parameter structs of this header: poulpy_amd/abi.py lists untagged structs in abi.STRUCTS, whose exact contents -
+ * the six parameter structs - tests/test_abi_and_host.py pins; the node is typed from this declaration all the same, into abi.TAGGED_STRUCTS) */
+typedef struct pz_bdd_node { uint32_t kind, sel, hi, lo; } pz_bdd_node;
+typedef struct pz_bdd_circuit pz_bdd_circuit;
+/* Host only (no module, no device).  nodes[o] / node_count[o] / state_size[o]: the node list of output bit o, o < output_size; input_size:
+ * the number of input bits (every selector is below it).  Validates - node_count a positive multiple of state_size, hi and lo below
+ * state_size, sel below input_size, the last chunk [cmux, none, ...], no nodes on a state_size-0 output - and returns NULL on a violation,
+ * pz_last_error naming the output bit and the node.  Compiles the schedule the device runs:
+ *   levels   level l holds level l of every output that is that deep (start-aligned); all its gates are ONE launch, so no gate of a level
+ *            writes a slot a gate of the same level reads or writes
+ *   slots    every live value has a physical slot, at most 2 state_size per output, plus two shared by all: slot 0 = zero, slot 1 = one.
+ *            A COPY moves nothing: the value keeps its slot and its readers are pointed at it (moved_copies == 0)
+ *   order    the gates of a level sorted by selector; the root gates write the output itself
+ * The handle is immutable and may be used by any number of modules and threads; freeing it before a module that has run it is safe (a module
+ * keeps its own device copy of the tables). */
+pz_bdd_circuit* pz_bdd_circuit_new(const pz_bdd_node* const* nodes, const size_t* node_count, const size_t* state_size, size_t output_size,
+                                   size_t input_size);
+void   pz_bdd_circuit_free(pz_bdd_circuit* c);
+size_t pz_bdd_circuit_input_size(const pz_bdd_circuit* c);
+size_t pz_bdd_circuit_output_size(const pz_bdd_circuit* c);
+size_t pz_bdd_circuit_max_state_size(const pz_bdd_circuit* c);
+size_t pz_bdd_circuit_levels(const pz_bdd_circuit* c);         /* launches of the gathered route */
+size_t pz_bdd_circuit_gates(const pz_bdd_circuit* c);          /* = the CMUX nodes of the circuit */
+size_t pz_bdd_circuit_moved_copies(const pz_bdd_circuit* c);   /* COPY nodes that cost a ciphertext copy: 0 */
+size_t pz_bdd_circuit_slots(const pz_bdd_circuit* c);          /* the two shared slots + every output's */
+/* the slots of output bit o: [*first, *first + *count), count <= 2 state_size; returns 0, or -1 for an o out of range */
+int    pz_bdd_circuit_output_slots(const pz_bdd_circuit* c, size_t o, size_t* first, size_t* count);
+/* the gates of level `level` as 4 words each - t slot, f slot, res (a slot, or 0x80000000 | output bit), selector - the first `cap` of them into
+ * gates4 (may be NULL with cap 0); returns the number of gates of the level */
+size_t pz_bdd_circuit_level_gates(const pz_bdd_circuit* c, size_t level, uint32_t* gates4, size_t cap);
+/* ExecuteBDDCircuit::execute_bdd_circuit on `batch` independent inputs; bit-identical to the node-by-node walk through pz_glwe_cmux_batched.
+ *   out    dense slot-major device buffer [n_out][batch] of GLWEs of p->res_size limbs, n_out >= output_size; output bit o of input b at
+ *          out + (o * batch + b) * n * (rank + 1) * res_size.  Slots of state_size-0 outputs and slots beyond output_size are zeroed (:225-237).
+ *          out overlaps neither tmp nor a key: PZ_ERR_ALIAS
+ *   bits   HOST array [batch][nbits], nbits >= input_size: bits[b * nbits + i] = the prepared GGSW of input bit i of input b, resolved as for
+ *          every GLWE call (pinned, host with a device mirror, device); the same pointer may occur many times; an entry the circuit never
+ *          selects may be NULL, a selected NULL entry is PZ_ERR_INVALID.  Host-resident entries cost what they cost every GLWE call - each distinct one
+ *          is fingerprinted on EVERY call to validate its mirror (a sampled hash: its first and last 4 KiB and about 8 000 words strided over
+ *          the rest, read on the host) - and a module holds at most 64 mirrors (48 GiB):
+ *          more distinct host-resident selected GGSWs than that in one call is PZ_ERR_UNSUPPORTED, nothing launched; keys of an adder belong on the device
+ *   p      rank, the GGSWs (dnum, any dsize >= 1, key_size, key_base2k), a_size == res_size (take_glwe_slice(.., res): one layout), ONE
+ *          base2k for state, result and GGSWs; anything else PZ_ERR_INVALID with nothing launched
+ *   tmp    device scratch of pz_bdd_circuit_execute_tmp_bytes:
+ *            align256(slots * batch * ct)                      the state pool, ct = n * (rank + 1) * res_size * 8
+ *          + align256(gates * batch * 32)                      the per-call gather table
+ *          + align256(batch * nbits * 8)                       the per-call key pointers, nbits = input_size in the query (a call with a
+ *                                                              larger nbits needs batch * (nbits - input_size) * 8 more)
+ *          + batch * selected * align256(key bytes)            row-sliced copies of the selected keys that are not pinned (worst case: all
+ *                                                              distinct, none pinned); key bytes = n * 8 * dnum * (rank + 1)^2 * key_size
+ *          a short tmp is refused before anything is launched
+ * Routes: N = 1024 / 2048 / 4096 on the small-ring kernels (dsize 1, fusion on) run every level as ONE launch of the gathered CMUX kernels
+ * ("bdd: gathered small-one" / "bdd: gathered small two-kernel"); every other shape - and every shape under POULPY_DBG_BDD_GATHER=0 - runs the
+ * same schedule by one CMUX per (gate, input) on the existing kernels ("bdd: per-gate (...)").  The module's grow-only workspace is reserved
+ * as the CMUX does it.  A call repeated with the same arguments is replayed as one HIP graph (pz_module_set_graphs); the keys are not part of
+ * the graph on the gathered route - a new bits array behind the same arguments is picked up.
+ * batch == 0 or output_size == 0: PZ_OK; only the zeroing of out happens, if any. */
+size_t pz_bdd_circuit_execute_tmp_bytes(const pz_module* m, const pz_bdd_circuit* c, const pz_glwe_op_params* p, size_t batch);
+int    pz_bdd_circuit_execute_batched(pz_module* m, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                                      const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
 /* CoreImpl ggsw_external_product (poulpy-core/src/external_product/ggsw.rs:54-58): res[row][col] = a[row][col] (x) ggsw
  * for the a_dnum * (rank+1) GLWE entries of the GGSW `a` (MatZnx layout: entries are contiguous), device pointers. */
 int pz_ggsw_external_product(pz_module* m, int64_t* res, const int64_t* a, size_t a_dnum, const double* ggsw_pmat,

@@ -187,6 +187,15 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
     size_t glwe_blind_retrieval_workspace_bytes(const pz_glwe_op_params& p, size_t nslots, size_t nbits, size_t batch) const {
         return pz_glwe_blind_retrieval_workspace_bytes(m_, &p, nslots, nbits, batch);
     }
+    // ExecuteBDDCircuit::execute_bdd_circuit (bdd_arithmetic/eval.rs:123-239) on `batch` inputs: c = a compiled circuit (BddCircuit below), out = dense
+    // [n_out][batch], bits = HOST array [batch][nbits] of prepared GGSWs (null where the circuit never selects the bit), tmp = device scratch
+    size_t bdd_circuit_execute_tmp_bytes(const pz_bdd_circuit* c, const pz_glwe_op_params& p, size_t batch) const {
+        return pz_bdd_circuit_execute_tmp_bytes(m_, c, &p, batch);
+    }
+    void bdd_circuit_execute_batched(const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                                     const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_bdd_circuit_execute_batched(m_, c, out, n_out, bits, nbits, &p, tmp, tmp_bytes, batch), "bdd_circuit_execute_batched");
+    }
     void blind_rotation_execute_batched(int64_t* res, const int64_t* lwe_2n, const int64_t* lut, const double* brk, const pz_blind_rotation_params& p, size_t batch) {
         check(pz_blind_rotation_execute_batched(m_, res, lwe_2n, lut, brk, &p, batch), "blind_rotation_execute_batched");
     }
@@ -329,6 +338,31 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
 
   private:
     pz_module* m_ = nullptr;
+};
+
+// A BDD circuit in the evaluator's node format (bdd_arithmetic/eval.rs:22-63, 318-332), validated and compiled on the host: outputs[o] = the node list
+// of output bit o, state_size[o] its state size.  Throws pz::Error with a message naming the output bit and the node when the circuit is malformed.
+class BddCircuit {
+  public:
+    BddCircuit(const std::vector<std::vector<pz_bdd_node>>& outputs, const std::vector<size_t>& state_size, size_t input_size) {
+        if (outputs.size() != state_size.size()) throw Error(PZ_ERR_INVALID, "BddCircuit: one state size per output");
+        std::vector<const pz_bdd_node*> ptrs;
+        std::vector<size_t> counts;
+        for (const auto& o : outputs) { ptrs.push_back(o.data()); counts.push_back(o.size()); }
+        c_ = pz_bdd_circuit_new(ptrs.data(), counts.data(), state_size.data(), outputs.size(), input_size);
+        if (!c_) throw Error(PZ_ERR_INVALID, std::string("BddCircuit: ") + pz_last_error());
+    }
+    ~BddCircuit() { pz_bdd_circuit_free(c_); }
+    BddCircuit(const BddCircuit&) = delete;
+    BddCircuit& operator=(const BddCircuit&) = delete;
+    const pz_bdd_circuit* raw() const { return c_; }
+    size_t input_size() const { return pz_bdd_circuit_input_size(c_); }
+    size_t output_size() const { return pz_bdd_circuit_output_size(c_); }
+    size_t levels() const { return pz_bdd_circuit_levels(c_); }
+    size_t gates() const { return pz_bdd_circuit_gates(c_); }
+
+  private:
+    pz_bdd_circuit* c_ = nullptr;
 };
 
 }  // namespace pz

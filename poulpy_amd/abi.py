@@ -3,7 +3,9 @@
 `parse()` is the one header parser: tools/gen_rust_ffi.py renders the Rust `extern "C"` block from it, and importing this module
 builds the ctypes view of the header from it:
 
-* one ``ctypes.Structure`` per ``typedef struct``, under its C name (``pz_glwe_op_params``, ...), in ``STRUCTS``;
+* one ``ctypes.Structure`` per ``typedef struct``, under its C name (``pz_glwe_op_params``, ...), in ``STRUCTS`` - the parameter
+  structs, declared without a tag; a struct declared WITH its tag (``typedef struct pz_bdd_node {...} pz_bdd_node;``: an element type
+  of an array argument, not a parameter block) is typed the same way and listed in ``TAGGED_STRUCTS``;
 * the enum constants (``PZ_OK``, ``PZ_AUTO_ADD``, ``PZ_K_FUSED_TAIL``, ...), in ``CONSTANTS``;
 * ``PROTOTYPES``: ``name -> (restype, argtypes)`` of every ``pz_*`` function, which hal.load_library() applies.
 
@@ -48,6 +50,7 @@ def parse(header_text: str):
                 fields.append((name.strip(), first))
         structs.append((m.group(2), fields))
     text_wo = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    text_wo = re.sub(TAGGED_STRUCT, " ", text_wo, flags=re.S)
     for m in re.finditer(r"(?:typedef\s+)?enum\s*\{(.*?)\}\s*(\w*)\s*;", text_wo, flags=re.S):
         vals, nxt = [], 0
         for item in m.group(1).split(","):
@@ -81,6 +84,25 @@ def parse(header_text: str):
     return structs, enums, funcs
 
 
+TAGGED_STRUCT = r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;"
+
+
+def parse_tagged(header_text: str):
+    """-> [(name, [(field, C type)])] of the structs declared with their tag, in header order."""
+    text = re.sub(r"#[^\n]*", " ", strip_comments(header_text))
+    out = []
+    for m in re.finditer(TAGGED_STRUCT, text, flags=re.S):
+        assert m.group(1) == m.group(3), m.group(0)
+        fields = []
+        for decl in m.group(2).split(";"):
+            decl = " ".join(decl.split())
+            if decl:
+                first, rest = decl.split(" ", 1)
+                fields += [(name.strip(), first) for name in rest.split(",")]
+        out.append((m.group(3), fields))
+    return out
+
+
 def _ctype(decl: str, structs: dict, ret: bool = False):
     """C type of a parameter, field or return value -> ctypes type (None: a void return)."""
     toks = decl.replace("*", " * ").split()
@@ -101,11 +123,17 @@ def _load():
     for name, fields in structs:
         classes[name] = type(name, (C.Structure,), {"_fields_": [(f, _ctype(t, classes)) for f, t in fields],
                                                     "__doc__": f"{name} (include/poulpy_hip.h)"})
+    tagged = {}
+    for name, fields in parse_tagged(open(HEADER).read()):
+        tagged[name] = type(name, (C.Structure,), {"_fields_": [(f, _ctype(t, classes)) for f, t in fields],
+                                                   "__doc__": f"{name} (include/poulpy_hip.h)"})
     constants = {k: v for _, vals in enums for k, v in vals}
-    protos = {name: (_ctype(ret, classes, ret=True), [_ctype(t, classes) for _, t in args]) for name, ret, args in funcs}
-    return classes, constants, protos
+    known = {**classes, **tagged}
+    protos = {name: (_ctype(ret, known, ret=True), [_ctype(t, known) for _, t in args]) for name, ret, args in funcs}
+    return classes, tagged, constants, protos
 
 
-STRUCTS, CONSTANTS, PROTOTYPES = _load()
+STRUCTS, TAGGED_STRUCTS, CONSTANTS, PROTOTYPES = _load()
 globals().update(STRUCTS)
+globals().update(TAGGED_STRUCTS)
 globals().update(CONSTANTS)

@@ -189,7 +189,7 @@ int resolve_key(pz_module* M, const double* pmat, size_t bytes, const double** o
     }
     size_t total = bytes;
     for (auto& mr : M->mirrors) total += mr.bytes;
-    while (!M->mirrors.empty() && (M->mirrors.size() >= 64 || total > ((size_t)48 << 30))) {   // LRU: at most 64 keys / 48 GiB mirrored
+    while (!M->mirrors.empty() && (M->mirrors.size() >= kKeyMirrorMax || total > kKeyMirrorBytes)) {   // LRU: at most 64 keys / 48 GiB mirrored
         size_t lru = 0;
         for (size_t i = 1; i < M->mirrors.size(); ++i) if (M->mirrors[i].stamp < M->mirrors[lru].stamp) lru = i;
         total -= M->mirrors[lru].bytes;
@@ -320,6 +320,9 @@ void pz_module_free(pz_module* M) {
     for (auto& c : M->arena) (void)hipFree(c.p);
     for (auto& k : M->pinned) if (k.sliced) (void)hipFree(k.sliced);
     for (auto& mr : M->mirrors) if (mr.dev) (void)hipFree(mr.dev);
+    for (auto& bt : M->bdd_tables) { (void)hipFree(bt.gates); (void)hipFree(bt.level_start); }
+    if (M->bdd_stage) (void)hipHostFree(M->bdd_stage);
+    if (M->bdd_stage_ev) (void)hipEventDestroy(M->bdd_stage_ev);
     if (M->comm) (void)pz_comm_destroy(M);
     for (auto& t : M->timed) { (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); }
     for (auto e : M->event_pool) (void)hipEventDestroy(e);

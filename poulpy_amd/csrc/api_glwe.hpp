@@ -96,7 +96,10 @@ struct OpLayout {
 // api.hip: drops the device mirror of a host-resident prepared key (a rewritten buffer's mirror would be stale)
 int forget_host_key(pz_module* M, const void* host);
 void host_key_invalidate(const void* p, size_t bytes);   // api.hip: process-wide (every module's mirrors of that host range)
-// api.hip: device pointer of a prepared key - itself when it is one, else its validated (possibly refreshed) device mirror
+// api.hip: device pointer of a prepared key - itself when it is one, else its validated (possibly refreshed) device mirror.  A module keeps at most
+// kKeyMirrorMax mirrors / kKeyMirrorBytes of them; beyond that the least recently used one is FREED - a call that resolves several host keys must
+// not need more of them at once than fit (pz_bdd_circuit_execute_batched checks before it resolves the first one)
+constexpr size_t kKeyMirrorMax = 64, kKeyMirrorBytes = (size_t)48 << 30;
 int resolve_key(pz_module* M, const double* pmat, size_t bytes, const double** out);
 
 // what a call of glwe_op computes; the values are the `keyswitch` argument of pz_glwe_op_workspace_bytes

@@ -175,6 +175,15 @@ struct SmallDiff {
     unsigned rot;         // rotated form, mod 2n: coefficient i of t is f[(i - rot) mod 2n], negated where that index is >= n
 };
 
+// Gathered CMUX (pz_bdd_circuit_execute_batched): ciphertext c of a launch takes its two sources, its result and its row-sliced key from
+// entry c of a device table instead of base + c * stride and one key.  All three ciphertexts have the layout of the result; res is no source of the launch.
+struct SmallGather {
+    const long long* t;   // minuend (the value a set bit selects)
+    const long long* f;   // subtrahend, and the operand added on every column
+    long long* res;
+    const cplx* Pp;       // P'[q1][r][c][q2] of this ciphertext's GGSW
+};
+
 // Rust `(x).round() as i64`: half away from zero, saturating, NaN -> 0 (reim/conversion.rs:43-60).
 // Branch-free: round = trunc(x) +- 1 when the (exactly computed) fraction reaches one half.
 __device__ __forceinline__ double round_half_away(double x) {

@@ -60,14 +60,22 @@ struct SmallOneArgs {
 // DUAL (Cswap::cswap): stage F runs two carry chains on the coefficient's big value x - x + small into res, small2 - x into res2; both operands are
 // loaded at the positions the thread then stores, before its first store (in place on both: nobody else touches them; stage A read both sources
 // of the whole ciphertext four barriers earlier).
-template <int M1, int KS, int SRC = 0, bool DUAL = false>
-__global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneArgs g) {   // (waves per SIMD: two workgroups per CU at N = 1024, one at 2048)
+// GATHER (the BDD evaluator's level launches, SRC = 1): workgroup c takes t, f (= the operand), res and the key from tab[c]; everything else - shape,
+// strides inside a ciphertext, tables - from g as before.  A compile-time form: the kernels below instantiate the body with GATHER fixed.
+template <int M1, int KS, int SRC, bool DUAL, bool GATHER>
+__device__ __forceinline__ void small_one_body(SmallOneArgs& g, const SmallGather* __restrict__ tab) {
+    static_assert(!GATHER || (SRC == 1 && !DUAL), "gathered form: the two-source CMUX with one result");
     constexpr int NT = 512, M2 = kSmallM2, RS = kSmallRS, CO = 2, NPO = CO * KS, PP = M1 / 4;
     constexpr long long m = (long long)M1 * M2, n = 2 * m;
     static_assert(M1 == 4 || M1 == 8, "one-kernel product: N = 1024 / 2048 (see the capacity argument above)");
     extern __shared__ cplx lds[];   // tile: 8 polynomials x M1 rows x RS | wL2[128] | tw1inv[M1]
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
+    int b = blockIdx.x;
+    if constexpr (GATHER) {   // this workgroup's ciphertexts: addressed as ciphertext 0 of their own pointers
+        const SmallGather e = tab[blockIdx.x];
+        g.diff.t = e.t; g.diff.f = e.f; g.small = e.f; g.res = e.res; g.Pp = e.Pp;
+        b = 0;
+    }
     cplx* wl = lds + 8 * M1 * RS;
     cplx* tw1i = wl + M2;
     if (tid < M2) wl[tid] = g.wL2[tid];
@@ -388,6 +396,14 @@ __global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneAr
                (int)blockIdx.x, tid >> 6, (unsigned long long)(so_t - so_t0), so_acc[0], so_acc[1], so_acc[2], so_acc[3], so_acc[4], so_acc[5], so_acc[6], so_acc[7], so_acc[8], so_acc[9], so_acc[10], so_acc[11]);
 #endif
 #undef PZ_OSTAMP
+}
+template <int M1, int KS, int SRC = 0, bool DUAL = false>
+__global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one(SmallOneArgs g) {   // (waves per SIMD: two workgroups per CU at N = 1024, one at 2048)
+    small_one_body<M1, KS, SRC, DUAL, false>(g, nullptr);
+}
+template <int M1, int KS>
+__global__ void __launch_bounds__(512, (M1 == 4 ? 4 : 2)) k_small_one_gather(SmallOneArgs g, const SmallGather* __restrict__ tab) {
+    small_one_body<M1, KS, 1, false, true>(g, tab);
 }
 
 }  // namespace pz

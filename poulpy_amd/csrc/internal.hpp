@@ -4,6 +4,8 @@
 //   launch_tail.hip  fused inverse column pass + carry chain (k_inv_tail)
 //   launch_mid.hip   fused row pass + VMP + inverse row pass (device_mid.hpp), key re-slicing
 //   launch_small.hip small-ring pipelines for N = 1024 / 2048 / 4096: whole polynomials in LDS (device_small.hpp, device_small_one.hpp)
+//   launch_bdd.hip   the BDD evaluator's gather table and the gathered forms of the small-ring CMUX kernels
+//   bdd_schedule.cpp the BDD circuit compiler (plain C++, no HIP)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
@@ -271,6 +273,33 @@ struct SmallOneCall {
     SmallOperand small2;
 };
 int launch_small_one(pz_module* M, int batch, const SmallOneCall& c);
+
+int ensure_small_tables(pz_module* M);   // the m = M1 x 128 tables of the small-ring kernels, built on first use
+
+// ---- launch_bdd.hip -----------------------------------------------------------------------------------------------
+// The BDD evaluator's kernels (pz_bdd_circuit_execute_batched): the per-call gather table, and the gathered forms of the small-ring
+// CMUX kernels - one launch per level, ciphertext c of the launch addressed through tab[c] (SmallGather, device_fft.hpp).
+struct BddGate;
+struct BddTableCall {
+    const BddGate* gates = nullptr;          // device: the circuit's compact level tables (immutable)
+    const uint32_t* level_start = nullptr;   // device: levels + 1 offsets
+    int levels = 0;
+    uint32_t total = 0;                      // gates of all levels
+    int batch = 0, nbits = 0;
+    long long* state = nullptr;              // slot-major [slots][batch]
+    long long* out = nullptr;                // slot-major [n_out][batch]
+    long long ct = 0;                        // i64 elements of one ciphertext
+    const cplx* const* keys = nullptr;       // device: [batch][nbits] row-sliced keys (entries the circuit never selects are not read)
+    SmallGather* tab = nullptr;              // out: level l at tab + level_start[l] * batch, input-major, the level's gates (sorted by selector) inside
+};
+int launch_bdd_table(pz_module* M, const BddTableCall& c);
+// the constant one of the initial state in a zeroed slot: digits d0 / d1 at limbs 0 / 1 of coefficient 0, column 0 (limb_stride elements apart)
+int launch_bdd_one(pz_module* M, long long* slot, long long ct, int batch, long long limb_stride, long long d0, long long d1, int used);
+struct SmallGatherShape { int cols = 0, size = 0, ksz = 0, dnum = 0, base2k = 0; };   // t, f and res: `size` limbs of `cols` columns
+bool small_one_gather_supported(const pz_module* M, const SmallGatherShape& s);
+int launch_small_one_gather(pz_module* M, int batch, const SmallGatherShape& s, const SmallGather* tab);
+int launch_small_fwd_gather(pz_module* M, int batch, const SmallGatherShape& s, const SmallGather* tab, cplx* S);
+int launch_small_inv_gather(pz_module* M, int batch, const SmallGatherShape& s, const SmallGather* tab, const cplx* S);
 
 // ---- launch_ops.hip -----------------------------------------------------------------------------------------------
 int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_ls, const void* a, long long a_bs,

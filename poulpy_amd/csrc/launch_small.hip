@@ -19,7 +19,7 @@ bool small_supported(const pz_module* M, int npi, int key_limbs) {
 
 // The small pipeline splits m = M1 x 128 whatever the module's own plan is (N = 1024 / 2048 use 16 x 32 / 32 x 32 for the per-op kernels):
 // its four tables are built on first use — the module's own where the plan already is M1 x 128 (N = 4096).
-static int ensure_small_tables(pz_module* M) {
+int ensure_small_tables(pz_module* M) {
     if (M->s_tw1) return PZ_OK;
     const int m1 = small_m1(M);
     if (M->plan.m1 == m1 && M->plan.m2 == kSmallM2) {

@@ -21,8 +21,8 @@
 
 namespace pz {
 
-// Run-time switches: the twelve a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
-// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST, _CMUX_FUSED;
+// Run-time switches: the thirteen a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
+// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST, _CMUX_FUSED, _BDD_GATHER;
 // DESIGN.md section 9).
 inline int rt_knob(const char* name, int dflt) {
     const char* e = getenv(name);
@@ -193,6 +193,15 @@ struct pz_module {
     // API call returns (canary_verify, from PZ_ENTER's scope object).  An overrun into the slack between segments stays bit-exact
     // and therefore invisible to the parity tests (the spectral automorphism's body operand).
     std::vector<void*> guards;
+    // device copies of the level tables of the BDD circuits this module has run (api_glwe.hip, pz_bdd_circuit_execute_batched): found by the circuit's
+    // id, never by its address - the handle may be freed and its address reused; freed with the module, the least recently used one beyond 16
+    struct BddTables { uint64_t uid; void* gates; void* level_start; uint64_t stamp; };
+    std::vector<BddTables> bdd_tables;
+    // page-locked host staging of a call's key-pointer array: the copy engine reads it after the call has returned, so the next call waits for
+    // bdd_stage_ev (recorded behind the copy) before it rewrites the buffer
+    const void** bdd_stage = nullptr;
+    size_t bdd_stage_count = 0;
+    hipEvent_t bdd_stage_ev = nullptr;
     // the distinct kernel instantiations the hot dispatch sites chose since the last pz_module_dispatch_notes(reset) (bench tools print
     // them next to their numbers: "which variant ran" is part of a measurement)
     std::vector<std::string> notes;

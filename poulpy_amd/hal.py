@@ -479,6 +479,28 @@ class Module:
     def glwe_blind_retrieval_workspace_bytes(self, params: GlweOpParams, nslots: int, nbits: int, batch: int) -> int:
         return self.lib.pz_glwe_blind_retrieval_workspace_bytes(self.handle, C.byref(params), nslots, nbits, batch)
 
+    # -- BDD circuits (poulpy-bin-fhe bdd_arithmetic/eval.rs:104-305) -------------------------------------------------------
+    def bdd_circuit_new(self, circuit) -> c_void_p:
+        """pz_bdd_circuit_new: validate and compile `circuit` (poulpy_amd.bdd.Circuit, or anything with input_size and outputs = [(nodes,
+        state_size)], a node being (kind, sel, hi, lo)); host only - see bdd_circuit_new below.  Free with bdd_circuit_free."""
+        return bdd_circuit_new(circuit, self.lib)
+
+    def bdd_circuit_free(self, handle: c_void_p):
+        self.lib.pz_bdd_circuit_free(handle)
+
+    def bdd_circuit_execute_tmp_bytes(self, handle: c_void_p, params: GlweOpParams, batch: int) -> int:
+        return self.lib.pz_bdd_circuit_execute_tmp_bytes(self.handle, handle, C.byref(params), batch)
+
+    def bdd_circuit_execute_batched(self, handle: c_void_p, out: c_void_p, n_out: int, bits, params: GlweOpParams, tmp: c_void_p, tmp_bytes: int,
+                                    batch: int):
+        """ExecuteBDDCircuit on `batch` inputs: out = dense slot-major [n_out][batch]; bits[b][i] = the prepared GGSW of input bit i of input b
+        (a pointer, or None where the circuit never selects the bit); every row has the same length nbits >= input_size."""
+        nbits = len(bits[0]) if batch else 0
+        assert all(len(row) == nbits for row in bits) and len(bits) == batch
+        flat = [0 if p is None else (p.value if isinstance(p, c_void_p) else int(p)) or 0 for row in bits for p in row]
+        arr = (c_void_p * max(len(flat), 1))(*flat)
+        self._ck(self.lib.pz_bdd_circuit_execute_batched(self.handle, handle, out, n_out, arr, nbits, C.byref(params), tmp, tmp_bytes, batch))
+
     def ggsw_external_product(self, res: c_void_p, a: c_void_p, a_dnum: int, ggsw_pmat: c_void_p, params: GlweOpParams):
         """poulpy-core external_product/ggsw.rs:54-58 on a device-resident GGSW (MatZnx layout)."""
         self._ck(self.lib.pz_ggsw_external_product(self.handle, res, a, a_dnum, ggsw_pmat, C.byref(params)))
@@ -818,3 +840,25 @@ class Module:
         ms = C.c_float()
         self._ck(self.lib.pz_event_elapsed_ms(e0, e1, C.byref(ms)))
         return ms.value
+
+
+BddNode = abi.pz_bdd_node
+
+
+def bdd_circuit_new(circuit, lib: C.CDLL | None = None) -> c_void_p:
+    """pz_bdd_circuit_new on a circuit in the evaluator's node format: host only (no module, no device).  Raises PoulpyHipError with the
+    library's message - it names the output bit and the node - when the circuit is not well formed."""
+    lib = lib or load_library()
+    outs = list(circuit.outputs)
+    arrays = [(BddNode * max(len(nodes), 1))(*[BddNode(*nd) for nd in nodes]) for nodes, _ in outs]
+    ptrs = (c_void_p * max(len(outs), 1))(*[C.addressof(a) for a in arrays])
+    counts = (C.c_size_t * max(len(outs), 1))(*[len(nodes) for nodes, _ in outs])
+    states = (C.c_size_t * max(len(outs), 1))(*[int(s) for _, s in outs])
+    handle = lib.pz_bdd_circuit_new(ptrs, counts, states, len(outs), int(circuit.input_size))
+    if not handle:
+        raise PoulpyHipError(f"[{abi.PZ_ERR_INVALID}] {lib.pz_last_error().decode()}")
+    return c_void_p(handle)
+
+
+def bdd_circuit_free(handle: c_void_p, lib: C.CDLL | None = None):
+    (lib or load_library()).pz_bdd_circuit_free(handle)

@@ -27,7 +27,7 @@ mod core_impl;
 #[cfg(feature = "core-fused")]
 pub mod batched;
 #[cfg(feature = "core-fused")]
-pub use batched::{AutomorphismMode, DeviceBuf, DeviceVecZnx, DeviceVecZnxDft, DeviceVmpPMat, HipBatched, HipBatchedCore, TensorMode};
+pub use batched::{AutomorphismMode, BddCircuit, BddNode, DeviceBuf, DeviceVecZnx, DeviceVecZnxDft, DeviceVmpPMat, HipBatched, HipBatchedCore, TensorMode};
 
 #[cfg(test)]
 mod tests;
