@@ -4,8 +4,8 @@ tests/test_core_semantics.py (oracle) and tests/test_gpu_core_semantics.py (devi
 device: keys and ciphertexts come from tests/fhe_sk.py, and each case carries what every output must decrypt to and the reference's bound.
 
 The other families built the same way: tests/key_ops_cases.py (automorphism-key composition, the GGSW forms), tests/tensor_cases.py
-(tensoring, relinearization, the one-call multiply, the plaintext and constant products) and tests/trace_cases.py (trace, packing).  LWE
-conversions and blind rotation remain."""
+(tensoring, relinearization, the one-call multiply, the plaintext and constant products), tests/trace_cases.py (trace, packing) and
+tests/lwe_cases.py (LWE key switch, LWE <-> GLWE conversion, blind rotation, the gate bootstrap chain, circuit bootstrapping)."""
 from __future__ import annotations
 
 import math

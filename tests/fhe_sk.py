@@ -20,6 +20,9 @@ BOUND = 6.0 * SIGMA
 
 # above this ring degree the products go through numpy.fft (checked to lie within 1/4 of an integer before rounding)
 SCHOOLBOOK_MAX_N = 4096
+# mul_small takes the same FFT route from this ring degree on where its digits allow (keys of many entries: a blind-rotation key)
+FFT_MIN_N = 512
+FFT_MAX_DIGIT = 1 << 24      # |result| <= N 2^24 <= 2^41 up to N = 2^17, far below 2^52
 
 
 def limbs_for(k: int, base2k: int) -> int:
@@ -65,12 +68,13 @@ def galois_inv(p: int, n: int) -> int:
 
 
 def mul_small(a: np.ndarray, s: np.ndarray) -> np.ndarray:
-    """a * s in Z[X]/(X^N+1) along the last axis, exactly: a int64 digits (|a| < 2^17), s a small secret polynomial (|s| <= 1)."""
+    """a * s in Z[X]/(X^N+1) along the last axis, exactly: a int64 digits (|a| < 2^24 on the FFT route), s a small secret polynomial
+    (|s| <= 1)."""
     a = np.asarray(a, dtype=np.int64)
     s = np.asarray(s, dtype=np.int64)
     n = a.shape[-1]
     assert s.shape == (n,) and np.abs(s).max(initial=0) <= 1
-    if n <= SCHOOLBOOK_MAX_N:
+    if n <= SCHOOLBOOK_MAX_N and (n < FFT_MIN_N or np.abs(a).max(initial=0) >= FFT_MAX_DIGIT):
         out = np.zeros_like(a)
         for k in np.flatnonzero(s):
             r = np.roll(a, int(k), axis=-1)
@@ -80,8 +84,8 @@ def mul_small(a: np.ndarray, s: np.ndarray) -> np.ndarray:
             else:
                 out -= r
         return out
-    # negacyclic product by a twisted cyclic FFT: |result| <= N 2^17 < 2^34, far below 2^52
-    assert np.abs(a).max(initial=0) < (1 << 17)
+    # negacyclic product by a twisted cyclic FFT, its rounding checked below
+    assert np.abs(a).max(initial=0) < FFT_MAX_DIGIT and n <= (1 << 17)
     w = np.exp(1j * np.pi * np.arange(n) / n)
     c = np.fft.ifft(np.fft.fft(a * w, axis=-1) * np.fft.fft(s * w), axis=-1) / w
     r = np.rint(c.real)
@@ -372,3 +376,189 @@ def glwe_tensor_phase(ct: np.ndarray, sk: np.ndarray, base2k: int, reverse_pairs
                 col = rank * (rank + 1) // 2 - 1 - col
             body += mul_small(normalize(mul_small(ct[:, rank + 1 + col], sk[i]), base2k), sk[j])
     return body
+
+
+# ---- LWE: secrets, encryption, phase (poulpy-core layouts/lwe_secret.rs, encryption/lwe.rs, decryption/lwe.rs) ----
+# an LWE is a (size, n_lwe + 1) int64 array, limb i = [b, a_0 .. a_{n_lwe - 1}]: the body at index 0, the mask behind it
+def ternary_lwe_secret(n_lwe: int, rng: np.random.Generator, prob: float = 0.5) -> np.ndarray:
+    """lwe_secret.rs:61-64: (n_lwe,) in {-1, 0, 1}."""
+    return ternary_secret(n_lwe, 1, rng, prob)[0]
+
+
+def binary_block_secret(n_lwe: int, block_size: int, rng: np.random.Generator) -> np.ndarray:
+    """lwe_secret.rs:81 / scalar_znx.rs:154-166: every block of block_size coefficients holds at most one 1, at an index drawn uniformly
+    from 0 .. block_size (block_size itself: none)."""
+    assert n_lwe % block_size == 0
+    s = np.zeros(n_lwe, dtype=np.int64)
+    for blk in range(0, n_lwe, block_size):
+        idx = int(rng.integers(0, block_size + 1))
+        if idx != block_size:
+            s[blk + idx] = 1
+    return s
+
+
+def encode_int(value: int, base2k: int, k: int, size: int | None = None) -> np.ndarray:
+    """encode_coeff_i64 (encoding.rs:116-155) of one integer: value 2^-k as (size, 1) normalized limbs."""
+    return encode(np.array([int(value)], dtype=np.int64), base2k, k, limbs_for(k, base2k) if size is None else size)
+
+
+def _div_round(a: int, b: int) -> int:
+    """encoding.rs:311-320: round half away from zero."""
+    q, r = abs(a) // b, abs(a) % b
+    q += 2 * r >= b
+    return q if a >= 0 else -q
+
+
+def decode_coeff(limbs: np.ndarray, base2k: int, k: int, idx: int = 0) -> int:
+    """decode_coeff_i64 (encoding.rs:240-263): the integer that coefficient idx of the (size, n) limbs holds at 2^-k; the last limb used
+    is rounded to the bits it has above 2^-k."""
+    size = limbs_for(k, base2k)
+    rem = base2k - (k % base2k)
+    res = 0
+    for j in range(size):
+        x = int(limbs[j][idx])
+        if j == size - 1 and rem != base2k:
+            res = (res << ((base2k - rem) % base2k)) + _div_round(x, 1 << rem)
+        else:
+            res = (res << base2k) + x
+    return res
+
+
+def lwe_encrypt(sk: np.ndarray, value_limbs: np.ndarray, base2k: int, k: int, rng: np.random.Generator, sigma: float = SIGMA) -> np.ndarray:
+    """encryption/lwe.rs:88-120: the mask uniform, b = pt - <a, s> + e limb by limb (limbs the plaintext lacks: -<a, s>), e of deviation
+    sigma at 2^-k, the body normalized.  value_limbs: (size_pt,) or (size_pt, 1) at base2k.  (size, n_lwe + 1), size = ceil(k / base2k)."""
+    n_lwe = sk.shape[0]
+    size = limbs_for(k, base2k)
+    pt = np.asarray(value_limbs, dtype=np.int64).reshape(-1)
+    ct = np.empty((size, n_lwe + 1), dtype=np.int64)
+    ct[:, 1:] = uniform_digits((size, n_lwe), base2k, rng)
+    body = -(ct[:, 1:] @ sk.astype(np.int64))
+    m = min(size, pt.shape[0])
+    body[:m] += pt[:m]
+    body[size - 1] += int(gaussian(1, rng, sigma)[0]) << (base2k * size - k)
+    ct[:, 0] = normalize(body[:, None], base2k)[:, 0]
+    return ct
+
+
+def lwe_phase(ct: np.ndarray, sk: np.ndarray) -> np.ndarray:
+    """decryption/lwe.rs: b + <a, s> per limb (un-normalized, exact), as (size, 1) limbs."""
+    return (ct[:, 0] + ct[:, 1:] @ sk.astype(np.int64))[:, None]
+
+
+def lwe_decrypt(ct: np.ndarray, sk: np.ndarray, base2k: int) -> np.ndarray:
+    """The normalized phase, (size, 1)."""
+    return normalize(lwe_phase(ct, sk), base2k)
+
+
+def lwe_error(ct: np.ndarray, ct_base2k: int, sk: np.ndarray, pt_want: np.ndarray, pt_base2k: int) -> float:
+    """phase(ct) - pt_want as a centred torus value."""
+    return float(torus_diff(lwe_phase(ct, sk), ct_base2k, np.asarray(pt_want).reshape(-1, 1), pt_base2k)[0])
+
+
+def rms_log2(errors) -> float:
+    """log2 of the root mean square of a few error samples (an LWE has one coefficient: the deviation is taken over the batch, about zero)."""
+    e = np.asarray(list(errors), dtype=np.float64)
+    r = float(np.sqrt(np.mean(e * e)))
+    return math.log2(r) if r > 0 else -math.inf
+
+
+def lwe_noise_log2(cts, ct_base2k: int, sk: np.ndarray, pts_want, pt_base2k: int) -> float:
+    return rms_log2(lwe_error(ct, ct_base2k, sk, pt, pt_base2k) for ct, pt in zip(cts, pts_want))
+
+
+def rebase(limbs: np.ndarray, from_base2k: int, to_base2k: int, size: int) -> np.ndarray:
+    """The torus value of (size_a, n) limbs at from_base2k as `size` normalized limbs at to_base2k (vec_znx_normalize across bases, offset
+    0), for values the target holds exactly: dropped bits must be zero."""
+    ka, kr = from_base2k * limbs.shape[0], to_base2k * size
+    v = to_int(normalize(limbs, from_base2k), from_base2k)
+    if kr >= ka:
+        v = v * (1 << (kr - ka))
+    else:
+        assert all(int(x) % (1 << (ka - kr)) == 0 for x in v.reshape(-1)), "rebase would round"
+        v = v // (1 << (ka - kr))
+    return torus_from_int(v, kr, to_base2k)
+
+
+def lwe_as_glwe_secret(sk_lwe: np.ndarray, n: int, embed: bool = True) -> np.ndarray:
+    """phi_{-1}(s_lwe || 0) as a rank-1 GLWE secret, (1, n) (lwe_switching_key.rs:101-107): the constant coefficient of a(X) phi_{-1}(s)(X)
+    is <a, s>.  embed=False leaves phi_{-1} out (a negative control)."""
+    s = np.zeros((1, n), dtype=np.int64)
+    s[0, :sk_lwe.shape[0]] = sk_lwe
+    return automorphism(s, -1) if embed else s
+
+
+def lwe_switching_key(sk_lwe_in, sk_lwe_out, n, base2k, k, dnum, rng, dsize: int = 1) -> np.ndarray:
+    """lwe_switching_key.rs:95-109: the rank-1 GLWE switching key between the two embedded secrets."""
+    return switching_key(lwe_as_glwe_secret(sk_lwe_in, n), lwe_as_glwe_secret(sk_lwe_out, n), base2k, k, dnum, dsize, rng)
+
+
+def lwe_to_glwe_key(sk_lwe, sk_glwe, base2k, k, dnum, rng, dsize: int = 1, embed: bool = True) -> np.ndarray:
+    """lwe_to_glwe_key.rs:92-99: the GGLWE of the embedded LWE secret under sk_glwe."""
+    return gglwe_encrypt(sk_glwe, lwe_as_glwe_secret(sk_lwe, sk_glwe.shape[1], embed), base2k, k, dnum, dsize, rng)
+
+
+def glwe_to_lwe_key(sk_lwe, sk_glwe, base2k, k, dnum, rng, dsize: int = 1, embed: bool = True) -> np.ndarray:
+    """glwe_to_lwe_key.rs:88-107: the GGLWE of sk_glwe under the embedded LWE secret (rank_in = rank of sk_glwe, rank_out = 1)."""
+    return gglwe_encrypt(lwe_as_glwe_secret(sk_lwe, sk_glwe.shape[1], embed), sk_glwe, base2k, k, dnum, dsize, rng)
+
+
+# ---- blind rotation (poulpy-bin-fhe blind_rotation: algorithms/cggi/key.rs, lut.rs, algorithms/mod.rs) ----
+def blind_rotation_key(sk_glwe, sk_lwe, base2k, k, dnum, rng, dsize: int = 1) -> np.ndarray:
+    """cggi/key.rs:53-59: entry i is the GGSW under sk_glwe of the constant polynomial s_lwe[i].  (n_lwe, dnum, rank + 1, size, rank + 1, n)."""
+    n = sk_glwe.shape[1]
+    keys = []
+    for bit in sk_lwe:
+        msg = np.zeros(n, dtype=np.int64)
+        msg[0] = int(bit)
+        keys.append(ggsw_encrypt(sk_glwe, msg, base2k, k, dnum, dsize, rng))
+    return np.stack(keys)
+
+
+def lut_rotate(data: np.ndarray, k: int) -> np.ndarray:
+    """lut.rs:342-363: X^k on a table of ext polynomials, data (ext, size, n), in Z[X]/(X^(n ext) + 1) where polynomial i holds the
+    coefficients i, i + ext, ...: the first ext - k_lo polynomials turn by k_hi, the others by k_hi + 1, then the list turns by k_lo."""
+    ext, _, n = data.shape
+    two_n_ext = 2 * n * ext
+    k_pos = int(k) % two_n_ext
+    k_hi, k_lo = k_pos // ext, k_pos % ext
+    out = [rotate(data[i], k_hi if i < ext - k_lo else k_hi + 1) for i in range(ext)]
+    return np.stack(out[ext - k_lo:] + out[:ext - k_lo])
+
+
+def lut_set(f, k: int, n: int, ext: int, base2k: int, lut_k: int, with_drift: bool = True):
+    """lut.rs:271-340: the table of f (at most n values) at k message bits: value f[i] 2^-k on the step coefficients [i step, (i + 1) step)
+    of the domain n ext, step = round(domain / len(f)); polynomial j takes the coefficients j, j + ext, ...; every polynomial normalized;
+    the whole turned by -drift, drift = step / 2, so that a phase within half a step of i step reads f[i].  with_drift=False leaves that
+    turn out (a negative control).  Returns (data (ext, size, n), drift)."""
+    f = [int(x) for x in f]
+    assert len(f) <= n and ext > 0 and ext & (ext - 1) == 0
+    limbs = limbs_for(k, base2k)
+    size = limbs_for(lut_k, base2k)
+    assert limbs <= size
+    scale = 1 << (base2k - k % base2k) if k % base2k else 1
+    domain = n * ext
+    step = (domain + len(f) // 2) // len(f)
+    full = np.zeros((size, domain), dtype=np.int64)
+    for i, fi in enumerate(f):
+        full[limbs - 1, i * step:(i + 1) * step] = fi * scale
+    data = np.stack([normalize(full[:, j::ext], base2k) for j in range(ext)])
+    drift = step >> 1
+    return (lut_rotate(data, -drift) if with_drift else data), drift
+
+
+def mod_switch_2n(n2: int, lwe: np.ndarray, base2k: int, negate: bool) -> np.ndarray:
+    """algorithms/mod.rs:136-176 on exact integers: the (size, n_lwe + 1) LWE to n_lwe + 1 exponents at n2 = 2 N ext; negate (direction
+    Left) flips every sign first.  One limb wider than log2n: rounded to its top bits; else limbs are concatenated (the last one partly)."""
+    log2n = (n2 - 1).bit_length() + 1
+    res = [-int(x) if negate else int(x) for x in lwe[0]]
+    if base2k > log2n:
+        diff = base2k - (log2n - 1)
+        return np.array([(x + (1 << (diff - 1))) >> diff for x in res], dtype=np.int64)
+    rem = base2k - (log2n % base2k)
+    size = limbs_for(log2n, base2k)
+    for i in range(1, size):
+        if i == size - 1 and rem != base2k:
+            res = [(y << (base2k - rem)) + (int(x) >> rem) for x, y in zip(lwe[i], res)]
+        else:
+            res = [(y << base2k) + int(x) for x, y in zip(lwe[i], res)]
+    return np.array(res, dtype=np.int64)

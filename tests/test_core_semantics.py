@@ -29,12 +29,12 @@ def test_toolkit_products_and_fresh_noise():
     n = 8192
     a = fs.uniform_digits((2, n), 17, rng)
     s = fs.ternary_secret(n, 1, rng)[0]
-    old = fs.SCHOOLBOOK_MAX_N
+    old = fs.SCHOOLBOOK_MAX_N, fs.FFT_MIN_N
     try:
-        fs.SCHOOLBOOK_MAX_N = n
+        fs.SCHOOLBOOK_MAX_N, fs.FFT_MIN_N = n, 2 * n
         slow = fs.mul_small(a, s)
     finally:
-        fs.SCHOOLBOOK_MAX_N = old
+        fs.SCHOOLBOOK_MAX_N, fs.FFT_MIN_N = old
     assert np.array_equal(fs.mul_small(a, s), slow)
     assert np.array_equal(fs.mul_small(fs.rotate(a, 3), s), fs.rotate(slow, 3))
     for (n, rank, base2k, k) in ((256, 2, 17, 65), (65536, 1, 12, 96)):
