@@ -714,6 +714,27 @@ int pz_glwe_from_lwe_batched(pz_module* m, int64_t* res, const int64_t* lwe, siz
  * p->rank -> 1 into a GLWE with the LWE's base and size, sample extract.  a = batch GLWEs (p->rank + 1, p->a_size). */
 int pz_lwe_from_glwe_batched(pz_module* m, int64_t* res, size_t res_n_lwe, const int64_t* a, size_t a_idx, const double* ksk_pmat,
                              const pz_glwe_op_params* p, size_t batch);
+/* lwe_from_glwe of every one of `batch` GLWEs at every one of `nidx` coefficient indices (the bits of FheUint words):
+ * one launch chain over all nidx * batch ciphertexts.  Where the one-kernel small-ring key switch serves the shape with every object in
+ * the key's base (N = 1024) X^-idx[j] is applied where that kernel reads its source, from a per-ciphertext device table, and
+ * the rotated copies are never written; elsewhere ONE table-driven rotation launch writes them.  Then one batched key switch, one
+ * fused tail.  Index-major result: LWE (j, b) at res + (j*batch + b) * (res_n_lwe+1) * p->res_size.  Bit-identical to nidx calls of
+ * pz_lwe_from_glwe_batched; idx[j] == 0 is no special case.
+ *   idx      HOST array of nidx coefficient indices, each < n
+ *   res      may be NULL when lwe_2n is given (the LWE limbs are then never written)
+ *   lwe_2n   optional: the nidx * batch vectors [b, a_1 .. a_n_lwe] of mod_switch_2n(n2, negate) of the results, in the order of
+ *            res, written by the kernel that extracts the sample (base2k = p->res_base2k; n2 / negate as for
+ *            pz_lwe_mod_switch_2n_batched); NULL: no mod switch
+ *   tmp      device scratch of pz_lwe_from_glwe_many_tmp_bytes */
+size_t pz_lwe_from_glwe_many_tmp_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t nidx, size_t batch);
+int pz_lwe_from_glwe_many_batched(pz_module* m, int64_t* res, size_t res_n_lwe, const int64_t* a, size_t nidx, const size_t* idx /*HOST*/,
+                                  const double* ksk_pmat, const pz_glwe_op_params* p, int64_t* lwe_2n, size_t n2, int negate, void* tmp,
+                                  size_t tmp_bytes, size_t batch);
+/* ggsw_prepare (poulpy-core GGSWPrepare: vmp_prepare of the GGSW's MatZnx) on `count` contiguous GGSWs, device to device: MatZnx layout
+ * in (rows = dnum, cols_in = cols_out = rank+1, `size` limbs), VmpPMat layout out.  The transform of pz_vmp_prepare on one grid over
+ * all count * dnum * (rank+1)^2 * size polynomials (one launch pair, or one per workspace chunk): equal as bytes to pz_vmp_prepare on
+ * each matrix.  No host-key bookkeeping: both pointers are device pointers, and pmat must not overlap ggsw (PZ_ERR_ALIAS). */
+int pz_ggsw_prepare_batched(pz_module* m, double* pmat, const int64_t* ggsw, size_t count, size_t dnum, size_t rank, size_t size);
 /* execute_block_binary_extended (algorithm.rs:121-273): extension_factor > 1 (a power of two), block_size > 1.  lwe_2n is the
  * output of mod_switch_2n(2 * n * extension_factor); lut = the extension_factor polynomials lut.data[j], each
  * VecZnx(1, lut_size), contiguous; tmp = device scratch of pz_blind_rotation_extended_tmp_bytes; batch * extension_factor
@@ -770,6 +791,43 @@ int pz_circuit_bootstrapping_execute_to_exponent_batched(pz_module* m, int64_t* 
                                                          const double* const* tsk_pmats, const pz_circuit_bootstrapping_params* p,
                                                          size_t log_gap_in, size_t log_gap_out, size_t log_domain, void* tmp,
                                                          size_t tmp_bytes, size_t batch);
+/* FheUintPrepared::prepare (poulpy-bin-fhe/src/bdd_arithmetic/ciphertexts/fhe_uint_prepared.rs:399-460, fhe_uint_prepare_custom) on
+ * `batch` FheUint words: each word is one GLWE (rank+1 columns, ks_glwe.a_size limbs, or ks_lwe.a_size without ks_glwe) carrying bit i
+ * at coefficient bit_index(i) << log_gap, bit_index(i) = ((i & 7) << log2(word_bits / 8)) | (i >> 3), log_gap = log2(n / word_bits)
+ * (bdd_arithmetic/mod.rs:97-99, fhe_uint.rs:384).  Per bit i in [bit_start, bit_start + bit_count), in the reference's order:
+ *   get_bit_lwe (fhe_uint.rs:369-399): [glwe_keyswitch by ks_glwe] -> X^-coefficient -> glwe_keyswitch by ks_lwe -> sample extract
+ *   mod_switch_2n(2 n, negated: constant mode keeps the table's default direction, Left) -> circuit bootstrapping to constant
+ *   (log_domain = 1, extension_factor = 1) -> ggsw_prepare
+ * The reference runs the ks_glwe key switch once per BIT on the same word; it is deterministic, so this call runs it ONCE PER WORD and
+ * takes every bit from that one result - the outputs are the same bits.  Bits outside the range are zeroed (ggsw_zero, :453-459).
+ *   words         batch GLWEs
+ *   ks_glwe_pmat  may be NULL; else the rank -> ks_glwe.rank_out key switch of fhe_uint.rs:385-394 (ks_glwe.res_* = the intermediate:
+ *                 the LWE key's base, k = min(ks_lwe.max_k, word.max_k)); then ks_lwe.rank = ks_glwe.rank_out and ks_lwe.a_* = ks_glwe.res_*
+ *   ks_lwe_pmat   the rank -> 1 key switch of lwe_from_glwe; ks_lwe.res_size / res_base2k = lwe_size / lwe_base2k
+ *   lut .. tsk_pmats   exactly as pz_circuit_bootstrapping_execute_to_constant_batched takes them
+ *   res_pmat      word-major [batch][word_bits] prepared GGSWs (rows = cbt.res_dnum, cols = cbt.br.rank+1, size = cbt.res_size)
+ *   ggsw_out      optional, same order: the unprepared i64 GGSWs       lwe_out   optional: [batch][bit_count] LWEs (n_lwe+1, lwe_size)
+ *   tmp           device scratch; pz_fhe_uint_prepare_tmp_bytes(m, p, batch, 0) holds every bit of every word at once,
+ *                 (m, p, batch, chunk_bits) the call's fixed part + `chunk_bits` (word, bit) pairs per pass: the call splits
+ *                 batch * bit_count into the passes that fit tmp (each at most 65535, the blind rotation's limit).
+ * Plain stream launches.  Refused with PZ_ERR_INVALID before anything is launched: a null params / key / table pointer, word_bits
+ * not one of the five, n no multiple of it, a bit range that leaves the word, an LWE or key-switch shape that is empty or does not
+ * chain (ks_glwe -> ks_lwe -> LWE), limbs that do not reach 2n in mod_switch_2n, a tmp below one pair per pass.  The remaining shape
+ * checks of the circuit bootstrapping (its bases, atk_glwe_size, trace_size) and of the key switches are made by those stages
+ * themselves: such a call also returns PZ_ERR_INVALID, but the zero fills and the stages in front of the refusing one have run. */
+struct pz_fhe_uint_prepare_params {
+    pz_circuit_bootstrapping_params cbt;
+    pz_glwe_op_params ks_glwe, ks_lwe;
+    uint64_t n_lwe, lwe_size, lwe_base2k;
+    uint64_t word_bits;           /* 8 / 16 / 32 / 64 / 128; n is a multiple of it */
+    uint64_t bit_start, bit_count;
+};
+typedef struct pz_fhe_uint_prepare_params pz_fhe_uint_prepare_params;
+size_t pz_fhe_uint_prepare_tmp_bytes(const pz_module* m, const pz_fhe_uint_prepare_params* p, size_t batch, size_t chunk_bits);
+int pz_fhe_uint_prepare_batched(pz_module* m, double* res_pmat, int64_t* ggsw_out, int64_t* lwe_out, const int64_t* words,
+                                const double* ks_glwe_pmat, const double* ks_lwe_pmat, const int64_t* lut, const double* brk, size_t nsteps,
+                                const int64_t* gals, const double* const* atk_pmats, const double* const* tsk_pmats,
+                                const pz_fhe_uint_prepare_params* p, void* tmp, size_t tmp_bytes, size_t batch);
 /* device workspace the GLWE-level calls reserve for `batch` ciphertexts, for the pipeline the call will actually take (fused
  * three-kernel or five-kernel) incl. the growth slack of the module's grow-only arena; keyswitch: 0 external product, 1 key switch,
  * 2 automorphism family, 3 tensor relinearization */

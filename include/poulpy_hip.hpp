@@ -226,6 +226,29 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
         check(pz_circuit_bootstrapping_execute_to_constant_batched(m_, ggsw, lwe_2n, lut, brk, nsteps, gals, atk, tsk, &p, tmp, tmp_bytes, batch),
               "circuit_bootstrapping_execute_to_constant_batched");
     }
+    size_t lwe_from_glwe_many_tmp_bytes(const pz_glwe_op_params& p, size_t nidx, size_t batch) const {
+        return pz_lwe_from_glwe_many_tmp_bytes(m_, &p, nidx, batch);
+    }
+    void lwe_from_glwe_many_batched(int64_t* res, size_t res_n_lwe, const int64_t* a, size_t nidx, const size_t* idx, const double* ksk,
+                                    const pz_glwe_op_params& p, int64_t* lwe_2n, size_t n2, bool negate, void* tmp, size_t tmp_bytes,
+                                    size_t batch) {
+        check(pz_lwe_from_glwe_many_batched(m_, res, res_n_lwe, a, nidx, idx, ksk, &p, lwe_2n, n2, negate ? 1 : 0, tmp, tmp_bytes, batch),
+              "lwe_from_glwe_many_batched");
+    }
+    void ggsw_prepare_batched(double* pmat, const int64_t* ggsw, size_t count, size_t dnum, size_t rank, size_t size) {
+        check(pz_ggsw_prepare_batched(m_, pmat, ggsw, count, dnum, rank, size), "ggsw_prepare_batched");
+    }
+    size_t fhe_uint_prepare_tmp_bytes(const pz_fhe_uint_prepare_params& p, size_t batch, size_t chunk_bits = 0) const {
+        return pz_fhe_uint_prepare_tmp_bytes(m_, &p, batch, chunk_bits);
+    }
+    void fhe_uint_prepare_batched(double* res_pmat, int64_t* ggsw_out, int64_t* lwe_out, const int64_t* words, const double* ks_glwe,
+                                  const double* ks_lwe, const int64_t* lut, const double* brk, size_t nsteps, const int64_t* gals,
+                                  const double* const* atk, const double* const* tsk, const pz_fhe_uint_prepare_params& p, void* tmp,
+                                  size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_prepare_batched(m_, res_pmat, ggsw_out, lwe_out, words, ks_glwe, ks_lwe, lut, brk, nsteps, gals, atk, tsk, &p, tmp,
+                                          tmp_bytes, batch),
+              "fhe_uint_prepare_batched");
+    }
     void circuit_bootstrapping_execute_to_exponent_batched(int64_t* ggsw, const int64_t* lwe_2n, const int64_t* lut, const double* brk,
                                                            const int64_t* gals, const double* const* atk, const double* const* tsk,
                                                            const pz_circuit_bootstrapping_params& p, size_t log_gap_in, size_t log_gap_out,

@@ -6,6 +6,10 @@ builds the ctypes view of the header from it:
 * one ``ctypes.Structure`` per ``typedef struct``, under its C name (``pz_glwe_op_params``, ...), in ``STRUCTS`` - the parameter
   structs, declared without a tag; a struct declared WITH its tag (``typedef struct pz_bdd_node {...} pz_bdd_node;``: an element type
   of an array argument, not a parameter block) is typed the same way and listed in ``TAGGED_STRUCTS``;
+* a struct composed OF parameter structs and declared ``struct name {...};`` with its typedef on a line of its own
+  (``pz_fhe_uint_prepare_params``) is typed the same way and listed in ``COMPOSITE_STRUCTS``; a pointer to one is passed as ``c_void_p``
+  (``byref(...)``), like every pointer that is not to a parameter block.  (``STRUCTS`` is the list of the parameter BLOCKS, flat or
+  with one block inside, which tests/test_abi_and_host.py pins; a struct that aggregates several of them is kept apart from it.)
 * the enum constants (``PZ_OK``, ``PZ_AUTO_ADD``, ``PZ_K_FUSED_TAIL``, ...), in ``CONSTANTS``;
 * ``PROTOTYPES``: ``name -> (restype, argtypes)`` of every ``pz_*`` function, which hal.load_library() applies.
 
@@ -51,6 +55,7 @@ def parse(header_text: str):
         structs.append((m.group(2), fields))
     text_wo = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
     text_wo = re.sub(TAGGED_STRUCT, " ", text_wo, flags=re.S)
+    text_wo = re.sub(COMPOSITE_STRUCT, " ", text_wo, flags=re.S)
     for m in re.finditer(r"(?:typedef\s+)?enum\s*\{(.*?)\}\s*(\w*)\s*;", text_wo, flags=re.S):
         vals, nxt = [], 0
         for item in m.group(1).split(","):
@@ -85,6 +90,24 @@ def parse(header_text: str):
 
 
 TAGGED_STRUCT = r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;"
+
+
+COMPOSITE_STRUCT = r"(?<![\w])(?<!typedef )struct\s+(\w+)\s*\{([^{}]*)\}\s*;"
+
+
+def parse_composite(header_text: str):
+    """-> [(name, [(field, C type)])] of the structs declared `struct name {...};` (their typedef follows on its own), in header order."""
+    text = re.sub(r"#[^\n]*", " ", strip_comments(header_text))
+    out = []
+    for m in re.finditer(COMPOSITE_STRUCT, text, flags=re.S):
+        fields = []
+        for decl in m.group(2).split(";"):
+            decl = " ".join(decl.split())
+            if decl:
+                first, rest = decl.split(" ", 1)
+                fields += [(name.strip(), first) for name in rest.split(",")]
+        out.append((m.group(1), fields))
+    return out
 
 
 def parse_tagged(header_text: str):
@@ -127,13 +150,18 @@ def _load():
     for name, fields in parse_tagged(open(HEADER).read()):
         tagged[name] = type(name, (C.Structure,), {"_fields_": [(f, _ctype(t, classes)) for f, t in fields],
                                                    "__doc__": f"{name} (include/poulpy_hip.h)"})
+    composite = {}
+    for name, fields in parse_composite(open(HEADER).read()):
+        composite[name] = type(name, (C.Structure,), {"_fields_": [(f, _ctype(t, classes)) for f, t in fields],
+                                                      "__doc__": f"{name} (include/poulpy_hip.h)"})
     constants = {k: v for _, vals in enums for k, v in vals}
     known = {**classes, **tagged}
     protos = {name: (_ctype(ret, known, ret=True), [_ctype(t, known) for _, t in args]) for name, ret, args in funcs}
-    return classes, tagged, constants, protos
+    return classes, tagged, composite, constants, protos
 
 
-STRUCTS, TAGGED_STRUCTS, CONSTANTS, PROTOTYPES = _load()
+STRUCTS, TAGGED_STRUCTS, COMPOSITE_STRUCTS, CONSTANTS, PROTOTYPES = _load()
 globals().update(STRUCTS)
 globals().update(TAGGED_STRUCTS)
+globals().update(COMPOSITE_STRUCTS)
 globals().update(CONSTANTS)

@@ -289,3 +289,63 @@ def execute_bdd_circuit(mod, circuit, out, bits, params, batch: int, tmp=None):
     finally:
         if own:
             mod.bdd_circuit_free(handle)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# FheUint words (bdd_arithmetic/ciphertexts/fhe_uint.rs): one GLWE per integer, bit i at coefficient bit_index(i) << log_gap.  A word becomes
+# the evaluator's selectors through fhe_uint_prepare (pz_fhe_uint_prepare_batched), the evaluator's output a word again through fhe_uint_pack.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def bit_index(i: int, word_bits: int) -> int:
+    """bdd_arithmetic/mod.rs:97-99: the bytes of a word are interleaved - bit i of the integer lies at ((i & 7) << LOG_BYTES) | (i >> 3)."""
+    assert word_bits in (8, 16, 32, 64, 128) and 0 <= i < word_bits
+    log_bytes = (word_bits // 8).bit_length() - 1
+    return ((i & 7) << log_bytes) | (i >> 3)
+
+
+def fhe_uint_prepare(mod, res_pmat, words, key, params, batch: int, tmp=None, ggsw_out=None, lwe_out=None) -> list:
+    """FheUintPrepared::prepare (fhe_uint_prepared.rs:399-460) on `batch` words: pz_fhe_uint_prepare_batched.
+
+    res_pmat: device pointer to batch * word_bits prepared GGSWs (word-major).  words: device pointer to the batch GLWEs.  key: an object with
+    the device pointers ks_glwe (or None), ks_lwe, lut, brk, the list gals and the pointer lists atk, tsk.  params: FheUintPrepareParams.
+    tmp: a DeviceBuffer of at least mod.fhe_uint_prepare_tmp_bytes(params, batch, chunk) bytes for some chunk >= 1; allocated for the whole
+    batch, and freed, here when absent (the call is synchronized then).
+    Returns bits[b][i], the device address of the prepared GGSW of bit i of word b: the table execute_bdd_circuit takes; the rows of two
+    words concatenate to the 2 w inputs of adder / sub / ltu."""
+    need = mod.fhe_uint_prepare_tmp_bytes(params, batch)
+    buf = tmp if tmp is not None else mod.device_alloc(max(need, 8))
+    try:
+        mod.fhe_uint_prepare_batched(res_pmat, words, key.ks_glwe, key.ks_lwe, key.lut, key.brk, key.gals, key.atk, key.tsk, params, buf.ptr,
+                                     buf.nbytes, batch, ggsw_out=ggsw_out, lwe_out=lwe_out)
+        if tmp is None:
+            mod.sync()
+    finally:
+        if tmp is None:
+            buf.free()
+    cols = int(params.cbt.br.rank) + 1
+    ggsw_bytes = int(params.cbt.res_dnum) * cols * cols * int(params.cbt.res_size) * mod.n() * 8
+    w = int(params.word_bits)
+    base = _addr(res_pmat)
+    return [[base + (b * w + i) * ggsw_bytes for i in range(w)] for b in range(batch)]
+
+
+def fhe_uint_pack(mod, res, out, word_bits: int, gals, key_ptrs, params, batch: int, tmp=None, index=bit_index):
+    """FheUint::pack (fhe_uint.rs:239-255) on `batch` words through pz_glwe_pack_batched: out = the evaluator's dense slot-major buffer
+    [word_bits][batch] (slot s = bit s of every word; CLOBBERED), res = device pointer to the batch packed words.  gals / key_ptrs: the
+    log2(n) trace steps (-1, then 5^(2^(i-1))) and their prepared automorphism keys; params: a_size = res_size = the limbs of the GLWEs.
+    index (tests: a negative control) maps a bit to its slot of the word."""
+    n = mod.n()
+    assert n % word_bits == 0 and params.a_size == params.res_size
+    log_gap = (n // word_bits).bit_length() - 1
+    ct_bytes = batch * n * (int(params.rank) + 1) * int(params.res_size) * 8
+    base = _addr(out)
+    cts = [c_void_p(base + s * ct_bytes) for s in range(word_bits)]
+    indices = [index(s, word_bits) << log_gap for s in range(word_bits)]
+    need = mod.glwe_pack_tmp_bytes(params, batch)
+    buf = tmp if tmp is not None else mod.device_alloc(max(need, 8))
+    try:
+        mod.glwe_pack_batched(res, indices, cts, log_gap, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch)
+        if tmp is None:
+            mod.sync()
+    finally:
+        if tmp is None:
+            buf.free()

@@ -707,3 +707,12 @@ int pz_glwe_pack_bases_batched(pz_module* M, int64_t* res, size_t nslots, const 
 }
 
 }  // extern "C"
+
+namespace pz {
+// the constant-mode circuit bootstrapping on plain stream launches, for a caller that holds the module lock (pz_fhe_uint_prepare_batched)
+int circuit_bootstrapping_nolock(pz_module* M, int64_t* ggsw, const int64_t* lwe_2n, const int64_t* lut, const double* brk, size_t nsteps,
+                                 const int64_t* gals, const double* const* atk_pmats, const double* const* tsk_pmats,
+                                 const pz_circuit_bootstrapping_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    return circuit_bootstrapping(M, ggsw, lwe_2n, lut, brk, nsteps, gals, atk_pmats, tsk_pmats, p, tmp, tmp_bytes, batch);
+}
+}  // namespace pz

@@ -215,6 +215,9 @@ struct GlweCall {
     int64_t* res2 = nullptr;
     long long res2_bs = 0;
     int res2_size = 0;
+    // rotated-source key switch (glwe_keyswitch_rot below): ciphertext b of the call is X^rot of ciphertext `word` of `a`, (word, rot) =
+    // rot_tab[b] on the device; the one-kernel small-ring form applies the rotation where it reads the mask columns and the body operand
+    const RotSrc* rot_tab = nullptr;
     int64_t* res2_at(size_t b0) const { return res2 + (long long)b0 * res2_bs; }
     int cols_in() const { return s.cols_in; }
     int64_t* res_at(size_t b0) const { return res + (long long)b0 * res_bs; }
@@ -244,6 +247,7 @@ size_t pz_glwe_op_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p
 // the wave's input in the key's base: `a` itself, or glwe_normalize into a_conv (external_product/glwe.rs:124-132)
 static int wave_input(const GlweCall& c, size_t b0, int nb, int64_t* a_conv, DV* av) {
     if (c.diff) { *av = DV{nullptr, c.a_bs, c.s.cols_a, (int)c.p->a_size}; return PZ_OK; }   // (CMUX, fused routes: the forward stage reads c.diff)
+    if (c.rot_tab) { *av = DV{(void*)c.a, c.a_bs, c.s.cols_a, (int)c.p->a_size}; return PZ_OK; }   // (the table names the source ciphertext: no wave offset)
     *av = DV{(void*)(c.a + (long long)b0 * c.a_bs), c.a_bs, c.s.cols_a, (int)c.p->a_size};
     if (!c.s.convert) return PZ_OK;
     DV cv{a_conv, c.n * c.s.cols_a * c.s.a_size_eff, c.s.cols_a, c.s.a_size_eff};
@@ -616,9 +620,10 @@ static int glwe_small_ring(const GlweCall& c) {
         if (!c.au && !c.cross_out && small_one_supported(M, c.npi, c.nrows, c.ncols, c.s.cols_out, c.ksz, nb)) {
             if (c.diff) dispatch_note(M, "%s: fused small-one (k_small_one<.., difference>)", gate_name(c));
             PZ_TRY(launch_small_one(M, nb, SmallOneCall{(const long long*)av.p, sm, key, small_res(c, b0), body, c.diff ? &wd : nullptr,
-                                                        small_res2(c, b0), small_operand2(c, b0)}));
+                                                        small_res2(c, b0), small_operand2(c, b0), c.rot_tab ? c.rot_tab + b0 : nullptr}));
             continue;
         }
+        if (c.rot_tab) return fail(PZ_ERR_UNSUPPORTED, "rotated-source key switch: the one-kernel small-ring form only");
         if (c.diff) {
             dispatch_note(M, "%s: fused small two-kernel (k_small_fwd<.., difference> -> k_small_inv)", gate_name(c));
             PZ_TRY(launch_small_fwd_diff(M, nb * c.npi, wd, S));
@@ -1977,6 +1982,30 @@ int pz_ggsw_automorphism_batched(pz_module* M, int64_t* res, size_t res_dnum, co
 
 // api_lwe.hip composes the LWE <-> GLWE conversions around the batched key switch while holding the module lock
 namespace pz {
+// Key switch of `batch` ciphertexts that are rotations of the ciphertexts of `a`: ciphertext b = X^rot a[word], (word, rot mod 2n) = rot_tab[b] (device).
+// Served where the one-kernel small-ring form takes the key switch with every object in the key's base (N = 1024, and the N = 2048 shapes
+// small_one_supported names): its forward column pass and its operand load read `a` through the monomial's index and sign map, so the rotated
+// ciphertexts are never written.  glwe_keyswitch_rot_applies says whether a shape is served; the caller materialises the rotation otherwise.
+bool glwe_keyswitch_rot_applies(const pz_module* M, const pz_glwe_op_params* p) {
+    if (!p || p->dsize < 1 || p->dnum < 1 || p->key_size < 1 || p->a_size < 1 || p->res_size < 1 || p->rank < 1) return false;
+    if (rt_knob("POULPY_DBG_LWE_ROT_ON_LOAD", 1) == 0) return false;   // (read per call: tests flip it)
+    const OpShape s = op_shape(p, GlweKind::KeySwitch);
+    if (s.convert || p->res_base2k != p->key_base2k) return false;     // the first reader is a cross-base pass / the digits leave through one
+    if (fused_applies(M, p, s, GlweKind::KeySwitch) || !small_ring_applies(M, p, s, GlweKind::KeySwitch, true)) return false;
+    return small_one_supported(M, s.cols_in * s.a_size_eff, (int)p->dnum * s.cols_in, s.cols_out * (int)p->key_size, s.cols_out, (int)p->key_size, 1);
+}
+int glwe_keyswitch_rot_nolock(pz_module* M, int64_t* res, const int64_t* a, const RotSrc* rot_tab, const double* key_pmat, const pz_glwe_op_params* p,
+                              size_t batch) {
+    PZ_REQUIRE(glwe_keyswitch_rot_applies(M, p) && rot_tab != nullptr, "rotated-source key switch: shape not served");
+    const OpShape s = op_shape(p, GlweKind::KeySwitch);
+    const double* key = nullptr;
+    PZ_TRY(resolve_key(M, key_pmat, (size_t)M->n * 8 * p->dnum * s.cols_in * s.cols_out * p->key_size, &key));
+    GlweCall c;
+    PZ_TRY(glwe_call_init(c, M, GlweKind::KeySwitch, res, a, key, p, batch, nullptr, nullptr, nullptr));
+    if (batch == 0) return PZ_OK;
+    c.rot_tab = rot_tab;
+    return glwe_small_ring(c);
+}
 int glwe_keyswitch_nolock(pz_module* M, int64_t* res, const int64_t* a, const double* key_pmat, const pz_glwe_op_params* p, size_t batch) {
     return glwe_entry(M, GlweKind::KeySwitch, res, a, key_pmat, p, batch, nullptr);
 }

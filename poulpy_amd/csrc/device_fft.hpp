@@ -175,6 +175,11 @@ struct SmallDiff {
     unsigned rot;         // rotated form, mod 2n: coefficient i of t is f[(i - rot) mod 2n], negated where that index is >= n
 };
 
+// One ciphertext of a rotated-source key switch (pz_lwe_from_glwe_many_batched): X^rot (rot mod 2n) of ciphertext `word` of the source batch
+struct RotSrc {
+    unsigned word, rot;
+};
+
 // Gathered CMUX (pz_bdd_circuit_execute_batched): ciphertext c of a launch takes its two sources, its result and its row-sliced key from
 // entry c of a device table instead of base + c * stride and one key.  All three ciphertexts have the layout of the result; res is no source of the launch.
 struct SmallGather {

@@ -74,6 +74,21 @@ __device__ __forceinline__ void small_diff_load(const SmallDiff& d, int p, int t
     for (int j1 = 0; j1 < M1; ++j1) { re[j1] = (long long)(tr[j1] - fr[j1]); im[j1] = (long long)(ti[j1] - fi[j1]); }
 }
 
+// Rotated source of a key switch (pz_lwe_from_glwe_many_batched): the 2 M1 coefficients thread t owns of X^rot a, read from `a`
+// through the monomial's index and sign map (coefficient i = a[(i - rot) mod 2n], negated where that index is >= n), as SRC = 2 above reads t = X^rot f
+template <int M1>
+__device__ __forceinline__ void small_rot_load(const long long* a, unsigned rot, int t, long long (&re)[M1], long long (&im)[M1]) {
+    constexpr int M2 = 128;
+    constexpr unsigned m = (unsigned)M1 * M2, n = 2 * m;
+#pragma unroll
+    for (int j1 = 0; j1 < M1; ++j1) {
+        const unsigned s0 = ((unsigned)(j1 * M2 + t) - rot) & (2 * n - 1), s1 = (m + (unsigned)(j1 * M2 + t) - rot) & (2 * n - 1);
+        const unsigned long long v0 = (unsigned long long)a[s0 & (n - 1)], v1 = (unsigned long long)a[s1 & (n - 1)];
+        re[j1] = (long long)(s0 >= n ? 0ull - v0 : v0);
+        im[j1] = (long long)(s1 >= n ? 0ull - v1 : v1);
+    }
+}
+
 struct SmallFwdArgs {
     const long long* src;
     PolyMap smap;

@@ -49,6 +49,9 @@ struct SmallOneArgs {
     const long long* small2;
     long long res2_bs, small2_bs;
     int res2_size, small2_size;
+    // SRC = 3 (pz_lwe_from_glwe_many_batched): ciphertext b of the launch is X^rot of ciphertext `word` of src (and of `small`), both
+    // from rot_tab[b]; the rotation is applied where the limbs are read - by stage A and by stage F's operand load - and the rotated copy never exists
+    const RotSrc* rot_tab;
 };
 
 // (Measured and dropped, round 6: input groups of 4 polynomials through a 32-row tile at N = 2048 - 73.7 KiB, two workgroups per CU, the product's sums
@@ -102,6 +105,9 @@ __device__ __forceinline__ void small_one_body(SmallOneArgs& g, const SmallGathe
                     re[j1] = ld_stream(a + j1 * M2 + t);
                     im[j1] = ld_stream(a + m + j1 * M2 + t);
                 }
+            } else if constexpr (SRC == 3) {
+                const RotSrc e = g.rot_tab[b];
+                small_rot_load<M1>(g.src + (long long)e.word * g.smap.sb + map_off(g.smap, p), e.rot, t, re, im);
             } else {
                 small_diff_load<M1, SRC>(g.diff, b * g.npi + p, t, re, im);
             }
@@ -314,6 +320,23 @@ __device__ __forceinline__ void small_one_body(SmallOneArgs& g, const SmallGathe
             for (int j = 0; j < KS; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) smv[j][e] = 0;
+            if constexpr (SRC == 3) {
+                if (small_col && g.small_size > 0) {   // the operand is X^rot of its word: coefficient i comes from (i - rot) mod 2n, negated beyond n
+                    const RotSrc rs = g.rot_tab[b];
+                    const long long* base = g.small + (long long)rs.word * g.small_bs + (g.body_col < 0 ? (long long)col * n : 0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned i = (unsigned)((ch ? m : 0) + cj2 + (long long)(JG * e + jq) * M2);
+                        const unsigned sidx = (i - rs.rot) & (unsigned)(2 * n - 1);
+                        const long long* at = base + (sidx & (unsigned)(n - 1));
+#pragma unroll
+                        for (int j = 0; j < KS; ++j) {
+                            const unsigned long long v = (unsigned long long)at[(long long)min(j, g.small_size - 1) * small_ls];
+                            smv[j][e] = (long long)(sidx >= (unsigned)n ? 0ull - v : v);
+                        }
+                    }
+                }
+            } else
             if (small_col && g.small_size > 0) {   // the body operand of this thread's coefficients, all limbs, in one batch
 #pragma unroll
                 for (int j = 0; j < KS; ++j)

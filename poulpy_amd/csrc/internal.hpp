@@ -271,6 +271,8 @@ struct SmallOneCall {
     const SmallDiff* diff = nullptr;  // CMUX: the input polynomials are differences of two sources (src / smap are not read)
     SmallRes res2;                    // conditional swap: res2.p != null - res2 = normalize(small2 - big) beside res (SmallInvCall)
     SmallOperand small2;
+    // rotated-source key switch: ciphertext b = X^rot of ciphertext `word` of src / small, (word, rot) = rot_tab[b] (device); no diff, no res2
+    const RotSrc* rot_tab = nullptr;
 };
 int launch_small_one(pz_module* M, int batch, const SmallOneCall& c);
 

@@ -87,6 +87,7 @@ int launch_small_one_gather(pz_module* M, int batch, const SmallGatherShape& s, 
     SmallOneArgs g;
     g.diff = gather_diff(M, s);
     g.src = nullptr; g.smap = g.diff.fmap; g.Pp = nullptr; g.res = nullptr; g.small = nullptr;   // (t, f, res, Pp: tab[c])
+    g.rot_tab = nullptr;
     g.res_bs = g.small_bs = n * s.cols * s.size;
     g.batch = batch; g.npi = s.cols * s.size; g.nrows = s.dnum * s.cols; g.ncols = s.cols * s.ksz; g.ksz = s.ksz;
     g.res_cols = s.cols; g.res_size = s.size; g.small_cols = s.cols; g.small_size = s.size; g.base2k = s.base2k; g.body_col = -1;

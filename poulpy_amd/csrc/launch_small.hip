@@ -210,8 +210,10 @@ int launch_small_one(pz_module* M, int batch, const SmallOneCall& c) {
     g.res_cols = c.res.cols; g.res_size = c.res.size; g.small_cols = c.small.cols; g.small_size = c.small.size; g.base2k = c.res.base2k; g.body_col = c.small.body_col;
     g.tw1 = M->s_tw1; g.tw12t = M->s_tw12t; g.wL2 = M->s_wL2; g.tw1inv = M->s_tw1inv; g.margin = M->probe ? M->margin : nullptr;
     g.diff = c.diff ? *c.diff : SmallDiff{nullptr, nullptr, c.smap, c.smap, 0, 0, 0u};
-    const int src_form = !c.diff ? 0 : (c.diff->t ? 1 : 2);
+    const int src_form = c.rot_tab ? 3 : (!c.diff ? 0 : (c.diff->t ? 1 : 2));
     const bool dual = c.res2.p != nullptr;
+    g.rot_tab = c.rot_tab;
+    if (c.rot_tab && (c.diff || dual)) return fail(PZ_ERR_INVALID, "one-kernel product: the rotated source is a plain key switch (no difference, one result)");
     g.res2 = c.res2.p; g.small2 = c.small2.p; g.res2_bs = c.res2.bs; g.small2_bs = c.small2.bs; g.res2_size = c.res2.size; g.small2_size = c.small2.size;
     if (dual && (src_form == 2 || c.small.p == nullptr || c.small.body_col >= 0 || c.small2.p == nullptr || c.small2.size < 1 || c.res2.cols != c.res.cols ||
                  c.small2.cols != c.res.cols || c.small.cols != c.res.cols || c.res2.base2k != c.res.base2k))
@@ -225,6 +227,7 @@ int launch_small_one(pz_module* M, int batch, const SmallOneCall& c) {
         else if (dual) PZ_TRY(launch_k((k_small_one<M1_, KS_, 1, true>), dim3(batch), dim3(512), lds, M->stream, g));              \
         else if (src_form == 0) PZ_TRY(launch_k((k_small_one<M1_, KS_, 0>), dim3(batch), dim3(512), lds, M->stream, g));   \
         else if (src_form == 1) PZ_TRY(launch_k((k_small_one<M1_, KS_, 1>), dim3(batch), dim3(512), lds, M->stream, g));   \
+        else if (src_form == 3) PZ_TRY(launch_k((k_small_one<M1_, KS_, 3>), dim3(batch), dim3(512), lds, M->stream, g));   \
         else PZ_TRY(launch_k((k_small_one<M1_, KS_, 2>), dim3(batch), dim3(512), lds, M->stream, g));                     \
         dispatch_note(M, "k_small_one<M1=%d,KS=%d> (one kernel per ciphertext, %d input polynomials)", M1_, KS_, npi); \
         PZ_HIP(hipGetLastError());                                                                            \

@@ -22,7 +22,7 @@
 namespace pz {
 
 // Run-time switches: the thirteen a build reads - alternative paths kept for cross-checks, each exercised by a -m gpu test
-// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST, _CMUX_FUSED, _BDD_GATHER;
+// (POULPY_DBG_CANARY, _GRAPHS, _SPLIT, _MID_R, _TENSOR_FUSED, _TENSOR_COMBINE, _TENSOR_ALLTERMS, _MULPLAIN_FUSED, _MULCONST_FUSED, _KEYAUTO_SPECTRAL, _ROT_HOIST, _CMUX_FUSED, _BDD_GATHER, _LWE_ROT_ON_LOAD, _PREPARE_GROUP;
 // DESIGN.md section 9).
 inline int rt_knob(const char* name, int dflt) {
     const char* e = getenv(name);

@@ -32,6 +32,7 @@ class PoulpyHipError(RuntimeError):
 GlweOpParams = abi.pz_glwe_op_params
 BlindRotationParams = abi.pz_blind_rotation_params
 CircuitBootstrappingParams = abi.pz_circuit_bootstrapping_params
+FheUintPrepareParams = abi.pz_fhe_uint_prepare_params
 GlweTensorParams = abi.pz_glwe_tensor_params
 GlweMulConstParams = abi.pz_glwe_mul_const_params
 GlweTerm = abi.pz_glwe_term   # one term of pz_glwe_combine_batched
@@ -790,6 +791,36 @@ class Module:
     def lwe_from_glwe_batched(self, res: c_void_p, res_n_lwe: int, a: c_void_p, a_idx: int, ksk_pmat: c_void_p, params: GlweOpParams, batch: int):
         """poulpy-core conversion/glwe_to_lwe.rs:42-90."""
         self._ck(self.lib.pz_lwe_from_glwe_batched(self.handle, res, res_n_lwe, a, a_idx, ksk_pmat, C.byref(params), batch))
+
+    def lwe_from_glwe_many_tmp_bytes(self, params: GlweOpParams, nidx: int, batch: int) -> int:
+        return self.lib.pz_lwe_from_glwe_many_tmp_bytes(self.handle, C.byref(params), nidx, batch)
+
+    def lwe_from_glwe_many_batched(self, res: c_void_p, res_n_lwe: int, a: c_void_p, idx, ksk_pmat: c_void_p, params: GlweOpParams, tmp: c_void_p,
+                                   tmp_bytes: int, batch: int, lwe_2n: c_void_p = None, n2: int = 0, negate: bool = False):
+        """lwe_from_glwe (glwe_to_lwe.rs:42-90) of every one of `batch` GLWEs at every coefficient of `idx`: index-major LWEs in `res`
+        (None: not written) and, with `lwe_2n`, their mod_switch_2n(n2, negate) vectors from the same kernel."""
+        arr = (C.c_size_t * max(len(idx), 1))(*[int(i) for i in idx])
+        self._ck(self.lib.pz_lwe_from_glwe_many_batched(self.handle, res, res_n_lwe, a, len(idx), arr, ksk_pmat, C.byref(params), lwe_2n, n2,
+                                                        1 if negate else 0, tmp, tmp_bytes, batch))
+
+    def ggsw_prepare_batched(self, pmat: c_void_p, ggsw: c_void_p, count: int, dnum: int, rank: int, size: int):
+        """ggsw_prepare on `count` contiguous device GGSWs (MatZnx layout) -> VmpPMat layout, equal as bytes to vmp_prepare per matrix."""
+        self._ck(self.lib.pz_ggsw_prepare_batched(self.handle, pmat, ggsw, count, dnum, rank, size))
+
+    def fhe_uint_prepare_tmp_bytes(self, params: FheUintPrepareParams, batch: int, chunk_bits: int = 0) -> int:
+        return self.lib.pz_fhe_uint_prepare_tmp_bytes(self.handle, C.byref(params), batch, chunk_bits)
+
+    def fhe_uint_prepare_batched(self, res_pmat: c_void_p, words: c_void_p, ks_glwe_pmat, ks_lwe_pmat: c_void_p, lut: c_void_p, brk: c_void_p, gals,
+                                 atk_ptrs, tsk_ptrs, params: FheUintPrepareParams, tmp: c_void_p, tmp_bytes: int, batch: int,
+                                 ggsw_out: c_void_p = None, lwe_out: c_void_p = None):
+        """FheUintPrepared::prepare (bdd_arithmetic/ciphertexts/fhe_uint_prepared.rs:399-460) on `batch` words -> word-major
+        [batch][word_bits] prepared GGSWs; ks_glwe_pmat may be None."""
+        ns = len(gals)
+        g = (c_int64 * max(ns, 1))(*[int(x) for x in gals])
+        ap = _ptrs(atk_ptrs)
+        tp = _ptrs(tsk_ptrs)
+        self._ck(self.lib.pz_fhe_uint_prepare_batched(self.handle, res_pmat, ggsw_out, lwe_out, words, ks_glwe_pmat, ks_lwe_pmat, lut, brk, ns, g,
+                                                      ap, tp, C.byref(params), tmp, tmp_bytes, batch))
 
     # -- multi-GPU (SURVEY.md 8e): RCCL broadcast of prepared keys on the module stream ---------------------
     def comm_available(self):
