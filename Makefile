@@ -49,9 +49,14 @@ cpp-test-bdd:
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_bdd_schedule.cpp $(CSRC)/bdd_schedule.cpp -o tests/cpp/test_bdd_schedule
 	tests/cpp/test_bdd_schedule
 
+# host-only check of the level map of FheUint::pack under the host sanitizers (tests/test_fhe_uint_pack_host.py builds and runs the same program)
+cpp-test-pack:
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_pack_levels.cpp $(CSRC)/pack_levels.cpp -o tests/cpp/test_pack_levels
+	tests/cpp/test_pack_levels
+
 clean:
-	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 
-.PHONY: all oracle cpp-test cpp-test-bdd kres test-cpu test-gpu bench clean
+.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack kres test-cpu test-gpu bench clean

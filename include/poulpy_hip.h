@@ -828,6 +828,52 @@ int pz_fhe_uint_prepare_batched(pz_module* m, double* res_pmat, int64_t* ggsw_ou
                                 const double* ks_glwe_pmat, const double* ks_lwe_pmat, const int64_t* lut, const double* brk, size_t nsteps,
                                 const int64_t* gals, const double* const* atk_pmats, const double* const* tsk_pmats,
                                 const pz_fhe_uint_prepare_params* p, void* tmp, size_t tmp_bytes, size_t batch);
+/* FheUint::pack (bdd_arithmetic/ciphertexts/fhe_uint.rs:239-255) on `batch` words: the word_bits single-bit GLWEs of every word become one
+ * GLWE with bit i at coefficient bit_index(i) << log_gap, log_gap = log2(n / word_bits).  Bit-identical, on every limb, to
+ * pz_glwe_pack_batched (trace_size == 0) / pz_glwe_pack_bases_batched (trace_size >= 1) called with indices[s] = bit_index(s) << log_gap,
+ * cts[s] = bits + s * batch * ct, log_gap_out = log_gap.  Every index of the word is occupied, so only the both-present branch of
+ * pack_internal (glwe_packing.rs:42-69) runs, and the merges of one level are independent and share one key: each of the log2(word_bits)
+ * levels is ONE batch of pairs * batch ciphertexts - a pre-kernel (a X^-t -+ b, halved; the half-difference normalized), one automorphism
+ * call, a post-kernel (normalize(a' - automorphism), turned by X^t into the survivor's slot) - and the closing glwe_trace of log_gap steps.
+ *   bits        dense slot-major device buffer [word_bits][batch] of GLWEs of p->res_size limbs: slot s = bit s of every word (the evaluator's
+ *               `out`).  CLOBBERED: its contents after the call are unspecified
+ *   res         the batch packed words
+ *   gals / key_pmats   HOST arrays, the log2(n) trace steps and their prepared automorphism keys, as for pz_glwe_pack_batched; every one of
+ *               them is used (the first log2(word_bits) by the merges, the others by the trace): a null key or an even element is PZ_ERR_INVALID
+ *   p           as for pz_glwe_pack_batched: a_size == res_size, a_base2k == res_base2k, dsize == 1, rank_out == rank
+ *   trace_size  0: ciphertexts and keys share one base2k (another key_base2k is PZ_ERR_INVALID); else the keys have their own base and
+ *               trace_size is what it is for pz_glwe_pack_bases_batched
+ *   word_bits   8 / 16 / 32 / 64 / 128 with n % word_bits == 0; n == word_bits: log_gap = 0, no closing trace
+ *   tmp         device scratch of pz_fhe_uint_pack_tmp_bytes: align256(word_bits / 2 * batch * ct) for the half-differences of a level
+ *               + align256(batch * n * (rank + 1) * trace_size * 8) for the trace in the keys' base (never below what the general pack takes)
+ * res, bits, tmp and the keys are pairwise disjoint: PZ_ERR_ALIAS otherwise.  A refused call launches nothing; batch == 0 is PZ_OK and
+ * launches nothing.  Routes: "fhe_uint_pack: by levels (...)" by default; POULPY_DBG_PACK_LEVELS=0 (read per call) sends the call through
+ * the general pack, one merge at a time ("fhe_uint_pack: per pair (...)").  On the level route a call repeated with the same arguments is
+ * replayed as one HIP graph of kernel nodes (pz_module_set_graphs). */
+size_t pz_fhe_uint_pack_tmp_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t word_bits, size_t trace_size, size_t batch);
+int    pz_fhe_uint_pack_batched(pz_module* m, int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals,
+                                const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size,
+                                void* tmp, size_t tmp_bytes, size_t batch);
+/* Host only (no module, no device): the merges of level `level` < log2(word_bits) of pz_fhe_uint_pack_batched as 3 words each - the slot of
+ * the survivor a, the slot of b, t (the level turns a by X^-t and the survivor back by X^t) - in the order of the survivor's index, the first
+ * `cap` of them into pairs3 (may be NULL with cap 0); returns the number of pairs of the level, 0 for a shape or level out of range. */
+size_t pz_fhe_uint_pack_level_pairs(size_t n, size_t word_bits, size_t level, uint32_t* pairs3, size_t cap);
+/* execute_bdd_circuit_2w_to_1w / _1w_to_1w (bdd_arithmetic/bdd_2w_to_1w.rs:103-136, bdd_1w_to_1w.rs:46-70): the evaluator into a slot buffer
+ * [word_bits][batch] carved from tmp, then pz_fhe_uint_pack_batched into res - bit-identical to pz_bdd_circuit_execute_batched (out = that
+ * buffer, n_out = word_bits) followed by pz_fhe_uint_pack_batched, under one module lock.
+ *   c, bits, nbits, gate_p    exactly the arguments of pz_bdd_circuit_execute_batched (the rows of the one or two prepared words concatenated);
+ *                             output_size <= word_bits, slots beyond output_size and zero outputs are zero ciphertexts
+ *   gals, atk_pmats, pack_p, trace_size   exactly the arguments of pz_fhe_uint_pack_batched; pack_p->res_size == gate_p->res_size and
+ *                             pack_p->res_base2k == gate_p->res_base2k, anything else PZ_ERR_INVALID with nothing launched
+ *   tmp    [align256(word_bits * batch * ct) slot buffer][max(evaluator tmp, pack tmp)] (bdd_2w_to_1w.rs:70-74); the query returns the sum
+ * The two halves replay as their own HIP graphs, one behind the other (the evaluator's rule holds: on its gathered route a new bits
+ * array behind the same arguments is picked up). */
+size_t pz_fhe_uint_execute_tmp_bytes(const pz_module* m, const pz_bdd_circuit* c, const pz_glwe_op_params* gate_p,
+                                     const pz_glwe_op_params* pack_p, size_t word_bits, size_t trace_size, size_t batch);
+int    pz_fhe_uint_execute_batched(pz_module* m, const pz_bdd_circuit* c, int64_t* res, size_t word_bits,
+                                   const double* const* bits, size_t nbits, const pz_glwe_op_params* gate_p,
+                                   const int64_t* gals, const double* const* atk_pmats, const pz_glwe_op_params* pack_p,
+                                   size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch);
 /* device workspace the GLWE-level calls reserve for `batch` ciphertexts, for the pipeline the call will actually take (fused
  * three-kernel or five-kernel) incl. the growth slack of the module's grow-only arena; keyswitch: 0 external product, 1 key switch,
  * 2 automorphism family, 3 tensor relinearization */

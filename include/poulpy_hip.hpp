@@ -249,6 +249,23 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                                           tmp_bytes, batch),
               "fhe_uint_prepare_batched");
     }
+    size_t fhe_uint_pack_tmp_bytes(const pz_glwe_op_params& p, size_t word_bits, size_t trace_size, size_t batch) const {
+        return pz_fhe_uint_pack_tmp_bytes(m_, &p, word_bits, trace_size, batch);
+    }
+    void fhe_uint_pack_batched(int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* keys,
+                               const pz_glwe_op_params& p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_pack_batched(m_, res, bits, word_bits, gals, keys, &p, trace_size, tmp, tmp_bytes, batch), "fhe_uint_pack_batched");
+    }
+    size_t fhe_uint_execute_tmp_bytes(const pz_bdd_circuit* c, const pz_glwe_op_params& gate_p, const pz_glwe_op_params& pack_p, size_t word_bits,
+                                      size_t trace_size, size_t batch) const {
+        return pz_fhe_uint_execute_tmp_bytes(m_, c, &gate_p, &pack_p, word_bits, trace_size, batch);
+    }
+    void fhe_uint_execute_batched(const pz_bdd_circuit* c, int64_t* res, size_t word_bits, const double* const* bits, size_t nbits,
+                                  const pz_glwe_op_params& gate_p, const int64_t* gals, const double* const* atk, const pz_glwe_op_params& pack_p,
+                                  size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_execute_batched(m_, c, res, word_bits, bits, nbits, &gate_p, gals, atk, &pack_p, trace_size, tmp, tmp_bytes, batch),
+              "fhe_uint_execute_batched");
+    }
     void circuit_bootstrapping_execute_to_exponent_batched(int64_t* ggsw, const int64_t* lwe_2n, const int64_t* lut, const double* brk,
                                                            const int64_t* gals, const double* const* atk, const double* const* tsk,
                                                            const pz_circuit_bootstrapping_params& p, size_t log_gap_in, size_t log_gap_out,

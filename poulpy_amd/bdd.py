@@ -349,3 +349,44 @@ def fhe_uint_pack(mod, res, out, word_bits: int, gals, key_ptrs, params, batch: 
     finally:
         if tmp is None:
             buf.free()
+
+
+def fhe_uint_pack_words(mod, res, out, word_bits: int, gals, key_ptrs, params, batch: int, tmp=None, trace_size: int = 0):
+    """FheUint::pack (fhe_uint.rs:239-255) on `batch` words through pz_fhe_uint_pack_batched, level by level: the arguments of fhe_uint_pack
+    (out = the evaluator's dense slot-major buffer [word_bits][batch], CLOBBERED; res = the batch packed words), bit-identical to it.
+    trace_size >= 1: the automorphism keys have their own base2k (as for glwe_pack_bases_batched)."""
+    need = mod.fhe_uint_pack_tmp_bytes(params, word_bits, batch, trace_size)
+    buf = tmp if tmp is not None else mod.device_alloc(max(need, 8))
+    try:
+        mod.fhe_uint_pack_batched(res, out, word_bits, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch, trace_size)
+        if tmp is None:
+            mod.sync()
+    finally:
+        if tmp is None:
+            buf.free()
+
+
+def fhe_uint_execute(mod, circuit, res, word_bits: int, bits, gate, gals, key_ptrs, pack, batch: int, tmp=None, trace_size: int = 0):
+    """execute_bdd_circuit_2w_to_1w / _1w_to_1w (bdd_2w_to_1w.rs:103-136, bdd_1w_to_1w.rs:46-70) on `batch` inputs: pz_fhe_uint_execute_batched.
+
+    circuit: a compiled handle of mod.bdd_circuit_new (a Circuit is compiled, and freed, around the call), output_size <= word_bits.  res: device
+    pointer to the batch packed words.  bits[b][i]: the prepared GGSW of input bit i of input b - the rows of the one or two prepared words of
+    fhe_uint_prepare, concatenated.  gate: the evaluator's params; gals / key_ptrs / pack: the arguments of fhe_uint_pack_words.  tmp: a
+    DeviceBuffer of at least mod.fhe_uint_execute_tmp_bytes(...) bytes; allocated and freed here when absent (the call is synchronized then)."""
+    handle = circuit
+    own = isinstance(circuit, Circuit)
+    if own:
+        handle = mod.bdd_circuit_new(circuit)
+    try:
+        need = mod.fhe_uint_execute_tmp_bytes(handle, gate, pack, word_bits, batch, trace_size)
+        buf = tmp if tmp is not None else mod.device_alloc(max(need, 8))
+        try:
+            mod.fhe_uint_execute_batched(handle, res, word_bits, bits, gate, gals, key_ptrs, pack, buf.ptr, buf.nbytes, batch, trace_size)
+            if tmp is None:
+                mod.sync()
+        finally:
+            if tmp is None:
+                buf.free()
+    finally:
+        if own:
+            mod.bdd_circuit_free(handle)

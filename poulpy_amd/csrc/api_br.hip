@@ -1,8 +1,11 @@
 // api_br.hip — C ABI of the composite calls built on the batched GLWE product: CGGI blind rotation (block-binary, standard, extended),
 // circuit bootstrapping (constant / exponent mode) and GLWE packing.  poulpy-bin-fhe blind_rotation/algorithms/cggi/algorithm.rs,
 // circuit_bootstrapping/circuit.rs; poulpy-core glwe_packing.rs.  SURVEY.md §8f rank 2.
+#include <string>
+
 #include "api_common.hpp"
 #include "api_glwe.hpp"
+#include "pack_levels.hpp"
 
 using namespace pz;
 
@@ -704,6 +707,170 @@ int pz_glwe_pack_bases_batched(pz_module* M, int64_t* res, size_t nslots, const 
     PZ_ENTER(M);
     PZ_REQUIRE(trace_size >= 1, "glwe_pack: trace_size = 0");
     return glwe_pack(M, res, nslots, indices, cts, log_gap_out, gals, key_pmats, p, tmp, tmp_bytes, batch, trace_size);
+}
+
+// ------------------------------------------------------------------------------
+// public: FheUint::pack (bdd_arithmetic/ciphertexts/fhe_uint.rs:239-255) on `batch` words.  All word_bits indices are occupied,
+// so glwe_pack's tree has log2(word_bits) levels of both-present merges (pack_levels.cpp) and a trace of log_gap steps.  By levels: every
+// level is k_pack_pre, ONE automorphism call on pairs * batch half-differences, k_pack_post.  tmp = [diff: word_bits / 2 slots][trace
+// temporary in the keys' base].  Per pair (POULPY_DBG_PACK_LEVELS=0): glwe_pack above, on the first three slots' worth of tmp.
+// ------------------------------------------------------------------------------
+static inline bool pack_ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return a_bytes != 0 && b_bytes != 0 && (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+size_t pz_fhe_uint_pack_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t word_bits, size_t trace_size, size_t batch) {
+    if (!M || !p) return 0;
+    const size_t ctb = batch * (size_t)M->n * (p->rank + 1) * p->res_size * 8;
+    const size_t by_levels = align256(word_bits / 2 * ctb) + align256(batch * (size_t)M->n * (p->rank + 1) * trace_size * 8);
+    return std::max(by_levels, pz_glwe_pack_bases_tmp_bytes(M, p, trace_size, batch));
+}
+size_t pz_fhe_uint_pack_level_pairs(size_t n, size_t word_bits, size_t level, uint32_t* pairs3, size_t cap) {
+    std::vector<PackLevel> levels;
+    if (!fhe_uint_pack_levels(n, word_bits, &levels, nullptr) || level >= levels.size()) return 0;
+    const PackLevel& lv = levels[level];
+    for (size_t k = 0; pairs3 && k < std::min(lv.pairs(), cap); ++k) { pairs3[3 * k] = lv.lo[k]; pairs3[3 * k + 1] = lv.hi[k]; pairs3[3 * k + 2] = lv.t; }
+    return lv.pairs();
+}
+// every refusal of pz_fhe_uint_pack_batched, before anything is launched; *levels: the level map
+static int fhe_uint_pack_refusals(pz_module* M, const int64_t* res, const int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
+                               const pz_glwe_op_params* p, size_t trace_size, const void* tmp, size_t tmp_bytes, size_t batch,
+                               std::vector<PackLevel>* levels) {
+    PZ_REQUIRE(p != nullptr && gals != nullptr && key_pmats != nullptr, "fhe_uint_pack: null argument");
+    PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k && p->rank_out == p->rank && p->dsize == 1,
+               "fhe_uint_pack: ciphertexts and result share base2k and size (dsize 1, rank_out = rank)");
+    PZ_REQUIRE(p->res_size >= 1 && p->rank >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->res_base2k >= 1 && p->res_base2k <= 62 && p->key_base2k >= 1,
+               "fhe_uint_pack: empty shape");
+    PZ_REQUIRE(p->res_base2k == p->key_base2k || trace_size >= 1, "fhe_uint_pack: keys in another base than the ciphertexts need trace_size >= 1");
+    std::string err;
+    if (!fhe_uint_pack_levels((size_t)M->n, word_bits, levels, &err) || !fhe_uint_pack_check((size_t)M->n, word_bits, *levels, &err))
+        return fail(PZ_ERR_INVALID, "%s", err.c_str());
+    PZ_REQUIRE(batch <= (1u << 24), "fhe_uint_pack: batch out of range");
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    for (size_t s = 0; s < log_n; ++s)
+        PZ_REQUIRE((gals[s] & 1) != 0 && key_pmats[s] != nullptr, "fhe_uint_pack: trace step %zu has an even Galois element or a null key", s);
+    if (batch == 0) return PZ_OK;
+    PZ_REQUIRE(res != nullptr && bits != nullptr && tmp != nullptr, "fhe_uint_pack: null argument");
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(bits) && is_device_ptr(tmp), "batched entry points take device pointers");
+    const size_t need = pz_fhe_uint_pack_tmp_bytes(M, p, word_bits, p->res_base2k == p->key_base2k ? 0 : trace_size, batch);
+    PZ_REQUIRE(tmp_bytes >= need, "fhe_uint_pack: tmp too small (%zu bytes, %zu needed)", tmp_bytes, need);
+    const size_t cols = p->rank + 1, ctb = batch * (size_t)M->n * cols * p->res_size * 8, bits_bytes = word_bits * ctb;
+    const size_t key_bytes = (size_t)M->n * 8 * p->dnum * p->rank * cols * p->key_size;
+    if (pack_ranges_overlap(res, ctb, bits, bits_bytes)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps bits");
+    if (pack_ranges_overlap(res, ctb, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps tmp");
+    if (pack_ranges_overlap(bits, bits_bytes, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: bits overlaps tmp");
+    for (size_t s = 0; s < log_n; ++s)
+        if (pack_ranges_overlap(res, ctb, key_pmats[s], key_bytes) || pack_ranges_overlap(bits, bits_bytes, key_pmats[s], key_bytes) ||
+            pack_ranges_overlap(tmp, need, key_pmats[s], key_bytes))
+            return fail(PZ_ERR_ALIAS, "fhe_uint_pack: the key of trace step %zu overlaps res, bits or tmp", s);
+    return PZ_OK;
+}
+// the checked call on the stream (no lock, no graph); batch >= 1
+static int fhe_uint_pack_levels_run(pz_module* M, int64_t* res, int64_t* bits, const std::vector<PackLevel>& levels, const int64_t* gals,
+                                    const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t batch) {
+    const long long n = (long long)M->n;
+    const int cols = (int)p->rank + 1, size = (int)p->res_size, k = (int)p->res_base2k, B = (int)batch;
+    const long long ct = n * cols * size;
+    const size_t word_bits = 2 * levels[0].pairs();
+    int64_t* diff = (int64_t*)tmp;
+    dispatch_note(M, "fhe_uint_pack: by levels (k_pack_pre, one automorphism of pairs x batch, k_pack_post per level)");
+    for (size_t l = 0; l < levels.size(); ++l) {
+        const PackLevel& lv = levels[l];
+        PackLevelCall pc;
+        pc.bits = (long long*)bits; pc.diff = (long long*)diff;
+        // the last survivor (slot 0) goes straight to res when the trace runs there (glwe_copy, glwe_packing.rs:175)
+        pc.dst = (l + 1 == levels.size() && trace_size == 0) ? (long long*)res : (long long*)bits;
+        pc.cols = cols; pc.size = size; pc.base2k = k; pc.batch = B; pc.pairs = (int)lv.pairs(); pc.t = lv.t;
+        pc.lo = lv.lo.data(); pc.hi = lv.hi.data();
+        PZ_TRY(launch_pack_level(M, false, pc));
+        AutoSpec au{(long long)gals[l], 0};
+        PZ_TRY(glwe_op(M, GlweKind::Automorphism, diff, diff, key_pmats[l], p, lv.pairs() * batch, &au));
+        PZ_TRY(launch_pack_level(M, true, pc));
+    }
+    const size_t skip = levels.size();
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    if (trace_size == 0) return glwe_trace(M, res, log_n - skip, gals + skip, key_pmats + skip, p, batch);
+    // glwe_trace on a temporary of trace_size limbs in the keys' base (glwe_trace.rs:91-127), as glwe_pack above
+    const int kk = (int)p->key_base2k, tsz = (int)trace_size;
+    const long long ct_t = n * cols * tsz;
+    int64_t* tr = (int64_t*)((char*)tmp + align256(word_bits / 2 * (size_t)B * (size_t)ct * 8));
+    DV tv{tr, ct_t, cols, tsz}, sv{bits, ct, cols, size}, rv{res, ct, cols, size};
+    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, tv, kk, 0, c, sv, k, c));
+    pz_glwe_op_params q = *p;
+    q.a_size = q.res_size = (uint64_t)tsz; q.a_base2k = q.res_base2k = p->key_base2k;
+    PZ_TRY(glwe_trace(M, tr, log_n - skip, gals + skip, key_pmats + skip, &q, batch));
+    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, k, 0, c, tv, kk, c));
+    return PZ_OK;
+}
+static int fhe_uint_pack_per_pair(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
+                                  const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch, const char* why) {
+    dispatch_note(M, "fhe_uint_pack: per pair (%s)", why);
+    size_t log_bytes = 0, log_gap = 0;
+    while (((size_t)8 << log_bytes) < word_bits) ++log_bytes;
+    while ((word_bits << log_gap) < (size_t)M->n) ++log_gap;
+    const size_t ct = (size_t)M->n * (p->rank + 1) * p->res_size;
+    std::vector<uint64_t> indices(word_bits);
+    std::vector<int64_t*> cts(word_bits);
+    for (size_t s = 0; s < word_bits; ++s) { indices[s] = (uint64_t)fhe_uint_bit_index((uint32_t)s, (uint32_t)log_bytes) << log_gap; cts[s] = bits + s * batch * ct; }
+    return glwe_pack(M, res, word_bits, indices.data(), cts.data(), log_gap, gals, key_pmats, p, tmp, tmp_bytes, batch, trace_size);
+}
+// both routes for a caller that holds the module lock and has run fhe_uint_pack_refusals; the level route replays as a graph
+static int fhe_uint_pack(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const std::vector<PackLevel>& levels, const int64_t* gals,
+                         const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
+    if (batch == 0) return PZ_OK;
+    if (p->res_base2k == p->key_base2k) trace_size = 0;
+    if (rt_knob("POULPY_DBG_PACK_LEVELS", 1) == 0)   // (read per call: tests flip it)
+        return fhe_uint_pack_per_pair(M, res, bits, word_bits, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch, "POULPY_DBG_PACK_LEVELS=0");
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    KeyHash k;
+    k.add((int)11); k.add(res); k.add(bits); k.add(word_bits); k.add(tmp); k.add(batch); k.add(trace_size); k.add(*p);
+    for (size_t s = 0; s < log_n; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
+    graph_key_module(M, k);
+    return with_graph(M, k.h, [&]() { return fhe_uint_pack_levels_run(M, res, bits, levels, gals, key_pmats, p, trace_size, tmp, batch); });
+}
+int pz_fhe_uint_pack_batched(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
+                             const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_ENTER(M);
+    std::vector<PackLevel> levels;
+    PZ_TRY(fhe_uint_pack_refusals(M, res, bits, word_bits, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch, &levels));
+    return fhe_uint_pack(M, res, bits, word_bits, levels, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch);
+}
+
+// ------------------------------------------------------------------------------
+// public: execute_bdd_circuit_2w_to_1w / _1w_to_1w (bdd_2w_to_1w.rs:103-136, bdd_1w_to_1w.rs:46-70): the evaluator into the slot buffer at the
+// head of tmp, then the pack above into res, both behind every refusal of either.  tmp = [slot buffer][max(evaluator, pack)] (:70-74).
+// The halves keep their own graphs (the evaluator's gathered route writes the call's keys to tmp outside its graph).
+// ------------------------------------------------------------------------------
+size_t pz_fhe_uint_execute_tmp_bytes(const pz_module* M, const pz_bdd_circuit* c, const pz_glwe_op_params* gate_p, const pz_glwe_op_params* pack_p,
+                                     size_t word_bits, size_t trace_size, size_t batch) {
+    if (!M || !c || !gate_p || !pack_p) return 0;
+    const size_t slots = align256(word_bits * batch * (size_t)M->n * (gate_p->rank + 1) * gate_p->res_size * 8);
+    return slots + std::max(align256(pz_bdd_circuit_execute_tmp_bytes(M, c, gate_p, batch)), pz_fhe_uint_pack_tmp_bytes(M, pack_p, word_bits, trace_size, batch));
+}
+int pz_fhe_uint_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* res, size_t word_bits, const double* const* bits, size_t nbits,
+                                const pz_glwe_op_params* gate_p, const int64_t* gals, const double* const* atk_pmats, const pz_glwe_op_params* pack_p,
+                                size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_REQUIRE(gate_p != nullptr && pack_p != nullptr && c != nullptr, "fhe_uint_execute: null argument");
+    PZ_REQUIRE(gate_p->res_size == pack_p->res_size && gate_p->res_base2k == pack_p->res_base2k && gate_p->rank == pack_p->rank,
+               "fhe_uint_execute: the evaluator's result is the pack's ciphertext (res_size, res_base2k, rank of gate_p and pack_p)");
+    PZ_REQUIRE(pz_bdd_circuit_output_size(c) <= word_bits, "fhe_uint_execute: output_size %zu > word_bits %zu", pz_bdd_circuit_output_size(c), word_bits);
+    PZ_REQUIRE(batch == 0 || tmp != nullptr, "fhe_uint_execute: null argument");
+    bool nothing = false;
+    PZ_TRY(bdd_circuit_execute_precheck(M, c, (const int64_t*)tmp, word_bits, bits, nbits, gate_p, batch, &nothing));
+    PZ_ENTER(M);
+    const size_t slot_bytes = align256(word_bits * batch * (size_t)M->n * (gate_p->rank + 1) * gate_p->res_size * 8);
+    const size_t need = pz_fhe_uint_execute_tmp_bytes(M, c, gate_p, pack_p, word_bits, trace_size, batch);
+    PZ_REQUIRE(tmp_bytes >= need, "fhe_uint_execute: tmp too small (%zu bytes, %zu needed)", tmp_bytes, need);
+    int64_t* slots = (int64_t*)tmp;
+    void* rest = (char*)tmp + slot_bytes;
+    std::vector<PackLevel> levels;
+    PZ_TRY(fhe_uint_pack_refusals(M, res, slots, word_bits, gals, atk_pmats, pack_p, trace_size, rest, tmp_bytes - slot_bytes, batch, &levels));
+    if (batch == 0 || nothing) return PZ_OK;
+    PZ_TRY(bdd_circuit_execute(M, c, slots, word_bits, bits, nbits, gate_p, rest, tmp_bytes - slot_bytes, batch));
+    PZ_TRY(fhe_uint_pack(M, res, slots, word_bits, levels, gals, atk_pmats, pack_p, trace_size, rest, tmp_bytes - slot_bytes, batch));
+    return finish_call(M, false);
 }
 
 }  // extern "C"

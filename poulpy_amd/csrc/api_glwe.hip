@@ -1563,8 +1563,9 @@ static int bdd_levels_per_gate(pz_module* M, const BddSchedule& s, int64_t* stat
 }
 
 extern "C" {
-int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                                   const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+int bdd_circuit_execute_precheck(const pz_module* M, const pz_bdd_circuit* c, const int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                                 const pz_glwe_op_params* p, size_t batch, bool* nothing) {
+    *nothing = false;
     PZ_REQUIRE(p != nullptr, "bdd_circuit_execute: null params");
     PZ_REQUIRE(c != nullptr, "bdd_circuit_execute: null circuit");
     const BddSchedule& s = c->s;
@@ -1575,7 +1576,7 @@ int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_
     PZ_REQUIRE(p->res_size * p->res_base2k >= 2, "bdd_circuit_execute: the result cannot hold the constant 2^-2");
     PZ_REQUIRE(n_out >= s.output_size, "bdd_circuit_execute: n_out %zu < output_size %zu", n_out, s.output_size);
     PZ_REQUIRE(batch <= (1u << 24) && n_out < kBddOut, "bdd_circuit_execute: batch or n_out out of range");
-    if (batch == 0 || n_out == 0) return M ? PZ_OK : fail(PZ_ERR_INVALID, "null module");   // no ciphertext to write
+    if (batch == 0 || n_out == 0) { *nothing = true; return M ? PZ_OK : fail(PZ_ERR_INVALID, "null module"); }   // no ciphertext to write
     PZ_REQUIRE(nbits >= s.input_size, "bdd_circuit_execute: nbits %zu < input_size %zu", nbits, s.input_size);
     PZ_REQUIRE(out != nullptr, "bdd_circuit_execute: null argument");
     if (!s.gates.empty()) {
@@ -1584,14 +1585,15 @@ int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_
             for (size_t i = 0; i < s.input_size; ++i)
                 PZ_REQUIRE(!s.selected[i] || bits[b * nbits + i] != nullptr, "bdd_circuit_execute: the GGSW of input bit %zu of input %zu is null and the circuit selects it", i, b);
     }
-    PZ_ENTER(M);
+    return PZ_OK;
+}
+int bdd_circuit_execute(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                        const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    const BddSchedule& s = c->s;
     PZ_REQUIRE(is_device_ptr(out), "batched entry points take device pointers");
     const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8, ct = (size_t)M->n * cols * p->res_size;
     const size_t out_bytes = n_out * batch * ct * 8, key_bytes = n8 * p->dnum * cols * cols * p->key_size;
-    if (s.gates.empty()) {   // nothing but zero outputs
-        PZ_TRY(launch_zero_bytes(M, out, out_bytes));
-        return finish_call(M, false);
-    }
+    if (s.gates.empty()) return launch_zero_bytes(M, out, out_bytes);   // nothing but zero outputs
     const BddWs w = bdd_ws(M, s, p, batch, nbits);
     PZ_REQUIRE(tmp != nullptr && is_device_ptr(tmp) && tmp_bytes >= w.total, "bdd_circuit_execute: tmp too small (%zu bytes, %zu needed)", tmp_bytes, w.total);
     if (ranges_overlap(out, out_bytes, tmp, w.total)) return fail(PZ_ERR_ALIAS, "bdd_circuit_execute: out overlaps tmp");
@@ -1639,7 +1641,7 @@ int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_
             PZ_TRY(bdd_init(M, s, state, out, n_out, p, batch));
             return bdd_levels_per_gate(M, s, state, out, keys.data(), nbits, p, batch);
         }));
-        return finish_call(M, false);
+        return PZ_OK;
     }
     // ---- gathered: everything that depends on the keys is written to tmp here, outside the graph ----
     const BddGate* d_gates; const uint32_t* d_levels;
@@ -1697,6 +1699,15 @@ int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_
         PZ_TRY(launch_bdd_table(M, tc));
         return bdd_levels_gathered(M, s, sh, one, tab, S, chunk, batch);
     }));
+    return PZ_OK;
+}
+int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                                   const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    bool nothing = false;
+    PZ_TRY(bdd_circuit_execute_precheck(M, c, out, n_out, bits, nbits, p, batch, &nothing));
+    if (nothing) return PZ_OK;
+    PZ_ENTER(M);
+    PZ_TRY(bdd_circuit_execute(M, c, out, n_out, bits, nbits, p, tmp, tmp_bytes, batch));
     return finish_call(M, false);
 }
 }  // extern "C"

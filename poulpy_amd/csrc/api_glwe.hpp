@@ -120,6 +120,12 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
 bool glwe_relin_t16_supported(const pz_module* M, const pz_glwe_op_params* p);
 size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch);
 int glwe_relin_t16(pz_module* M, int64_t* res, const short* a16, long long a16_cs, const double* pmat, const pz_glwe_op_params* p, size_t batch);
+// pz_bdd_circuit_execute_batched without the module lock and the closing finish_call: the argument checks that need no module (precheck; *nothing:
+// the call has no ciphertext to write), then the call itself (pz_fhe_uint_execute_batched runs both halves under one lock)
+int bdd_circuit_execute_precheck(const pz_module* M, const pz_bdd_circuit* c, const int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                                 const pz_glwe_op_params* p, size_t batch, bool* nothing);
+int bdd_circuit_execute(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
+                        const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
 // ggsw_expand_row on `count` GGSWs (conversion/gglwe_to_ggsw.rs:116-268)
 int ggsw_expand_row(pz_module* M, int64_t* ggsw, size_t dnum, const double* const* tsk_pmat, const pz_glwe_op_params* p, size_t count);
 }

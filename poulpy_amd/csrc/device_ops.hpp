@@ -860,4 +860,98 @@ __global__ void __launch_bounds__(256) k_rsh_assign(RshArgs g) {
     }
 }
 
+// =================================================================================
+// FheUint::pack by levels (pz_fhe_uint_pack_batched): the element-wise steps of the both-present branch of pack_internal
+// (glwe_packing.rs:42-69) around its automorphism, for all pairs of a level at once.  Ciphertext `item` = pair * batch + b of the launch:
+// a = slot lo[pair], b = slot hi[pair] of the dense buffer [slot][batch].  One thread owns one coefficient of one column and walks the
+// limbs from the last to the first, every carry in a register and every limb loaded when its step needs it: no per-thread arrays.
+//   k_pack_pre   a <- X^-t a (gather, as k_rotate);  d = a - b, s = a + b (wrapping, as k_ew);  one-bit vec_znx_rsh_assign on both
+//                (k_rsh_assign's step sequence for k = 1: the last limb gives a carry only, limb L takes the shifted step of limb L - 1,
+//                limb 0 the carry);  d also through vec_znx_normalize's same-base steps (k_normalize_inter, offset 0, equal sizes).
+//                s lands on b's slot - the coefficient this thread alone reads - and d in diff[item]; a is only read.
+//   k_pack_post  r = normalize(s - diff[item]), stored through X^t (scatter: coefficient e to e + t, negated past n) into a's slot (`dst`),
+//                which nothing in the launch reads.
+// =================================================================================
+struct PackArgs {
+    long long* bits;          // [slot][batch] ciphertexts of ct elements
+    long long* diff;          // [pairs][batch]
+    long long* dst;           // k_pack_post: where slot lo[pair] is written (bits, or the call's result on the last level)
+    long long ct;
+    int n, cols, size, base2k, batch, items, item0;
+    unsigned t;
+    unsigned char lo[64], hi[64];
+};
+__device__ __forceinline__ long long wsub(long long a, long long b) {
+    return (long long)((unsigned long long)a - (unsigned long long)b);
+}
+// one step of the one-bit shift: limb value v in front of the carry; returns the limb's new value
+__device__ __forceinline__ long long pack_rsh_step(int bk, int lsh, long long v, long long& carry) {
+    const long long d = nz_digit(1, v);
+    const long long cr = nz_carry(1, v, d);
+    const long long dpc = wadd(wshl(d, lsh), carry);
+    const long long nv = nz_digit(bk, dpc);
+    carry = wadd(cr, nz_carry(bk, dpc, nv));
+    return nv;
+}
+// znx_normalize_middle_step<true> with lsh = 0 (normalization.rs:179-221)
+__device__ __forceinline__ long long pack_nz_step(int bk, long long x, long long& carry) {
+    const long long d = nz_digit(bk, x);
+    const long long cr = nz_carry(bk, x, d);
+    const long long dpc = wadd(d, carry);
+    const long long x1 = nz_digit(bk, dpc);
+    carry = wadd(cr, nz_carry(bk, dpc, x1));
+    return x1;
+}
+
+__global__ void __launch_bounds__(256) k_pack_pre(PackArgs g) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= g.n) return;
+    const int item = g.item0 + (int)blockIdx.z;
+    if (item >= g.items) return;
+    const int pair = item / g.batch, b = item - pair * g.batch;
+    const long long col = (long long)blockIdx.y * g.n, ls = (long long)g.cols * g.n;
+    const unsigned nn = (unsigned)g.n, i0 = ((unsigned)e + g.t) & (2u * nn - 1u);   // (X^-t a)[e] = +-a[(e + t) mod 2n]
+    const bool neg = i0 >= nn;
+    const long long* a = g.bits + ((long long)g.lo[pair] * g.batch + b) * g.ct + col + (long long)(i0 & (nn - 1u));
+    long long* bp = g.bits + ((long long)g.hi[pair] * g.batch + b) * g.ct + col + e;
+    long long* dp = g.diff + (long long)item * g.ct + col + e;
+    const int bk = g.base2k, lsh = bk - 1;
+    long long av = a[(long long)(g.size - 1) * ls], bv = bp[(long long)(g.size - 1) * ls];
+    if (neg) av = wsub(0, av);
+    long long s = wadd(av, bv), d = wsub(av, bv);
+    long long cs = nz_carry(1, s, nz_digit(1, s)), cd = nz_carry(1, d, nz_digit(1, d));   // the limb that falls off: carry only
+    long long cn = 0;
+    for (int L = g.size - 1; L >= 1; --L) {
+        av = a[(long long)(L - 1) * ls];
+        bv = bp[(long long)(L - 1) * ls];
+        if (neg) av = wsub(0, av);
+        s = wadd(av, bv);
+        d = wsub(av, bv);
+        bp[(long long)L * ls] = pack_rsh_step(bk, lsh, s, cs);
+        dp[(long long)L * ls] = pack_nz_step(bk, pack_rsh_step(bk, lsh, d, cd), cn);
+    }
+    bp[0] = nz_digit(bk, cs);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
+    dp[0] = pack_nz_step(bk, nz_digit(bk, cd), cn);
+}
+
+__global__ void __launch_bounds__(256) k_pack_post(PackArgs g) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= g.n) return;
+    const int item = g.item0 + (int)blockIdx.z;
+    if (item >= g.items) return;
+    const int pair = item / g.batch, b = item - pair * g.batch;
+    const long long col = (long long)blockIdx.y * g.n, ls = (long long)g.cols * g.n;
+    const unsigned nn = (unsigned)g.n, j0 = (unsigned)e + g.t;   // t <= n / 2: below 2n
+    const bool neg = j0 >= nn;
+    const long long* sp = g.bits + ((long long)g.hi[pair] * g.batch + b) * g.ct + col + e;
+    const long long* dp = g.diff + (long long)item * g.ct + col + e;
+    long long* r = g.dst + ((long long)g.lo[pair] * g.batch + b) * g.ct + col + (long long)(j0 & (nn - 1u));
+    const int bk = g.base2k;
+    long long cn = 0;
+    for (int L = g.size - 1; L >= 0; --L) {
+        const long long x1 = pack_nz_step(bk, wsub(sp[(long long)L * ls], dp[(long long)L * ls]), cn);
+        r[(long long)L * ls] = neg ? wsub(0, x1) : x1;
+    }
+}
+
 }  // namespace pz

@@ -6,6 +6,7 @@
 //   launch_small.hip small-ring pipelines for N = 1024 / 2048 / 4096: whole polynomials in LDS (device_small.hpp, device_small_one.hpp)
 //   launch_bdd.hip   the BDD evaluator's gather table and the gathered forms of the small-ring CMUX kernels
 //   bdd_schedule.cpp the BDD circuit compiler (plain C++, no HIP)
+//   pack_levels.cpp  the level map of FheUint::pack (plain C++, no HIP)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
@@ -332,6 +333,18 @@ inline int launch_rotate(pz_module* M, int npolys, const long long* src, PolyMap
     return launch_rotate(M, npolys, src, sm, dst, dm, 0, npolys, nullptr, 0, 0, k);
 }
 int launch_rsh(pz_module* M, int batch, long long* data, long long bs, int cols, int size, int col0, int ncols, int base2k, int k);
+// One level of FheUint::pack (pz_fhe_uint_pack_batched) on the dense buffer bits[slot][batch]: pair k merges slot lo[k] (a, the
+// survivor) and slot hi[k] (b).  pre: hi[k] <- rsh1(X^-t a + b), diff[k][batch] <- normalize(rsh1(X^-t a - b)); post: slot lo[k] of `dst` <-
+// X^t normalize(hi[k] - diff[k]).  diff overlaps neither bits nor dst; dst = bits or a buffer apart from both.
+struct PackLevelCall {
+    long long* bits = nullptr;
+    long long* diff = nullptr;
+    long long* dst = nullptr;
+    int cols = 0, size = 0, base2k = 0, batch = 0, pairs = 0;
+    unsigned t = 0;
+    const unsigned char *lo = nullptr, *hi = nullptr;
+};
+int launch_pack_level(pz_module* M, bool post, const PackLevelCall& c);
 // vmp_apply_dft_to_dft  [vmp.rs:144-264, zero-tail semantics for limb_offset > 0]
 int dev_vmp(pz_module* M, int batch, DV res, DV a, const double* pmat, int rows, int cols_in, int cols_out, int size, int limb_offset);
 // vec_znx_(big_)normalize on one column  [normalize.rs:18-401]

@@ -155,6 +155,25 @@ int launch_rsh(pz_module* M, int batch, long long* data, long long bs, int cols,
     return PZ_OK;
 }
 
+// one level of FheUint::pack (k_pack_pre / k_pack_post, device_ops.hpp): pairs * batch ciphertexts, chunked over gridDim.z
+int launch_pack_level(pz_module* M, bool post, const PackLevelCall& c) {
+    if (c.batch <= 0 || c.pairs <= 0) return PZ_OK;
+    if (c.pairs > 64) return fail(PZ_ERR_INVALID, "fhe_uint_pack: more than 64 pairs in a level");
+    PackArgs g;
+    g.bits = c.bits; g.diff = c.diff; g.dst = c.dst; g.ct = (long long)M->n * c.cols * c.size;
+    g.n = (int)M->n; g.cols = c.cols; g.size = c.size; g.base2k = c.base2k; g.batch = c.batch; g.items = c.pairs * c.batch; g.t = c.t;
+    for (int k = 0; k < 64; ++k) { g.lo[k] = k < c.pairs ? c.lo[k] : 0; g.hi[k] = k < c.pairs ? c.hi[k] : 0; }
+    KTimer kt(M, PZ_K_NORMALIZE);
+    for (int i0 = 0; i0 < g.items; i0 += 65535) {   // gridDim.z limit
+        g.item0 = i0;
+        const dim3 grid((unsigned)((M->n + 255) / 256), (unsigned)c.cols, (unsigned)std::min(65535, g.items - i0));
+        if (post) hipLaunchKernelGGL(k_pack_post, grid, dim3(256), 0, M->stream, g);
+        else hipLaunchKernelGGL(k_pack_pre, grid, dim3(256), 0, M->stream, g);
+    }
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+
 // vmp_apply_dft_to_dft  [vmp.rs:144-264, zero-tail semantics for limb_offset > 0]
 int dev_vmp(pz_module* M, int batch, DV res, DV a, const double* pmat, int rows, int cols_in, int cols_out, int size,
                    int limb_offset) {

@@ -576,6 +576,39 @@ class Module:
         self._ck(self.lib.pz_glwe_pack_bases_batched(self.handle, res, ns, idx, cp, log_gap_out, g, kp, C.byref(params),
                                                      trace_size, tmp, tmp_bytes, batch))
 
+    # -- FheUint words: the evaluator's bits to one word (bdd_arithmetic/ciphertexts/fhe_uint.rs:239-255, bdd_2w_to_1w.rs:103-136) ----------
+    def fhe_uint_pack_tmp_bytes(self, params: GlweOpParams, word_bits: int, batch: int, trace_size: int = 0) -> int:
+        return self.lib.pz_fhe_uint_pack_tmp_bytes(self.handle, C.byref(params), word_bits, trace_size, batch)
+
+    def fhe_uint_pack_batched(self, res: c_void_p, bits: c_void_p, word_bits: int, gals, key_ptrs, params: GlweOpParams, tmp: c_void_p,
+                              tmp_bytes: int, batch: int, trace_size: int = 0):
+        """FheUint::pack on `batch` words, level by level: bits = dense slot-major [word_bits][batch] (CLOBBERED), res = the batch words;
+        gals / key_ptrs: the log2(n) trace steps and their prepared automorphism keys (None: a null key); trace_size >= 1: the keys have
+        their own base2k."""
+        g = (c_int64 * max(len(gals), 1))(*[int(x) for x in gals])
+        kp = _ptrs([0 if k is None else k for k in key_ptrs]) if len(key_ptrs) else (c_void_p * 1)()
+        self._ck(self.lib.pz_fhe_uint_pack_batched(self.handle, res, bits, word_bits, g, kp, C.byref(params), trace_size, tmp, tmp_bytes, batch))
+
+    def fhe_uint_pack_level_pairs(self, word_bits: int, level: int, n: int = None) -> list:
+        """Host only: the merges of one level of fhe_uint_pack_batched as (slot of the survivor, slot merged into it, t); [] beyond the last."""
+        return fhe_uint_pack_level_pairs(self.n() if n is None else n, word_bits, level, self.lib)
+
+    def fhe_uint_execute_tmp_bytes(self, handle: c_void_p, gate_params: GlweOpParams, pack_params: GlweOpParams, word_bits: int, batch: int,
+                                   trace_size: int = 0) -> int:
+        return self.lib.pz_fhe_uint_execute_tmp_bytes(self.handle, handle, C.byref(gate_params), C.byref(pack_params), word_bits, trace_size, batch)
+
+    def fhe_uint_execute_batched(self, handle: c_void_p, res: c_void_p, word_bits: int, bits, gate_params: GlweOpParams, gals, key_ptrs,
+                                 pack_params: GlweOpParams, tmp: c_void_p, tmp_bytes: int, batch: int, trace_size: int = 0):
+        """execute_bdd_circuit_2w_to_1w / _1w_to_1w on `batch` inputs: bits[b][i] as for bdd_circuit_execute_batched, the packed words in res."""
+        nbits = len(bits[0]) if batch else 0
+        assert all(len(row) == nbits for row in bits) and len(bits) == batch
+        flat = [0 if p is None else (p.value if isinstance(p, c_void_p) else int(p)) or 0 for row in bits for p in row]
+        arr = (c_void_p * max(len(flat), 1))(*flat)
+        g = (c_int64 * max(len(gals), 1))(*[int(x) for x in gals])
+        kp = _ptrs([0 if k is None else k for k in key_ptrs]) if len(key_ptrs) else (c_void_p * 1)()
+        self._ck(self.lib.pz_fhe_uint_execute_batched(self.handle, handle, res, word_bits, arr, nbits, C.byref(gate_params), g, kp,
+                                                      C.byref(pack_params), trace_size, tmp, tmp_bytes, batch))
+
     def set_graphs(self, enable: bool):
         """HIP-graph replay of the launch-bound composite calls (blind rotation, trace, circuit bootstrapping); on by default."""
         self._ck(self.lib.pz_module_set_graphs(self.handle, 1 if enable else 0))
@@ -893,3 +926,13 @@ def bdd_circuit_new(circuit, lib: C.CDLL | None = None) -> c_void_p:
 
 def bdd_circuit_free(handle: c_void_p, lib: C.CDLL | None = None):
     (lib or load_library()).pz_bdd_circuit_free(handle)
+
+
+def fhe_uint_pack_level_pairs(n: int, word_bits: int, level: int, lib: C.CDLL | None = None) -> list:
+    """pz_fhe_uint_pack_level_pairs: host only (no module, no device) - the (lo slot, hi slot, t) triples of one merge level of
+    pz_fhe_uint_pack_batched, [] for a shape or level out of range."""
+    lib = lib or load_library()
+    cnt = int(lib.pz_fhe_uint_pack_level_pairs(n, word_bits, level, None, 0))
+    buf = (C.c_uint32 * max(3 * cnt, 1))()
+    lib.pz_fhe_uint_pack_level_pairs(n, word_bits, level, buf, cnt)
+    return [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(cnt)]
