@@ -54,9 +54,14 @@ cpp-test-pack:
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_pack_levels.cpp $(CSRC)/pack_levels.cpp -o tests/cpp/test_pack_levels
 	tests/cpp/test_pack_levels
 
+# host-only check of the stage plan of the FheUint byte operations under the host sanitizers (tests/test_fhe_uint_bytes_host.py builds and runs the same program)
+cpp-test-word:
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_word_ops.cpp $(CSRC)/word_ops.cpp -o tests/cpp/test_word_ops
+	tests/cpp/test_word_ops
+
 clean:
-	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 
-.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack kres test-cpu test-gpu bench clean
+.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack cpp-test-word kres test-cpu test-gpu bench clean

@@ -874,6 +874,56 @@ int    pz_fhe_uint_execute_batched(pz_module* m, const pz_bdd_circuit* c, int64_
                                    const double* const* bits, size_t nbits, const pz_glwe_op_params* gate_p,
                                    const int64_t* gals, const double* const* atk_pmats, const pz_glwe_op_params* pack_p,
                                    size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch);
+/* The byte operations of FheUint (bdd_arithmetic/ciphertexts/fhe_uint.rs:259-524) on `batch` words: get_bit_glwe / get_byte, zero_byte,
+ * splice_u8 / splice_u16, sext - the operations that move bytes between words without a bootstrap.  With g = log2(n / word_bits),
+ * c(i) = bit_index(i) << g (pz_fhe_uint_bit_coefficient), ts = 3 and tr_s = glwe_trace_assign from step s:
+ *   get         res[i][b] = tr_0(X^-c(idx[i]) words[b]) (PZ_WORD_BIT) or tr_ts(X^-c(8 idx[i]) words[b]) (PZ_WORD_BYTE); index-major [nidx][batch],
+ *               nidx <= 128, normalized (the trace ends in a normalizing tail).  All bits of a word: the inverse of pz_fhe_uint_pack_batched
+ *   zero_byte   res = a - X^r tr_ts(X^-r a), r = c(8 byte)
+ *   splice      width 8: res = a with byte dst replaced by byte src of b = a + X^rd (tr_ts(X^-rs b) - tr_ts(X^-rd a)); width 16: bytes
+ *               2 dst, 2 dst + 1 from 2 src, 2 src + 1 (dst, src < word_bits / 16), the second splice on the first one's result
+ *   sext        in place: the bytes above `byte` become copies of its sign (byte = the last one: PZ_OK, nothing launched)
+ * The last three return the reference's limbs, UN-normalized: its rotations, adds and subs are wrapping i64 operations that neither
+ * normalize nor carry, and regrouping them around the traces changes no bit.  The traces are not regrouped: each sees exactly the word the
+ * reference traces.  The traces an operation needs fall into stages; those of a stage are independent and share their keys, so a stage is one
+ * pre-kernel (the rotations into a dense array [item][batch]; with the words in the keys' base also the trace's first one-bit shift), ONE
+ * trace call on items * batch ciphertexts, and one closing kernel: 1 stage for a get, zero_byte and splice_u8 (the reference: nidx, 1, 2
+ * traces), 2 for splice_u16 (4), 1 + k for sext, k = bytes above `byte` (1 + 2k).
+ *   words, a, b, res   `batch` contiguous GLWEs of one layout (p->res_size limbs in base p->res_base2k)
+ *   gals / key_pmats   HOST arrays, all log2(n) trace steps and their prepared automorphism keys, as for pz_fhe_uint_pack_batched (the call
+ *               takes skip .. log2(n) itself): a null key or an even element is PZ_ERR_INVALID
+ *   p           exactly what pz_glwe_trace_batched takes, its form for keys in another base than the words included
+ *   tmp         device scratch of pz_fhe_uint_word_op_tmp_bytes (max_items: nidx of a get, anything up to 128 otherwise): six ciphertext
+ *               arrays [batch]; a shorter one is PZ_ERR_INVALID
+ * res == a and res == b (whole) and a == b are allowed (every source of a stage is consumed by its pre-kernel before the closing kernel
+ * writes); a get's res, and any other overlap among res, a, b, tmp and the keys, is PZ_ERR_ALIAS.  word_bits outside 8 / 16 / 32 / 64 / 128,
+ * n % word_bits != 0, an index out of range, a width other than 8 or 16: PZ_ERR_INVALID.  A refused call launches nothing; batch == 0 and
+ * nidx == 0 are PZ_OK and launch nothing.  Routes: "fhe_uint_word: by stages (...)" by default, replayed as one HIP graph of kernel nodes
+ * when repeated with the same arguments; POULPY_DBG_WORD_STAGES=0 (read per call) takes the reference's literal order - one rotation, one
+ * trace, one add or sub at a time, plain launches ("fhe_uint_word: literal (...)"), byte for byte the same result. */
+enum { PZ_WORD_BIT = 0, PZ_WORD_BYTE = 1 };
+size_t pz_fhe_uint_word_op_tmp_bytes(const pz_module* m, const pz_glwe_op_params* p, size_t word_bits, size_t max_items, size_t batch);
+int    pz_fhe_uint_get_batched(pz_module* m, int64_t* res, const int64_t* words, size_t word_bits, int unit, size_t nidx, const uint32_t* idx,
+                               const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes,
+                               size_t batch);
+int    pz_fhe_uint_zero_byte_batched(pz_module* m, int64_t* res, const int64_t* a, size_t word_bits, size_t byte, const int64_t* gals,
+                                     const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
+int    pz_fhe_uint_splice_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* b, size_t word_bits, size_t width, size_t dst,
+                                  size_t src, const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp,
+                                  size_t tmp_bytes, size_t batch);
+int    pz_fhe_uint_sext_batched(pz_module* m, int64_t* word, size_t word_bits, size_t byte, const int64_t* gals, const double* const* key_pmats,
+                                const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
+/* Host only (no module, no device).  pz_fhe_uint_bit_coefficient: bit_index(bit) << log_gap, (size_t)-1 for a shape or bit out of range.
+ * pz_fhe_uint_word_plan: the stages of one operation as plain words - per stage  skip, nitems, nitems x (source, exponent, slot), closing
+ * step, its first operand, the slot added, the slot subtracted, r  (sources: 0 a, 1 b, 2 the running word, 3 sext's replicated sign;
+ * closing steps: 0 none, 1 res = operand + X^r (T[added] - T[subtracted]), 2 sext's eight-term sum from slot 0 into slot 1; 0xFFFFFFFF: no
+ * slot) - the first `cap` of them into words (may be NULL with cap 0); returns their number.  args: the indices of a get, {byte}, or
+ * {dst, src}.  *status (may be NULL): PZ_OK, or PZ_ERR_INVALID for what the calls above refuse (0 is returned then; an empty plan is valid). */
+enum { PZ_WORD_OP_GET_BIT = 0, PZ_WORD_OP_GET_BYTE = 1, PZ_WORD_OP_ZERO_BYTE = 2, PZ_WORD_OP_SPLICE_U8 = 3, PZ_WORD_OP_SPLICE_U16 = 4,
+       PZ_WORD_OP_SEXT = 5 };
+size_t pz_fhe_uint_bit_coefficient(size_t n, size_t word_bits, size_t bit);
+size_t pz_fhe_uint_word_plan(size_t n, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs, uint32_t* words, size_t cap,
+                             int* status);
 /* device workspace the GLWE-level calls reserve for `batch` ciphertexts, for the pipeline the call will actually take (fused
  * three-kernel or five-kernel) incl. the growth slack of the module's grow-only arena; keyswitch: 0 external product, 1 key switch,
  * 2 automorphism family, 3 tensor relinearization */

@@ -266,6 +266,26 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
         check(pz_fhe_uint_execute_batched(m_, c, res, word_bits, bits, nbits, &gate_p, gals, atk, &pack_p, trace_size, tmp, tmp_bytes, batch),
               "fhe_uint_execute_batched");
     }
+    size_t fhe_uint_word_op_tmp_bytes(const pz_glwe_op_params& p, size_t word_bits, size_t max_items, size_t batch) const {
+        return pz_fhe_uint_word_op_tmp_bytes(m_, &p, word_bits, max_items, batch);
+    }
+    void fhe_uint_get_batched(int64_t* res, const int64_t* words, size_t word_bits, int unit, size_t nidx, const uint32_t* idx, const int64_t* gals,
+                              const double* const* keys, const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_get_batched(m_, res, words, word_bits, unit, nidx, idx, gals, keys, &p, tmp, tmp_bytes, batch), "fhe_uint_get_batched");
+    }
+    void fhe_uint_zero_byte_batched(int64_t* res, const int64_t* a, size_t word_bits, size_t byte, const int64_t* gals, const double* const* keys,
+                                    const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_zero_byte_batched(m_, res, a, word_bits, byte, gals, keys, &p, tmp, tmp_bytes, batch), "fhe_uint_zero_byte_batched");
+    }
+    void fhe_uint_splice_batched(int64_t* res, const int64_t* a, const int64_t* b, size_t word_bits, size_t width, size_t dst, size_t src,
+                                 const int64_t* gals, const double* const* keys, const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes,
+                                 size_t batch) {
+        check(pz_fhe_uint_splice_batched(m_, res, a, b, word_bits, width, dst, src, gals, keys, &p, tmp, tmp_bytes, batch), "fhe_uint_splice_batched");
+    }
+    void fhe_uint_sext_batched(int64_t* word, size_t word_bits, size_t byte, const int64_t* gals, const double* const* keys,
+                               const pz_glwe_op_params& p, void* tmp, size_t tmp_bytes, size_t batch) {
+        check(pz_fhe_uint_sext_batched(m_, word, word_bits, byte, gals, keys, &p, tmp, tmp_bytes, batch), "fhe_uint_sext_batched");
+    }
     void circuit_bootstrapping_execute_to_exponent_batched(int64_t* ggsw, const int64_t* lwe_2n, const int64_t* lut, const double* brk,
                                                            const int64_t* gals, const double* const* atk, const double* const* tsk,
                                                            const pz_circuit_bootstrapping_params& p, size_t log_gap_in, size_t log_gap_out,

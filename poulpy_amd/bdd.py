@@ -390,3 +390,50 @@ def fhe_uint_execute(mod, circuit, res, word_bits: int, bits, gate, gals, key_pt
     finally:
         if own:
             mod.bdd_circuit_free(handle)
+
+
+def _with_word_tmp(mod, params, word_bits, batch, max_items, tmp, call):
+    need = mod.fhe_uint_word_op_tmp_bytes(params, word_bits, batch, max_items)
+    buf = tmp if tmp is not None else mod.device_alloc(max(need, 8))
+    try:
+        call(buf)
+        if tmp is None:
+            mod.sync()
+    finally:
+        if tmp is None:
+            buf.free()
+
+
+def fhe_uint_get_bits(mod, res, words, word_bits: int, bits, gals, key_ptrs, params, batch: int, tmp=None):
+    """FheUint::get_bit_glwe (fhe_uint.rs:401-414) of `batch` words at every bit of `bits`: res = device pointer to [len(bits)][batch] GLWEs,
+    bit-major - with bits = range(word_bits) the inverse of fhe_uint_pack_words.  gals / key_ptrs: all log2(n) trace steps; tmp: a
+    DeviceBuffer of at least mod.fhe_uint_word_op_tmp_bytes(...) bytes, allocated and freed here when absent (the call is synchronized then)."""
+    from .abi import PZ_WORD_BIT
+    _with_word_tmp(mod, params, word_bits, batch, len(bits), tmp,
+                   lambda buf: mod.fhe_uint_get_batched(res, words, word_bits, PZ_WORD_BIT, bits, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch))
+
+
+def fhe_uint_get_bytes(mod, res, words, word_bits: int, byte_indices, gals, key_ptrs, params, batch: int, tmp=None):
+    """FheUint::get_byte (fhe_uint.rs:416-430): as fhe_uint_get_bits, the byte at coefficient 0 .. of every result and nothing else."""
+    from .abi import PZ_WORD_BYTE
+    _with_word_tmp(mod, params, word_bits, batch, len(byte_indices), tmp,
+                   lambda buf: mod.fhe_uint_get_batched(res, words, word_bits, PZ_WORD_BYTE, byte_indices, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch))
+
+
+def fhe_uint_zero_byte(mod, res, a, word_bits: int, byte: int, gals, key_ptrs, params, batch: int, tmp=None):
+    """FheUint::zero_byte (fhe_uint.rs:466-489) on `batch` words: res = a with byte `byte` zeroed (res may be a)."""
+    _with_word_tmp(mod, params, word_bits, batch, 1, tmp,
+                   lambda buf: mod.fhe_uint_zero_byte_batched(res, a, word_bits, byte, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch))
+
+
+def fhe_uint_splice(mod, res, a, b, word_bits: int, width: int, dst: int, src: int, gals, key_ptrs, params, batch: int, tmp=None):
+    """FheUint::splice_u8 / splice_u16 (fhe_uint.rs:259-329; width 8 / 16) on `batch` words: res = a with byte (half-word) dst replaced by
+    byte (half-word) src of b; res may be a or b."""
+    _with_word_tmp(mod, params, word_bits, batch, 3, tmp,
+                   lambda buf: mod.fhe_uint_splice_batched(res, a, b, word_bits, width, dst, src, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch))
+
+
+def fhe_uint_sext(mod, word, word_bits: int, byte: int, gals, key_ptrs, params, batch: int, tmp=None):
+    """FheUint::sext (fhe_uint.rs:491-524) on `batch` words, in place: the bytes above `byte` become copies of its sign bit."""
+    _with_word_tmp(mod, params, word_bits, batch, 2, tmp,
+                   lambda buf: mod.fhe_uint_sext_batched(word, word_bits, byte, gals, key_ptrs, params, buf.ptr, buf.nbytes, batch))

@@ -6,6 +6,7 @@
 #include "api_common.hpp"
 #include "api_glwe.hpp"
 #include "pack_levels.hpp"
+#include "word_ops.hpp"
 
 using namespace pz;
 
@@ -871,6 +872,249 @@ int pz_fhe_uint_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* 
     PZ_TRY(bdd_circuit_execute(M, c, slots, word_bits, bits, nbits, gate_p, rest, tmp_bytes - slot_bytes, batch));
     PZ_TRY(fhe_uint_pack(M, res, slots, word_bits, levels, gals, atk_pmats, pack_p, trace_size, rest, tmp_bytes - slot_bytes, batch));
     return finish_call(M, false);
+}
+
+// ------------------------------------------------------------------------------
+// public: the FheUint byte operations (bdd_arithmetic/ciphertexts/fhe_uint.rs:259-524): get_bit_glwe / get_byte, zero_byte,
+// splice_u8 / splice_u16 and sext on `batch` words.  By stages (word_ops.cpp): every stage is k_word_pre (the rotated items into a dense array
+// [item][batch], with the first one-bit shift of the trace where the word is in the keys' base), ONE glwe_trace on items * batch ciphertexts,
+// and a closing k_word_post / k_word_replicate.  tmp = kWordSlots ciphertext arrays [batch].  Literal (POULPY_DBG_WORD_STAGES=0): the
+// reference's calls in its order - one rotation launch, one glwe_trace per trace, launch_ew adds and subs.
+// ------------------------------------------------------------------------------
+size_t pz_fhe_uint_bit_coefficient(size_t n, size_t word_bits, size_t bit) {
+    if ((word_bits != 8 && word_bits != 16 && word_bits != 32 && word_bits != 64 && word_bits != 128) || n == 0 || (n & (n - 1)) != 0 || n % word_bits != 0 ||
+        bit >= word_bits)
+        return (size_t)-1;
+    return fhe_uint_word_coefficient(n, word_bits, (uint32_t)bit);
+}
+size_t pz_fhe_uint_word_plan(size_t n, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs, uint32_t* words, size_t cap, int* status) {
+    std::vector<WordStage> plan;
+    std::string err;
+    const bool ok = fhe_uint_word_plan(n, word_bits, op, args, nargs, &plan, &err) &&
+                    fhe_uint_word_plan_check(n, op <= WORD_GET_BYTE ? std::max<size_t>(nargs, 1) : kWordSlots, plan, &err);
+    if (status) *status = ok ? PZ_OK : PZ_ERR_INVALID;
+    if (!ok) { fail(PZ_ERR_INVALID, "%s", err.c_str()); return 0; }
+    const std::vector<uint32_t> w = fhe_uint_word_plan_words(plan);
+    for (size_t i = 0; words && i < std::min(w.size(), cap); ++i) words[i] = w[i];
+    return w.size();
+}
+size_t pz_fhe_uint_word_op_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t word_bits, size_t max_items, size_t batch) {
+    if (!M || !p || max_items > kWordMaxItems) return 0;
+    if (word_bits != 8 && word_bits != 16 && word_bits != 32 && word_bits != 64 && word_bits != 128) return 0;
+    // (a get traces its items in res itself: whatever max_items, the six arrays of the other operations)
+    return align256(kWordSlots * batch * (size_t)M->n * (p->rank + 1) * p->res_size * 8);
+}
+
+namespace {
+struct WordCall {
+    pz_module* M;
+    const char* what;
+    int64_t* res;           // get: [nitems][batch]; else `batch` words
+    const int64_t* a;       // get: the words; sext: the word itself (= res)
+    const int64_t* b;       // splice only
+    const int64_t* gals;
+    const double* const* key_pmats;
+    const pz_glwe_op_params* p;
+    void* tmp;
+    size_t tmp_bytes, batch, res_items;
+    bool is_get;
+};
+}  // namespace
+// every refusal of the four calls, after the plan's own and before anything is launched
+static int fhe_uint_word_refusals(const WordCall& c, size_t word_bits) {
+    pz_module* M = c.M;
+    const pz_glwe_op_params* p = c.p;
+    PZ_REQUIRE(p != nullptr && c.gals != nullptr && c.key_pmats != nullptr, "%s: null argument", c.what);
+    PZ_REQUIRE(p->rank_out == p->rank && p->dsize == 1, "%s: dsize 1, rank_out = rank", c.what);
+    PZ_REQUIRE(p->res_size >= 1 && p->rank >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->res_base2k >= 1 && p->res_base2k <= 62 && p->key_base2k >= 1,
+               "%s: empty shape", c.what);
+    if (p->res_base2k == p->key_base2k)
+        PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k, "%s: a and res describe the same words when they are in the keys' base", c.what);
+    else
+        PZ_REQUIRE(p->a_base2k == p->key_base2k && p->a_size >= 1, "%s: with the words in another base than the keys, (a_size, a_base2k) is their layout in the keys' base", c.what);
+    PZ_REQUIRE(c.batch <= (1u << 20), "%s: batch out of range", c.what);
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    for (size_t s = 0; s < log_n; ++s)
+        PZ_REQUIRE((c.gals[s] & 1) != 0 && c.key_pmats[s] != nullptr, "%s: trace step %zu has an even Galois element or a null key", c.what, s);
+    if (c.batch == 0 || c.res_items == 0) return PZ_OK;
+    PZ_REQUIRE(c.res != nullptr && c.a != nullptr && c.tmp != nullptr, "%s: null argument", c.what);
+    PZ_REQUIRE(is_device_ptr(c.res) && is_device_ptr(c.a) && is_device_ptr(c.tmp) && (c.b == nullptr || is_device_ptr(c.b)), "batched entry points take device pointers");
+    const size_t need = pz_fhe_uint_word_op_tmp_bytes(M, p, word_bits, c.is_get ? c.res_items : 0, c.batch);
+    PZ_REQUIRE(c.tmp_bytes >= need, "%s: tmp too small (%zu bytes, %zu needed)", c.what, c.tmp_bytes, need);
+    const size_t cols = p->rank + 1, ctb = c.batch * (size_t)M->n * cols * p->res_size * 8, res_bytes = c.res_items * ctb;
+    const size_t key_bytes = (size_t)M->n * 8 * p->dnum * p->rank * cols * p->key_size;
+    // res == a, res == b (whole) and a == b are allowed for everything but a get
+    if (pack_ranges_overlap(c.res, res_bytes, c.a, ctb) && (c.is_get || (const void*)c.res != (const void*)c.a)) return fail(PZ_ERR_ALIAS, "%s: res overlaps a", c.what);
+    if (c.b && pack_ranges_overlap(c.res, res_bytes, c.b, ctb) && (const void*)c.res != (const void*)c.b) return fail(PZ_ERR_ALIAS, "%s: res overlaps b", c.what);
+    if (c.b && pack_ranges_overlap(c.a, ctb, c.b, ctb) && (const void*)c.a != (const void*)c.b) return fail(PZ_ERR_ALIAS, "%s: a overlaps b", c.what);
+    if (pack_ranges_overlap(c.res, res_bytes, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: res overlaps tmp", c.what);
+    if (pack_ranges_overlap(c.a, ctb, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: a overlaps tmp", c.what);
+    if (c.b && pack_ranges_overlap(c.b, ctb, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: b overlaps tmp", c.what);
+    for (size_t s = 0; s < log_n; ++s)
+        if (pack_ranges_overlap(c.res, res_bytes, c.key_pmats[s], key_bytes) || pack_ranges_overlap(c.a, ctb, c.key_pmats[s], key_bytes) ||
+            (c.b && pack_ranges_overlap(c.b, ctb, c.key_pmats[s], key_bytes)) || pack_ranges_overlap(c.tmp, need, c.key_pmats[s], key_bytes))
+            return fail(PZ_ERR_ALIAS, "%s: the key of trace step %zu overlaps res, a, b or tmp", c.what, s);
+    return PZ_OK;
+}
+// the checked call by stages on the stream (no lock, no graph); batch >= 1
+static int fhe_uint_word_stages_run(const WordCall& c, const std::vector<WordStage>& plan) {
+    pz_module* M = c.M;
+    const pz_glwe_op_params* p = c.p;
+    const long long n = (long long)M->n;
+    const int cols = (int)p->rank + 1, size = (int)p->res_size, B = (int)c.batch;
+    const long long ct = n * cols * size;
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    const bool same = p->res_base2k == p->key_base2k;
+    dispatch_note(M, "fhe_uint_word: by stages (%zu: k_word_pre%s, one trace of items x batch, one closing kernel)", plan.size(),
+                  same ? " with the trace's first shift" : "");
+    long long* dense = c.is_get ? (long long*)c.res : (long long*)c.tmp;
+    auto slot = [&](uint32_t s) { return dense + (long long)s * B * ct; };
+    for (const WordStage& st : plan) {
+        const size_t nsteps = log_n - st.skip;
+        const int items = (int)st.items.size();
+        unsigned exp[kWordMaxItems];
+        unsigned char sel[kWordMaxItems];
+        for (int i = 0; i < items; ++i) { exp[i] = st.items[i].exp; sel[i] = (unsigned char)st.items[i].src; }
+        WordPreCall pc;
+        pc.src[WORD_SRC_A] = (const long long*)c.a; pc.src[WORD_SRC_B] = (const long long*)c.b; pc.src[WORD_SRC_RES] = (const long long*)c.res;
+        pc.src[WORD_SRC_S] = c.is_get ? nullptr : slot(1);
+        pc.out = slot(st.items[0].slot);
+        pc.cols = cols; pc.size = size; pc.base2k = (int)p->res_base2k; pc.batch = B; pc.items = items;
+        pc.shift = same && nsteps >= 1;
+        pc.exp = exp; pc.sel = sel;
+        PZ_TRY(launch_word_pre(M, pc));
+        PZ_TRY(glwe_trace(M, (int64_t*)pc.out, nsteps, c.gals + st.skip, c.key_pmats + st.skip, p, (size_t)items * c.batch, pc.shift));
+        if (st.close == WORD_CLOSE_REPLICATE) {
+            PZ_TRY(launch_word_replicate(M, slot(1), slot(0), cols, size, B));
+        } else if (st.close == WORD_CLOSE_COMBINE) {
+            const long long* base = st.base == WORD_SRC_A ? (const long long*)c.a : (const long long*)c.res;
+            PZ_TRY(launch_word_post(M, (long long*)c.res, base, st.plus == kWordNone ? nullptr : slot(st.plus), st.minus == kWordNone ? nullptr : slot(st.minus),
+                                    st.r, cols, size, B));
+        }
+    }
+    return PZ_OK;
+}
+// the reference's calls in its order on today's launchers: the byte-for-byte twin of the staged route
+namespace {
+struct WordLiteral {
+    pz_module* M;
+    const WordCall& c;
+    long long n, ct;
+    int cols, size, B;
+    size_t log_n;
+    int64_t* slot(int s) const { return (int64_t*)c.tmp + (long long)s * B * ct; }
+    int rot(int64_t* dst, const int64_t* src, long long k) const {
+        const PolyMap pm{1, 1, n, 0, 0, 0};
+        return launch_rotate(M, B * size * cols, (const long long*)src, pm, (long long*)dst, pm, k);
+    }
+    int trace(int64_t* x, size_t skip) const { return glwe_trace(M, x, log_n - skip, c.gals + skip, c.key_pmats + skip, c.p, (size_t)B); }
+    int ew(int op, int64_t* r, const int64_t* x, const int64_t* y) const { return launch_ew(M, op, r, ct, n, x, ct, n, y, ct, n, size * cols, B); }
+    int get(int64_t* res, const int64_t* a, uint32_t exp, size_t skip) const {   // fhe_uint.rs:401-430
+        PZ_TRY(rot(res, a, -(long long)exp));
+        return trace(res, skip);
+    }
+    int zero_byte(int64_t* res, const int64_t* a, uint32_t r) const {   // :466-489 on a copy of a; glwe_trace = glwe_trace_assign on a copy
+        PZ_TRY(rot(slot(0), a, -(long long)r));
+        PZ_TRY(ew(EW_COPY, slot(1), slot(0), nullptr));
+        PZ_TRY(trace(slot(1), 3));
+        PZ_TRY(ew(EW_SUB_I64, slot(0), slot(0), slot(1)));
+        return rot(res, slot(0), (long long)r);
+    }
+    int splice_u8(int64_t* res, const int64_t* a, const int64_t* b, uint32_t rd, uint32_t rs) const {   // :286-329; b's side first: res may be b
+        PZ_TRY(rot(slot(2), b, -(long long)rs));
+        PZ_TRY(trace(slot(2), 3));
+        PZ_TRY(rot(slot(3), slot(2), (long long)rd));
+        PZ_TRY(zero_byte(res, a, rd));
+        return ew(EW_ADD_I64, res, res, slot(3));
+    }
+};
+}  // namespace
+static int fhe_uint_word_literal_run(const WordCall& c, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs) {
+    pz_module* M = c.M;
+    dispatch_note(M, "fhe_uint_word: literal (POULPY_DBG_WORD_STAGES=0: one rotation, one trace, one add or sub at a time)");
+    WordLiteral w{M, c, (long long)M->n, (long long)M->n * (long long)(c.p->rank + 1) * (long long)c.p->res_size, (int)c.p->rank + 1, (int)c.p->res_size,
+                  (int)c.batch, 0};
+    while (((size_t)1 << w.log_n) < (size_t)M->n) ++w.log_n;
+    const size_t n = (size_t)M->n;
+    auto cf = [&](uint32_t bit) { return fhe_uint_word_coefficient(n, word_bits, bit); };
+    switch (op) {
+    case WORD_GET_BIT:
+    case WORD_GET_BYTE:
+        for (size_t i = 0; i < nargs; ++i)
+            PZ_TRY(w.get(c.res + (long long)i * w.B * w.ct, c.a, cf(op == WORD_GET_BIT ? args[i] : 8 * args[i]), op == WORD_GET_BIT ? 0 : 3));
+        return PZ_OK;
+    case WORD_ZERO_BYTE:
+        return w.zero_byte(c.res, c.a, cf(8 * args[0]));
+    case WORD_SPLICE_U8:
+        return w.splice_u8(c.res, c.a, c.b, cf(8 * args[0]), cf(8 * args[1]));
+    case WORD_SPLICE_U16:   // :259-282
+        PZ_TRY(w.splice_u8(w.slot(4), c.a, c.b, cf(16 * args[0]), cf(16 * args[1])));
+        return w.splice_u8(c.res, w.slot(4), c.b, cf(16 * args[0] + 8), cf(16 * args[1] + 8));
+    default: {   // WORD_SEXT, :491-524
+        const uint32_t byte = args[0], bytes = (uint32_t)(word_bits / 8);
+        if (byte + 1 == bytes) return PZ_OK;
+        PZ_TRY(w.get(w.slot(4), c.res, cf(8 * byte + 7), 0));
+        for (int i = 0; i < 3; ++i) {
+            PZ_TRY(w.rot(w.slot(5), w.slot(4), (long long)((n / 8) << i)));
+            PZ_TRY(w.ew(EW_ADD_I64, w.slot(4), w.slot(4), w.slot(5)));
+        }
+        for (uint32_t i = byte + 1; i < bytes; ++i) PZ_TRY(w.splice_u8(c.res, c.res, w.slot(4), cf(8 * i), 0));
+        return PZ_OK;
+    }
+    }
+}
+// plan, refusals, route, graph: the body of the four calls under the module lock
+static int fhe_uint_word_call(const WordCall& c, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs) {
+    pz_module* M = c.M;
+    std::vector<WordStage> plan;
+    std::string err;
+    if (!fhe_uint_word_plan((size_t)M->n, word_bits, op, args, nargs, &plan, &err) ||
+        !fhe_uint_word_plan_check((size_t)M->n, c.is_get ? std::max<size_t>(nargs, 1) : kWordSlots, plan, &err))
+        return fail(PZ_ERR_INVALID, "%s", err.c_str());
+    PZ_TRY(fhe_uint_word_refusals(c, word_bits));
+    if (c.batch == 0 || plan.empty()) return PZ_OK;
+    if (rt_knob("POULPY_DBG_WORD_STAGES", 1) == 0) return fhe_uint_word_literal_run(c, word_bits, op, args, nargs);   // (read per call: tests flip it)
+    size_t log_n = 0;
+    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    KeyHash k;
+    k.add((int)12); k.add(c.res); k.add(c.a); k.add(c.b); k.add(word_bits); k.add(op); k.add(nargs); k.add(c.tmp); k.add(c.batch); k.add(*c.p);
+    for (size_t i = 0; i < nargs; ++i) k.add(args[i]);
+    for (size_t s = 0; s < log_n; ++s) { k.add(c.gals[s]); k.add(c.key_pmats[s]); }
+    graph_key_module(M, k);
+    return with_graph(M, k.h, [&]() { return fhe_uint_word_stages_run(c, plan); });
+}
+int pz_fhe_uint_get_batched(pz_module* M, int64_t* res, const int64_t* words, size_t word_bits, int unit, size_t nidx, const uint32_t* idx,
+                            const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_ENTER(M);
+    PZ_REQUIRE(unit == PZ_WORD_BIT || unit == PZ_WORD_BYTE, "fhe_uint_get: unit %d is neither PZ_WORD_BIT nor PZ_WORD_BYTE", unit);
+    PZ_REQUIRE(nidx == 0 || idx != nullptr, "fhe_uint_get: null argument");
+    const WordCall c{M, "fhe_uint_get", res, words, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, nidx, true};
+    return fhe_uint_word_call(c, word_bits, unit == PZ_WORD_BIT ? WORD_GET_BIT : WORD_GET_BYTE, idx, nidx);
+}
+int pz_fhe_uint_zero_byte_batched(pz_module* M, int64_t* res, const int64_t* a, size_t word_bits, size_t byte, const int64_t* gals,
+                                  const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_ENTER(M);
+    const uint32_t args[1] = {(uint32_t)std::min<size_t>(byte, 0xFFFFu)};
+    const WordCall c{M, "fhe_uint_zero_byte", res, a, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
+    return fhe_uint_word_call(c, word_bits, WORD_ZERO_BYTE, args, 1);
+}
+int pz_fhe_uint_splice_batched(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, size_t word_bits, size_t width, size_t dst, size_t src,
+                               const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_ENTER(M);
+    PZ_REQUIRE(width == 8 || width == 16, "fhe_uint_splice: width %zu is neither 8 nor 16", width);
+    PZ_REQUIRE(batch == 0 || b != nullptr, "fhe_uint_splice: null argument");
+    const uint32_t args[2] = {(uint32_t)std::min<size_t>(dst, 0xFFFFu), (uint32_t)std::min<size_t>(src, 0xFFFFu)};
+    const WordCall c{M, "fhe_uint_splice", res, a, b, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
+    return fhe_uint_word_call(c, word_bits, width == 8 ? WORD_SPLICE_U8 : WORD_SPLICE_U16, args, 2);
+}
+int pz_fhe_uint_sext_batched(pz_module* M, int64_t* word, size_t word_bits, size_t byte, const int64_t* gals, const double* const* key_pmats,
+                             const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
+    PZ_ENTER(M);
+    const uint32_t args[1] = {(uint32_t)std::min<size_t>(byte, 0xFFFFu)};
+    const WordCall c{M, "fhe_uint_sext", word, word, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
+    return fhe_uint_word_call(c, word_bits, WORD_SEXT, args, 1);
 }
 
 }  // extern "C"

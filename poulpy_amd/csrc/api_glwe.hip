@@ -1057,8 +1057,9 @@ int pz_ggsw_from_gglwe_batched(pz_module* M, int64_t* ggsw, const int64_t* a, si
 // res in another base than the keys (:153-163; test_suite/trace.rs:36-39): (a_size, a_base2k = key_base2k) describe res re-expressed in
 // the keys' base (a_size = ceil(res.max_k / key_base2k)); normalize into a temporary of that layout, trace there, normalize back.
 int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, const double* const* key_pmats,
-                      const pz_glwe_op_params* p, size_t batch) {
+                      const pz_glwe_op_params* p, size_t batch, bool first_shifted) {
     PZ_REQUIRE(p != nullptr && (nsteps == 0 || (gals != nullptr && key_pmats != nullptr)), "glwe_trace: null argument");
+    PZ_REQUIRE(!first_shifted || (p->res_base2k == p->key_base2k && nsteps >= 1), "glwe_trace: the first shift can only be the caller's in the keys' base");
     PZ_REQUIRE(p->rank_out == p->rank, "glwe_trace: rank_out != rank");
     PZ_REQUIRE(is_device_ptr(res), "batched entry points take device pointers");
     if (p->res_base2k != p->key_base2k) {
@@ -1074,7 +1075,7 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
         for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, cv, (int)p->key_base2k, 0, c, rv, (int)p->res_base2k, c));
         pz_glwe_op_params q = *p;
         q.res_size = p->a_size; q.res_base2k = p->key_base2k;
-        PZ_TRY(glwe_trace(M, conv, nsteps, gals, key_pmats, &q, batch));
+        PZ_TRY(glwe_trace(M, conv, nsteps, gals, key_pmats, &q, batch, false));
         for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, (int)p->res_base2k, 0, c, cv, (int)p->key_base2k, c));
         return PZ_OK;
     }
@@ -1085,7 +1086,7 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
     const int cols = (int)p->rank + 1;
     const long long ct = n * cols * (long long)p->res_size;
     // the one-bit shift in front of step s + 1 rides on the tail of step s where that path has the shifted-store variant
-    bool shifted = false;
+    bool shifted = first_shifted;   // (the FheUint byte operations' pre-kernel shifts on its way out: k_word_pre)
     for (size_t s = 0; s < nsteps; ++s) {
         PZ_REQUIRE((gals[s] & 1) != 0, "glwe_trace: Galois elements must be odd");
         if (!shifted) PZ_TRY(launch_rsh(M, (int)batch, (long long*)res, ct, cols, (int)p->res_size, 0, cols, (int)p->res_base2k, 1));
@@ -1105,7 +1106,7 @@ int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64
     if (p) k.add(*p);
     for (size_t s = 0; s < nsteps && gals && key_pmats; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
     graph_key_module(M, k);
-    return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch); });
+    return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch, false); });
 }
 }  // extern "C"
 

@@ -113,9 +113,10 @@ int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const d
             const AutoSpec* au = nullptr, const OpLayout* lay = nullptr, bool* post_rsh = nullptr);
 // post_rsh (glwe_trace): in: the caller would like the result shifted right by one bit (vec_znx_rsh_assign on every column) as it is
 // stored; out: whether the path taken did that (spectral automorphism forms on the 256 x 128 plan) - otherwise the caller shifts itself
-// glwe_trace_assign on a batch (poulpy-core glwe_trace.rs:129-176): one prepared key per step
+// glwe_trace_assign on a batch (poulpy-core glwe_trace.rs:129-176): one prepared key per step.  first_shifted (res in the keys' base,
+// nsteps >= 1): the caller has already applied the one-bit vec_znx_rsh_assign the first step opens with (k_word_pre)
 int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p,
-               size_t batch);
+               size_t batch, bool first_shifted = false);
 // tensor relinearization of GLWETensors held as 16-bit digits in the fused tail's tile order (api_cnv.hip's fused multiply + relinearize)
 bool glwe_relin_t16_supported(const pz_module* M, const pz_glwe_op_params* p);
 size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch);

@@ -954,4 +954,105 @@ __global__ void __launch_bounds__(256) k_pack_post(PackArgs g) {
     }
 }
 
+// =================================================================================
+// FheUint byte operations by stages (pz_fhe_uint_get_batched / _zero_byte_ / _splice_ / _sext_; DESIGN.md 4.4i, word_ops.hpp): the element-wise
+// steps around the ONE trace call of a stage.  Ciphertext `item` = it * batch + b of the launch, it = an entry of the stage's item table.  As in
+// k_pack_*: one thread owns one coefficient of one column and walks the limbs, carries in registers, no per-thread arrays.
+//   k_word_pre        out[item] = X^-exp[it] src[sel[it]][b] (gather, index and sign as k_rotate); with `shift` the one-bit vec_znx_rsh_assign
+//                     glwe_trace opens its first step with (k_rsh_assign's step sequence for k = 1, as k_pack_pre) on the way out
+//   k_word_post       res[b][j] = base[b][j] + (X^r (Tp[b] - Tm[b]))[j], a null T is zero; wrapping, no normalization; gather form: a thread
+//                     reads only its own coefficient of base, so res == base is allowed
+//   k_word_replicate  out[b] = sum_{m < 8} X^(m n / 8) s[b]  (sext's three doubling steps, fhe_uint.rs:512-516)
+// =================================================================================
+struct WordPreArgs {
+    const long long* src[4];   // WordSrc -> `batch` ciphertexts of ct elements
+    long long* out;            // [item][batch]
+    long long ct;
+    int n, cols, size, base2k, batch, items, item0, shift;
+    unsigned exp[128];
+    unsigned char sel[128];
+};
+__global__ void __launch_bounds__(256) k_word_pre(WordPreArgs g) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= g.n) return;
+    const int item = g.item0 + (int)blockIdx.z;
+    if (item >= g.items) return;
+    const int it = item / g.batch, b = item - it * g.batch;
+    const long long col = (long long)blockIdx.y * g.n, ls = (long long)g.cols * g.n;
+    const unsigned nn = (unsigned)g.n, i0 = ((unsigned)e + g.exp[it]) & (2u * nn - 1u);   // (X^-t a)[e] = +-a[(e + t) mod 2n]
+    const bool neg = i0 >= nn;
+    const long long* a = g.src[g.sel[it]] + (long long)b * g.ct + col + (long long)(i0 & (nn - 1u));
+    long long* o = g.out + (long long)item * g.ct + col + e;
+    if (!g.shift) {
+        for (int L = 0; L < g.size; ++L) {
+            const long long v = a[(long long)L * ls];
+            o[(long long)L * ls] = neg ? wsub(0, v) : v;
+        }
+        return;
+    }
+    const int bk = g.base2k, lsh = bk - 1;
+    long long v = a[(long long)(g.size - 1) * ls];
+    if (neg) v = wsub(0, v);
+    long long carry = nz_carry(1, v, nz_digit(1, v));   // the limb that falls off: carry only
+    for (int L = g.size - 1; L >= 1; --L) {
+        v = a[(long long)(L - 1) * ls];
+        if (neg) v = wsub(0, v);
+        o[(long long)L * ls] = pack_rsh_step(bk, lsh, v, carry);
+    }
+    o[0] = nz_digit(bk, carry);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
+}
+
+struct WordPostArgs {
+    const long long* base;     // `batch` ciphertexts
+    const long long* tp;       // added, or null
+    const long long* tm;       // subtracted, or null
+    long long* res;
+    long long ct;
+    int n, cols, size, batch, item0;
+    unsigned r;
+};
+__global__ void __launch_bounds__(256) k_word_post(WordPostArgs g) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= g.n) return;
+    const int b = g.item0 + (int)blockIdx.z;
+    if (b >= g.batch) return;
+    const long long col = (long long)blockIdx.y * g.n, ls = (long long)g.cols * g.n;
+    const unsigned nn = (unsigned)g.n, i0 = ((unsigned)e + 2u * nn - g.r) & (2u * nn - 1u);   // (X^r T)[e] = +-T[(e - r) mod 2n]
+    const bool neg = i0 >= nn;
+    const long long at = (long long)b * g.ct + col, src = at + (long long)(i0 & (nn - 1u));
+    for (int L = 0; L < g.size; ++L) {
+        const long long off = (long long)L * ls;
+        long long t = g.tp ? g.tp[src + off] : 0;
+        if (g.tm) t = wsub(t, g.tm[src + off]);
+        const long long x = g.base[at + e + off];
+        g.res[at + e + off] = neg ? wsub(x, t) : wadd(x, t);
+    }
+}
+
+struct WordRepArgs {
+    const long long* s;
+    long long* out;
+    long long ct;
+    int n, cols, size, batch, item0;
+};
+__global__ void __launch_bounds__(256) k_word_replicate(WordRepArgs g) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= g.n) return;
+    const int b = g.item0 + (int)blockIdx.z;
+    if (b >= g.batch) return;
+    const long long col = (long long)blockIdx.y * g.n, ls = (long long)g.cols * g.n, at = (long long)b * g.ct + col;
+    const unsigned nn = (unsigned)g.n, step = nn >> 3;
+    for (int L = 0; L < g.size; ++L) {
+        const long long* s = g.s + at + (long long)L * ls;
+        long long acc = 0;
+#pragma unroll
+        for (unsigned m = 0; m < 8; ++m) {
+            const unsigned i0 = ((unsigned)e + 2u * nn - m * step) & (2u * nn - 1u);
+            const long long v = s[i0 & (nn - 1u)];
+            acc = i0 >= nn ? wsub(acc, v) : wadd(acc, v);
+        }
+        g.out[at + (long long)L * ls + e] = acc;
+    }
+}
+
 }  // namespace pz

@@ -7,6 +7,7 @@
 //   launch_bdd.hip   the BDD evaluator's gather table and the gathered forms of the small-ring CMUX kernels
 //   bdd_schedule.cpp the BDD circuit compiler (plain C++, no HIP)
 //   pack_levels.cpp  the level map of FheUint::pack (plain C++, no HIP)
+//   word_ops.cpp     the stage plan of the FheUint byte operations (plain C++, no HIP)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
@@ -345,6 +346,24 @@ struct PackLevelCall {
     const unsigned char *lo = nullptr, *hi = nullptr;
 };
 int launch_pack_level(pz_module* M, bool post, const PackLevelCall& c);
+// The element-wise kernels of the FheUint byte operations (pz_fhe_uint_get_batched / _zero_byte_ / _splice_ / _sext_): `batch`
+// ciphertexts of cols columns and size limbs behind every pointer.
+//   launch_word_pre        out[it][batch] <- X^-exp[it] src[sel[it]], it < items <= 128; shift: followed by the one-bit vec_znx_rsh_assign in base2k.
+//                          out overlaps no source
+//   launch_word_post       res <- base + X^r (tp - tm), wrapping; tp / tm may be null; res == base allowed, res overlaps neither tp nor tm
+//   launch_word_replicate  out <- sum_{m < 8} X^(m n / 8) s; out overlaps s nowhere
+struct WordPreCall {
+    const long long* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    long long* out = nullptr;
+    int cols = 0, size = 0, base2k = 0, batch = 0, items = 0;
+    bool shift = false;
+    const unsigned* exp = nullptr;
+    const unsigned char* sel = nullptr;
+};
+int launch_word_pre(pz_module* M, const WordPreCall& c);
+int launch_word_post(pz_module* M, long long* res, const long long* base, const long long* tp, const long long* tm, unsigned r, int cols, int size,
+                     int batch);
+int launch_word_replicate(pz_module* M, long long* out, const long long* s, int cols, int size, int batch);
 // vmp_apply_dft_to_dft  [vmp.rs:144-264, zero-tail semantics for limb_offset > 0]
 int dev_vmp(pz_module* M, int batch, DV res, DV a, const double* pmat, int rows, int cols_in, int cols_out, int size, int limb_offset);
 // vec_znx_(big_)normalize on one column  [normalize.rs:18-401]

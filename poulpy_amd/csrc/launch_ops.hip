@@ -174,6 +174,58 @@ int launch_pack_level(pz_module* M, bool post, const PackLevelCall& c) {
     return PZ_OK;
 }
 
+// the FheUint byte operations' kernels (k_word_pre / k_word_post / k_word_replicate, device_ops.hpp), chunked over gridDim.z
+int launch_word_pre(pz_module* M, const WordPreCall& c) {
+    if (c.batch <= 0 || c.items <= 0) return PZ_OK;
+    if (c.items > 128 || (long long)c.items * c.batch > (1ll << 30)) return fail(PZ_ERR_INVALID, "fhe_uint_word: more than 128 items in a stage, or 2^30 ciphertexts");
+    WordPreArgs g;
+    for (int s = 0; s < 4; ++s) g.src[s] = c.src[s];
+    g.out = c.out; g.ct = (long long)M->n * c.cols * c.size;
+    g.n = (int)M->n; g.cols = c.cols; g.size = c.size; g.base2k = c.base2k; g.batch = c.batch; g.items = c.items * c.batch; g.shift = c.shift ? 1 : 0;
+    for (int k = 0; k < 128; ++k) { g.exp[k] = k < c.items ? c.exp[k] : 0; g.sel[k] = k < c.items ? c.sel[k] : 0; }
+    for (int k = 0; k < c.items; ++k)
+        if (g.sel[k] > 3 || g.src[g.sel[k]] == nullptr || g.exp[k] >= 2u * (unsigned)M->n) return fail(PZ_ERR_INVALID, "fhe_uint_word: item %d has no source or turns too far", k);
+    KTimer kt(M, PZ_K_ELEMENTWISE);   // (counted with the rotation it replaces: the normalize class then shows the trace's shift gone)
+    for (int i0 = 0; i0 < g.items; i0 += 65535) {   // gridDim.z limit
+        g.item0 = i0;
+        const dim3 grid((unsigned)((M->n + 255) / 256), (unsigned)c.cols, (unsigned)std::min(65535, g.items - i0));
+        hipLaunchKernelGGL(k_word_pre, grid, dim3(256), 0, M->stream, g);
+    }
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+int launch_word_post(pz_module* M, long long* res, const long long* base, const long long* tp, const long long* tm, unsigned r, int cols, int size,
+                     int batch) {
+    if (batch <= 0) return PZ_OK;
+    if (r >= 2u * (unsigned)M->n) return fail(PZ_ERR_INVALID, "fhe_uint_word: the closing step turns too far");
+    WordPostArgs g;
+    g.base = base; g.tp = tp; g.tm = tm; g.res = res; g.ct = (long long)M->n * cols * size;
+    g.n = (int)M->n; g.cols = cols; g.size = size; g.batch = batch; g.r = r;
+    KTimer kt(M, PZ_K_ELEMENTWISE);
+    for (int i0 = 0; i0 < batch; i0 += 65535) {
+        g.item0 = i0;
+        const dim3 grid((unsigned)((M->n + 255) / 256), (unsigned)cols, (unsigned)std::min(65535, batch - i0));
+        hipLaunchKernelGGL(k_word_post, grid, dim3(256), 0, M->stream, g);
+    }
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+int launch_word_replicate(pz_module* M, long long* out, const long long* s, int cols, int size, int batch) {
+    if (batch <= 0) return PZ_OK;
+    if (M->n < 8) return fail(PZ_ERR_INVALID, "fhe_uint_word: ring smaller than a byte");
+    WordRepArgs g;
+    g.s = s; g.out = out; g.ct = (long long)M->n * cols * size;
+    g.n = (int)M->n; g.cols = cols; g.size = size; g.batch = batch;
+    KTimer kt(M, PZ_K_ELEMENTWISE);
+    for (int i0 = 0; i0 < batch; i0 += 65535) {
+        g.item0 = i0;
+        const dim3 grid((unsigned)((M->n + 255) / 256), (unsigned)cols, (unsigned)std::min(65535, batch - i0));
+        hipLaunchKernelGGL(k_word_replicate, grid, dim3(256), 0, M->stream, g);
+    }
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+
 // vmp_apply_dft_to_dft  [vmp.rs:144-264, zero-tail semantics for limb_offset > 0]
 int dev_vmp(pz_module* M, int batch, DV res, DV a, const double* pmat, int rows, int cols_in, int cols_out, int size,
                    int limb_offset) {

@@ -609,6 +609,42 @@ class Module:
         self._ck(self.lib.pz_fhe_uint_execute_batched(self.handle, handle, res, word_bits, arr, nbits, C.byref(gate_params), g, kp,
                                                       C.byref(pack_params), trace_size, tmp, tmp_bytes, batch))
 
+    # -- FheUint byte operations (bdd_arithmetic/ciphertexts/fhe_uint.rs:259-524) ---------------------------------------------
+    def fhe_uint_word_op_tmp_bytes(self, params: GlweOpParams, word_bits: int, batch: int, max_items: int = 1) -> int:
+        return self.lib.pz_fhe_uint_word_op_tmp_bytes(self.handle, C.byref(params), word_bits, max_items, batch)
+
+    def _word_keys(self, gals, key_ptrs):
+        g = (c_int64 * max(len(gals), 1))(*[int(x) for x in gals])
+        kp = _ptrs([0 if k is None else k for k in key_ptrs]) if len(key_ptrs) else (c_void_p * 1)()
+        return g, kp
+
+    def fhe_uint_get_batched(self, res: c_void_p, words: c_void_p, word_bits: int, unit: int, idx, gals, key_ptrs, params: GlweOpParams,
+                             tmp: c_void_p, tmp_bytes: int, batch: int):
+        """get_bit_glwe (unit = abi.PZ_WORD_BIT) / get_byte (PZ_WORD_BYTE) of every word at every index of idx: res = index-major
+        [len(idx)][batch], normalized; gals / key_ptrs: all log2(n) trace steps."""
+        g, kp = self._word_keys(gals, key_ptrs)
+        ix = (C.c_uint32 * max(len(idx), 1))(*[int(i) for i in idx])
+        self._ck(self.lib.pz_fhe_uint_get_batched(self.handle, res, words, word_bits, unit, len(idx), ix, g, kp, C.byref(params), tmp, tmp_bytes, batch))
+
+    def fhe_uint_zero_byte_batched(self, res: c_void_p, a: c_void_p, word_bits: int, byte: int, gals, key_ptrs, params: GlweOpParams,
+                                   tmp: c_void_p, tmp_bytes: int, batch: int):
+        """zero_byte: res = a with byte `byte` zeroed (res == a allowed); un-normalized, as the reference's."""
+        g, kp = self._word_keys(gals, key_ptrs)
+        self._ck(self.lib.pz_fhe_uint_zero_byte_batched(self.handle, res, a, word_bits, byte, g, kp, C.byref(params), tmp, tmp_bytes, batch))
+
+    def fhe_uint_splice_batched(self, res: c_void_p, a: c_void_p, b: c_void_p, word_bits: int, width: int, dst: int, src: int, gals, key_ptrs,
+                                params: GlweOpParams, tmp: c_void_p, tmp_bytes: int, batch: int):
+        """splice_u8 (width 8) / splice_u16 (width 16): res = a with byte / half-word dst replaced by byte / half-word src of b (res == a,
+        res == b, a == b allowed); un-normalized, as the reference's."""
+        g, kp = self._word_keys(gals, key_ptrs)
+        self._ck(self.lib.pz_fhe_uint_splice_batched(self.handle, res, a, b, word_bits, width, dst, src, g, kp, C.byref(params), tmp, tmp_bytes, batch))
+
+    def fhe_uint_sext_batched(self, word: c_void_p, word_bits: int, byte: int, gals, key_ptrs, params: GlweOpParams, tmp: c_void_p,
+                              tmp_bytes: int, batch: int):
+        """sext, in place: the bytes above `byte` become copies of its sign bit."""
+        g, kp = self._word_keys(gals, key_ptrs)
+        self._ck(self.lib.pz_fhe_uint_sext_batched(self.handle, word, word_bits, byte, g, kp, C.byref(params), tmp, tmp_bytes, batch))
+
     def set_graphs(self, enable: bool):
         """HIP-graph replay of the launch-bound composite calls (blind rotation, trace, circuit bootstrapping); on by default."""
         self._ck(self.lib.pz_module_set_graphs(self.handle, 1 if enable else 0))
@@ -936,3 +972,33 @@ def fhe_uint_pack_level_pairs(n: int, word_bits: int, level: int, lib: C.CDLL | 
     buf = (C.c_uint32 * max(3 * cnt, 1))()
     lib.pz_fhe_uint_pack_level_pairs(n, word_bits, level, buf, cnt)
     return [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(cnt)]
+
+
+def fhe_uint_bit_coefficient(n: int, word_bits: int, bit: int, lib: C.CDLL | None = None) -> int:
+    """pz_fhe_uint_bit_coefficient: host only - the coefficient bit_index(bit) << log_gap of a bit of a word; ValueError out of range."""
+    v = int((lib or load_library()).pz_fhe_uint_bit_coefficient(n, word_bits, bit))
+    if v >= n:
+        raise ValueError("fhe_uint_bit_coefficient: n %d, word_bits %d, bit %d out of range" % (n, word_bits, bit))
+    return v
+
+
+def fhe_uint_word_plan(n: int, word_bits: int, op: int, args, lib: C.CDLL | None = None) -> list:
+    """pz_fhe_uint_word_plan: host only - the stages of one FheUint byte operation (op: abi.PZ_WORD_OP_*; args: the indices of a get, [byte]
+    or [dst, src]) as dicts {skip, items: [(source, exponent, slot)], close, base, plus, minus, r}; ValueError for what the calls refuse."""
+    lib = lib or load_library()
+    a = (C.c_uint32 * max(len(args), 1))(*[int(x) for x in args])
+    st = C.c_int(0)
+    cnt = int(lib.pz_fhe_uint_word_plan(n, word_bits, op, a, len(args), None, 0, C.byref(st)))
+    if st.value != 0:
+        raise ValueError(lib.pz_last_error().decode())
+    buf = (C.c_uint32 * max(cnt, 1))()
+    lib.pz_fhe_uint_word_plan(n, word_bits, op, a, len(args), buf, cnt, C.byref(st))
+    w, stages, i = [int(x) for x in buf[:cnt]], [], 0
+    while i < cnt:
+        skip, nitems = w[i], w[i + 1]
+        items = [tuple(w[i + 2 + 3 * k:i + 5 + 3 * k]) for k in range(nitems)]
+        i += 2 + 3 * nitems
+        none = lambda v: None if v == 0xFFFFFFFF else v   # noqa: E731
+        stages.append(dict(skip=skip, items=items, close=w[i], base=w[i + 1], plus=none(w[i + 2]), minus=none(w[i + 3]), r=w[i + 4]))
+        i += 5
+    return stages
