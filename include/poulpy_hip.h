@@ -661,6 +661,32 @@ typedef struct {
 int pz_glwe_combine_batched(pz_module* m, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
                             const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch);
 
+/* Weighted sum of `batch` device-resident ciphertexts by constants, one pass over HBM: poulpy-ckks's ckks_mul_add_pt_const_* /
+ * ckks_mul_sub_pt_const_* / ckks_dot_product_pt_const_znx (leveled/delegates/composite.rs:290-330, :423-463, :760-784; the mapping is
+ * poulpy_amd/ckks.py and DESIGN.md 4.6d).  res = batch GLWEs VecZnx(rank+1, res_size) at base2k.  init = PZ_LINCOMB_INIT_RES: the
+ * accumulator starts as res (mul_add / mul_sub); PZ_LINCOMB_INIT_NONE: term 0's product overwrites it and its join is ignored (the dot
+ * product).  Term t, in order: the product of operands[t] (batch GLWEs VecZnx(rank+1, a_size[t]) back to back, or one when shared[t]) by
+ * the constant re[t] + i im[t] (HOST arrays of b_size[t] digits, either or both NULL) with cnv_offset[t], exactly as
+ * pz_glwe_mul_const_batched (PZ_MUL_CONST) writes it into a res_size-limb container; then, with sign[t] = +1 / -1 (ckks_add_assign_unsafe
+ * / ckks_sub_assign_unsafe, leveled/default/add.rs:122-146):
+ *   PZ_JOIN_PLAIN     acc +- product (k[t] must be 0)
+ *   PZ_JOIN_LSH_TERM  acc +- lsh(product, k[t])                  (glwe_lsh_add / glwe_lsh_sub)
+ *   PZ_JOIN_LSH_ACC   lsh(acc, k[t]), then +- product            (glwe_lsh_assign on the running sum)
+ * then, with normalize = 1, glwe_normalize_assign; every limb of res is stored once.  Every array has nterms entries.
+ * PZ_ERR_INVALID: sizes, shifts or digit counts out of range, nterms = 0 or nterms > 2^(63 - base2k) (ensure_accumulation_fits).
+ * PZ_ERR_ALIAS: an operand that overlaps res, unless init = PZ_LINCOMB_INIT_RES and it IS res (same pointer, a_size = res_size, not
+ * shared).  PZ_ERR_UNSUPPORTED: more than 64 terms, a_size > 64 or b_size > 32, or
+ *   (max_t a_size[t] + s res_size) x (2 if any im[t] is given, else 1) x 128 x 8 bytes > 160 KiB (the workgroup's LDS), with s = 2 if any
+ *   join but a dot product's first is not PZ_JOIN_PLAIN, else 1.
+ * Nothing is launched on a refusal.  Device pointers for res / operands.  No workspace; inside a graph, kernel nodes only: the constants
+ * travel through a module-owned table written in front of the graph, so a repeated call picks up new constants behind the same arguments. */
+enum { PZ_LINCOMB_INIT_NONE = 0, PZ_LINCOMB_INIT_RES = 1 };
+enum { PZ_JOIN_PLAIN = 0, PZ_JOIN_LSH_TERM = 1, PZ_JOIN_LSH_ACC = 2 };
+int pz_glwe_lincomb_const_batched(pz_module* m, int64_t* res, size_t rank, size_t res_size, size_t base2k, const int64_t* const* operands,
+                                  const int* shared, const size_t* a_size, const size_t* cnv_offset, const int64_t* const* re,
+                                  const int64_t* const* im, const size_t* b_size, const int* join, const size_t* k, const int* sign, size_t nterms,
+                                  int init, int normalize, size_t batch);
+
 /* BlindRotationExecute<CGGI>::blind_rotation_execute (poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs:76-118)
  * on `batch` LWE ciphertexts that share the lookup table and the prepared blind-rotation key:
  *   block_size > 1 : execute_block_binary  (:265-368)       block_size == 1 : execute_standard (:370-440)

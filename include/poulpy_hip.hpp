@@ -395,6 +395,15 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                                 const pz_glwe_mul_const_params& p, int mode, size_t batch) {
         check(pz_glwe_mul_const_batched(m_, res, a, re, im, b_size, &p, mode, batch), "glwe_mul_const_batched");
     }
+    // res = [res] +- sum_t constant_t x operands[t] in one pass; every array has nterms entries (poulpy_hip.h)
+    void glwe_lincomb_const_batched(int64_t* res, size_t rank, size_t res_size, size_t base2k, const int64_t* const* operands, const int* shared,
+                                    const size_t* a_size, const size_t* cnv_offset, const int64_t* const* re, const int64_t* const* im,
+                                    const size_t* b_size, const int* join, const size_t* k, const int* sign, size_t nterms, int init, bool normalize,
+                                    size_t batch) {
+        check(pz_glwe_lincomb_const_batched(m_, res, rank, res_size, base2k, operands, shared, a_size, cnv_offset, re, im, b_size, join, k, sign,
+                                            nterms, init, normalize ? 1 : 0, batch),
+              "glwe_lincomb_const_batched");
+    }
 
   private:
     pz_module* m_ = nullptr;

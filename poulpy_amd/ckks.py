@@ -7,6 +7,10 @@ pz_glwe_combine_batched call (include/poulpy_hip.h) whose terms 
 the reference's branch conditions and the same order of arguments in the shift amounts.  `plan_*` returns the Plan (terms, normalize
 flag, new metadata) without touching a device; `Plan.launch` issues the call.  A plan that the reference would reject
 (CKKSCompositionError) raises CKKSError before anything is launched.
+
+Products and weighted sums by constants (mul.rs:342-415; leveled/delegates/composite.rs mul_add_pt_const / mul_sub_pt_const /
+dot_product_pt_const) are at the end of the file: plan_mul_pt_const_* launch pz_glwe_mul_const_batched, the composites one
+pz_glwe_lincomb_const_batched or, where that measured slower, the same sum term by term.
 """
 from __future__ import annotations
 
@@ -283,3 +287,210 @@ def plan_rotate_many(dsts, src: Ct) -> RotatePlan:
 def plan_rotate_into(dst: Ct, src: Ct) -> RotatePlan:
     """rotate.rs:23-56."""
     return plan_rotate_many([dst], src)
+
+
+# ---- products and weighted sums by constants (leveled/default/mul.rs:342-415, leveled/delegates/composite.rs) ---------------------------
+PLAIN, LSH_TERM, LSH_ACC = 0, 1, 2   # PZ_JOIN_PLAIN / _LSH_TERM / _LSH_ACC
+
+
+@dataclass
+class Cst:
+    """CKKSPlaintextCstZnx (layouts/plaintext/cst.rs): the digits of re + i im at the ciphertext's base2k (either or both None) and the
+    constant's metadata."""
+    log_delta: int
+    log_budget: int
+    re: object = None
+    im: object = None
+
+    @property
+    def empty(self) -> bool:
+        return self.re is None and self.im is None
+
+
+def min_k(log_delta: int, log_budget: int, base2k: int) -> int:   # lib.rs:79-81
+    return -(-(log_delta + log_budget) // base2k) * base2k
+
+
+def checked_mul_pt_log_budget(op: str, lhs_log_budget: int, rhs_log_budget: int, lhs_log_delta: int, rhs_log_delta: int) -> int:   # error.rs:177-194
+    if rhs_log_delta > lhs_log_budget:
+        raise CKKSError(f"{op}: multiplication precision underflow (lhs log_budget {lhs_log_budget}, log_delta {lhs_log_delta}; "
+                        f"rhs log_budget {rhs_log_budget}, log_delta {rhs_log_delta})")
+    return lhs_log_budget - rhs_log_delta
+
+
+def get_mul_const_params(res: Ct, a: Ct, prec: Cst):
+    """leveled/default/mul.rs:498-513 -> (res_log_budget, res_log_delta, cnv_offset)."""
+    res_log_budget = checked_mul_pt_log_budget("mul_const", a.log_budget, prec.log_budget, a.log_delta, prec.log_delta)
+    res_log_delta = a.log_delta
+    res_offset = max(res_log_budget + res_log_delta - res.max_k, 0)
+    cnv_offset = min_k(prec.log_delta, prec.log_budget, res.base2k) + res_offset
+    return checked_log_budget_sub("mul_const", res_log_budget, res_offset), res_log_delta, cnv_offset
+
+
+@dataclass
+class ConstPlan:
+    """ckks_mul_pt_const_znx_into / _assign (mul.rs:342-407): one pz_glwe_mul_const_batched."""
+    name: str
+    cnv_offset: int
+    log_delta: int
+    log_budget: int
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, a: Ct | None, cst: Cst):
+        from .hal import GlweMulConstParams
+        assign = self.name.endswith("assign")
+        src = dst if assign else a
+        p = GlweMulConstParams(rank=dst.cols - 1, a_size=src.size, a_base2k=src.base2k, res_size=dst.size, res_base2k=dst.base2k,
+                               cnv_offset=self.cnv_offset)
+        module.glwe_mul_const_batched(dst.data, None if assign else a.data, cst.re, cst.im, p, "assign" if assign else "into", batch)
+        self.apply_meta(dst)
+
+
+def plan_mul_pt_const_into(dst: Ct, a: Ct, cst: Cst) -> ConstPlan:
+    """mul.rs:342-374."""
+    _same_layout("mul_pt_const_into", dst, a)
+    log_budget, log_delta, cnv_offset = get_mul_const_params(dst, a, cst)
+    return ConstPlan("mul_pt_const_into", cnv_offset, log_delta, log_budget)
+
+
+def plan_mul_pt_const_assign(dst: Ct, cst: Cst) -> ConstPlan:
+    """mul.rs:376-407."""
+    log_budget, log_delta, cnv_offset = get_mul_const_params(dst, dst, cst)
+    return ConstPlan("mul_pt_const_assign", cnv_offset, log_delta, log_budget)
+
+
+@dataclass
+class LinTerm:
+    index: int                     # which operand / constant of the call
+    cnv_offset: int
+    join: int = PLAIN
+    k: int = 0
+    sign: int = 1
+    log_delta: int = 0             # the product's own metadata (what the reference's scratch ciphertext carries)
+    log_budget: int = 0
+
+
+# Routing by measurement (tools/bench_ckks_lincomb.py, DESIGN.md 4.6d): (nterms, complex) -> does the one-pass kernel beat the composition
+# of pz_glwe_mul_const_batched into a scratch batch and pz_glwe_combine_batched by more than the run-to-run spread?  Where it does not,
+# LincombPlan.launch takes the composition when the caller hands it a scratch batch.  Measured at N = 2^16, 16 limbs, 256 ciphertexts
+# (profiles/ckks_lincomb_lines.jsonl): the one-pass kernel takes 1.6 - 2.2 x the composition's time at 1, 2, 8 and 32 terms, real and
+# complex, so no case is routed to it; it remains the route that needs no scratch batch.
+FUSED_WINS = frozenset()             # (nterms, complex) pairs measured in favour of the one-pass kernel
+
+
+def fused_route(nterms: int, complex_terms: bool) -> bool:
+    return (nterms, bool(complex_terms)) in FUSED_WINS
+
+
+@dataclass
+class LincombPlan:
+    """ckks_mul_add_pt_const_* / ckks_mul_sub_pt_const_* / ckks_dot_product_pt_const_znx: one pz_glwe_lincomb_const_batched."""
+    name: str
+    init_res: bool
+    terms: list = field(default_factory=list)
+    normalize: bool = False
+    log_delta: int = 0
+    log_budget: int = 0
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def call_terms(self, ops, csts, shared=()):
+        out = []
+        for t in self.terms:
+            o, c = ops[t.index], csts[t.index]
+            out.append(dict(a=o.data, a_size=o.size, cnv_offset=t.cnv_offset, re=c.re, im=c.im, shared=t.index in shared, join=t.join, k=t.k,
+                            sign=t.sign))
+        return out
+
+    def launch(self, module, dst: Ct, batch: int, ops, csts, shared=(), tmp=None, route=None):
+        """ops[i].data / dst.data: device pointers; csts[i]: the constants (host digits); shared: indices of the operands that hold one
+        ciphertext for the whole batch.  No launch when there are no terms (an empty constant in mul_add / mul_sub).  route: "fused" |
+        "composed" | None (fused_route(); the composition needs `tmp`, a device pointer to `batch` ciphertexts of dst's layout)."""
+        if self.terms:
+            if route is None:
+                fused = tmp is None or fused_route(len(self.terms), any(csts[t.index].im is not None for t in self.terms))
+                route = "fused" if fused else "composed"
+            if route == "fused":
+                module.glwe_lincomb_const_batched(dst.data, dst.cols - 1, dst.size, dst.base2k, self.call_terms(ops, csts, shared), self.init_res,
+                                                  self.normalize, batch)
+            else:
+                self.launch_composed(module, dst, batch, ops, csts, shared, tmp)
+        self.apply_meta(dst)
+
+    def launch_composed(self, module, dst: Ct, batch: int, ops, csts, shared, tmp):
+        """The same sum term by term, as the reference runs it: pz_glwe_mul_const_batched into `tmp`, then one pz_glwe_combine_batched that
+        joins it to dst (the closing glwe_normalize_assign rides on the last one)."""
+        from .hal import GlweMulConstParams
+        if tmp is None:
+            raise CKKSError(f"{self.name}: the composed route needs a scratch batch of dst's layout")
+        for n, t in enumerate(self.terms):
+            o, c = ops[t.index], csts[t.index]
+            p = GlweMulConstParams(rank=dst.cols - 1, a_size=o.size, a_base2k=o.base2k, res_size=dst.size, res_base2k=dst.base2k,
+                                   cnv_offset=t.cnv_offset)
+            last = n == len(self.terms) - 1
+            one = t.index in shared
+            if n == 0 and not self.init_res and not one:
+                module.glwe_mul_const_batched(dst.data, o.data, c.re, c.im, p, "into", batch)
+                if last and self.normalize:
+                    module.glwe_combine_batched(dst.data, dst.cols, dst.size, dst.base2k, [dict(a=dst.data, a_size=dst.size, kind=RAW)], True, batch)
+                continue
+            module.glwe_mul_const_batched(tmp, o.data, c.re, c.im, p, "into", 1 if one else batch)
+            prod = dict(a=tmp, a_size=dst.size, kind=LSH if t.join == LSH_TERM else RAW, k=t.k if t.join == LSH_TERM else 0, sign=t.sign, shared=one)
+            acc = dict(a=dst.data, a_size=dst.size, kind=LSH if t.join == LSH_ACC else RAW, k=t.k if t.join == LSH_ACC else 0)
+            terms = [prod] if n == 0 and not self.init_res else [acc, prod]
+            module.glwe_combine_batched(dst.data, dst.cols, dst.size, dst.base2k, terms, last and self.normalize, batch)
+
+
+def _join(acc_log_budget: int, tmp_log_budget: int):
+    """the branch of ckks_add_assign_unsafe / ckks_sub_assign_unsafe (add.rs:132-141, sub.rs:132-141) -> (join, k)"""
+    if acc_log_budget < tmp_log_budget:
+        return LSH_TERM, tmp_log_budget - acc_log_budget
+    if acc_log_budget > tmp_log_budget:
+        return LSH_ACC, acc_log_budget - tmp_log_budget
+    return PLAIN, 0
+
+
+def plan_mul_add_pt_const(dst: Ct, a: Ct, cst: Cst, sub=False) -> LincombPlan:
+    """composite.rs:290-308 / :423-441: the product into a scratch ciphertext of dst's layout, then ckks_add_assign / ckks_sub_assign
+    (normalized).  An empty constant: no launch, dst and its metadata untouched (:301-303)."""
+    name = "mul_sub_pt_const" if sub else "mul_add_pt_const"
+    if cst.empty:
+        return LincombPlan(name, True, [], False, dst.log_delta, dst.log_budget)
+    _same_layout(name, dst, a)
+    log_budget, log_delta, cnv_offset = get_mul_const_params(dst, a, cst)
+    join, k = _join(dst.log_budget, log_budget)
+    term = LinTerm(0, cnv_offset, join, k, -1 if sub else 1, log_delta, log_budget)
+    return LincombPlan(name, True, [term], True, min(dst.log_delta, log_delta), min(dst.log_budget, log_budget))
+
+
+def plan_mul_sub_pt_const(dst: Ct, a: Ct, cst: Cst) -> LincombPlan:
+    return plan_mul_add_pt_const(dst, a, cst, sub=True)
+
+
+def plan_dot_product_pt_const(dst: Ct, ops, csts) -> LincombPlan:
+    """composite.rs:760-784 with accumulate_unnormalized (:478-506): dst = sum_i csts[i] * ops[i].  n = 1 is the plain product; an
+    all-empty constant is a zero product that still takes part in the budget alignment."""
+    name = "dot_product_pt_const"
+    if len(ops) == 0:                                                     # check_lengths, :468-476
+        raise CKKSError(f"{name}: inputs must contain at least one pair")
+    if len(ops) != len(csts):
+        raise CKKSError(f"{name}: length mismatch between ct vector ({len(ops)}) and weight vector ({len(csts)})")
+    n = len(ops)
+    if dst.base2k >= 64 or n > (1 << (63 - dst.base2k)):                  # ensure_accumulation_fits, :43-51
+        raise CKKSError(f"{name}: {n} terms risks i64 overflow at base2k={dst.base2k}")
+    terms = []
+    log_delta = log_budget = 0
+    for i, (a, c) in enumerate(zip(ops, csts)):
+        _same_layout(name, dst, a)
+        tb, td, cnv_offset = get_mul_const_params(dst, a, c)
+        if i == 0:
+            terms.append(LinTerm(0, cnv_offset, PLAIN, 0, 1, td, tb))
+            log_delta, log_budget = td, tb
+            continue
+        join, k = _join(log_budget, tb)
+        terms.append(LinTerm(i, cnv_offset, join, k, 1, td, tb))
+        log_delta, log_budget = min(log_delta, td), min(log_budget, tb)
+    return LincombPlan(name, False, terms, n > 1, log_delta, log_budget)

@@ -323,6 +323,9 @@ void pz_module_free(pz_module* M) {
     for (auto& bt : M->bdd_tables) { (void)hipFree(bt.gates); (void)hipFree(bt.level_start); }
     if (M->bdd_stage) (void)hipHostFree(M->bdd_stage);
     if (M->bdd_stage_ev) (void)hipEventDestroy(M->bdd_stage_ev);
+    if (M->lin_tab) (void)hipFree(M->lin_tab);
+    if (M->lin_stage) (void)hipHostFree(M->lin_stage);
+    if (M->lin_stage_ev) (void)hipEventDestroy(M->lin_stage_ev);
     if (M->comm) (void)pz_comm_destroy(M);
     for (auto& t : M->timed) { (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); }
     for (auto e : M->event_pool) (void)hipEventDestroy(e);

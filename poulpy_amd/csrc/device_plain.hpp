@@ -34,33 +34,33 @@ struct MulConstArgs {
     MulConstArm arm[2];
 };
 
-__device__ __forceinline__ long long mc_digit(int k, long long x) { return (long long)((unsigned long long)x << (64 - k)) >> (64 - k); }
-__device__ __forceinline__ long long mc_carry(int k, long long x, long long d) { return (long long)((unsigned long long)x - (unsigned long long)d) >> k; }
-__device__ __forceinline__ long long mc_add(long long a, long long b) { return (long long)((unsigned long long)a + (unsigned long long)b); }
-__device__ __forceinline__ long long mc_shl(long long a, int s) { return (long long)((unsigned long long)a << s); }
+__host__ __device__ __forceinline__ long long mc_digit(int k, long long x) { return (long long)((unsigned long long)x << (64 - k)) >> (64 - k); }
+__host__ __device__ __forceinline__ long long mc_carry(int k, long long x, long long d) { return (long long)((unsigned long long)x - (unsigned long long)d) >> k; }
+__host__ __device__ __forceinline__ long long mc_add(long long a, long long b) { return (long long)((unsigned long long)a + (unsigned long long)b); }
+__host__ __device__ __forceinline__ long long mc_shl(long long a, int s) { return (long long)((unsigned long long)a << s); }
 
 // product limb kk of res_big (convolution.rs:395-421; limbs >= min_size are the zeroed tail, :199-202); `la` = the operand limbs of
 // this thread's coefficient, limb l at la[l * kMulConstBlock]
-__device__ __forceinline__ long long mc_big(const MulConstArm& w, const long long* la, int a_size, int kk) {
+__host__ __device__ __forceinline__ long long mc_big(const MulConstArm& w, const long long* la, int a_size, int kk) {
     if (kk >= w.min_size) return 0;
     const int k = kk + w.offset;
     unsigned long long acc = 0;
     if (k < a_size + w.b_size) {
         const int j_min = k >= a_size - 1 ? k - (a_size - 1) : 0;
-        const int j_max = min(k + 1, w.b_size);
+        const int j_max = k + 1 < w.b_size ? k + 1 : w.b_size;
         for (int j = j_min; j < j_max; ++j) acc += (unsigned long long)la[(k - j) * kMulConstBlock] * (unsigned long long)w.b[j];
     }
     return (long long)acc;
 }
 // res limb j at `r` (limb stride rls): mode 1 = v, 2 = -v, 3 += v, 4 -= v (wrapping)
-__device__ __forceinline__ void mc_put(long long* r, int mode, long long v) {
+__host__ __device__ __forceinline__ void mc_put(long long* r, int mode, long long v) {
     if (mode == 1) *r = v;
     else if (mode == 2) *r = (long long)(0ull - (unsigned long long)v);
     else if (mode == 3) *r = mc_add(*r, v);
     else *r = (long long)((unsigned long long)*r - (unsigned long long)v);
 }
 // vec_znx_normalize_inter_base2k (normalize.rs:50-144), the walk of k_normalize_inter (device_ops.hpp) on the product limbs
-__device__ __forceinline__ void mc_walk(const MulConstArgs& g, const MulConstArm& w, const long long* la, long long* r, long long rls, int mode) {
+__host__ __device__ __forceinline__ void mc_walk(const MulConstArgs& g, const MulConstArm& w, const long long* la, long long* r, long long rls, int mode) {
     const int k = g.k, lsh = g.lsh, kk = lsh == 0 ? k : k - lsh;
     long long c = 0;
     const int a_out_range = w.big_size > w.a_start ? w.big_size - w.a_start : 0;
@@ -90,6 +90,29 @@ __device__ __forceinline__ void mc_walk(const MulConstArgs& g, const MulConstArm
         mc_put(r + (long long)(w.res_end - j - 1) * rls, mode, x1);
         if (j != w.res_end - 1) c = mc_carry(k, c, x1);
     }
+}
+
+// the normalization plan of a product (normalize.rs:83-101) and of its arms (convolution.rs:160-162) into g: everything but the pointers,
+// the strides and the grid
+inline void mul_const_plan(MulConstArgs& g, int a_size, int res_size, int base2k, long long res_offset, int form, const MulConstArmSpec* arms) {
+    g.a_size = a_size; g.res_size = res_size; g.k = base2k; g.form = form;
+    const long long k = base2k;
+    long long lsh = res_offset % k, lo = res_offset / k;   // normalize.rs:83-101
+    if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
+    g.lsh = (int)lsh;
+    auto cl = [](long long v, long long lo_, long long hi_) { return v < lo_ ? lo_ : (v > hi_ ? hi_ : v); };
+    for (int u = 0; u < (form == 2 ? 2 : 1); ++u) {
+        const MulConstArmSpec& s = arms[u];
+        MulConstArm& w = g.arm[u];
+        for (int j = 0; j < kMulConstMaxB; ++j) w.b[j] = j < s.b_size ? (long long)s.b[j] : 0;
+        const int bound = a_size + s.b_size - 1;   // convolution.rs:160-162
+        w.b_size = s.b_size; w.big_size = s.big_size; w.min_size = (s.big_size < bound ? s.big_size : bound); w.offset = (s.hi < bound ? s.hi : bound);
+        w.res_end = (int)cl(-lo, 0, res_size);
+        w.res_start = (int)cl((long long)s.big_size - lo, 0, res_size);
+        w.a_end = (int)cl(lo, 0, s.big_size);
+        w.a_start = (int)cl((long long)res_size + lo, 0, s.big_size);
+    }
+    if (form != 2) g.arm[1] = g.arm[0];
 }
 
 // grid: ceil(batch * npts / kMulConstBlock) workgroups, npts = n (form 0) or n / 2; dynamic LDS = a_size x (2 if paired, else 1) x kMulConstBlock i64

@@ -11,12 +11,13 @@
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
-//   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp)
+//   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp), weighted sums by constants (device_lincomb.hpp)
 //   api.hip          C ABI: module, memory, key pinning / mirrors
 //   api_glwe.hip     C ABI: the batched GLWE product (glwe_op) and its direct callers
 //   api_hal.hip      C ABI: the per-op HalImpl methods (VecZnxDft, SVP, VMP, VecZnxBig, i64 VecZnx family)
 //   api_br.hip       C ABI: blind rotation, circuit bootstrapping, GLWE packing (composites on glwe_op; HIP-graph replay)
 //   api_cnv.hip      C ABI: convolution family, GLWE tensoring, batched i64 family
+//   api_lincomb.hip  C ABI: weighted sums of GLWE batches by constants
 //   api_lwe.hip      C ABI: LWE glue of the gate bootstrap (+ its index kernels)
 //   api_dist.hip     C ABI: RCCL key broadcast (dlopen)
 //   api_common.hpp / api_glwe.hpp   what those share (staging, graph cache, glwe_op / glwe_trace / ggsw_expand_row)
@@ -414,5 +415,26 @@ bool mul_const_nz_supported(const pz_module* M, int a_size, int b_size);
 // form 0: arm0; 1: X^{N/2} arm0; 2: arm0 + X^{N/2} arm1 - every column of `batch` ciphertexts (a: a_size limbs, res: res_size limbs, cols columns)
 int launch_mul_const_nz(pz_module* M, int batch, long long* res, long long res_bs, const long long* a, long long a_bs, int cols, int a_size,
                         int res_size, int base2k, long long res_offset, int form, const MulConstArmSpec* arms);
+// k_lincomb_const (device_lincomb.hpp): res = [res] +- sum_t (constant_t x a_t), every column of `batch` ciphertexts in one pass.  One term:
+// the operand (a_bs 0: shared by the batch), the constant re + i im (host digits, either or both null) with the product's cnv_offset, and
+// how the product joins the accumulator (0: acc +- tmp; 1: acc +- lsh(tmp, k); 2: lsh(acc, k) +- tmp)
+struct LinTermSpec {
+    const long long* a;
+    long long a_bs;
+    int a_size;
+    size_t cnv_offset;
+    const int64_t *re, *im;
+    int b_size;
+    int join, neg;
+    size_t k;
+};
+constexpr int kLincombMaxTerms = 64;
+constexpr size_t kLincombMaxLds = (size_t)160 * 1024;
+// dynamic LDS of a launch: (a_max + res_size, + res_size again where a join shifts) x (2 if paired) x 128 threads x 8 B
+size_t lincomb_lds_bytes(int a_max, int res_size, bool pair, bool has_tmp);
+// plans the terms into the module's page-locked staging and copies them to its device table, on the stream, outside any graph
+int lincomb_stage(pz_module* M, const LinTermSpec* terms, int nterms, int res_size, int base2k);
+int launch_lincomb(pz_module* M, int batch, long long* res, long long res_bs, int cols, int res_size, int base2k, int nterms, int init_res,
+                   int normalize, bool pair, int a_max, bool has_tmp);
 
 }  // namespace pz

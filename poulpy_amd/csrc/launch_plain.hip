@@ -1,10 +1,11 @@
-// launch_plain.hip — GLWE x constant (device_plain.hpp).
+// launch_plain.hip — GLWE x constant (device_plain.hpp) and sums of such products (device_lincomb.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "internal.hpp"
 #include "device_plain.hpp"
+#include "device_lincomb.hpp"
 
 namespace pz {
 
@@ -19,30 +20,52 @@ int launch_mul_const_nz(pz_module* M, int batch, long long* res, long long res_b
         return fail(PZ_ERR_INVALID, "k_mul_const_nz: shape outside the kernel (a_size %d, b_size %d)", a_size, arms[0].b_size);
     MulConstArgs g;
     g.res = res; g.a = a; g.res_bs = res_bs; g.a_bs = a_bs;
-    g.n = (int)M->n; g.batch = batch; g.cols = cols; g.a_size = a_size; g.res_size = res_size; g.k = base2k; g.form = form;
-    const long long k = base2k;
-    long long lsh = res_offset % k, lo = res_offset / k;   // normalize.rs:83-101
-    if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
-    g.lsh = (int)lsh;
-    auto cl = [](long long v, long long lo_, long long hi_) { return v < lo_ ? lo_ : (v > hi_ ? hi_ : v); };
-    for (int u = 0; u < (form == 2 ? 2 : 1); ++u) {
-        const MulConstArmSpec& s = arms[u];
-        MulConstArm& w = g.arm[u];
-        for (int j = 0; j < kMulConstMaxB; ++j) w.b[j] = j < s.b_size ? (long long)s.b[j] : 0;
-        const int bound = a_size + s.b_size - 1;   // convolution.rs:160-162
-        w.b_size = s.b_size; w.big_size = s.big_size; w.min_size = std::min(s.big_size, bound); w.offset = std::min(s.hi, bound);
-        w.res_end = (int)cl(-lo, 0, res_size);
-        w.res_start = (int)cl((long long)s.big_size - lo, 0, res_size);
-        w.a_end = (int)cl(lo, 0, s.big_size);
-        w.a_start = (int)cl((long long)res_size + lo, 0, s.big_size);
-    }
-    if (form != 2) g.arm[1] = g.arm[0];
+    g.n = (int)M->n; g.batch = batch; g.cols = cols;
+    mul_const_plan(g, a_size, res_size, base2k, res_offset, form, arms);
     const long long npts = form == 0 ? M->n : M->n / 2;
     const long long threads = (long long)batch * npts;
     const size_t lds = (size_t)a_size * (form == 0 ? 1 : 2) * kMulConstBlock * sizeof(long long);
     KTimer kt(M, PZ_K_NORMALIZE);
     PZ_TRY(launch_k(k_mul_const_nz, dim3((unsigned)((threads + kMulConstBlock - 1) / kMulConstBlock)), dim3(kMulConstBlock), lds, M->stream, g));
     dispatch_note(M, "k_mul_const_nz (form %d, a %d limbs x %d digits -> %d, lds=%zu)", form, a_size, arms[0].b_size, res_size, lds);
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+
+static_assert(kLinMaxTerms == kLincombMaxTerms, "the device table holds every term of a call");
+size_t lincomb_lds_bytes(int a_max, int res_size, bool pair, bool has_tmp) {
+    return (size_t)lc_slots(a_max, res_size, pair ? 1 : 0, has_tmp ? 1 : 0) * kMulConstBlock * sizeof(long long);
+}
+
+int lincomb_stage(pz_module* M, const LinTermSpec* terms, int nterms, int res_size, int base2k) {
+    if (nterms < 1 || nterms > kLinMaxTerms) return fail(PZ_ERR_INVALID, "k_lincomb_const: %d terms (1 to %d)", nterms, kLinMaxTerms);
+    const size_t bytes = sizeof(LinTerm) * kLinMaxTerms;
+    if (!M->lin_tab) PZ_HIP(hipMalloc(&M->lin_tab, bytes));
+    if (!M->lin_stage) PZ_HIP(hipHostMalloc(&M->lin_stage, bytes, hipHostMallocDefault));
+    // the previous call's copy out of the staging has finished before it is rewritten
+    if (M->lin_stage_ev) PZ_HIP(hipEventSynchronize(M->lin_stage_ev));
+    else PZ_HIP(hipEventCreateWithFlags(&M->lin_stage_ev, hipEventDisableTiming));
+    LinTerm* st = (LinTerm*)M->lin_stage;
+    for (int u = 0; u < nterms; ++u) lc_plan_term(st[u], terms[u], res_size, base2k);
+    PZ_HIP(hipMemcpyAsync(M->lin_tab, M->lin_stage, sizeof(LinTerm) * (size_t)nterms, hipMemcpyHostToDevice, M->stream));
+    PZ_HIP(hipEventRecord(M->lin_stage_ev, M->stream));
+    return PZ_OK;
+}
+
+int launch_lincomb(pz_module* M, int batch, long long* res, long long res_bs, int cols, int res_size, int base2k, int nterms, int init_res,
+                   int normalize, bool pair, int a_max, bool has_tmp) {
+    if (batch <= 0) return PZ_OK;
+    const size_t lds = lincomb_lds_bytes(a_max, res_size, pair, has_tmp);
+    if (lds > kLincombMaxLds || !M->lin_tab || M->n < 2) return fail(PZ_ERR_INVALID, "k_lincomb_const: shape outside the kernel (lds %zu)", lds);
+    LinArgs g;
+    g.res = res; g.res_bs = res_bs; g.terms = (const LinTerm*)M->lin_tab;
+    g.n = (int)M->n; g.batch = batch; g.cols = cols; g.res_size = res_size; g.k = base2k; g.nterms = nterms;
+    g.init_res = init_res; g.normalize = normalize; g.pair = pair ? 1 : 0; g.a_max = a_max; g.has_tmp = has_tmp ? 1 : 0;
+    const long long threads = (long long)batch * (pair ? M->n / 2 : M->n);
+    KTimer kt(M, PZ_K_NORMALIZE);
+    PZ_TRY(launch_k(k_lincomb_const, dim3((unsigned)((threads + kMulConstBlock - 1) / kMulConstBlock)), dim3(kMulConstBlock), lds, M->stream, g));
+    dispatch_note(M, "k_lincomb_const (%d terms, %s, %d operand limbs -> %d, normalize %d, lds=%zu)", nterms, pair ? "paired" : "unpaired", a_max,
+                  res_size, normalize, lds);
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }

@@ -202,6 +202,11 @@ struct pz_module {
     const void** bdd_stage = nullptr;
     size_t bdd_stage_count = 0;
     hipEvent_t bdd_stage_ev = nullptr;
+    // pz_glwe_lincomb_const_batched: the device table of the call's planned terms (kLinMaxTerms entries, device_lincomb.hpp) and its
+    // page-locked staging, under the same rule: the next call waits for lin_stage_ev before it rewrites the staging
+    void* lin_tab = nullptr;
+    void* lin_stage = nullptr;
+    hipEvent_t lin_stage_ev = nullptr;
     // the distinct kernel instantiations the hot dispatch sites chose since the last pz_module_dispatch_notes(reset) (bench tools print
     // them next to their numbers: "which variant ran" is part of a measurement)
     std::vector<std::string> notes;

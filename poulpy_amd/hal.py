@@ -820,6 +820,34 @@ class Module:
                               int(bool(t.get("col0_only", False))), int(bool(t.get("shared", False))))
         self._ck(self.lib.pz_glwe_combine_batched(self.handle, res, res_cols, res_size, base2k, ops, arr, len(terms), int(bool(normalize)), batch))
 
+    JOIN_KINDS = {"plain": abi.PZ_JOIN_PLAIN, "lsh_term": abi.PZ_JOIN_LSH_TERM, "lsh_acc": abi.PZ_JOIN_LSH_ACC}
+
+    def glwe_lincomb_const_batched(self, res: c_void_p, rank: int, res_size: int, base2k: int, terms, init_res: bool, normalize: bool, batch: int):
+        """res = [res] +- sum_t constant_t x a_t in one pass (include/poulpy_hip.h): poulpy-ckks's mul_add / mul_sub /
+        dot product by constants.  terms: dicts with keys a (device pointer), a_size, cnv_offset, re / im (host digit arrays or None) and
+        optional shared, join ("plain" | "lsh_term" | "lsh_acc"), k, sign (+1 / -1).  init_res: the accumulator starts as res."""
+        nt = max(len(terms), 1)
+        ops, rp, ip = (c_void_p * nt)(), (c_void_p * nt)(), (c_void_p * nt)()
+        shared, join, sign = (C.c_int * nt)(), (C.c_int * nt)(), (C.c_int * nt)()
+        a_size, cnv, b_size, k = (C.c_size_t * nt)(), (C.c_size_t * nt)(), (C.c_size_t * nt)(), (C.c_size_t * nt)()
+        keep = []
+        for i, t in enumerate(terms):
+            a = t["a"]
+            ops[i] = a.value if isinstance(a, c_void_p) else a
+            arrs = [None if t.get(x) is None else np.ascontiguousarray(t[x], dtype=np.int64) for x in ("re", "im")]
+            sizes = {x.size for x in arrs if x is not None}
+            assert len(sizes) <= 1, "re and im carry the same number of digits"
+            keep.append(arrs)
+            rp[i], ip[i] = [None if x is None else x.ctypes.data for x in arrs]
+            b_size[i] = int(t["b_size"]) if "b_size" in t else (sizes.pop() if sizes else 0)
+            shared[i], a_size[i], cnv[i] = int(bool(t.get("shared", False))), int(t["a_size"]), int(t["cnv_offset"])
+            j = t.get("join", "plain")
+            join[i] = self.JOIN_KINDS[j] if isinstance(j, str) else int(j)
+            k[i], sign[i] = int(t.get("k", 0)), int(t.get("sign", 1))
+        init = abi.PZ_LINCOMB_INIT_RES if init_res else abi.PZ_LINCOMB_INIT_NONE
+        self._ck(self.lib.pz_glwe_lincomb_const_batched(self.handle, res, rank, res_size, base2k, ops, shared, a_size, cnv, rp, ip, b_size, join, k,
+                                                        sign, len(terms), init, int(bool(normalize)), batch))
+
     def _shift_acc(self, name, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col):
         self._ck(getattr(self.lib, name)(self.handle, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col))
 
