@@ -1,12 +1,8 @@
-// api_br.hip — C ABI of the composite calls built on the batched GLWE product: CGGI blind rotation (block-binary, standard, extended),
-// circuit bootstrapping (constant / exponent mode) and GLWE packing.  poulpy-bin-fhe blind_rotation/algorithms/cggi/algorithm.rs,
-// circuit_bootstrapping/circuit.rs; poulpy-core glwe_packing.rs.  SURVEY.md §8f rank 2.
-#include <string>
-
+// api_br.hip — C ABI of the CGGI blind rotation (block-binary, standard, extended: all four paths) and of the circuit bootstrapping built on it
+// (constant / exponent mode; its traces, packing and row expansion are api_trace.hip and api_ggsw.hip).  poulpy-bin-fhe
+// blind_rotation/algorithms/cggi/algorithm.rs, circuit_bootstrapping/circuit.rs.  SURVEY.md §8f rank 2.
 #include "api_common.hpp"
-#include "api_glwe.hpp"
-#include "pack_levels.hpp"
-#include "word_ops.hpp"
+#include "glwe_call.hpp"
 
 using namespace pz;
 
@@ -383,10 +379,8 @@ int pz_blind_rotation_execute_extended_batched(pz_module* M, int64_t* res, const
 int pz_blind_rotation_execute_batched(pz_module* M, int64_t* res, const int64_t* lwe_2n, const int64_t* lut, const double* brk,
                                       const pz_blind_rotation_params* p, size_t batch) {
     PZ_ENTER(M);
-    KeyHash k;
-    k.add((int)2); k.add(res); k.add(lwe_2n); k.add(lut); k.add(brk); k.add(batch);
+    KeyHash k = graph_key(M, GRAPH_BLIND_ROTATION, res, lwe_2n, lut, brk, batch);
     if (p) k.add(*p);
-    graph_key_module(M, k);
     return with_graph(M, k.h, [&]() { return blind_rotation(M, res, lwe_2n, lut, brk, p, batch); });
 }
 
@@ -398,9 +392,6 @@ int pz_blind_rotation_execute_batched(pz_module* M, int64_t* res, const int64_t*
 //   :369      ggsw_expand_row
 // The dnum_res traces of one LWE are independent, so all batch * dnum_res of them run as one batched trace.
 // ------------------------------------------------------------------------------
-static int glwe_pack(pz_module* M, int64_t* res, size_t nslots, const uint64_t* indices, int64_t* const* cts, size_t log_gap_out,
-                     const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes,
-                     size_t batch, size_t trace_size);
 struct CbtRepack { size_t log_gap_in, log_gap_out, log_domain; };  // exponent mode with log_gap_in != log_gap_out (post_process)
 static inline size_t cbt_atk_size(const pz_circuit_bootstrapping_params* p) { return (size_t)(p->atk_glwe_size ? p->atk_glwe_size : p->br.res_size); }
 static inline size_t cbt_tmp_size(const pz_circuit_bootstrapping_params* p) {
@@ -429,8 +420,7 @@ size_t pz_circuit_bootstrapping_to_exponent_tmp_bytes(const pz_module* M, const 
 static int cbt_repack_rows(pz_module* M, int64_t* tr, const int64_t** row_src, size_t nsteps, const int64_t* gals, const double* const* atk_pmats,
                            const pz_glwe_op_params* tp, const CbtRepack* rp, int count, int tsz, int gsz, int cols) {
     const long long n = (long long)M->n, ct_t = n * cols * tsz;
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    const size_t log_n = log2_n(M);
     PZ_REQUIRE(nsteps == log_n, "circuit_bootstrapping (exponent mode): gals / atk_pmats must cover all log2(n) trace steps");
     PZ_REQUIRE(tsz == gsz, "circuit_bootstrapping (exponent mode): the GGSW must not be more precise than the GLWE of the rotation");
     PZ_REQUIRE(rp->log_gap_in >= 1 && rp->log_gap_in <= log_n && rp->log_gap_out <= log_n && rp->log_domain <= 20 &&
@@ -530,14 +520,12 @@ int pz_circuit_bootstrapping_execute_to_constant_batched(pz_module* M, int64_t* 
                                                          const pz_circuit_bootstrapping_params* p, void* tmp, size_t tmp_bytes,
                                                          size_t batch) {
     PZ_ENTER(M);
-    KeyHash k;
-    k.add((int)3); k.add(ggsw); k.add(lwe_2n); k.add(lut); k.add(brk); k.add(nsteps); k.add(tmp); k.add(tmp_bytes); k.add(batch);
+    KeyHash k = graph_key(M, GRAPH_CIRCUIT_BOOTSTRAPPING, ggsw, lwe_2n, lut, brk, nsteps, tmp, tmp_bytes, batch);
     if (p) {
         k.add(*p);
         for (size_t s = 0; s < nsteps && gals && atk_pmats; ++s) { k.add(gals[s]); k.add(atk_pmats[s]); }
         for (size_t c = 0; c < p->br.rank && tsk_pmats; ++c) k.add(tsk_pmats[c]);
     }
-    graph_key_module(M, k);
     return with_graph(M, k.h, [&]() {
         return circuit_bootstrapping(M, ggsw, lwe_2n, lut, brk, nsteps, gals, atk_pmats, tsk_pmats, p, tmp, tmp_bytes, batch);
     });
@@ -552,8 +540,7 @@ int pz_circuit_bootstrapping_execute_to_exponent_batched(pz_module* M, int64_t* 
                                                          size_t tmp_bytes, size_t batch) {
     PZ_ENTER(M);
     PZ_REQUIRE(gals != nullptr && atk_pmats != nullptr, "circuit_bootstrapping: null argument");
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
+    const size_t log_n = log2_n(M);
     PZ_REQUIRE(log_gap_in >= 1 && log_gap_in <= log_n, "circuit_bootstrapping (exponent mode): log_gap_in out of range");
     if (log_gap_in == log_gap_out) {
         const size_t skip = log_n - log_gap_in + 1;
@@ -561,560 +548,6 @@ int pz_circuit_bootstrapping_execute_to_exponent_batched(pz_module* M, int64_t* 
     }
     CbtRepack rp{log_gap_in, log_gap_out, log_domain};
     return circuit_bootstrapping(M, ggsw, lwe_2n, lut, brk, log_n, gals, atk_pmats, tsk_pmats, p, tmp, tmp_bytes, batch, &rp);
-}
-
-// ------------------------------------------------------------------------------
-// public: GLWEPacking::glwe_pack (poulpy-core/src/glwe_packing.rs:122-176, pack_internal :15-87) on `batch` independent packing
-// problems with the same occupancy pattern, one base2k / size for ciphertexts, keys and result.  cts[s] points to the `batch`
-// contiguous GLWEs of index indices[s] (the reference's HashMap entry); they are clobbered, as the reference's `&mut` entries.
-// The tree is walked on the host exactly as the reference does; every step is a batched launch of the i64 kernels
-// (rotate, add / sub, rsh, normalize) or of the fused automorphism pipeline.
-// ------------------------------------------------------------------------------
-size_t pz_glwe_pack_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
-    if (!M || !p) return 0;
-    return 3 * align256(batch * (size_t)M->n * (p->rank + 1) * p->res_size * 8);
-}
-size_t pz_glwe_pack_bases_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t trace_size, size_t batch) {
-    if (!M || !p) return 0;
-    return pz_glwe_pack_tmp_bytes(M, p, batch) + align256(batch * (size_t)M->n * (p->rank + 1) * trace_size * 8);
-}
-// trace_size = 0: ciphertexts, keys and result share one base2k.  Otherwise the keys have their own (test_suite/glwe_packing.rs:40-42):
-// pack_internal's arithmetic stays in the ciphertexts' base, the automorphisms convert, and the closing glwe_trace (glwe_trace.rs:91-127)
-// runs on a temporary of trace_size limbs in the keys' base (behind the three ciphertext arrays of tmp).
-// The limb-wise steps of glwe_pack on `B` ciphertexts at a time (poulpy-core glwe_packing.rs:41-86), and one merge of two slots
-struct PackStep {
-    pz_module* M;
-    const pz_glwe_op_params* p;
-    size_t batch;
-    long long n, ct;
-    int cols, size, k, B;
-    int64_t *tmp_b, *t1, *t2;
-    PolyMap pm() const { return PolyMap{size, cols, ct, (long long)cols * n, n, 0}; }
-    int rotate_to(long long kk, int64_t* dst, const int64_t* src) {
-        return launch_rotate(M, B * size * cols, (const long long*)src, pm(), (long long*)dst, pm(), kk);
-    }
-    int rotate_assign(long long kk, int64_t* x) {
-        PZ_TRY(rotate_to(kk, t1, x));
-        return launch_ew(M, EW_COPY, x, ct, n, t1, ct, n, nullptr, 0, 0, cols * size, B);
-    }
-    int ew3(int op, int64_t* r, const int64_t* x, const int64_t* y) {   // limb-wise over whole ciphertexts (equal sizes)
-        return launch_ew(M, op, r, ct, n, x, ct, n, y, ct, n, cols * size, B);
-    }
-    int rsh1(int64_t* x) { return launch_rsh(M, B, (long long*)x, ct, cols, size, 0, cols, k, 1); }
-    int normalize_assign(int64_t* x) {
-        PZ_TRY(launch_ew(M, EW_COPY, t2, ct, n, x, ct, n, nullptr, 0, 0, cols * size, B));
-        DV xv{x, ct, cols, size}, tv{t2, ct, cols, size};
-        for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, xv, k, 0, c, tv, k, c));
-        return PZ_OK;
-    }
-    // slots j (a) and j + tt (b) of one level -> *out (null when both are empty)
-    int merge(int64_t* a, int64_t* b, size_t tt, int64_t gal, const double* key, int64_t** out) {
-        *out = nullptr;
-        if (a && b) {                                                       // :41-70
-            PZ_TRY(rotate_assign(-(long long)tt, a));
-            PZ_TRY(ew3(EW_SUB_I64, tmp_b, a, b));
-            PZ_TRY(rsh1(tmp_b));
-            PZ_TRY(ew3(EW_ADD_I64, a, a, b));
-            PZ_TRY(rsh1(a));
-            PZ_TRY(normalize_assign(tmp_b));
-            AutoSpec au{(long long)gal, 0};
-            PZ_TRY(glwe_op(M, GlweKind::Automorphism, tmp_b, tmp_b, key, p, batch, &au));
-            PZ_TRY(ew3(EW_SUB_I64, a, a, tmp_b));
-            PZ_TRY(normalize_assign(a));
-            PZ_TRY(rotate_assign((long long)tt, a));
-            *out = a;
-        } else if (a) {                                                     // :71-75
-            PZ_TRY(rsh1(a));
-            AutoSpec au{(long long)gal, 1};
-            PZ_TRY(glwe_op(M, GlweKind::Automorphism, a, a, key, p, batch, &au));
-            *out = a;
-        } else if (b) {                                                     // :76-86
-            PZ_TRY(rotate_to((long long)tt, tmp_b, b));
-            PZ_TRY(rsh1(tmp_b));
-            AutoSpec au{(long long)gal, 3};
-            PZ_TRY(glwe_op(M, GlweKind::Automorphism, b, tmp_b, key, p, batch, &au));
-            *out = b;
-        }
-        return PZ_OK;
-    }
-};
-static int glwe_pack(pz_module* M, int64_t* res, size_t nslots, const uint64_t* indices, int64_t* const* cts, size_t log_gap_out,
-                     const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes,
-                     size_t batch, size_t trace_size) {
-    PZ_REQUIRE(p != nullptr && indices != nullptr && cts != nullptr && gals != nullptr && key_pmats != nullptr, "glwe_pack: null argument");
-    PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k && p->rank_out == p->rank && p->dsize == 1,
-               "glwe_pack: ciphertexts and result share base2k and size");
-    PZ_REQUIRE(p->res_base2k == p->key_base2k || trace_size >= 1,
-               "glwe_pack: keys in another base than the ciphertexts need pz_glwe_pack_bases_batched (trace_size)");
-    if (p->res_base2k == p->key_base2k) trace_size = 0;
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    PZ_REQUIRE(log_gap_out <= log_n && nslots >= 1, "glwe_pack: bad shape");
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(tmp), "batched entry points take device pointers");
-    PZ_REQUIRE(tmp_bytes >= pz_glwe_pack_bases_tmp_bytes(M, p, trace_size, batch), "glwe_pack: tmp is smaller than pz_glwe_pack[_bases]_tmp_bytes");
-    if (batch == 0) return PZ_OK;
-    PackStep st;
-    st.M = M; st.p = p; st.batch = batch; st.n = (long long)M->n;
-    st.cols = (int)p->rank + 1; st.size = (int)p->res_size; st.k = (int)p->res_base2k; st.B = (int)batch;
-    st.ct = st.n * st.cols * st.size;
-    const long long n = st.n, ct = st.ct;
-    const int cols = st.cols, size = st.size, k = st.k, B = st.B;
-    const size_t ctb = align256((size_t)B * ct * 8);
-    st.tmp_b = (int64_t*)tmp;
-    st.t1 = (int64_t*)((char*)tmp + ctb);
-    st.t2 = (int64_t*)((char*)tmp + 2 * ctb);
-    std::vector<int64_t*> slots((size_t)M->n, nullptr);
-    for (size_t s_ = 0; s_ < nslots; ++s_) {
-        PZ_REQUIRE(indices[s_] < (uint64_t)M->n, "glwe_pack: index out of range");   // glwe_packing.rs:138
-        PZ_REQUIRE(cts[s_] != nullptr && is_device_ptr(cts[s_]) && slots[indices[s_]] == nullptr, "glwe_pack: bad or duplicate entry");
-        slots[indices[s_]] = cts[s_];
-    }
-    for (size_t i = 0; i + log_gap_out < log_n; ++i) {
-        const size_t tt = (size_t)1 << (log_n - 1 - i);
-        PZ_REQUIRE((gals[i] & 1) != 0 && key_pmats[i] != nullptr, "glwe_pack: bad automorphism key");
-        for (size_t j = 0; j < tt; ++j) {
-            int64_t* a = slots[j];
-            int64_t* b = slots[j + tt];
-            slots[j + tt] = nullptr;
-            PZ_TRY(st.merge(a, b, tt, gals[i], key_pmats[i], &slots[j]));
-        }
-    }
-    PZ_REQUIRE(slots[0] != nullptr, "glwe_pack: no ciphertext ends at index 0");   // :175 a.get(&0).unwrap()
-    const size_t skip = log_n - log_gap_out;
-    if (trace_size == 0) {   // glwe_copy both ways
-        PZ_TRY(launch_ew(M, EW_COPY, res, ct, n, slots[0], ct, n, nullptr, 0, 0, cols * size, B));
-        return glwe_trace(M, res, log_n - skip, gals + skip, key_pmats + skip, p, batch);
-    }
-    const int kk = (int)p->key_base2k, tsz = (int)trace_size;
-    const long long ct_t = n * cols * tsz;
-    int64_t* tr = (int64_t*)((char*)tmp + 3 * ctb);
-    DV tv{tr, ct_t, cols, tsz}, sv{slots[0], ct, cols, size}, rv{res, ct, cols, size};
-    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, tv, kk, 0, c, sv, k, c));
-    pz_glwe_op_params q = *p;
-    q.a_size = q.res_size = (uint64_t)tsz; q.a_base2k = q.res_base2k = p->key_base2k;
-    PZ_TRY(glwe_trace(M, tr, log_n - skip, gals + skip, key_pmats + skip, &q, batch));
-    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, k, 0, c, tv, kk, c));
-    return PZ_OK;
-}
-int pz_glwe_pack_batched(pz_module* M, int64_t* res, size_t nslots, const uint64_t* indices, int64_t* const* cts, size_t log_gap_out,
-                         const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes,
-                         size_t batch) {
-    PZ_ENTER(M);
-    return glwe_pack(M, res, nslots, indices, cts, log_gap_out, gals, key_pmats, p, tmp, tmp_bytes, batch, 0);
-}
-int pz_glwe_pack_bases_batched(pz_module* M, int64_t* res, size_t nslots, const uint64_t* indices, int64_t* const* cts, size_t log_gap_out,
-                               const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size, void* tmp,
-                               size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    PZ_REQUIRE(trace_size >= 1, "glwe_pack: trace_size = 0");
-    return glwe_pack(M, res, nslots, indices, cts, log_gap_out, gals, key_pmats, p, tmp, tmp_bytes, batch, trace_size);
-}
-
-// ------------------------------------------------------------------------------
-// public: FheUint::pack (bdd_arithmetic/ciphertexts/fhe_uint.rs:239-255) on `batch` words.  All word_bits indices are occupied,
-// so glwe_pack's tree has log2(word_bits) levels of both-present merges (pack_levels.cpp) and a trace of log_gap steps.  By levels: every
-// level is k_pack_pre, ONE automorphism call on pairs * batch half-differences, k_pack_post.  tmp = [diff: word_bits / 2 slots][trace
-// temporary in the keys' base].  Per pair (POULPY_DBG_PACK_LEVELS=0): glwe_pack above, on the first three slots' worth of tmp.
-// ------------------------------------------------------------------------------
-static inline bool pack_ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    return a_bytes != 0 && b_bytes != 0 && (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
-}
-size_t pz_fhe_uint_pack_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t word_bits, size_t trace_size, size_t batch) {
-    if (!M || !p) return 0;
-    const size_t ctb = batch * (size_t)M->n * (p->rank + 1) * p->res_size * 8;
-    const size_t by_levels = align256(word_bits / 2 * ctb) + align256(batch * (size_t)M->n * (p->rank + 1) * trace_size * 8);
-    return std::max(by_levels, pz_glwe_pack_bases_tmp_bytes(M, p, trace_size, batch));
-}
-size_t pz_fhe_uint_pack_level_pairs(size_t n, size_t word_bits, size_t level, uint32_t* pairs3, size_t cap) {
-    std::vector<PackLevel> levels;
-    if (!fhe_uint_pack_levels(n, word_bits, &levels, nullptr) || level >= levels.size()) return 0;
-    const PackLevel& lv = levels[level];
-    for (size_t k = 0; pairs3 && k < std::min(lv.pairs(), cap); ++k) { pairs3[3 * k] = lv.lo[k]; pairs3[3 * k + 1] = lv.hi[k]; pairs3[3 * k + 2] = lv.t; }
-    return lv.pairs();
-}
-// every refusal of pz_fhe_uint_pack_batched, before anything is launched; *levels: the level map
-static int fhe_uint_pack_refusals(pz_module* M, const int64_t* res, const int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
-                               const pz_glwe_op_params* p, size_t trace_size, const void* tmp, size_t tmp_bytes, size_t batch,
-                               std::vector<PackLevel>* levels) {
-    PZ_REQUIRE(p != nullptr && gals != nullptr && key_pmats != nullptr, "fhe_uint_pack: null argument");
-    PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k && p->rank_out == p->rank && p->dsize == 1,
-               "fhe_uint_pack: ciphertexts and result share base2k and size (dsize 1, rank_out = rank)");
-    PZ_REQUIRE(p->res_size >= 1 && p->rank >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->res_base2k >= 1 && p->res_base2k <= 62 && p->key_base2k >= 1,
-               "fhe_uint_pack: empty shape");
-    PZ_REQUIRE(p->res_base2k == p->key_base2k || trace_size >= 1, "fhe_uint_pack: keys in another base than the ciphertexts need trace_size >= 1");
-    std::string err;
-    if (!fhe_uint_pack_levels((size_t)M->n, word_bits, levels, &err) || !fhe_uint_pack_check((size_t)M->n, word_bits, *levels, &err))
-        return fail(PZ_ERR_INVALID, "%s", err.c_str());
-    PZ_REQUIRE(batch <= (1u << 24), "fhe_uint_pack: batch out of range");
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    for (size_t s = 0; s < log_n; ++s)
-        PZ_REQUIRE((gals[s] & 1) != 0 && key_pmats[s] != nullptr, "fhe_uint_pack: trace step %zu has an even Galois element or a null key", s);
-    if (batch == 0) return PZ_OK;
-    PZ_REQUIRE(res != nullptr && bits != nullptr && tmp != nullptr, "fhe_uint_pack: null argument");
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(bits) && is_device_ptr(tmp), "batched entry points take device pointers");
-    const size_t need = pz_fhe_uint_pack_tmp_bytes(M, p, word_bits, p->res_base2k == p->key_base2k ? 0 : trace_size, batch);
-    PZ_REQUIRE(tmp_bytes >= need, "fhe_uint_pack: tmp too small (%zu bytes, %zu needed)", tmp_bytes, need);
-    const size_t cols = p->rank + 1, ctb = batch * (size_t)M->n * cols * p->res_size * 8, bits_bytes = word_bits * ctb;
-    const size_t key_bytes = (size_t)M->n * 8 * p->dnum * p->rank * cols * p->key_size;
-    if (pack_ranges_overlap(res, ctb, bits, bits_bytes)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps bits");
-    if (pack_ranges_overlap(res, ctb, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps tmp");
-    if (pack_ranges_overlap(bits, bits_bytes, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: bits overlaps tmp");
-    for (size_t s = 0; s < log_n; ++s)
-        if (pack_ranges_overlap(res, ctb, key_pmats[s], key_bytes) || pack_ranges_overlap(bits, bits_bytes, key_pmats[s], key_bytes) ||
-            pack_ranges_overlap(tmp, need, key_pmats[s], key_bytes))
-            return fail(PZ_ERR_ALIAS, "fhe_uint_pack: the key of trace step %zu overlaps res, bits or tmp", s);
-    return PZ_OK;
-}
-// the checked call on the stream (no lock, no graph); batch >= 1
-static int fhe_uint_pack_levels_run(pz_module* M, int64_t* res, int64_t* bits, const std::vector<PackLevel>& levels, const int64_t* gals,
-                                    const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t batch) {
-    const long long n = (long long)M->n;
-    const int cols = (int)p->rank + 1, size = (int)p->res_size, k = (int)p->res_base2k, B = (int)batch;
-    const long long ct = n * cols * size;
-    const size_t word_bits = 2 * levels[0].pairs();
-    int64_t* diff = (int64_t*)tmp;
-    dispatch_note(M, "fhe_uint_pack: by levels (k_pack_pre, one automorphism of pairs x batch, k_pack_post per level)");
-    for (size_t l = 0; l < levels.size(); ++l) {
-        const PackLevel& lv = levels[l];
-        PackLevelCall pc;
-        pc.bits = (long long*)bits; pc.diff = (long long*)diff;
-        // the last survivor (slot 0) goes straight to res when the trace runs there (glwe_copy, glwe_packing.rs:175)
-        pc.dst = (l + 1 == levels.size() && trace_size == 0) ? (long long*)res : (long long*)bits;
-        pc.cols = cols; pc.size = size; pc.base2k = k; pc.batch = B; pc.pairs = (int)lv.pairs(); pc.t = lv.t;
-        pc.lo = lv.lo.data(); pc.hi = lv.hi.data();
-        PZ_TRY(launch_pack_level(M, false, pc));
-        AutoSpec au{(long long)gals[l], 0};
-        PZ_TRY(glwe_op(M, GlweKind::Automorphism, diff, diff, key_pmats[l], p, lv.pairs() * batch, &au));
-        PZ_TRY(launch_pack_level(M, true, pc));
-    }
-    const size_t skip = levels.size();
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    if (trace_size == 0) return glwe_trace(M, res, log_n - skip, gals + skip, key_pmats + skip, p, batch);
-    // glwe_trace on a temporary of trace_size limbs in the keys' base (glwe_trace.rs:91-127), as glwe_pack above
-    const int kk = (int)p->key_base2k, tsz = (int)trace_size;
-    const long long ct_t = n * cols * tsz;
-    int64_t* tr = (int64_t*)((char*)tmp + align256(word_bits / 2 * (size_t)B * (size_t)ct * 8));
-    DV tv{tr, ct_t, cols, tsz}, sv{bits, ct, cols, size}, rv{res, ct, cols, size};
-    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, tv, kk, 0, c, sv, k, c));
-    pz_glwe_op_params q = *p;
-    q.a_size = q.res_size = (uint64_t)tsz; q.a_base2k = q.res_base2k = p->key_base2k;
-    PZ_TRY(glwe_trace(M, tr, log_n - skip, gals + skip, key_pmats + skip, &q, batch));
-    for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, k, 0, c, tv, kk, c));
-    return PZ_OK;
-}
-static int fhe_uint_pack_per_pair(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
-                                  const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch, const char* why) {
-    dispatch_note(M, "fhe_uint_pack: per pair (%s)", why);
-    size_t log_bytes = 0, log_gap = 0;
-    while (((size_t)8 << log_bytes) < word_bits) ++log_bytes;
-    while ((word_bits << log_gap) < (size_t)M->n) ++log_gap;
-    const size_t ct = (size_t)M->n * (p->rank + 1) * p->res_size;
-    std::vector<uint64_t> indices(word_bits);
-    std::vector<int64_t*> cts(word_bits);
-    for (size_t s = 0; s < word_bits; ++s) { indices[s] = (uint64_t)fhe_uint_bit_index((uint32_t)s, (uint32_t)log_bytes) << log_gap; cts[s] = bits + s * batch * ct; }
-    return glwe_pack(M, res, word_bits, indices.data(), cts.data(), log_gap, gals, key_pmats, p, tmp, tmp_bytes, batch, trace_size);
-}
-// both routes for a caller that holds the module lock and has run fhe_uint_pack_refusals; the level route replays as a graph
-static int fhe_uint_pack(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const std::vector<PackLevel>& levels, const int64_t* gals,
-                         const double* const* key_pmats, const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
-    if (batch == 0) return PZ_OK;
-    if (p->res_base2k == p->key_base2k) trace_size = 0;
-    if (rt_knob("POULPY_DBG_PACK_LEVELS", 1) == 0)   // (read per call: tests flip it)
-        return fhe_uint_pack_per_pair(M, res, bits, word_bits, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch, "POULPY_DBG_PACK_LEVELS=0");
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    KeyHash k;
-    k.add((int)11); k.add(res); k.add(bits); k.add(word_bits); k.add(tmp); k.add(batch); k.add(trace_size); k.add(*p);
-    for (size_t s = 0; s < log_n; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
-    graph_key_module(M, k);
-    return with_graph(M, k.h, [&]() { return fhe_uint_pack_levels_run(M, res, bits, levels, gals, key_pmats, p, trace_size, tmp, batch); });
-}
-int pz_fhe_uint_pack_batched(pz_module* M, int64_t* res, int64_t* bits, size_t word_bits, const int64_t* gals, const double* const* key_pmats,
-                             const pz_glwe_op_params* p, size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    std::vector<PackLevel> levels;
-    PZ_TRY(fhe_uint_pack_refusals(M, res, bits, word_bits, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch, &levels));
-    return fhe_uint_pack(M, res, bits, word_bits, levels, gals, key_pmats, p, trace_size, tmp, tmp_bytes, batch);
-}
-
-// ------------------------------------------------------------------------------
-// public: execute_bdd_circuit_2w_to_1w / _1w_to_1w (bdd_2w_to_1w.rs:103-136, bdd_1w_to_1w.rs:46-70): the evaluator into the slot buffer at the
-// head of tmp, then the pack above into res, both behind every refusal of either.  tmp = [slot buffer][max(evaluator, pack)] (:70-74).
-// The halves keep their own graphs (the evaluator's gathered route writes the call's keys to tmp outside its graph).
-// ------------------------------------------------------------------------------
-size_t pz_fhe_uint_execute_tmp_bytes(const pz_module* M, const pz_bdd_circuit* c, const pz_glwe_op_params* gate_p, const pz_glwe_op_params* pack_p,
-                                     size_t word_bits, size_t trace_size, size_t batch) {
-    if (!M || !c || !gate_p || !pack_p) return 0;
-    const size_t slots = align256(word_bits * batch * (size_t)M->n * (gate_p->rank + 1) * gate_p->res_size * 8);
-    return slots + std::max(align256(pz_bdd_circuit_execute_tmp_bytes(M, c, gate_p, batch)), pz_fhe_uint_pack_tmp_bytes(M, pack_p, word_bits, trace_size, batch));
-}
-int pz_fhe_uint_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* res, size_t word_bits, const double* const* bits, size_t nbits,
-                                const pz_glwe_op_params* gate_p, const int64_t* gals, const double* const* atk_pmats, const pz_glwe_op_params* pack_p,
-                                size_t trace_size, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_REQUIRE(gate_p != nullptr && pack_p != nullptr && c != nullptr, "fhe_uint_execute: null argument");
-    PZ_REQUIRE(gate_p->res_size == pack_p->res_size && gate_p->res_base2k == pack_p->res_base2k && gate_p->rank == pack_p->rank,
-               "fhe_uint_execute: the evaluator's result is the pack's ciphertext (res_size, res_base2k, rank of gate_p and pack_p)");
-    PZ_REQUIRE(pz_bdd_circuit_output_size(c) <= word_bits, "fhe_uint_execute: output_size %zu > word_bits %zu", pz_bdd_circuit_output_size(c), word_bits);
-    PZ_REQUIRE(batch == 0 || tmp != nullptr, "fhe_uint_execute: null argument");
-    bool nothing = false;
-    PZ_TRY(bdd_circuit_execute_precheck(M, c, (const int64_t*)tmp, word_bits, bits, nbits, gate_p, batch, &nothing));
-    PZ_ENTER(M);
-    const size_t slot_bytes = align256(word_bits * batch * (size_t)M->n * (gate_p->rank + 1) * gate_p->res_size * 8);
-    const size_t need = pz_fhe_uint_execute_tmp_bytes(M, c, gate_p, pack_p, word_bits, trace_size, batch);
-    PZ_REQUIRE(tmp_bytes >= need, "fhe_uint_execute: tmp too small (%zu bytes, %zu needed)", tmp_bytes, need);
-    int64_t* slots = (int64_t*)tmp;
-    void* rest = (char*)tmp + slot_bytes;
-    std::vector<PackLevel> levels;
-    PZ_TRY(fhe_uint_pack_refusals(M, res, slots, word_bits, gals, atk_pmats, pack_p, trace_size, rest, tmp_bytes - slot_bytes, batch, &levels));
-    if (batch == 0 || nothing) return PZ_OK;
-    PZ_TRY(bdd_circuit_execute(M, c, slots, word_bits, bits, nbits, gate_p, rest, tmp_bytes - slot_bytes, batch));
-    PZ_TRY(fhe_uint_pack(M, res, slots, word_bits, levels, gals, atk_pmats, pack_p, trace_size, rest, tmp_bytes - slot_bytes, batch));
-    return finish_call(M, false);
-}
-
-// ------------------------------------------------------------------------------
-// public: the FheUint byte operations (bdd_arithmetic/ciphertexts/fhe_uint.rs:259-524): get_bit_glwe / get_byte, zero_byte,
-// splice_u8 / splice_u16 and sext on `batch` words.  By stages (word_ops.cpp): every stage is k_word_pre (the rotated items into a dense array
-// [item][batch], with the first one-bit shift of the trace where the word is in the keys' base), ONE glwe_trace on items * batch ciphertexts,
-// and a closing k_word_post / k_word_replicate.  tmp = kWordSlots ciphertext arrays [batch].  Literal (POULPY_DBG_WORD_STAGES=0): the
-// reference's calls in its order - one rotation launch, one glwe_trace per trace, launch_ew adds and subs.
-// ------------------------------------------------------------------------------
-size_t pz_fhe_uint_bit_coefficient(size_t n, size_t word_bits, size_t bit) {
-    if ((word_bits != 8 && word_bits != 16 && word_bits != 32 && word_bits != 64 && word_bits != 128) || n == 0 || (n & (n - 1)) != 0 || n % word_bits != 0 ||
-        bit >= word_bits)
-        return (size_t)-1;
-    return fhe_uint_word_coefficient(n, word_bits, (uint32_t)bit);
-}
-size_t pz_fhe_uint_word_plan(size_t n, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs, uint32_t* words, size_t cap, int* status) {
-    std::vector<WordStage> plan;
-    std::string err;
-    const bool ok = fhe_uint_word_plan(n, word_bits, op, args, nargs, &plan, &err) &&
-                    fhe_uint_word_plan_check(n, op <= WORD_GET_BYTE ? std::max<size_t>(nargs, 1) : kWordSlots, plan, &err);
-    if (status) *status = ok ? PZ_OK : PZ_ERR_INVALID;
-    if (!ok) { fail(PZ_ERR_INVALID, "%s", err.c_str()); return 0; }
-    const std::vector<uint32_t> w = fhe_uint_word_plan_words(plan);
-    for (size_t i = 0; words && i < std::min(w.size(), cap); ++i) words[i] = w[i];
-    return w.size();
-}
-size_t pz_fhe_uint_word_op_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t word_bits, size_t max_items, size_t batch) {
-    if (!M || !p || max_items > kWordMaxItems) return 0;
-    if (word_bits != 8 && word_bits != 16 && word_bits != 32 && word_bits != 64 && word_bits != 128) return 0;
-    // (a get traces its items in res itself: whatever max_items, the six arrays of the other operations)
-    return align256(kWordSlots * batch * (size_t)M->n * (p->rank + 1) * p->res_size * 8);
-}
-
-namespace {
-struct WordCall {
-    pz_module* M;
-    const char* what;
-    int64_t* res;           // get: [nitems][batch]; else `batch` words
-    const int64_t* a;       // get: the words; sext: the word itself (= res)
-    const int64_t* b;       // splice only
-    const int64_t* gals;
-    const double* const* key_pmats;
-    const pz_glwe_op_params* p;
-    void* tmp;
-    size_t tmp_bytes, batch, res_items;
-    bool is_get;
-};
-}  // namespace
-// every refusal of the four calls, after the plan's own and before anything is launched
-static int fhe_uint_word_refusals(const WordCall& c, size_t word_bits) {
-    pz_module* M = c.M;
-    const pz_glwe_op_params* p = c.p;
-    PZ_REQUIRE(p != nullptr && c.gals != nullptr && c.key_pmats != nullptr, "%s: null argument", c.what);
-    PZ_REQUIRE(p->rank_out == p->rank && p->dsize == 1, "%s: dsize 1, rank_out = rank", c.what);
-    PZ_REQUIRE(p->res_size >= 1 && p->rank >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->res_base2k >= 1 && p->res_base2k <= 62 && p->key_base2k >= 1,
-               "%s: empty shape", c.what);
-    if (p->res_base2k == p->key_base2k)
-        PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k, "%s: a and res describe the same words when they are in the keys' base", c.what);
-    else
-        PZ_REQUIRE(p->a_base2k == p->key_base2k && p->a_size >= 1, "%s: with the words in another base than the keys, (a_size, a_base2k) is their layout in the keys' base", c.what);
-    PZ_REQUIRE(c.batch <= (1u << 20), "%s: batch out of range", c.what);
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    for (size_t s = 0; s < log_n; ++s)
-        PZ_REQUIRE((c.gals[s] & 1) != 0 && c.key_pmats[s] != nullptr, "%s: trace step %zu has an even Galois element or a null key", c.what, s);
-    if (c.batch == 0 || c.res_items == 0) return PZ_OK;
-    PZ_REQUIRE(c.res != nullptr && c.a != nullptr && c.tmp != nullptr, "%s: null argument", c.what);
-    PZ_REQUIRE(is_device_ptr(c.res) && is_device_ptr(c.a) && is_device_ptr(c.tmp) && (c.b == nullptr || is_device_ptr(c.b)), "batched entry points take device pointers");
-    const size_t need = pz_fhe_uint_word_op_tmp_bytes(M, p, word_bits, c.is_get ? c.res_items : 0, c.batch);
-    PZ_REQUIRE(c.tmp_bytes >= need, "%s: tmp too small (%zu bytes, %zu needed)", c.what, c.tmp_bytes, need);
-    const size_t cols = p->rank + 1, ctb = c.batch * (size_t)M->n * cols * p->res_size * 8, res_bytes = c.res_items * ctb;
-    const size_t key_bytes = (size_t)M->n * 8 * p->dnum * p->rank * cols * p->key_size;
-    // res == a, res == b (whole) and a == b are allowed for everything but a get
-    if (pack_ranges_overlap(c.res, res_bytes, c.a, ctb) && (c.is_get || (const void*)c.res != (const void*)c.a)) return fail(PZ_ERR_ALIAS, "%s: res overlaps a", c.what);
-    if (c.b && pack_ranges_overlap(c.res, res_bytes, c.b, ctb) && (const void*)c.res != (const void*)c.b) return fail(PZ_ERR_ALIAS, "%s: res overlaps b", c.what);
-    if (c.b && pack_ranges_overlap(c.a, ctb, c.b, ctb) && (const void*)c.a != (const void*)c.b) return fail(PZ_ERR_ALIAS, "%s: a overlaps b", c.what);
-    if (pack_ranges_overlap(c.res, res_bytes, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: res overlaps tmp", c.what);
-    if (pack_ranges_overlap(c.a, ctb, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: a overlaps tmp", c.what);
-    if (c.b && pack_ranges_overlap(c.b, ctb, c.tmp, need)) return fail(PZ_ERR_ALIAS, "%s: b overlaps tmp", c.what);
-    for (size_t s = 0; s < log_n; ++s)
-        if (pack_ranges_overlap(c.res, res_bytes, c.key_pmats[s], key_bytes) || pack_ranges_overlap(c.a, ctb, c.key_pmats[s], key_bytes) ||
-            (c.b && pack_ranges_overlap(c.b, ctb, c.key_pmats[s], key_bytes)) || pack_ranges_overlap(c.tmp, need, c.key_pmats[s], key_bytes))
-            return fail(PZ_ERR_ALIAS, "%s: the key of trace step %zu overlaps res, a, b or tmp", c.what, s);
-    return PZ_OK;
-}
-// the checked call by stages on the stream (no lock, no graph); batch >= 1
-static int fhe_uint_word_stages_run(const WordCall& c, const std::vector<WordStage>& plan) {
-    pz_module* M = c.M;
-    const pz_glwe_op_params* p = c.p;
-    const long long n = (long long)M->n;
-    const int cols = (int)p->rank + 1, size = (int)p->res_size, B = (int)c.batch;
-    const long long ct = n * cols * size;
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    const bool same = p->res_base2k == p->key_base2k;
-    dispatch_note(M, "fhe_uint_word: by stages (%zu: k_word_pre%s, one trace of items x batch, one closing kernel)", plan.size(),
-                  same ? " with the trace's first shift" : "");
-    long long* dense = c.is_get ? (long long*)c.res : (long long*)c.tmp;
-    auto slot = [&](uint32_t s) { return dense + (long long)s * B * ct; };
-    for (const WordStage& st : plan) {
-        const size_t nsteps = log_n - st.skip;
-        const int items = (int)st.items.size();
-        unsigned exp[kWordMaxItems];
-        unsigned char sel[kWordMaxItems];
-        for (int i = 0; i < items; ++i) { exp[i] = st.items[i].exp; sel[i] = (unsigned char)st.items[i].src; }
-        WordPreCall pc;
-        pc.src[WORD_SRC_A] = (const long long*)c.a; pc.src[WORD_SRC_B] = (const long long*)c.b; pc.src[WORD_SRC_RES] = (const long long*)c.res;
-        pc.src[WORD_SRC_S] = c.is_get ? nullptr : slot(1);
-        pc.out = slot(st.items[0].slot);
-        pc.cols = cols; pc.size = size; pc.base2k = (int)p->res_base2k; pc.batch = B; pc.items = items;
-        pc.shift = same && nsteps >= 1;
-        pc.exp = exp; pc.sel = sel;
-        PZ_TRY(launch_word_pre(M, pc));
-        PZ_TRY(glwe_trace(M, (int64_t*)pc.out, nsteps, c.gals + st.skip, c.key_pmats + st.skip, p, (size_t)items * c.batch, pc.shift));
-        if (st.close == WORD_CLOSE_REPLICATE) {
-            PZ_TRY(launch_word_replicate(M, slot(1), slot(0), cols, size, B));
-        } else if (st.close == WORD_CLOSE_COMBINE) {
-            const long long* base = st.base == WORD_SRC_A ? (const long long*)c.a : (const long long*)c.res;
-            PZ_TRY(launch_word_post(M, (long long*)c.res, base, st.plus == kWordNone ? nullptr : slot(st.plus), st.minus == kWordNone ? nullptr : slot(st.minus),
-                                    st.r, cols, size, B));
-        }
-    }
-    return PZ_OK;
-}
-// the reference's calls in its order on today's launchers: the byte-for-byte twin of the staged route
-namespace {
-struct WordLiteral {
-    pz_module* M;
-    const WordCall& c;
-    long long n, ct;
-    int cols, size, B;
-    size_t log_n;
-    int64_t* slot(int s) const { return (int64_t*)c.tmp + (long long)s * B * ct; }
-    int rot(int64_t* dst, const int64_t* src, long long k) const {
-        const PolyMap pm{1, 1, n, 0, 0, 0};
-        return launch_rotate(M, B * size * cols, (const long long*)src, pm, (long long*)dst, pm, k);
-    }
-    int trace(int64_t* x, size_t skip) const { return glwe_trace(M, x, log_n - skip, c.gals + skip, c.key_pmats + skip, c.p, (size_t)B); }
-    int ew(int op, int64_t* r, const int64_t* x, const int64_t* y) const { return launch_ew(M, op, r, ct, n, x, ct, n, y, ct, n, size * cols, B); }
-    int get(int64_t* res, const int64_t* a, uint32_t exp, size_t skip) const {   // fhe_uint.rs:401-430
-        PZ_TRY(rot(res, a, -(long long)exp));
-        return trace(res, skip);
-    }
-    int zero_byte(int64_t* res, const int64_t* a, uint32_t r) const {   // :466-489 on a copy of a; glwe_trace = glwe_trace_assign on a copy
-        PZ_TRY(rot(slot(0), a, -(long long)r));
-        PZ_TRY(ew(EW_COPY, slot(1), slot(0), nullptr));
-        PZ_TRY(trace(slot(1), 3));
-        PZ_TRY(ew(EW_SUB_I64, slot(0), slot(0), slot(1)));
-        return rot(res, slot(0), (long long)r);
-    }
-    int splice_u8(int64_t* res, const int64_t* a, const int64_t* b, uint32_t rd, uint32_t rs) const {   // :286-329; b's side first: res may be b
-        PZ_TRY(rot(slot(2), b, -(long long)rs));
-        PZ_TRY(trace(slot(2), 3));
-        PZ_TRY(rot(slot(3), slot(2), (long long)rd));
-        PZ_TRY(zero_byte(res, a, rd));
-        return ew(EW_ADD_I64, res, res, slot(3));
-    }
-};
-}  // namespace
-static int fhe_uint_word_literal_run(const WordCall& c, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs) {
-    pz_module* M = c.M;
-    dispatch_note(M, "fhe_uint_word: literal (POULPY_DBG_WORD_STAGES=0: one rotation, one trace, one add or sub at a time)");
-    WordLiteral w{M, c, (long long)M->n, (long long)M->n * (long long)(c.p->rank + 1) * (long long)c.p->res_size, (int)c.p->rank + 1, (int)c.p->res_size,
-                  (int)c.batch, 0};
-    while (((size_t)1 << w.log_n) < (size_t)M->n) ++w.log_n;
-    const size_t n = (size_t)M->n;
-    auto cf = [&](uint32_t bit) { return fhe_uint_word_coefficient(n, word_bits, bit); };
-    switch (op) {
-    case WORD_GET_BIT:
-    case WORD_GET_BYTE:
-        for (size_t i = 0; i < nargs; ++i)
-            PZ_TRY(w.get(c.res + (long long)i * w.B * w.ct, c.a, cf(op == WORD_GET_BIT ? args[i] : 8 * args[i]), op == WORD_GET_BIT ? 0 : 3));
-        return PZ_OK;
-    case WORD_ZERO_BYTE:
-        return w.zero_byte(c.res, c.a, cf(8 * args[0]));
-    case WORD_SPLICE_U8:
-        return w.splice_u8(c.res, c.a, c.b, cf(8 * args[0]), cf(8 * args[1]));
-    case WORD_SPLICE_U16:   // :259-282
-        PZ_TRY(w.splice_u8(w.slot(4), c.a, c.b, cf(16 * args[0]), cf(16 * args[1])));
-        return w.splice_u8(c.res, w.slot(4), c.b, cf(16 * args[0] + 8), cf(16 * args[1] + 8));
-    default: {   // WORD_SEXT, :491-524
-        const uint32_t byte = args[0], bytes = (uint32_t)(word_bits / 8);
-        if (byte + 1 == bytes) return PZ_OK;
-        PZ_TRY(w.get(w.slot(4), c.res, cf(8 * byte + 7), 0));
-        for (int i = 0; i < 3; ++i) {
-            PZ_TRY(w.rot(w.slot(5), w.slot(4), (long long)((n / 8) << i)));
-            PZ_TRY(w.ew(EW_ADD_I64, w.slot(4), w.slot(4), w.slot(5)));
-        }
-        for (uint32_t i = byte + 1; i < bytes; ++i) PZ_TRY(w.splice_u8(c.res, c.res, w.slot(4), cf(8 * i), 0));
-        return PZ_OK;
-    }
-    }
-}
-// plan, refusals, route, graph: the body of the four calls under the module lock
-static int fhe_uint_word_call(const WordCall& c, size_t word_bits, uint32_t op, const uint32_t* args, size_t nargs) {
-    pz_module* M = c.M;
-    std::vector<WordStage> plan;
-    std::string err;
-    if (!fhe_uint_word_plan((size_t)M->n, word_bits, op, args, nargs, &plan, &err) ||
-        !fhe_uint_word_plan_check((size_t)M->n, c.is_get ? std::max<size_t>(nargs, 1) : kWordSlots, plan, &err))
-        return fail(PZ_ERR_INVALID, "%s", err.c_str());
-    PZ_TRY(fhe_uint_word_refusals(c, word_bits));
-    if (c.batch == 0 || plan.empty()) return PZ_OK;
-    if (rt_knob("POULPY_DBG_WORD_STAGES", 1) == 0) return fhe_uint_word_literal_run(c, word_bits, op, args, nargs);   // (read per call: tests flip it)
-    size_t log_n = 0;
-    while (((size_t)1 << log_n) < (size_t)M->n) ++log_n;
-    KeyHash k;
-    k.add((int)12); k.add(c.res); k.add(c.a); k.add(c.b); k.add(word_bits); k.add(op); k.add(nargs); k.add(c.tmp); k.add(c.batch); k.add(*c.p);
-    for (size_t i = 0; i < nargs; ++i) k.add(args[i]);
-    for (size_t s = 0; s < log_n; ++s) { k.add(c.gals[s]); k.add(c.key_pmats[s]); }
-    graph_key_module(M, k);
-    return with_graph(M, k.h, [&]() { return fhe_uint_word_stages_run(c, plan); });
-}
-int pz_fhe_uint_get_batched(pz_module* M, int64_t* res, const int64_t* words, size_t word_bits, int unit, size_t nidx, const uint32_t* idx,
-                            const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    PZ_REQUIRE(unit == PZ_WORD_BIT || unit == PZ_WORD_BYTE, "fhe_uint_get: unit %d is neither PZ_WORD_BIT nor PZ_WORD_BYTE", unit);
-    PZ_REQUIRE(nidx == 0 || idx != nullptr, "fhe_uint_get: null argument");
-    const WordCall c{M, "fhe_uint_get", res, words, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, nidx, true};
-    return fhe_uint_word_call(c, word_bits, unit == PZ_WORD_BIT ? WORD_GET_BIT : WORD_GET_BYTE, idx, nidx);
-}
-int pz_fhe_uint_zero_byte_batched(pz_module* M, int64_t* res, const int64_t* a, size_t word_bits, size_t byte, const int64_t* gals,
-                                  const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    const uint32_t args[1] = {(uint32_t)std::min<size_t>(byte, 0xFFFFu)};
-    const WordCall c{M, "fhe_uint_zero_byte", res, a, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
-    return fhe_uint_word_call(c, word_bits, WORD_ZERO_BYTE, args, 1);
-}
-int pz_fhe_uint_splice_batched(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, size_t word_bits, size_t width, size_t dst, size_t src,
-                               const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    PZ_REQUIRE(width == 8 || width == 16, "fhe_uint_splice: width %zu is neither 8 nor 16", width);
-    PZ_REQUIRE(batch == 0 || b != nullptr, "fhe_uint_splice: null argument");
-    const uint32_t args[2] = {(uint32_t)std::min<size_t>(dst, 0xFFFFu), (uint32_t)std::min<size_t>(src, 0xFFFFu)};
-    const WordCall c{M, "fhe_uint_splice", res, a, b, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
-    return fhe_uint_word_call(c, word_bits, width == 8 ? WORD_SPLICE_U8 : WORD_SPLICE_U16, args, 2);
-}
-int pz_fhe_uint_sext_batched(pz_module* M, int64_t* word, size_t word_bits, size_t byte, const int64_t* gals, const double* const* key_pmats,
-                             const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_ENTER(M);
-    const uint32_t args[1] = {(uint32_t)std::min<size_t>(byte, 0xFFFFu)};
-    const WordCall c{M, "fhe_uint_sext", word, word, nullptr, gals, key_pmats, p, tmp, tmp_bytes, batch, 1, false};
-    return fhe_uint_word_call(c, word_bits, WORD_SEXT, args, 1);
 }
 
 }  // extern "C"

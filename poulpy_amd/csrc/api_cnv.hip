@@ -2,7 +2,7 @@
 // poulpy-cpu-ref/src/reference/fft64/convolution.rs) and of GLWE tensoring on device-resident batches
 // (poulpy-core/src/operations/glwe.rs:609-913), SURVEY.md §8f rank 4 / BASELINE configs[4].
 #include "api_common.hpp"
-#include "api_glwe.hpp"
+#include "glwe_call.hpp"
 
 // CnvPVecL / CnvPVecR bytes in this backend: polynomial (col, limb) = its spectrum in device order at (col*size + limb)*n doubles.
 static inline size_t cnv_bytes(const pz_module* M, size_t cols, size_t size) { return (size_t)M->n * cols * size * 8; }

@@ -172,3 +172,33 @@ static inline int need_T(pz_module* M, size_t npolys, cplx** T) {
 }
 
 #define PZ_CHECK_COL(col, cols, what) PZ_REQUIRE((col) < (cols), "%s: col %zu >= cols %zu", what, (size_t)(col), (size_t)(cols))
+
+// argument checks the composite entry points share: two byte ranges share a byte (an empty range overlaps nothing)
+static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return a_bytes != 0 && b_bytes != 0 && (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+static inline size_t log2_n(const pz_module* M) { size_t l = 0; while (((size_t)1 << l) < (size_t)M->n) ++l; return l; }
+// bytes of a prepared key (VmpPMat of dnum * cols_in rows, cols_out columns of key_size limbs); a GGSW; a GLWE switching / automorphism key
+static inline size_t prepared_key_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t cols_in, size_t cols_out) {
+    return (size_t)M->n * 8 * p->dnum * cols_in * cols_out * p->key_size;
+}
+static inline size_t ggsw_key_bytes(const pz_module* M, const pz_glwe_op_params* p) { return prepared_key_bytes(M, p, p->rank + 1, p->rank + 1); }
+static inline size_t glwe_key_bytes(const pz_module* M, const pz_glwe_op_params* p) { return prepared_key_bytes(M, p, p->rank, p->rank_out + 1); }
+// nothing of the product's shape is empty
+static inline int require_op_shape(const pz_glwe_op_params* p, const char* what) {
+    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "%s: empty shape", what);
+    return PZ_OK;
+}
+// the automorphism keys of a trace, one per step
+struct TraceKeys { const int64_t* gals; const double* const* key_pmats; size_t nsteps; };
+static inline int trace_keys_check(const TraceKeys& tk, const char* what) {
+    for (size_t s = 0; s < tk.nsteps; ++s)
+        PZ_REQUIRE((tk.gals[s] & 1) != 0 && tk.key_pmats[s] != nullptr, "%s: trace step %zu has an even Galois element or a null key", what, s);
+    return PZ_OK;
+}
+// the first step whose key (key_bytes each) overlaps the buffer; nsteps: none does
+static inline size_t trace_keys_overlap(const TraceKeys& tk, size_t key_bytes, const void* buf, size_t bytes) {
+    for (size_t s = 0; s < tk.nsteps; ++s)
+        if (ranges_overlap(buf, bytes, tk.key_pmats[s], key_bytes)) return s;
+    return tk.nsteps;
+}

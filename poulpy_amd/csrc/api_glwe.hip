@@ -1,5 +1,7 @@
 // api_glwe.hip — the batched GLWE product behind the C ABI: GLWE (x) GGSW external product, GLWE key switch, the glwe_automorphism family,
-// tensor relinearization, and the composites that are loops of those (ggsw_external_product, ggsw_expand_row, ggsw_from_gglwe, glwe_trace).
+// tensor relinearization.  The engine (shapes, workspace models, GlweCall, the three pipelines, glwe_op), the host-container path of the four GLWE
+// entry points, and the hoisted rotations (pz_glwe_automorphism_many_batched), which drive the fused pipeline's pieces directly.  The composites
+// live in their own units: api_ggsw.hip, api_gates.hip, api_bdd.hip, api_trace.hip, api_br.hip, api_fhe_uint.hip; glwe_call.hpp is what they see.
 // Reference call stacks: poulpy-core/src/external_product/glwe.rs:99-271, keyswitching/glwe.rs:53-380, automorphism/glwe_ct.rs:51-275,
 // operations/glwe.rs:541-607.
 //
@@ -12,12 +14,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <unordered_map>
 #include <vector>
 
 #include "api_common.hpp"
-#include "api_glwe.hpp"
-#include "bdd_schedule.hpp"
+#include "glwe_call.hpp"
 
 using namespace pz;
 
@@ -56,17 +56,12 @@ static int glwe_args_out(pz_module* M, GlweArgs& g) {
 // ------------------------------------------------------------------------------
 // shapes, workspaces, pipeline choice
 // ------------------------------------------------------------------------------
-struct OpShape {
-    int cols_a, cols_in, cols_out;  // columns of `a`, VMP input columns, output columns
-    int a_col0;                     // first column of `a` that enters the product
-    int a_size_eff;                 // limbs of `a` in the key's base (after optional conversion)
-    bool convert;
-};
+// (OpShape: glwe_call.hpp)
 // external product; key switch / automorphism (mask columns 1.. of a GLWE); tensor relinearization (operations/glwe.rs:541-607: `a` is
 // a GLWETensor of cols + pairs columns, the pairs = rank (rank + 1) / 2 columns behind the first cols = rank + 1 are key-switched
 // and the first cols are added to every column of the big value)
 static inline bool kind_ks(GlweKind k) { return k != GlweKind::ExternalProduct; }   // the product is gglwe_product_dft, as for a key switch
-static OpShape op_shape(const pz_glwe_op_params* p, GlweKind kind) {
+OpShape op_shape(const pz_glwe_op_params* p, GlweKind kind) {
     OpShape s;
     const bool ks = kind_ks(kind);
     if (kind == GlweKind::TensorRelin) {
@@ -103,7 +98,7 @@ static OpWs op_ws(const pz_module* M, const pz_glwe_op_params* p, const OpShape&
     w.total = w.a_conv + w.a_dft + w.res_dft + w.tmp_dft + w.T + w.res_tmp;
     return w;
 }
-static size_t pick_chunk(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, size_t batch) {
+size_t pick_chunk(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, size_t batch) {
     if (M->chunk) return std::min(M->chunk, batch);
     // Measured on MI355X (profiles/r01_chunk_sweep.txt, r01_batch_sweep.txt): the intermediates do not stay in the Infinity
     // Cache anyway and every wave re-streams the key and pays the pipeline fill of the persistent middle kernel, so larger
@@ -115,7 +110,7 @@ static size_t pick_chunk(const pz_module* M, const pz_glwe_op_params* p, const O
 }
 
 // which pipeline glwe_op takes for a shape, and what it reserves there (one definition for the call and for the workspace query)
-static bool fused_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind) {
+bool fused_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind) {
     const bool tensor = kind == GlweKind::TensorRelin, au = kind == GlweKind::Automorphism;
     const int npi = s.cols_in * s.a_size_eff, npo = s.cols_out * (int)p->key_size;
     const bool digits = p->dsize > 1, cross_out = p->res_base2k != p->key_base2k;
@@ -152,7 +147,7 @@ static FusedWs fused_ws(const pz_module* M, const pz_glwe_op_params* p, const Op
 }
 // N = 1024 / 2048: the two-kernel pipeline of device_small.hpp (plain products, key switches and the automorphism family; dsize 1, one
 // base2k, <= 4 key limbs); `packed` = no OpLayout (the automorphism family needs it)
-static bool small_ring_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind, bool packed) {
+bool small_ring_applies(const pz_module* M, const pz_glwe_op_params* p, const OpShape& s, GlweKind kind, bool packed) {
     const bool ks = kind_ks(kind), tensor = kind == GlweKind::TensorRelin, au = kind == GlweKind::Automorphism;
     const bool cross_out = p->res_base2k != p->key_base2k;   // (with an automorphism: phi and the cross-base pass do not commute)
     return M->small_path && M->fuse_mid && M->fuse_tail && M->n < 4096 && (!au || (ks && packed && !cross_out)) &&
@@ -172,56 +167,7 @@ static SmallWs small_ws(const pz_module* M, const pz_glwe_op_params* p, const Op
     return w;
 }
 
-// everything a call of glwe_op derives from its arguments before it launches anything
-struct GlweCall {
-    pz_module* M;
-    const pz_glwe_op_params* p;
-    OpShape s;
-    GlweKind kind;
-    bool ks, tensor;       // kind != ExternalProduct, kind == TensorRelin
-    const AutoSpec* au;
-    const OpLayout* lay;
-    int64_t* res; const int64_t* a; const double* pmat;
-    size_t batch, chunk;
-    long long n;
-    int dsize, dnum, ksz;
-    int npi, npo;          // polynomials per ciphertext entering / leaving the product
-    int nrows, ncols;      // the key matrix: dnum * cols_in rows, cols_out * key_size columns
-    long long a_ct, res_ct, a_bs, res_bs;   // packed sizes and actual strides of one ciphertext (i64 elements)
-    int body_col;
-    bool au_big;           // add / sub / sub_negate: phi acts on the big value
-    unsigned au_p, au_g;   // Galois element mod 2n and its inverse
-    bool digits, cross_out;
-    bool want_rsh;         // glwe_trace asked for the one-bit shift on the way out
-    bool* post_rsh;        // ... and is told here whether it happened
-    // relinearization of a GLWETensor that exists only as 16-bit digits in the fused tail's tile order (glwe_relin_t16 below):
-    // a16[column][ciphertext of this call][limb][n], a16_cs int16 elements between columns; `a` is not read
-    const short* a16 = nullptr;
-    long long a16_cs = 0;
-    // glwe_automorphism_key_automorphism, fast form (keyauto_entries below): a plain key switch by phi_g(key) - the row-sliced copy is read
-    // through ka_perm - whose carry chains run between the signs of X -> X^ka_p
-    bool keyauto = false;
-    unsigned ka_p = 0;
-    KeyPerm ka_perm;
-    // CMUX (glwe_cmux below; eval.rs:565-571): every column of `add` - add_size limbs, add_bs elements between ciphertexts - joins the big value in
-    // front of the carry chain (vec_znx_big_add_small_assign on every column).  diff != null, the fused routes: `a` = t - f is not in memory, the
-    // small-ring forward stage forms it from the two sources (SmallDiff; its maps address the whole call, wave_diff moves them to a wave)
-    const int64_t* add = nullptr;
-    long long add_bs = 0;
-    int add_size = 0;
-    const SmallDiff* diff = nullptr;
-    // conditional swap (glwe_cswap below; eval.rs:444-461): a SECOND result from the same big value, res2 = normalize(res2 - big) on every column
-    // (vec_znx_big_sub_small_a), in place on its own operand; res2_size limbs, res2_bs elements between ciphertexts.  `add` is the first one's operand
-    int64_t* res2 = nullptr;
-    long long res2_bs = 0;
-    int res2_size = 0;
-    // rotated-source key switch (glwe_keyswitch_rot below): ciphertext b of the call is X^rot of ciphertext `word` of `a`, (word, rot) =
-    // rot_tab[b] on the device; the one-kernel small-ring form applies the rotation where it reads the mask columns and the body operand
-    const RotSrc* rot_tab = nullptr;
-    int64_t* res2_at(size_t b0) const { return res2 + (long long)b0 * res2_bs; }
-    int cols_in() const { return s.cols_in; }
-    int64_t* res_at(size_t b0) const { return res + (long long)b0 * res_bs; }
-};
+// (GlweCall, everything a call of glwe_op derives from its arguments before it launches anything: glwe_call.hpp)
 
 extern "C" {
 // keyswitch: 0 external product, 1 key switch, 2 automorphism family, 3 tensor relinearization.  The figure is what the call reserves
@@ -305,7 +251,6 @@ static SmallOperand small_operand2(const GlweCall& c, size_t b0) {
     if (!c.res2) return SmallOperand{};
     return SmallOperand{(const long long*)c.res2_at(b0), c.res2_bs, c.s.cols_out, c.res2_size, -1};
 }
-static const char* gate_name(const GlweCall& c) { return c.res2 ? "cswap" : "cmux"; }
 // CMUX: the wave's part of the every-column operand f, and of the two sources of the fused forward stage
 static DV wave_add(const GlweCall& c, size_t b0) { return DV{(void*)(c.add + (long long)b0 * c.add_bs), c.add_bs, c.s.cols_out, c.add_size}; }
 static SmallDiff wave_diff(const GlweCall& c, size_t b0) {
@@ -375,13 +320,18 @@ static int fused_carve(const GlweCall& c, FusedBufs* f) {
 // N = 4096, plain external product / key switch / automorphism with <= 4 key limbs: two kernels, the spectra cross HBM once
 // (device_small.hpp).  (round 3: the 8-slot tile of k_mid128r - 8 polynomials in, 8 out, 8 product rows: the external product with 4
 // limbs, BASELINE configs[1] - beats the two-kernel form, 3.25 vs 3.16 M/s, profiles/r03_ab_small_vs_pipeline.txt)
-static bool n4096_two_kernel(const GlweCall& c) {
+bool n4096_two_kernel(const GlweCall& c) {
     const pz_module* M = c.M;
     // (CMUX at that shape stays on the two kernels: their forward stage forms the difference itself, where the pipeline needs it written out first
     //  and its tail takes the every-column operand - 2.51 against 2.05 M gates / s at batch 4096, profiles/cmux_lines.txt)
     const bool mid8 = !c.ks && !c.au && !c.add && c.npi == 8 && c.npo == 8 && std::min(c.nrows, c.npi) == 8;
     return M->small_path && (!c.au || (c.ks && !c.lay)) && !c.tensor && !c.digits && !c.cross_out &&
            M->dbg_stages == 7 && small_supported(M, c.npi, c.ksz) && !mid8;
+}
+// which pipeline serves the product of a CMUX, and whether its forward stage can take the two sources
+bool cmux_fused_route(const GlweCall& c) {
+    if (fused_applies(c.M, c.p, c.s, c.kind)) return n4096_two_kernel(c);
+    return small_ring_applies(c.M, c.p, c.s, c.kind, true);
 }
 static int wave_n4096_two_kernel(const GlweCall& c, const FusedBufs& f, size_t b0, int nb, const DV& av, const PolyMap& sm) {
     const bool rsh = c.want_rsh && c.au && c.au->mode != 0 && c.p->res_base2k <= 29;
@@ -541,7 +491,7 @@ static int wave_keyauto_tail(const GlweCall& c, const FusedBufs& f, size_t b0, i
     return launch_inv_tail(c.M, t);
 }
 
-static int glwe_fused(const GlweCall& c) {
+int glwe_fused(const GlweCall& c) {
     pz_module* M = c.M;
     FusedBufs f;
     PZ_TRY(fused_carve(c, &f));
@@ -595,7 +545,7 @@ static int glwe_fused(const GlweCall& c) {
 // result in another base = balanced key-base digits from the inverse kernel (all key limbs), then one cross-base pass.  The automorphism
 // family rides along: phi is an index / sign map inside the inverse kernel's carry-chain stage.
 // ------------------------------------------------------------------------------
-static int glwe_small_ring(const GlweCall& c) {
+int glwe_small_ring(const GlweCall& c) {
     pz_module* M = c.M;
     const SmallWs w = small_ws(M, c.p, c.s, c.chunk);
     PZ_TRY(ws_reserve(M, w.total));
@@ -724,7 +674,7 @@ static int wave_unfused_auto(const GlweCall& c, const UnfusedBufs& u, int nb, co
     }
     return PZ_OK;
 }
-static int glwe_unfused(const GlweCall& c) {
+int glwe_unfused(const GlweCall& c) {
     pz_module* M = c.M;
     const long long n = c.n;
     const OpWs w = op_ws(M, c.p, c.s, c.chunk, c.kind);
@@ -823,14 +773,14 @@ static void call_set_galois(GlweCall& c, const AutoSpec* au) {
     c.au_p = (unsigned)((unsigned long long)au->p & (2ull * (unsigned long long)c.n - 1ull));
     c.au_g = inv_mod_2n(au->p, c.n);
 }
-static int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
+int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
                           size_t batch, const AutoSpec* au, const OpLayout* lay, bool* post_rsh) {
     const bool ks = kind_ks(kind), tensor = kind == GlweKind::TensorRelin;
     c.want_rsh = post_rsh && *post_rsh;
     c.post_rsh = post_rsh;
     if (post_rsh) *post_rsh = false;
     PZ_REQUIRE(p != nullptr, "null params");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_TRY(require_op_shape(p, "glwe op"));
     PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && is_device_ptr(pmat), "batched entry points take device pointers");
     PZ_REQUIRE(!(tensor && (au || lay)), "glwe_tensor_relinearize: packed tensors, no automorphism");
     PZ_REQUIRE((kind == GlweKind::Automorphism) == (au != nullptr), "glwe op: the automorphism family and its Galois element go together");
@@ -859,8 +809,7 @@ static int glwe_call_init(GlweCall& c, pz_module* M, GlweKind kind, int64_t* res
     return PZ_OK;
 }
 
-extern "C" {
-
+namespace pz {
 int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
             const AutoSpec* au, const OpLayout* lay, bool* post_rsh) {
     GlweCall c;
@@ -868,7 +817,7 @@ int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const d
     if (batch == 0) return PZ_OK;
     // dsize > 1 (digit-selected product inside the middle kernel) and res_base2k != key_base2k (the tail normalizes into the key's base,
     // one cross-base pass follows) ride on the fused pipeline too; both need the 128-point-row plans and no automorphism (fused_applies)
-    // (keyauto_entries below enters glwe_fused directly, with GlweCall::keyauto set, where keyauto_fast_applies says this line would take it)
+    // (keyauto_entries, api_ggsw.hip, enters glwe_fused directly, with GlweCall::keyauto set, where keyauto_fast_applies says this line would take it)
     if (fused_applies(M, p, c.s, kind)) return glwe_fused(c);
     if (small_ring_applies(M, p, c.s, kind, lay == nullptr)) return glwe_small_ring(c);
     return glwe_unfused(c);
@@ -890,7 +839,9 @@ int glwe_relin_t16(pz_module* M, int64_t* res, const short* a16, long long a16_c
     c.a16 = a16; c.a16_cs = a16_cs;
     return glwe_fused(c);
 }
+}  // namespace pz
 
+extern "C" {
 // The four GLWE-level entry points accept device pointers (batched, device-resident: the measured path) or HOST containers
 // (what a CoreImpl override of the Rust shim passes): host ciphertexts are staged, a host-resident prepared key is mirrored on
 // the device (resolve_key); the call is then logically synchronous like every host-pointer call.
@@ -960,7 +911,7 @@ static int glwe_entry_duplex(pz_module* M, GlweKind kind, int64_t* res, const in
 static int glwe_entry(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p,
                       size_t batch, const AutoSpec* au) {
     PZ_REQUIRE(p != nullptr, "null params");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_TRY(require_op_shape(p, "glwe op"));
     const OpShape s = op_shape(p, kind);
     const size_t n8 = (size_t)M->n * 8;
     // in place (*_assign forms): one layout for a and res - checked HERE, in front of both host paths (the duplex path below does not go through
@@ -969,14 +920,14 @@ static int glwe_entry(pz_module* M, GlweKind kind, int64_t* res, const int64_t* 
     const size_t res_ct_bytes = n8 * s.cols_out * p->res_size, a_ct_bytes = n8 * s.cols_a * p->a_size;
     if (res != nullptr && (const void*)res == (const void*)a) PZ_REQUIRE(res_ct_bytes == a_ct_bytes, "in-place call with different layouts for a and res");
     const bool partial_overlap = res != nullptr && a != nullptr && (const void*)res != (const void*)a &&
-                                 (const char*)res < (const char*)a + batch * a_ct_bytes && (const char*)a < (const char*)res + batch * res_ct_bytes;
+                                 ranges_overlap(res, batch * res_ct_bytes, a, batch * a_ct_bytes);
     if (batch >= 2 && res != nullptr && a != nullptr && pmat != nullptr && !partial_overlap && !M->timing && !canary_mode() && is_pinned_host(a) && is_pinned_host(res)) {
         const double* key = nullptr;
-        PZ_TRY(resolve_key(M, pmat, n8 * p->dnum * s.cols_in * s.cols_out * p->key_size, &key));
+        PZ_TRY(resolve_key(M, pmat, prepared_key_bytes(M, p, s.cols_in, s.cols_out), &key));
         return glwe_entry_duplex(M, kind, res, a, key, p, batch, au, res_ct_bytes, a_ct_bytes);
     }
     GlweArgs g;
-    PZ_TRY(glwe_args_in(M, g, res, a, pmat, batch * res_ct_bytes, batch * a_ct_bytes, n8 * p->dnum * s.cols_in * s.cols_out * p->key_size));
+    PZ_TRY(glwe_args_in(M, g, res, a, pmat, batch * res_ct_bytes, batch * a_ct_bytes, prepared_key_bytes(M, p, s.cols_in, s.cols_out)));
     PZ_TRY(glwe_op(M, kind, g.res, g.a, g.key, p, batch, au));
     return glwe_args_out(M, g);
 }
@@ -1003,713 +954,6 @@ int pz_glwe_tensor_relinearize_batched(pz_module* M, int64_t* res, const int64_t
     PZ_REQUIRE(p != nullptr, "null params");
     PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_tensor_relinearize: the tensor key maps rank (rank + 1) / 2 -> rank");
     return glwe_entry(M, GlweKind::TensorRelin, res, a, tsk_pmat, p, batch, nullptr);
-}
-// ggsw_external_product (external_product/ggsw.rs:54-58): every (row, column) entry of the GGSW `a` is a GLWE and the entries
-// are contiguous in the MatZnx layout, so the operation is one batched external product over dnum_a * (rank+1) ciphertexts
-int pz_ggsw_external_product(pz_module* M, int64_t* res, const int64_t* a, size_t a_dnum, const double* ggsw_pmat,
-                             const pz_glwe_op_params* p) {
-    PZ_ENTER(M);
-    PZ_REQUIRE(p != nullptr, "null params");
-    return glwe_op(M, GlweKind::ExternalProduct, res, a, ggsw_pmat, p, a_dnum * (p->rank + 1));
-}
-
-// ggsw_expand_row (conversion/gglwe_to_ggsw.rs:116-268): column `col` >= 1 of every row is the key switch of the mask of
-// res.at(row, 0) by tsk.at(col - 1), with the body of res.at(row, 0) added to column `col` of the big value before the
-// normalization.  The entries (row, 0) of `count` contiguous GGSWs are `count * dnum` ciphertexts at a fixed stride, so
-// each column is one batched key switch; column 0 is left untouched.
-int ggsw_expand_row(pz_module* M, int64_t* ggsw, size_t dnum, const double* const* tsk_pmat, const pz_glwe_op_params* p, size_t count) {
-    PZ_REQUIRE(p != nullptr && tsk_pmat != nullptr, "null params");
-    PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k, "ggsw_expand_row: a and res describe the same GGSW");
-    PZ_REQUIRE(dnum >= 1, "ggsw_expand_row: empty GGSW");
-    const size_t cols = p->rank + 1;
-    const long long ct = (long long)M->n * (long long)cols * (long long)p->res_size;
-    for (size_t col = 1; col < cols; ++col) {
-        PZ_REQUIRE(tsk_pmat[col - 1] != nullptr, "ggsw_expand_row: null tensor key");
-        OpLayout lay{ct * (long long)cols, ct * (long long)cols, (int)col};
-        PZ_TRY(glwe_op(M, GlweKind::KeySwitch, ggsw + (long long)col * ct, ggsw, tsk_pmat[col - 1], p, count * dnum, nullptr, &lay));
-    }
-    return PZ_OK;
-}
-int pz_ggsw_expand_row_batched(pz_module* M, int64_t* ggsw, size_t dnum, const double* const* tsk_pmat, const pz_glwe_op_params* p,
-                               size_t count) {
-    PZ_ENTER(M);
-    return ggsw_expand_row(M, ggsw, dnum, tsk_pmat, p, count);
-}
-
-// ggsw_from_gglwe (conversion/gglwe_to_ggsw.rs:32-61): entries (row, 0) of the GGSW are copies of the entries (row, 0) of
-// the GGLWE `a` (glwe_copy), then ggsw_expand_row.  `count` contiguous GGLWEs -> `count` contiguous GGSWs, one strided copy.
-int pz_ggsw_from_gglwe_batched(pz_module* M, int64_t* ggsw, const int64_t* a, size_t a_cols_in, size_t dnum,
-                               const double* const* tsk_pmat, const pz_glwe_op_params* p, size_t count) {
-    PZ_ENTER(M);
-    PZ_REQUIRE(p != nullptr, "null params");
-    PZ_REQUIRE(is_device_ptr(ggsw) && is_device_ptr(a), "batched entry points take device pointers");
-    PZ_REQUIRE(a_cols_in >= 1 && dnum >= 1, "ggsw_from_gglwe: empty GGLWE");
-    PZ_REQUIRE((const void*)ggsw != (const void*)a, "ggsw_from_gglwe: res must not alias a");
-    const size_t cols = p->rank + 1;
-    const long long n = (long long)M->n, ct = n * (long long)cols * (long long)p->res_size;
-    PZ_TRY(launch_ew(M, EW_COPY, ggsw, (long long)cols * ct, n, a, (long long)a_cols_in * ct, n, nullptr, 0, 0, (int)(cols * p->res_size),
-                     (int)(count * dnum)));
-    return ggsw_expand_row(M, ggsw, dnum, tsk_pmat, p, count);  // (the module lock is not recursive)
-}
-
-// glwe_trace_assign (poulpy-core/src/glwe_trace.rs:129-176) on `batch` ciphertexts:
-//   for every step s:  res = rsh(res, 1 bit) on every column (operations/glwe.rs:1096-1112);  res = glwe_automorphism_add_assign(res, key_s)
-// res in another base than the keys (:153-163; test_suite/trace.rs:36-39): (a_size, a_base2k = key_base2k) describe res re-expressed in
-// the keys' base (a_size = ceil(res.max_k / key_base2k)); normalize into a temporary of that layout, trace there, normalize back.
-int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, const double* const* key_pmats,
-                      const pz_glwe_op_params* p, size_t batch, bool first_shifted) {
-    PZ_REQUIRE(p != nullptr && (nsteps == 0 || (gals != nullptr && key_pmats != nullptr)), "glwe_trace: null argument");
-    PZ_REQUIRE(!first_shifted || (p->res_base2k == p->key_base2k && nsteps >= 1), "glwe_trace: the first shift can only be the caller's in the keys' base");
-    PZ_REQUIRE(p->rank_out == p->rank, "glwe_trace: rank_out != rank");
-    PZ_REQUIRE(is_device_ptr(res), "batched entry points take device pointers");
-    if (p->res_base2k != p->key_base2k) {
-        PZ_REQUIRE(p->a_base2k == p->key_base2k && p->a_size >= 1 && p->res_size >= 1,
-                   "glwe_trace: with res in another base than the keys, (a_size, a_base2k) is its layout in the keys' base");
-        if (batch == 0) return PZ_OK;
-        const long long n = (long long)M->n;
-        const int cols = (int)p->rank + 1, B = (int)batch;
-        const long long ct_c = n * cols * (long long)p->a_size, ct_r = n * cols * (long long)p->res_size;
-        PZ_TRY(ws2_reserve(M, (size_t)B * ct_c * 8));
-        int64_t* conv = (int64_t*)M->ws2;
-        DV cv{conv, ct_c, cols, (int)p->a_size}, rv{res, ct_r, cols, (int)p->res_size};
-        for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, cv, (int)p->key_base2k, 0, c, rv, (int)p->res_base2k, c));
-        pz_glwe_op_params q = *p;
-        q.res_size = p->a_size; q.res_base2k = p->key_base2k;
-        PZ_TRY(glwe_trace(M, conv, nsteps, gals, key_pmats, &q, batch, false));
-        for (int c = 0; c < cols; ++c) PZ_TRY(dev_normalize(M, B, rv, (int)p->res_base2k, 0, c, cv, (int)p->key_base2k, c));
-        return PZ_OK;
-    }
-    PZ_REQUIRE(p->a_size == p->res_size && p->a_base2k == p->res_base2k,
-               "glwe_trace: a and res describe the same ciphertexts when res is in the keys' base");
-    if (batch == 0) return PZ_OK;
-    const long long n = (long long)M->n;
-    const int cols = (int)p->rank + 1;
-    const long long ct = n * cols * (long long)p->res_size;
-    // the one-bit shift in front of step s + 1 rides on the tail of step s where that path has the shifted-store variant
-    bool shifted = first_shifted;   // (the FheUint byte operations' pre-kernel shifts on its way out: k_word_pre)
-    for (size_t s = 0; s < nsteps; ++s) {
-        PZ_REQUIRE((gals[s] & 1) != 0, "glwe_trace: Galois elements must be odd");
-        if (!shifted) PZ_TRY(launch_rsh(M, (int)batch, (long long*)res, ct, cols, (int)p->res_size, 0, cols, (int)p->res_base2k, 1));
-        AutoSpec au{(long long)gals[s], 1};
-        bool rsh = s + 1 < nsteps;
-        PZ_TRY(glwe_op(M, GlweKind::Automorphism, res, res, key_pmats[s], p, batch, &au, nullptr, &rsh));
-        shifted = rsh;
-    }
-    return PZ_OK;
-}
-
-int pz_glwe_trace_batched(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, const double* const* key_pmats,
-                          const pz_glwe_op_params* p, size_t batch) {
-    PZ_ENTER(M);
-    KeyHash k;
-    k.add((int)1); k.add(res); k.add(nsteps); k.add(batch);
-    if (p) k.add(*p);
-    for (size_t s = 0; s < nsteps && gals && key_pmats; ++s) { k.add(gals[s]); k.add(key_pmats[s]); }
-    graph_key_module(M, k);
-    return with_graph(M, k.h, [&]() { return glwe_trace(M, res, nsteps, gals, key_pmats, p, batch, false); });
-}
-}  // extern "C"
-
-// ------------------------------------------------------------------------------
-// CMUX, the gate of poulpy-bin-fhe's bdd_arithmetic (eval.rs:524-626): res = normalize((t - f) (x) GGSW + f), f added to the big
-// value on every column BEFORE the carry chain - which is why the gate is not an external product followed by an addition.  Routes:
-//   fused         N = 1024 / 2048 / 4096 on the small-ring kernels: the forward stage reads t and f (or f twice through the monomial map of
-//                 X^rot) and forms the difference in registers; the inverse stage adds f as its every-column operand
-//   materialised  every other shape the external product serves: D = t - f written to the second workspace by the element-wise / rotate kernels,
-//                 then the shape's pipeline on D with f as the tail's every-column operand.  POULPY_DBG_CMUX_FUSED=0 sends every shape here.
-// In place (res == t, res == f): every kernel that reads t or f of a ciphertext runs before the one that writes its result, and the inverse
-// stages read f at the positions they then write - as for the automorphism family's add forms.
-// ------------------------------------------------------------------------------
-struct CmuxOperands { uint64_t t_size, f_size; int64_t t_rot; };   // limbs of t and of f; t null: t = X^t_rot f
-struct CmuxShape {
-    long long cols, t_ct, f_ct, d_ct, res_ct;   // i64 elements of one ciphertext of t / f / D / res
-    size_t t_bytes, f_bytes, res_bytes;         // bytes of the whole batch
-};
-static CmuxShape cmux_shape(const pz_module* M, const pz_glwe_op_params* p, const CmuxOperands* o, size_t batch) {
-    CmuxShape s;
-    const long long n = (long long)M->n;
-    s.cols = (long long)p->rank + 1;
-    s.t_ct = n * s.cols * (long long)o->t_size; s.f_ct = n * s.cols * (long long)o->f_size;
-    s.d_ct = n * s.cols * (long long)p->a_size; s.res_ct = n * s.cols * (long long)p->res_size;
-    s.t_bytes = batch * (size_t)s.t_ct * 8; s.f_bytes = batch * (size_t)s.f_ct * 8; s.res_bytes = batch * (size_t)s.res_ct * 8;
-    return s;
-}
-// the argument checks that need no module (nothing is launched when one fails)
-static int cmux_check_args(const int64_t* res, const int64_t* t, const int64_t* f, const double* pmat, const pz_glwe_op_params* p,
-                           const CmuxOperands* o) {
-    PZ_REQUIRE(p != nullptr, "glwe_cmux: null params");
-    PZ_REQUIRE(res != nullptr && f != nullptr && pmat != nullptr, "glwe_cmux: null argument");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1 && o->f_size >= 1, "glwe_cmux: empty shape");
-    // external_product/glwe.rs:213 (and glwe_sub, operations.rs:343-344): t, f, res and the GGSW share one base2k
-    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_cmux: t, f, res and the GGSW share one base2k (%llu / %llu / %llu)",
-               (unsigned long long)p->a_base2k, (unsigned long long)p->res_base2k, (unsigned long long)p->key_base2k);
-    if (t == nullptr) {
-        PZ_REQUIRE(o->t_size == o->f_size, "glwe_cmux: the rotated source t = X^t_rot f has the layout of f (t_size == f_size)");
-        if ((const void*)res == (const void*)f) return fail(PZ_ERR_ALIAS, "glwe_cmux: with the rotated source res must not overlap f");
-    } else {
-        PZ_REQUIRE(o->t_size >= 1, "glwe_cmux: empty shape");
-        if ((const void*)res == (const void*)t) PZ_REQUIRE(p->res_size == o->t_size, "in-place call with different layouts for t and res");
-    }
-    if ((const void*)res == (const void*)f && t != nullptr) PZ_REQUIRE(p->res_size == o->f_size, "in-place call with different layouts for f and res");
-    return PZ_OK;
-}
-static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
-}
-// the checks that need the ring degree: res may BE t or f (the assign forms), any other overlap is refused
-static int cmux_check_overlap(const CmuxShape& s, const int64_t* res, const int64_t* t, const int64_t* f) {
-    if (t != nullptr && (const void*)res != (const void*)t && ranges_overlap(res, s.res_bytes, t, s.t_bytes))
-        return fail(PZ_ERR_ALIAS, "glwe_cmux: res overlaps t without being t");
-    if (((const void*)res != (const void*)f || t == nullptr) && ranges_overlap(res, s.res_bytes, f, s.f_bytes))
-        return fail(PZ_ERR_ALIAS, t ? "glwe_cmux: res overlaps f without being f" : "glwe_cmux: with the rotated source res must not overlap f");
-    return PZ_OK;
-}
-// which pipeline serves the product of a CMUX, and whether its forward stage can take the two sources
-static bool cmux_fused_route(const GlweCall& c) {
-    if (fused_applies(c.M, c.p, c.s, c.kind)) return n4096_two_kernel(c);
-    return small_ring_applies(c.M, c.p, c.s, c.kind, true);
-}
-// D = t - f (t null: X^rot f - f) on the limbs of D, missing limbs of either side zero (vec_znx_sub, sub.rs:6-58; vec_znx_sub_assign :60-84)
-static int cmux_materialise(pz_module* M, int64_t* D, const CmuxShape& s, const int64_t* t, const int64_t* f, const pz_glwe_op_params* p,
-                            const CmuxOperands* o, size_t batch) {
-    const long long n = (long long)M->n;
-    const int cols = (int)s.cols, B = (int)batch, d_size = (int)p->a_size;
-    const int f_sz = std::min((int)o->f_size, d_size), t_sz = t ? std::min((int)o->t_size, d_size) : f_sz;
-    const int common = std::min(t_sz, f_sz), top = std::max(t_sz, f_sz);
-    auto limb = [&](const int64_t* v, int l) { return v + (long long)l * cols * n; };
-    if (t == nullptr) {   // glwe_rotate + glwe_sub_assign in one pass (k_rotate mode 1)
-        PolyMap sm{common * cols, 1, s.f_ct, n, 0, 0}, dm{common * cols, 1, s.d_ct, n, 0, 0};
-        PZ_TRY(launch_rotate(M, B * common * cols, (const long long*)f, sm, (long long*)D, dm, 1, B * common * cols, nullptr, 0, 0, (long long)o->t_rot));
-    } else {
-        PZ_TRY(launch_ew(M, EW_SUB_I64, D, s.d_ct, n, t, s.t_ct, n, f, s.f_ct, n, common * cols, B));
-        if (t_sz > common) PZ_TRY(launch_ew(M, EW_COPY, (void*)limb(D, common), s.d_ct, n, limb(t, common), s.t_ct, n, nullptr, 0, 0, (t_sz - common) * cols, B));
-        else if (f_sz > common) PZ_TRY(launch_ew(M, EW_NEG_I64, (void*)limb(D, common), s.d_ct, n, limb(f, common), s.f_ct, n, nullptr, 0, 0, (f_sz - common) * cols, B));
-    }
-    return launch_ew(M, EW_ZERO, (void*)limb(D, top), s.d_ct, n, nullptr, 0, 0, nullptr, 0, 0, (d_size - top) * cols, B);
-}
-// device pointers, the key resolved, the module lock held (pz_glwe_cmux_batched and the ladder of pz_glwe_blind_rotation_batched).
-// res2 != null: the conditional swap (glwe_cswap below) - res == f, res2 == t, and t takes the second result normalize(t - big) in place
-static int glwe_cmux(pz_module* M, int64_t* res, const int64_t* t, const int64_t* f, const double* key, const pz_glwe_op_params* p,
-                     const CmuxOperands* o, size_t batch, int64_t* res2 = nullptr) {
-    GlweCall c;
-    PZ_TRY(glwe_call_init(c, M, GlweKind::ExternalProduct, res, f, key, p, batch, nullptr, nullptr, nullptr));   // (`a` is set below: D, or nothing)
-    if (batch == 0) return PZ_OK;
-    const CmuxShape s = cmux_shape(M, p, o, batch);
-    c.add = f; c.add_bs = s.f_ct; c.add_size = (int)o->f_size;
-    c.res2 = res2; c.res2_bs = s.t_ct; c.res2_size = (int)o->t_size;
-    const bool pipeline = fused_applies(M, p, c.s, c.kind), small_ring = !pipeline && small_ring_applies(M, p, c.s, c.kind, true);
-    const int knob = rt_knob("POULPY_DBG_CMUX_FUSED", 1);   // (read per call: tests flip it)
-    SmallDiff d;
-    if (knob != 0 && cmux_fused_route(c)) {
-        const long long n = c.n;
-        const int d_size = (int)p->a_size, cols = (int)s.cols;
-        d.t = (const long long*)t; d.f = (const long long*)f;
-        d.tmap = PolyMap{d_size, cols, s.t_ct, (long long)cols * n, n, 0};
-        d.fmap = PolyMap{d_size, cols, s.f_ct, (long long)cols * n, n, 0};
-        d.t_size = t ? (int)o->t_size : (int)o->f_size; d.f_size = (int)o->f_size;
-        d.rot = (unsigned)((unsigned long long)o->t_rot & (2ull * (unsigned long long)n - 1ull));
-        c.diff = &d; c.a = nullptr;
-        return pipeline ? glwe_fused(c) : glwe_small_ring(c);
-    }
-    dispatch_note(M, "%s: materialised difference (%s)", gate_name(c), knob == 0 ? "POULPY_DBG_CMUX_FUSED=0" : (pipeline ? "three-kernel pipeline" : (small_ring ? "small ring" : "five-kernel path")));
-    PZ_TRY(ws2_reserve(M, batch * (size_t)s.d_ct * 8));
-    int64_t* D = (int64_t*)M->ws2;
-    PZ_TRY(cmux_materialise(M, D, s, t, f, p, o, batch));
-    c.a = D;
-    if (pipeline) return glwe_fused(c);
-    if (small_ring) return glwe_small_ring(c);
-    return glwe_unfused(c);
-}
-
-extern "C" {
-size_t pz_glwe_cmux_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
-    // the external product's reservation (D has a_size limbs); the materialised route keeps D in the module's second workspace on top of it
-    return pz_glwe_op_workspace_bytes(M, p, batch, (int)GlweKind::ExternalProduct);
-}
-int pz_glwe_cmux_batched(pz_module* M, int64_t* res, const int64_t* t, size_t t_size, int64_t t_rot, const int64_t* f, size_t f_size,
-                         const double* ggsw_pmat, const pz_glwe_op_params* p, size_t batch) {
-    const CmuxOperands ops{t_size, f_size, t ? 0 : t_rot};
-    const CmuxOperands* o = &ops;
-    PZ_TRY(cmux_check_args(res, t, f, ggsw_pmat, p, o));
-    PZ_ENTER(M);
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(f) && (t == nullptr || is_device_ptr(t)), "batched entry points take device pointers");
-    PZ_TRY(cmux_check_overlap(cmux_shape(M, p, o, batch), res, t, f));
-    const size_t cols = p->rank + 1;
-    const double* key = nullptr;
-    PZ_TRY(resolve_key(M, ggsw_pmat, (size_t)M->n * 8 * p->dnum * cols * cols * p->key_size, &key));
-    PZ_TRY(glwe_cmux(M, res, t, f, key, p, o, batch));
-    return finish_call(M, false);
-}
-
-// GLWEBlindRotation::glwe_blind_rotation / _assign (bdd_arithmetic/blind_rotation.rs:196-264) on `batch` ciphertexts: nbits rotated-source CMUX
-// steps that ping-pong between res and tmp (:218-236), the final copy when the step count is odd (:238-241)
-size_t pz_glwe_blind_rotation_tmp_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
-    if (!M || !p) return 0;
-    return batch * (size_t)M->n * 8 * (p->rank + 1) * p->res_size;
-}
-static int glwe_blind_rotation_steps(pz_module* M, int64_t* res, const int64_t* a, size_t nbits, const double* const* keys, int sign, size_t bit_lsh,
-                                     const pz_glwe_op_params* p, int64_t* tmp, size_t batch) {
-    const long long n = (long long)M->n;
-    const int cols = (int)p->rank + 1, B = (int)batch;
-    const long long res_ct = n * cols * (long long)p->res_size, a_ct = n * cols * (long long)p->a_size;
-    // glwe_copy (:262): the common limbs, zero beyond.  With one layout for a and res the copy only feeds step 0, which then reads `a` itself:
-    // the same digits, one pass over the batch less (res is first written by step 1, or by the final copy)
-    const int64_t* first = (p->a_size == p->res_size && nbits > 0) ? a : res;
-    if ((const void*)res != (const void*)a && first == res) {
-        const int mn = (int)std::min(p->a_size, p->res_size);
-        PZ_TRY(launch_ew(M, EW_COPY, res, res_ct, n, a, a_ct, n, nullptr, 0, 0, mn * cols, B));
-        PZ_TRY(launch_ew(M, EW_ZERO, res + (long long)mn * cols * n, res_ct, n, nullptr, 0, 0, nullptr, 0, 0, ((int)p->res_size - mn) * cols, B));
-    }
-    pz_glwe_op_params q = *p;
-    q.a_size = p->res_size;   // every step works on the layout of res (:212)
-    CmuxOperands o;
-    o.t_size = o.f_size = p->res_size;
-    int64_t *cur = res, *other = tmp;
-    if (first != res && (nbits & 1)) std::swap(cur, other);   // step 0 does not read res: an odd count starts INTO res and ends there, no final copy
-    for (size_t i = 0; i < nbits; ++i) {
-        const int64_t* src = i == 0 ? first : cur;
-        const size_t sh = i + bit_lsh;
-        const long long pw = sh < 62 ? (1ll << sh) : 0;   // (X^(2^sh) = 1 once 2^sh is a multiple of 2n)
-        o.t_rot = sign ? pw : -pw;   // :226-229
-        PZ_TRY(glwe_cmux(M, other, nullptr, src, keys[i], &q, &o, batch));   // :232, b <- (X^rot a - a) GGSW(bit) + a
-        std::swap(cur, other);
-    }
-    if (cur != res) PZ_TRY(launch_ew(M, EW_COPY, res, res_ct, n, tmp, res_ct, n, nullptr, 0, 0, (int)p->res_size * cols, B));   // :238-241
-    return PZ_OK;
-}
-int pz_glwe_blind_rotation_batched(pz_module* M, int64_t* res, const int64_t* a, size_t nbits, const double* const* bits, int sign, size_t bit_lsh,
-                                   const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    PZ_REQUIRE(p != nullptr, "null params");
-    PZ_REQUIRE(res != nullptr && a != nullptr && (nbits == 0 || bits != nullptr), "glwe_blind_rotation: null argument");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
-    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_blind_rotation: a, res and the GGSWs share one base2k");
-    for (size_t i = 0; i < nbits; ++i) PZ_REQUIRE(bits[i] != nullptr, "glwe_blind_rotation: GGSW %zu is null", i);
-    if ((const void*)res == (const void*)a) PZ_REQUIRE(p->res_size == p->a_size, "in-place call with different layouts for a and res");
-    PZ_ENTER(M);
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a), "batched entry points take device pointers");
-    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
-    const size_t res_bytes = batch * n8 * cols * p->res_size, a_bytes = batch * n8 * cols * p->a_size;
-    if ((const void*)res != (const void*)a && ranges_overlap(res, res_bytes, a, a_bytes)) return fail(PZ_ERR_ALIAS, "glwe_blind_rotation: res overlaps a without being a");
-    if (nbits > 0 && batch > 0) {
-        PZ_REQUIRE(tmp != nullptr && is_device_ptr(tmp) && tmp_bytes >= pz_glwe_blind_rotation_tmp_bytes(M, p, batch), "glwe_blind_rotation: tmp too small (%zu bytes)", tmp_bytes);
-        if (ranges_overlap(tmp, res_bytes, res, res_bytes) || ranges_overlap(tmp, res_bytes, a, a_bytes)) return fail(PZ_ERR_ALIAS, "glwe_blind_rotation: tmp overlaps res or a");
-    }
-    std::vector<const double*> keys(nbits);
-    for (size_t i = 0; i < nbits; ++i) PZ_TRY(resolve_key(M, bits[i], n8 * p->dnum * cols * cols * p->key_size, &keys[i]));
-    if (batch == 0) return PZ_OK;
-    KeyHash k;
-    k.add((int)7); k.add(res); k.add(a); k.add(tmp); k.add(nbits); k.add(sign != 0); k.add(bit_lsh); k.add(batch); k.add(*p);
-    k.add(rt_knob("POULPY_DBG_CMUX_FUSED", 1));
-    for (size_t i = 0; i < nbits; ++i) k.add(keys[i]);
-    graph_key_module(M, k);
-    PZ_TRY(with_graph(M, k.h, [&]() { return glwe_blind_rotation_steps(M, res, a, nbits, keys.data(), sign, bit_lsh, p, (int64_t*)tmp, batch); }));
-    return finish_call(M, false);
-}
-}  // extern "C"
-
-// ------------------------------------------------------------------------------
-// Conditional swap, the other gate of bdd_arithmetic (Cswap::cswap, eval.rs:417-461, the equal-base branch), IN PLACE on a and b:
-//   D = b - a (glwe_sub into tmp_c of max(a, b) limbs, not normalized);  big = D (x) GGSW - ONE external product;
-//   a' = normalize(big + a) (vec_znx_big_add_small_into),  b' = normalize(b - big) (vec_znx_big_sub_small_a) on every column.
-// The forward half is the CMUX's with t = b, f = a (fused: SmallDiff; materialised: cmux_materialise into the second workspace).  The inverse half leaves
-// two results from the one big value:
-//   small-ring kernels  the dual forms k_small_inv<.., DUAL> / k_small_one<.., DUAL>: two carry chains behind one inverse transform
-//   pipeline            two tails over the same T2' (the tail only reads it), the second with the big value negated (TailCall::big_neg)
-//   five-kernel path    the i64 big value in the workspace feeds both normalizations
-// In place: every kernel that reads a or b of a ciphertext as a SOURCE runs before the one that writes its results (or, in the one-kernel form, four
-// barriers earlier in the same workgroup), and the chains read their operands at the positions they then write.
-// ------------------------------------------------------------------------------
-static int cswap_check_args(const int64_t* a, size_t a_size, const int64_t* b, size_t b_size, const double* pmat, const pz_glwe_op_params* p, size_t batch) {
-    PZ_REQUIRE(p != nullptr, "glwe_cswap: null params");
-    PZ_REQUIRE(a != nullptr && b != nullptr && pmat != nullptr, "glwe_cswap: null argument");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1 && a_size >= 1 && b_size >= 1, "glwe_cswap: empty shape");
-    // eval.rs:427 (this branch) and external_product/glwe.rs:213
-    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_cswap: a, b and the GGSW share one base2k (%llu / %llu / %llu)",
-               (unsigned long long)p->a_base2k, (unsigned long long)p->res_base2k, (unsigned long long)p->key_base2k);
-    PZ_REQUIRE(p->a_size == std::max(a_size, b_size), "glwe_cswap: p->a_size is the limb count of the difference, max(a_size, b_size) = %zu, not %llu",
-               std::max(a_size, b_size), (unsigned long long)p->a_size);   // tmp_c: k = max(res_a.max_k, res_b.max_k), eval.rs:437-442
-    PZ_REQUIRE(p->res_size == a_size, "glwe_cswap: p->res_size is a_size = %zu, not %llu", a_size, (unsigned long long)p->res_size);
-    // what the pointers alone tell: the same buffer, or two ranges that overlap at the smallest ring degree a module can have (n = 2)
-    const size_t cols = p->rank + 1;
-    if ((const void*)a == (const void*)b || (batch > 0 && ranges_overlap(a, batch * cols * a_size * 16, b, batch * cols * b_size * 16)))
-        return fail(PZ_ERR_ALIAS, "glwe_cswap: a and b overlap");
-    return PZ_OK;
-}
-// device pointers, the key resolved, the module lock held (pz_glwe_cswap_batched and the levels of pz_glwe_blind_retrieval_batched): the CMUX with
-// t = b, f = a, res = a, and b taking the second result
-static int glwe_cswap(pz_module* M, int64_t* a, size_t a_size, int64_t* b, size_t b_size, const double* key, const pz_glwe_op_params* p, size_t batch) {
-    const CmuxOperands ops{b_size, a_size, 0};
-    return glwe_cmux(M, a, b, a, key, p, &ops, batch, b);
-}
-// the levels of the retrieval network in its dense form: level i pairs slot j with slot j + t, t = 2^(nbits - 1 - i), for j < cnt (blind_retrieval.rs:222-233)
-static size_t retrieval_cnt(size_t nslots, size_t t) { return t < nslots ? std::min(t, nslots - t) : 0; }
-static int glwe_blind_retrieval_levels(pz_module* M, int64_t* slots, size_t nslots, size_t nbits, const double* const* keys, int reverse,
-                                       const pz_glwe_op_params* p, size_t batch) {
-    const size_t slot_elems = batch * (size_t)M->n * (p->rank + 1) * p->res_size;
-    for (size_t s = 0; s < nbits; ++s) {
-        const size_t i = reverse ? nbits - 1 - s : s;
-        if (nbits - 1 - i >= 63) continue;   // (t beyond any slot count)
-        const size_t t = (size_t)1 << (nbits - 1 - i), cnt = retrieval_cnt(nslots, t);
-        if (cnt == 0) continue;
-        PZ_TRY(glwe_cswap(M, slots, p->res_size, slots + t * slot_elems, p->res_size, keys[nbits - 1 - i], p, cnt * batch));
-    }
-    return PZ_OK;
-}
-
-extern "C" {
-size_t pz_glwe_cswap_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t batch) {
-    // the external product's reservation (D has p->a_size limbs); the materialised route keeps D in the module's second workspace on top of it
-    return pz_glwe_op_workspace_bytes(M, p, batch, (int)GlweKind::ExternalProduct);
-}
-int pz_glwe_cswap_batched(pz_module* M, int64_t* a, size_t a_size, int64_t* b, size_t b_size, const double* ggsw_pmat, const pz_glwe_op_params* p,
-                          size_t batch) {
-    PZ_TRY(cswap_check_args(a, a_size, b, b_size, ggsw_pmat, p, batch));
-    PZ_ENTER(M);
-    PZ_REQUIRE(is_device_ptr(a) && is_device_ptr(b), "batched entry points take device pointers");
-    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
-    if (ranges_overlap(a, batch * n8 * cols * a_size, b, batch * n8 * cols * b_size)) return fail(PZ_ERR_ALIAS, "glwe_cswap: a and b overlap");
-    const double* key = nullptr;
-    PZ_TRY(resolve_key(M, ggsw_pmat, n8 * p->dnum * cols * cols * p->key_size, &key));
-    PZ_TRY(glwe_cswap(M, a, a_size, b, b_size, key, p, batch));
-    return finish_call(M, false);
-}
-
-// GLWEBlindRetrieval::glwe_blind_retrieval_statefull / _rev (bdd_arithmetic/blind_retrieval.rs:195-266) on `batch` vectors of nslots ciphertexts in
-// a dense slot-major buffer: every level of the butterfly network is one conditional swap on cnt * batch contiguous pairs
-size_t pz_glwe_blind_retrieval_workspace_bytes(const pz_module* M, const pz_glwe_op_params* p, size_t nslots, size_t nbits, size_t batch) {
-    if (!M || !p) return 0;
-    size_t most = 0;   // the swap's figure at the largest level
-    for (size_t i = 0; i < nbits && i < 63; ++i) most = std::max(most, retrieval_cnt(nslots, (size_t)1 << i));
-    return most == 0 ? 0 : pz_glwe_cswap_workspace_bytes(M, p, most * batch);
-}
-int pz_glwe_blind_retrieval_batched(pz_module* M, int64_t* slots, size_t nslots, size_t nbits, const double* const* bits, int reverse,
-                                    const pz_glwe_op_params* p, size_t batch) {
-    PZ_REQUIRE(p != nullptr, "glwe_blind_retrieval: null params");
-    if (nslots == 0 || nbits == 0) return PZ_OK;
-    PZ_REQUIRE(slots != nullptr && bits != nullptr, "glwe_blind_retrieval: null argument");
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe_blind_retrieval: empty shape");
-    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "glwe_blind_retrieval: the slots and the GGSWs share one base2k");
-    PZ_REQUIRE(p->a_size == p->res_size, "glwe_blind_retrieval: all slots share one layout (p->a_size == p->res_size)");
-    for (size_t i = 0; i < nbits; ++i) PZ_REQUIRE(bits[i] != nullptr, "glwe_blind_retrieval: GGSW %zu is null", i);
-    PZ_ENTER(M);
-    PZ_REQUIRE(is_device_ptr(slots), "batched entry points take device pointers");
-    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
-    std::vector<const double*> keys(nbits);
-    for (size_t i = 0; i < nbits; ++i) PZ_TRY(resolve_key(M, bits[i], n8 * p->dnum * cols * cols * p->key_size, &keys[i]));
-    if (batch == 0) return PZ_OK;
-    KeyHash k;
-    k.add((int)8); k.add(slots); k.add(nslots); k.add(nbits); k.add(reverse != 0); k.add(batch); k.add(*p);
-    k.add(rt_knob("POULPY_DBG_CMUX_FUSED", 1));
-    for (size_t i = 0; i < nbits; ++i) k.add(keys[i]);
-    graph_key_module(M, k);
-    PZ_TRY(with_graph(M, k.h, [&]() { return glwe_blind_retrieval_levels(M, slots, nslots, nbits, keys.data(), reverse, p, batch); }));
-    return finish_call(M, false);
-}
-}  // extern "C"
-
-// ------------------------------------------------------------------------------
-// BDD circuits: ExecuteBDDCircuit (eval.rs:104-305).  pz_bdd_circuit_new compiles the node lists on the host (bdd_schedule.cpp) into
-// level tables of gates over physical slots; pz_bdd_circuit_execute_batched runs them on `batch` inputs.  tmp = [state pool, slot-major
-// [slots][batch]][gather table][key pointers][row-sliced copies of the selected keys that are not pinned].  Routes:
-//   gathered   N = 1024 / 2048 / 4096 where the small-ring kernels serve the CMUX: per call one table kernel turns (slot, slot, slot, selector) of
-//              every gate and input into (t, f, res, key) addresses, then every level is ONE launch (or one per wave of the module's chunk) of the
-//              gathered kernels - blocks input-major, the gates of an input sorted by selector, so the ciphertexts of one key sit side by side
-//   per-gate   every other shape, and POULPY_DBG_BDD_GATHER=0: the same schedule, one glwe_cmux per (gate, input)
-// What depends on the call's keys reaches the gathered kernels through tmp, written outside the graph (the slices, the pointer array); the graph
-// itself holds kernel nodes only and is keyed by the circuit, out, tmp and the shape.  The per-gate route bakes key pointers into kernel arguments,
-// so there the resolved keys are part of the key.
-// ------------------------------------------------------------------------------
-struct pz_bdd_circuit {
-    BddSchedule s;
-    uint64_t uid;
-};
-static std::atomic<uint64_t> g_bdd_uid{1};
-
-struct BddWs { size_t state, tab, ptrs, slice, nsel, total; };
-static BddWs bdd_ws(const pz_module* M, const BddSchedule& s, const pz_glwe_op_params* p, size_t batch, size_t nbits) {
-    BddWs w;
-    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
-    w.state = align256(s.slots * batch * n8 * cols * p->res_size);
-    w.tab = align256(s.gates.size() * batch * sizeof(SmallGather));
-    w.ptrs = align256(batch * nbits * sizeof(void*));
-    w.slice = align256(n8 * p->dnum * cols * cols * p->key_size);
-    w.nsel = 0;
-    for (uint8_t u : s.selected) w.nsel += u;
-    w.total = w.state + w.tab + w.ptrs + batch * w.nsel * w.slice;
-    return w;
-}
-// the module's device copy of the circuit's level tables (uploaded once per module and circuit, with a blocking copy: the handle may be freed
-// as soon as the call returns)
-static int bdd_device_tables(pz_module* M, const pz_bdd_circuit* c, const BddGate** gates, const uint32_t** level_start) {
-    for (auto& bt : M->bdd_tables)
-        if (bt.uid == c->uid) { bt.stamp = ++M->mirror_clock; *gates = (const BddGate*)bt.gates; *level_start = (const uint32_t*)bt.level_start; return PZ_OK; }
-    if (M->bdd_tables.size() >= 16) {   // (a captured graph may hold the evicted tables: it goes with them)
-        size_t lru = 0;
-        for (size_t i = 1; i < M->bdd_tables.size(); ++i) if (M->bdd_tables[i].stamp < M->bdd_tables[lru].stamp) lru = i;
-        PZ_HIP(hipStreamSynchronize(M->stream));
-        M->graph_epoch++;
-        (void)hipFree(M->bdd_tables[lru].gates); (void)hipFree(M->bdd_tables[lru].level_start);
-        M->bdd_tables.erase(M->bdd_tables.begin() + (long)lru);
-    }
-    void *dg = nullptr, *dl = nullptr;
-    const size_t gb = std::max<size_t>(c->s.gates.size(), 1) * sizeof(BddGate), lb = c->s.level_start.size() * sizeof(uint32_t);
-    PZ_TRY(device_malloc_retry(M, &dg, gb));
-    if (device_malloc_retry(M, &dl, lb) != PZ_OK) { (void)hipFree(dg); return PZ_ERR_HIP; }
-    if ((c->s.gates.empty() ? hipSuccess : hipMemcpy(dg, c->s.gates.data(), c->s.gates.size() * sizeof(BddGate), hipMemcpyHostToDevice)) != hipSuccess ||
-        hipMemcpy(dl, c->s.level_start.data(), lb, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dg); (void)hipFree(dl);
-        return fail(PZ_ERR_HIP, "bdd_circuit_execute: upload of the level tables failed");
-    }
-    M->bdd_tables.push_back({c->uid, dg, dl, ++M->mirror_clock});
-    *gates = (const BddGate*)dg; *level_start = (const uint32_t*)dl;
-    return PZ_OK;
-}
-// the initial state and the outputs no gate writes: slots 0 / 1 of the pool (zero, one), the zero outputs, the slots beyond output_size
-static int bdd_init(pz_module* M, const BddSchedule& s, int64_t* state, int64_t* out, size_t n_out, const pz_glwe_op_params* p, size_t batch) {
-    const long long n = (long long)M->n, cols = (long long)p->rank + 1, ct = n * cols * (long long)p->res_size;
-    const size_t slot_bytes = batch * (size_t)ct * 8;
-    PZ_TRY(launch_zero_bytes(M, state, 2 * slot_bytes));
-    // encode_coeff_i64(base2k, col 0, k = 2, idx 0, 1) (encoding.rs:116-155): 1 << (bits of limb `used - 1` below 2^-2), normalized
-    const int k = (int)p->res_base2k, used = (2 + k - 1) / k;
-    long long d[2] = {0, 0};
-    d[used - 1] = 1ll << (used * k - 2);
-    long long carry = 0;
-    for (int j = used - 1; j >= 0; --j) {
-        const long long v = d[j] + carry, half = 1ll << (k - 1), dg = ((v + half) & ((1ll << k) - 1)) - half;
-        carry = (v - dg) >> k;
-        d[j] = dg;
-    }
-    PZ_TRY(launch_bdd_one(M, (long long*)state + (long long)batch * ct, ct, (int)batch, cols * n, d[0], d[1], used));
-    for (uint32_t o : s.zero_outputs) PZ_TRY(launch_zero_bytes(M, out + (size_t)o * batch * (size_t)ct, slot_bytes));
-    if (n_out > s.output_size) PZ_TRY(launch_zero_bytes(M, out + s.output_size * batch * (size_t)ct, (n_out - s.output_size) * slot_bytes));
-    return PZ_OK;
-}
-
-extern "C" {
-pz_bdd_circuit* pz_bdd_circuit_new(const pz_bdd_node* const* nodes, const size_t* node_count, const size_t* state_size, size_t output_size,
-                                   size_t input_size) {
-    static_assert(sizeof(pz_bdd_node) == sizeof(BddNode) && (int)PZ_BDD_NONE == (int)kBddNone && (int)PZ_BDD_COPY == (int)kBddCopy && (int)PZ_BDD_CMUX == (int)kBddCmux,
-                  "pz_bdd_node is the compiler's node");
-    pz_bdd_circuit* c = new pz_bdd_circuit();
-    std::string err;
-    if (!bdd_compile(reinterpret_cast<const BddNode* const*>(nodes), node_count, state_size, output_size, input_size, &c->s, &err)) {
-        delete c;
-        (void)fail(PZ_ERR_INVALID, "%s", err.c_str());
-        return nullptr;
-    }
-    c->uid = g_bdd_uid.fetch_add(1);
-    return c;
-}
-void pz_bdd_circuit_free(pz_bdd_circuit* c) { delete c; }
-size_t pz_bdd_circuit_input_size(const pz_bdd_circuit* c) { return c ? c->s.input_size : 0; }
-size_t pz_bdd_circuit_output_size(const pz_bdd_circuit* c) { return c ? c->s.output_size : 0; }
-size_t pz_bdd_circuit_max_state_size(const pz_bdd_circuit* c) { return c ? c->s.max_state_size : 0; }
-size_t pz_bdd_circuit_levels(const pz_bdd_circuit* c) { return c ? c->s.levels() : 0; }
-size_t pz_bdd_circuit_gates(const pz_bdd_circuit* c) { return c ? c->s.gates.size() : 0; }
-size_t pz_bdd_circuit_moved_copies(const pz_bdd_circuit* c) { return c ? c->s.moved_copies : 0; }
-size_t pz_bdd_circuit_slots(const pz_bdd_circuit* c) { return c ? c->s.slots : 0; }
-int pz_bdd_circuit_output_slots(const pz_bdd_circuit* c, size_t o, size_t* first, size_t* count) {
-    if (!c || o >= c->s.output_size) return -1;
-    if (first) *first = c->s.slot_first[o];
-    if (count) *count = c->s.slot_count[o];
-    return 0;
-}
-size_t pz_bdd_circuit_level_gates(const pz_bdd_circuit* c, size_t level, uint32_t* gates4, size_t cap) {
-    if (!c || level >= c->s.levels()) return 0;
-    const size_t a = c->s.level_start[level], cnt = c->s.level_start[level + 1] - a;
-    for (size_t i = 0; gates4 && i < std::min(cnt, cap); ++i) {
-        const BddGate& g = c->s.gates[a + i];
-        gates4[4 * i] = g.t; gates4[4 * i + 1] = g.f; gates4[4 * i + 2] = g.res; gates4[4 * i + 3] = g.sel;
-    }
-    return cnt;
-}
-size_t pz_bdd_circuit_execute_tmp_bytes(const pz_module* M, const pz_bdd_circuit* c, const pz_glwe_op_params* p, size_t batch) {
-    if (!M || !c || !p) return 0;
-    return bdd_ws(M, c->s, p, batch, c->s.input_size).total;
-}
-}  // extern "C"
-
-// which route a call takes: null = gathered (*one: the one-kernel form), else why it walks gate by gate
-static const char* bdd_per_gate_reason(pz_module* M, const GlweCall& c, const SmallGatherShape& sh, bool* one) {
-    *one = false;
-    if (rt_knob("POULPY_DBG_BDD_GATHER", 1) == 0) return "POULPY_DBG_BDD_GATHER=0";   // (read per call: tests flip it)
-    if (c.digits) return "dsize > 1";
-    if (!cmux_fused_route(c)) return "no small-ring kernels for this shape";
-    *one = !fused_applies(M, c.p, c.s, c.kind) && small_one_gather_supported(M, sh);
-    return nullptr;
-}
-static int bdd_levels_gathered(pz_module* M, const BddSchedule& s, const SmallGatherShape& sh, bool one, const SmallGather* tab, cplx* S, size_t chunk, size_t batch) {
-    dispatch_note(M, one ? "bdd: gathered small-one (k_small_one_gather, one launch per level)" : "bdd: gathered small two-kernel (k_small_fwd_gather -> k_small_inv_gather per level)");
-    for (size_t lv = 0; lv < s.levels(); ++lv) {
-        const size_t first = (size_t)s.level_start[lv] * batch, total = (size_t)(s.level_start[lv + 1] - s.level_start[lv]) * batch;
-        for (size_t c0 = 0; c0 < total; c0 += chunk) {
-            const int nb = (int)std::min(chunk, total - c0);
-            if (one) { PZ_TRY(launch_small_one_gather(M, nb, sh, tab + first + c0)); continue; }
-            PZ_TRY(launch_small_fwd_gather(M, nb, sh, tab + first + c0, S));
-            PZ_TRY(launch_small_inv_gather(M, nb, sh, tab + first + c0, S));
-        }
-    }
-    return PZ_OK;
-}
-static int bdd_levels_per_gate(pz_module* M, const BddSchedule& s, int64_t* state, int64_t* out, const double* const* keys, size_t nbits,
-                               const pz_glwe_op_params* p, size_t batch) {
-    const size_t ct = (size_t)M->n * (p->rank + 1) * p->res_size;
-    const CmuxOperands ops{p->res_size, p->res_size, 0};
-    for (const BddGate& g : s.gates)   // (level-major: every gate of a level before any of the next)
-        for (size_t b = 0; b < batch; ++b) {
-            int64_t* res = (g.res & kBddOut) ? out + ((size_t)(g.res & ~kBddOut) * batch + b) * ct : state + ((size_t)g.res * batch + b) * ct;
-            PZ_TRY(glwe_cmux(M, res, state + ((size_t)g.t * batch + b) * ct, state + ((size_t)g.f * batch + b) * ct, keys[b * nbits + g.sel], p, &ops, 1));
-        }
-    return PZ_OK;
-}
-
-extern "C" {
-int bdd_circuit_execute_precheck(const pz_module* M, const pz_bdd_circuit* c, const int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                                 const pz_glwe_op_params* p, size_t batch, bool* nothing) {
-    *nothing = false;
-    PZ_REQUIRE(p != nullptr, "bdd_circuit_execute: null params");
-    PZ_REQUIRE(c != nullptr, "bdd_circuit_execute: null circuit");
-    const BddSchedule& s = c->s;
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1 && p->res_base2k >= 1 && p->res_base2k <= 62, "bdd_circuit_execute: empty shape");
-    PZ_REQUIRE(p->a_base2k == p->key_base2k && p->res_base2k == p->key_base2k, "bdd_circuit_execute: the state, the result and the GGSWs share one base2k (%llu / %llu / %llu)",
-               (unsigned long long)p->a_base2k, (unsigned long long)p->res_base2k, (unsigned long long)p->key_base2k);
-    PZ_REQUIRE(p->a_size == p->res_size, "bdd_circuit_execute: the state has the layout of the result (p->a_size == p->res_size)");
-    PZ_REQUIRE(p->res_size * p->res_base2k >= 2, "bdd_circuit_execute: the result cannot hold the constant 2^-2");
-    PZ_REQUIRE(n_out >= s.output_size, "bdd_circuit_execute: n_out %zu < output_size %zu", n_out, s.output_size);
-    PZ_REQUIRE(batch <= (1u << 24) && n_out < kBddOut, "bdd_circuit_execute: batch or n_out out of range");
-    if (batch == 0 || n_out == 0) { *nothing = true; return M ? PZ_OK : fail(PZ_ERR_INVALID, "null module"); }   // no ciphertext to write
-    PZ_REQUIRE(nbits >= s.input_size, "bdd_circuit_execute: nbits %zu < input_size %zu", nbits, s.input_size);
-    PZ_REQUIRE(out != nullptr, "bdd_circuit_execute: null argument");
-    if (!s.gates.empty()) {
-        PZ_REQUIRE(bits != nullptr, "bdd_circuit_execute: null argument");
-        for (size_t b = 0; b < batch; ++b)
-            for (size_t i = 0; i < s.input_size; ++i)
-                PZ_REQUIRE(!s.selected[i] || bits[b * nbits + i] != nullptr, "bdd_circuit_execute: the GGSW of input bit %zu of input %zu is null and the circuit selects it", i, b);
-    }
-    return PZ_OK;
-}
-int bdd_circuit_execute(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                        const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    const BddSchedule& s = c->s;
-    PZ_REQUIRE(is_device_ptr(out), "batched entry points take device pointers");
-    const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8, ct = (size_t)M->n * cols * p->res_size;
-    const size_t out_bytes = n_out * batch * ct * 8, key_bytes = n8 * p->dnum * cols * cols * p->key_size;
-    if (s.gates.empty()) return launch_zero_bytes(M, out, out_bytes);   // nothing but zero outputs
-    const BddWs w = bdd_ws(M, s, p, batch, nbits);
-    PZ_REQUIRE(tmp != nullptr && is_device_ptr(tmp) && tmp_bytes >= w.total, "bdd_circuit_execute: tmp too small (%zu bytes, %zu needed)", tmp_bytes, w.total);
-    if (ranges_overlap(out, out_bytes, tmp, w.total)) return fail(PZ_ERR_ALIAS, "bdd_circuit_execute: out overlaps tmp");
-    // Every selected entry resolves as every GLWE key does - and all of them must stay resolved until the call has been issued.  A module mirrors at
-    // most kKeyMirrorMax host keys (kKeyMirrorBytes) and frees the least recently used one beyond that: a call whose distinct host-resident keys
-    // do not fit at once is refused here, before the first of them is resolved (each distinct pointer is resolved once)
-    std::unordered_map<const double*, const double*> resolved;
-    size_t nhost = 0;
-    for (size_t b = 0; b < batch; ++b)
-        for (size_t i = 0; i < s.input_size; ++i)
-            if (s.selected[i] && resolved.emplace(bits[b * nbits + i], nullptr).second && !is_device_ptr(bits[b * nbits + i])) ++nhost;
-    if (nhost > kKeyMirrorMax || nhost * key_bytes > kKeyMirrorBytes)
-        return fail(PZ_ERR_UNSUPPORTED, "bdd_circuit_execute: %zu distinct host-resident GGSWs of %zu bytes in one call; a module mirrors at most %zu (%zu GiB) at a time - "
-                    "keep them on the device (pz_device_alloc, pz_memcpy_h2d)", nhost, key_bytes, kKeyMirrorMax, kKeyMirrorBytes >> 30);
-    for (auto& kv : resolved) PZ_TRY(resolve_key(M, kv.first, key_bytes, &kv.second));
-    std::vector<const double*> keys(batch * nbits, nullptr);
-    for (size_t b = 0; b < batch; ++b)
-        for (size_t i = 0; i < s.input_size; ++i) {
-            if (!s.selected[i]) continue;
-            keys[b * nbits + i] = resolved[bits[b * nbits + i]];
-            if (ranges_overlap(out, out_bytes, keys[b * nbits + i], key_bytes)) return fail(PZ_ERR_ALIAS, "bdd_circuit_execute: out overlaps the GGSW of input bit %zu of input %zu", i, b);
-            if (ranges_overlap(tmp, w.total, keys[b * nbits + i], key_bytes)) return fail(PZ_ERR_ALIAS, "bdd_circuit_execute: tmp overlaps the GGSW of input bit %zu of input %zu", i, b);
-        }
-    char* base = (char*)tmp;
-    int64_t* state = (int64_t*)base;
-    SmallGather* tab = (SmallGather*)(base + w.state);
-    const cplx** dptrs = (const cplx**)(base + w.state + w.tab);
-    char* slices = base + w.state + w.tab + w.ptrs;
-    GlweCall gc;
-    const double* any_key = nullptr;
-    for (const double* k : keys) if (k) { any_key = k; break; }
-    PZ_TRY(glwe_call_init(gc, M, GlweKind::ExternalProduct, out, state, any_key, p, batch, nullptr, nullptr, nullptr));
-    gc.add = state;   // (the CMUX's every-column operand: part of what cmux_fused_route looks at)
-    const SmallGatherShape sh{(int)cols, (int)p->res_size, (int)p->key_size, (int)p->dnum, (int)p->res_base2k};
-    bool one = false;
-    const char* why = bdd_per_gate_reason(M, gc, sh, &one);
-    KeyHash k;
-    k.add((int)9); k.add(c->uid); k.add(out); k.add(n_out); k.add(tmp); k.add(nbits); k.add(batch); k.add(*p); k.add(why != nullptr);
-    k.add(rt_knob("POULPY_DBG_CMUX_FUSED", 1));
-    if (why) {
-        for (const double* key : keys) k.add(key);
-        graph_key_module(M, k);
-        PZ_TRY(with_graph(M, k.h, [&]() {
-            dispatch_note(M, "bdd: per-gate (%s)", why);
-            PZ_TRY(bdd_init(M, s, state, out, n_out, p, batch));
-            return bdd_levels_per_gate(M, s, state, out, keys.data(), nbits, p, batch);
-        }));
-        return PZ_OK;
-    }
-    // ---- gathered: everything that depends on the keys is written to tmp here, outside the graph ----
-    const BddGate* d_gates; const uint32_t* d_levels;
-    PZ_TRY(bdd_device_tables(M, c, &d_gates, &d_levels));
-    const bool pipeline = fused_applies(M, p, gc.s, gc.kind);   // N = 4096: the key layout of the three-kernel pipeline's plan
-    // the pointer array goes through page-locked staging: the previous call's copy out of it has finished before it is rewritten
-    if (M->bdd_stage_ev) PZ_HIP(hipEventSynchronize(M->bdd_stage_ev));
-    else PZ_HIP(hipEventCreateWithFlags(&M->bdd_stage_ev, hipEventDisableTiming));
-    if (M->bdd_stage_count < batch * nbits) {
-        if (M->bdd_stage) PZ_HIP(hipHostFree(M->bdd_stage));
-        M->bdd_stage = nullptr; M->bdd_stage_count = 0;
-        PZ_HIP(hipHostMalloc((void**)&M->bdd_stage, batch * nbits * sizeof(void*), hipHostMallocDefault));
-        M->bdd_stage_count = batch * nbits;
-    }
-    std::fill(M->bdd_stage, M->bdd_stage + batch * nbits, nullptr);
-    // (hash maps: a batch of 64 additions brings 4096 keys, every one of them pinned)
-    std::unordered_map<const void*, const cplx*> sliced;   // the distinct keys of this call -> their row-sliced copies
-    std::unordered_map<const void*, const cplx*> pinned;
-    for (auto& pk : M->pinned)
-        if (pk.sliced && pk.bytes == key_bytes) pinned.emplace(pk.key, pk.sliced);   // (pinned_slices' test)
-    size_t nsliced = 0;
-    for (size_t i = 0; i < keys.size(); ++i) {
-        if (!keys[i]) continue;
-        auto it = sliced.find(keys[i]);
-        if (it == sliced.end()) {
-            const auto pin = pinned.find(keys[i]);
-            const cplx* Pp = pin != pinned.end() ? pin->second : nullptr;
-            if (!Pp) {
-                cplx* dst = (cplx*)(slices + (nsliced++) * w.slice);
-                if (pipeline) PZ_TRY(launch_permute_pmat(M, keys[i], dst, gc.nrows * gc.ncols));
-                else PZ_TRY(launch_small_permute(M, keys[i], dst, gc.nrows * gc.ncols));
-                Pp = dst;
-            }
-            it = sliced.emplace(keys[i], Pp).first;
-        }
-        M->bdd_stage[i] = it->second;
-    }
-    PZ_HIP(hipMemcpyAsync(dptrs, M->bdd_stage, batch * nbits * sizeof(void*), hipMemcpyHostToDevice, M->stream));
-    PZ_HIP(hipEventRecord(M->bdd_stage_ev, M->stream));
-    size_t widest = 0;
-    for (size_t lv = 0; lv < s.levels(); ++lv) widest = std::max<size_t>(widest, s.level_start[lv + 1] - s.level_start[lv]);
-    const size_t chunk = pick_chunk(M, p, gc.s, widest * batch);
-    const size_t s_bytes = one ? 0 : align256(chunk * (size_t)gc.npi * (size_t)M->m * sizeof(cplx));
-    PZ_TRY(ws_reserve(M, s_bytes));
-    char* wsb = (char*)M->ws;
-    cplx* S = nullptr;
-    PZ_TRY(ws_take(M, wsb, s_bytes, &S));
-    k.add(one);
-    graph_key_module(M, k);
-    PZ_TRY(with_graph(M, k.h, [&]() {
-        PZ_TRY(bdd_init(M, s, state, out, n_out, p, batch));
-        BddTableCall tc;
-        tc.gates = d_gates; tc.level_start = d_levels; tc.levels = (int)s.levels(); tc.total = (uint32_t)s.gates.size(); tc.batch = (int)batch; tc.nbits = (int)nbits;
-        tc.state = (long long*)state; tc.out = (long long*)out; tc.ct = (long long)ct; tc.keys = dptrs; tc.tab = tab;
-        PZ_TRY(launch_bdd_table(M, tc));
-        return bdd_levels_gathered(M, s, sh, one, tab, S, chunk, batch);
-    }));
-    return PZ_OK;
-}
-int pz_bdd_circuit_execute_batched(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                                   const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch) {
-    bool nothing = false;
-    PZ_TRY(bdd_circuit_execute_precheck(M, c, out, n_out, bits, nbits, p, batch, &nothing));
-    if (nothing) return PZ_OK;
-    PZ_ENTER(M);
-    PZ_TRY(bdd_circuit_execute(M, c, out, n_out, bits, nbits, p, tmp, tmp_bytes, batch));
-    return finish_call(M, false);
 }
 }  // extern "C"
 
@@ -1829,13 +1073,12 @@ int pz_glwe_automorphism_many_batched(pz_module* M, int64_t* res, const int64_t*
         PZ_REQUIRE(key_pmats[r] != nullptr, "glwe_automorphism_many: key %zu is null", r);
     }
     PZ_ENTER(M);
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
+    PZ_TRY(require_op_shape(p, "glwe op"));
     PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_automorphism_many: the keys map rank -> rank");
     const size_t cols = p->rank + 1, n8 = (size_t)M->n * 8;
     const size_t a_bytes = batch * n8 * cols * p->a_size, res_bytes = nrot * batch * n8 * cols * p->res_size;
     // every rotation reads `a` after the first one has written: no in-place form
-    PZ_REQUIRE(!((const char*)res < (const char*)a + a_bytes && (const char*)a < (const char*)res + res_bytes) && (const void*)res != (const void*)a,
-               "glwe_automorphism_many: res overlaps a");
+    PZ_REQUIRE(!ranges_overlap(res, res_bytes, a, a_bytes) && (const void*)res != (const void*)a, "glwe_automorphism_many: res overlaps a");
     for (size_t r = 0; r < nrot; ++r) PZ_REQUIRE(is_device_ptr(key_pmats[r]), "batched entry points take device pointers");
     AutoSpec au0{(long long)gals[0], 0};
     GlweCall c;
@@ -1855,142 +1098,6 @@ int pz_glwe_automorphism_many_batched(pz_module* M, int64_t* res, const int64_t*
 }
 }  // extern "C"
 
-// ------------------------------------------------------------------------------
-// glwe_automorphism_key_automorphism (automorphism/gglwe_atk.rs:42-155), ggsw_keyswitch (keyswitching/ggsw.rs:37-85), ggsw_automorphism
-// (automorphism/ggsw_ct.rs:32-82)
-// ------------------------------------------------------------------------------
-// the spectrum of phi_g(K) read from the spectrum of K (evaluation points w^(4q+1)): index q' holds K[g q' + (g-1)/4] for g = 1 mod 4,
-// the conjugate of K[-g q' - (g+1)/4] for g = 3 mod 4 - the map spectral_perm applies on the middle kernel's stores, here on the key
-static KeyPerm key_perm(unsigned g, unsigned mm) {
-    KeyPerm kp;
-    if ((g & 3u) == 1u) {
-        kp.mul = g & (mm - 1u);
-        kp.add = ((g - 1u) >> 2) & (mm - 1u);
-    } else {
-        kp.conj = true;
-        kp.mul = (mm - (g & (mm - 1u))) & (mm - 1u);
-        kp.add = (mm - (((g + 1u) >> 2) & (mm - 1u))) & (mm - 1u);
-    }
-    return kp;
-}
-// Route table: the fast form where the limbs of `a` reach the forward transform as they are and the three-kernel pipeline of
-// a 128-point-row plan runs the key switch - dsize 1, one base2k, not the N = 4096 two-kernel path, every stage on
-// Off by default: no rate of the fast form against the composition has been measured yet - POULPY_DBG_KEYAUTO_SPECTRAL=1 selects it
-constexpr int kKeyautoSpectralDefault = 0;
-static bool keyauto_fast_applies(const GlweCall& c) {
-    const bool env_on = (rt_knob("POULPY_DBG_KEYAUTO_SPECTRAL", kKeyautoSpectralDefault) != 0);   // (read per call: once per GGLWE batch, and tests flip it)
-    const pz_module* M = c.M;
-    return env_on && M->plan.m2 == 128 && M->dbg_stages == 7 && !c.digits && !c.cross_out && !c.s.convert &&
-           fused_applies(M, c.p, c.s, GlweKind::KeySwitch) && !n4096_two_kernel(c);
-}
-// `batch` packed entries: res[e] = phi_g(glwe_keyswitch(phi_p(a[e]), key)), p = a_gal, g = p^-1 mod 2N
-static int keyauto_entries(pz_module* M, int64_t* res, const int64_t* a, const double* key, const pz_glwe_op_params* p, size_t batch, int64_t a_gal) {
-    GlweCall c;
-    PZ_TRY(glwe_call_init(c, M, GlweKind::KeySwitch, res, a, key, p, batch, nullptr, nullptr, nullptr));
-    if (batch == 0) return PZ_OK;
-    const unsigned g = inv_mod_2n((long long)a_gal, c.n);
-    if (keyauto_fast_applies(c)) {
-        c.keyauto = true;
-        c.ka_p = (unsigned)((unsigned long long)a_gal & (2ull * (unsigned long long)c.n - 1ull));
-        c.ka_perm = key_perm(g, (unsigned)M->m);
-        dispatch_note(M, "key composition: key switch by the permuted key (spectral form)");
-        return glwe_fused(c);
-    }
-    // composition: phi_p of every entry into the second workspace (before anything is written: in-place calls included), then the
-    // automorphism family in mode 0 with the inverse element
-    dispatch_note(M, "key composition: automorphism + glwe_automorphism (composition)");
-    PZ_TRY(ws2_reserve(M, batch * (size_t)c.a_ct * 8));
-    int64_t* tmp = (int64_t*)M->ws2;
-    const int polys = c.s.cols_a * (int)p->a_size;
-    PolyMap pm{1, polys, c.a_ct, 0, c.n, 0};
-    PZ_TRY(launch_automorphism(M, (int)batch * polys, (const long long*)a, pm, (long long*)tmp, pm, g, AUTO_SIGN));
-    AutoSpec au{(long long)g, 0};
-    return glwe_op(M, GlweKind::Automorphism, res, tmp, key, p, batch, &au);
-}
-
-extern "C" {
-int pz_glwe_automorphism_key_automorphism_batched(pz_module* M, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, int64_t a_gal,
-                                                  const double* key_pmat, const pz_glwe_op_params* p, size_t count) {
-    // (the argument checks that need no module come first)
-    PZ_REQUIRE(p != nullptr, "null params");
-    PZ_REQUIRE((a_gal & 1) != 0, "glwe_automorphism_key_automorphism: the Galois element of the input key must be odd");
-    PZ_REQUIRE(res_dnum >= 1 && res_dnum <= a_dnum, "glwe_automorphism_key_automorphism: res has more rows than a (or none)");
-    PZ_REQUIRE(p->res_base2k == p->a_base2k, "glwe_automorphism_key_automorphism: res and a share one base2k");
-    PZ_REQUIRE(p->rank >= 1 && p->rank_out == p->rank, "glwe_automorphism_key_automorphism: the keys map rank -> rank");
-    PZ_ENTER(M);
-    PZ_REQUIRE(p->dsize >= 1 && p->dnum >= 1 && p->key_size >= 1 && p->a_size >= 1 && p->res_size >= 1, "glwe op: empty shape");
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
-    if ((const void*)res == (const void*)a)
-        PZ_REQUIRE(res_dnum == a_dnum && p->res_size == p->a_size, "in-place call with different layouts for a and res");
-    const size_t rank = p->rank, cols = rank + 1;
-    const double* key = nullptr;
-    PZ_TRY(resolve_key(M, key_pmat, (size_t)M->n * 8 * p->dnum * rank * cols * p->key_size, &key));
-    const long long a_ct = (long long)M->n * (long long)cols * (long long)p->a_size, res_ct = (long long)M->n * (long long)cols * (long long)p->res_size;
-    // rows of `a` beyond res_dnum are not computed: one call over everything when the row counts agree, else one per GGLWE
-    if (res_dnum == a_dnum || count <= 1) PZ_TRY(keyauto_entries(M, res, a, key, p, count * res_dnum * rank, a_gal));
-    else
-        for (size_t i = 0; i < count; ++i)
-            PZ_TRY(keyauto_entries(M, res + (long long)(i * res_dnum * rank) * res_ct, a + (long long)(i * a_dnum * rank) * a_ct, key, p,
-                                   res_dnum * rank, a_gal));
-    return finish_call(M, false);
-}
-
-// entries (row, 0) of `count` GGSWs through glwe_keyswitch (ggsw.rs:52-54, :80-82), then ggsw_expand_row on res
-int pz_ggsw_keyswitch_batched(pz_module* M, int64_t* res, const int64_t* a, size_t dnum, const double* key_pmat, const double* const* tsk_pmat,
-                              const pz_glwe_op_params* kp, const pz_glwe_op_params* tp, size_t count) {
-    PZ_REQUIRE(kp != nullptr && tp != nullptr && tsk_pmat != nullptr, "null params");
-    PZ_REQUIRE(dnum >= 1, "ggsw_keyswitch: empty GGSW");
-    PZ_REQUIRE(tp->rank == kp->rank_out && tp->res_size == kp->res_size && tp->res_base2k == kp->res_base2k,
-               "ggsw_keyswitch: the expansion's parameters describe res");
-    PZ_ENTER(M);
-    PZ_REQUIRE(kp->a_size >= 1 && kp->res_size >= 1 && kp->key_size >= 1 && kp->dnum >= 1, "glwe op: empty shape");
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
-    const long long n = (long long)M->n;
-    const long long a_row = n * (long long)(kp->rank + 1) * (long long)(kp->rank + 1) * (long long)kp->a_size;
-    const long long res_row = n * (long long)(kp->rank_out + 1) * (long long)(kp->rank_out + 1) * (long long)kp->res_size;
-    if ((const void*)res == (const void*)a) PZ_REQUIRE(a_row == res_row, "in-place call with different layouts for a and res");
-    const double* key = nullptr;
-    PZ_TRY(resolve_key(M, key_pmat, (size_t)n * 8 * kp->dnum * kp->rank * (kp->rank_out + 1) * kp->key_size, &key));
-    OpLayout lay{a_row, res_row, 0};
-    PZ_TRY(glwe_op(M, GlweKind::KeySwitch, res, a, key, kp, count * dnum, nullptr, &lay));
-    PZ_TRY(ggsw_expand_row(M, res, dnum, tsk_pmat, tp, count));   // (the module lock is not recursive)
-    return finish_call(M, false);
-}
-
-// entries (row, 0), row < res_dnum, of `count` GGSWs through glwe_automorphism (ggsw_ct.rs:54-56, :77-79), then ggsw_expand_row on res.  The
-// automorphism family takes packed ciphertexts: the entries are staged through a packed copy in the second workspace.
-int pz_ggsw_automorphism_batched(pz_module* M, int64_t* res, size_t res_dnum, const int64_t* a, size_t a_dnum, const double* key_pmat, int64_t gal,
-                                 const double* const* tsk_pmat, const pz_glwe_op_params* kp, const pz_glwe_op_params* tp, size_t count) {
-    PZ_REQUIRE(kp != nullptr && tp != nullptr && tsk_pmat != nullptr, "null params");
-    PZ_REQUIRE((gal & 1) != 0, "ggsw_automorphism: the Galois element must be odd");
-    PZ_REQUIRE(res_dnum >= 1 && res_dnum <= a_dnum, "ggsw_automorphism: res has more rows than a (or none)");
-    PZ_REQUIRE(kp->rank_out == kp->rank && tp->rank == kp->rank && tp->res_size == kp->res_size && tp->res_base2k == kp->res_base2k,
-               "ggsw_automorphism: rank -> rank, and the expansion's parameters describe res");
-    PZ_ENTER(M);
-    PZ_REQUIRE(kp->a_size >= 1 && kp->res_size >= 1 && kp->key_size >= 1 && kp->dnum >= 1, "glwe op: empty shape");
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && key_pmat != nullptr, "batched entry points take device pointers");
-    if ((const void*)res == (const void*)a)
-        PZ_REQUIRE(res_dnum == a_dnum && kp->res_size == kp->a_size, "in-place call with different layouts for a and res");
-    if (count == 0) return finish_call(M, false);
-    const long long n = (long long)M->n;
-    const size_t cols = kp->rank + 1;
-    const long long a_ct = n * (long long)cols * (long long)kp->a_size, res_ct = n * (long long)cols * (long long)kp->res_size;
-    const double* key = nullptr;
-    PZ_TRY(resolve_key(M, key_pmat, (size_t)n * 8 * kp->dnum * kp->rank * cols * kp->key_size, &key));
-    const size_t ent = count * res_dnum;
-    PZ_TRY(ws2_reserve(M, align256(ent * (size_t)a_ct * 8) + ent * (size_t)res_ct * 8));
-    int64_t* pa = (int64_t*)M->ws2;
-    int64_t* pr = (int64_t*)((char*)M->ws2 + align256(ent * (size_t)a_ct * 8));
-    for (size_t i = 0; i < count; ++i)
-        PZ_TRY(launch_ew(M, EW_COPY, pa + (long long)(i * res_dnum) * a_ct, a_ct, n, a + (long long)(i * a_dnum) * (long long)cols * a_ct,
-                         (long long)cols * a_ct, n, nullptr, 0, 0, (int)(cols * kp->a_size), (int)res_dnum));
-    AutoSpec au{(long long)gal, 0};
-    PZ_TRY(glwe_op(M, GlweKind::Automorphism, pr, pa, key, kp, ent, &au));
-    PZ_TRY(launch_ew(M, EW_COPY, res, (long long)cols * res_ct, n, pr, res_ct, n, nullptr, 0, 0, (int)(cols * kp->res_size), (int)ent));
-    PZ_TRY(ggsw_expand_row(M, res, res_dnum, tsk_pmat, tp, count));
-    return finish_call(M, false);
-}
-}  // extern "C"
 
 // api_lwe.hip composes the LWE <-> GLWE conversions around the batched key switch while holding the module lock
 namespace pz {
@@ -2011,7 +1118,7 @@ int glwe_keyswitch_rot_nolock(pz_module* M, int64_t* res, const int64_t* a, cons
     PZ_REQUIRE(glwe_keyswitch_rot_applies(M, p) && rot_tab != nullptr, "rotated-source key switch: shape not served");
     const OpShape s = op_shape(p, GlweKind::KeySwitch);
     const double* key = nullptr;
-    PZ_TRY(resolve_key(M, key_pmat, (size_t)M->n * 8 * p->dnum * s.cols_in * s.cols_out * p->key_size, &key));
+    PZ_TRY(resolve_key(M, key_pmat, prepared_key_bytes(M, p, s.cols_in, s.cols_out), &key));
     GlweCall c;
     PZ_TRY(glwe_call_init(c, M, GlweKind::KeySwitch, res, a, key, p, batch, nullptr, nullptr, nullptr));
     if (batch == 0) return PZ_OK;

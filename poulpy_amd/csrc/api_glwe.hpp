@@ -1,5 +1,5 @@
-// api_glwe.hpp — what the C-ABI translation units share above the launch layer: the batched GLWE product (api_glwe.hip), the composite
-// calls built on it (api_br.hip: blind rotation, circuit bootstrapping, packing) and the HIP-graph cache for launch-bound chains.
+// api_glwe.hpp — what the C-ABI translation units share above the launch layer: the HIP-graph cache for launch-bound chains and the
+// resolution of prepared keys (api.hip).  The batched GLWE product and the composite calls built on it are declared in glwe_call.hpp.
 #pragma once
 #include "api_common.hpp"
 
@@ -22,6 +22,27 @@ struct KeyHash {
 static void graph_key_module(const pz_module* M, KeyHash& k) {
     k.add(M->ws); k.add(M->ws2); k.add(M->ws_bytes); k.add(M->ws2_bytes); k.add(M->fuse_mid); k.add(M->fuse_tail); k.add(M->small_path); k.add(M->chunk);
     k.add(M->dbg_stages); k.add(M->probe); k.add(M->graph_epoch); k.add(M->w2n);
+}
+// one tag per call that replays as a graph: two calls with the same arguments never share a key
+enum GraphTag : int {
+    GRAPH_GLWE_TRACE = 1,             // api_trace.hip
+    GRAPH_BLIND_ROTATION = 2,         // api_br.hip
+    GRAPH_CIRCUIT_BOOTSTRAPPING = 3,  // api_br.hip
+    GRAPH_GLWE_BLIND_ROTATION = 7,    // api_gates.hip
+    GRAPH_BLIND_RETRIEVAL = 8,        // api_gates.hip
+    GRAPH_BDD_EXECUTE = 9,            // api_bdd.hip
+    GRAPH_FHE_UINT_PACK = 11,         // api_fhe_uint.hip
+    GRAPH_FHE_UINT_WORD = 12,         // api_fhe_uint.hip
+    GRAPH_LINCOMB_CONST = 31,         // api_lincomb.hip (builds its key by hand)
+};
+// the key of a call from its tag, the arguments that are always there, and the module's state; the caller adds what is special to it
+template <typename... Args>
+static KeyHash graph_key(const pz_module* M, GraphTag tag, const Args&... args) {
+    KeyHash k;
+    k.add((int)tag);
+    (k.add(args), ...);
+    graph_key_module(M, k);
+    return k;
 }
 static void graph_drop(pz_module::GraphEntry& e) {
     if (e.exec) (void)hipGraphExecDestroy(e.exec);
@@ -82,17 +103,6 @@ static int with_graph(pz_module* M, uint64_t key, F&& body) {
 }
 
 
-// Automorphism family on top of the key switch / strided ciphertexts: see glwe_op in api_glwe.hip
-struct AutoSpec {
-    long long p;
-    int mode;
-};
-// ciphertexts that are not tightly packed (the entries of one column of a GGSW) and a body that lands in another column
-struct OpLayout {
-    long long a_stride, res_stride;  // in i64 elements between consecutive ciphertexts
-    int body_col;
-};
-
 // api.hip: drops the device mirror of a host-resident prepared key (a rewritten buffer's mirror would be stale)
 int forget_host_key(pz_module* M, const void* host);
 void host_key_invalidate(const void* p, size_t bytes);   // api.hip: process-wide (every module's mirrors of that host range)
@@ -101,32 +111,3 @@ void host_key_invalidate(const void* p, size_t bytes);   // api.hip: process-wid
 // not need more of them at once than fit (pz_bdd_circuit_execute_batched checks before it resolves the first one)
 constexpr size_t kKeyMirrorMax = 64, kKeyMirrorBytes = (size_t)48 << 30;
 int resolve_key(pz_module* M, const double* pmat, size_t bytes, const double** out);
-
-// what a call of glwe_op computes; the values are the `keyswitch` argument of pz_glwe_op_workspace_bytes
-enum class GlweKind : int { ExternalProduct = 0, KeySwitch = 1, Automorphism = 2, TensorRelin = 3 };
-
-// Defined inside api_glwe.hip's extern "C" block (C linkage, internal use; the caller holds the module lock):
-extern "C" {
-// the batched GLWE product on device-resident data: external product, key switch, automorphism family (kind Automorphism, with au), strided
-// ciphertexts with the body landing in another column (lay), tensor relinearization
-int glwe_op(pz_module* M, GlweKind kind, int64_t* res, const int64_t* a, const double* pmat, const pz_glwe_op_params* p, size_t batch,
-            const AutoSpec* au = nullptr, const OpLayout* lay = nullptr, bool* post_rsh = nullptr);
-// post_rsh (glwe_trace): in: the caller would like the result shifted right by one bit (vec_znx_rsh_assign on every column) as it is
-// stored; out: whether the path taken did that (spectral automorphism forms on the 256 x 128 plan) - otherwise the caller shifts itself
-// glwe_trace_assign on a batch (poulpy-core glwe_trace.rs:129-176): one prepared key per step.  first_shifted (res in the keys' base,
-// nsteps >= 1): the caller has already applied the one-bit vec_znx_rsh_assign the first step opens with (k_word_pre)
-int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, const double* const* key_pmats, const pz_glwe_op_params* p,
-               size_t batch, bool first_shifted = false);
-// tensor relinearization of GLWETensors held as 16-bit digits in the fused tail's tile order (api_cnv.hip's fused multiply + relinearize)
-bool glwe_relin_t16_supported(const pz_module* M, const pz_glwe_op_params* p);
-size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch);
-int glwe_relin_t16(pz_module* M, int64_t* res, const short* a16, long long a16_cs, const double* pmat, const pz_glwe_op_params* p, size_t batch);
-// pz_bdd_circuit_execute_batched without the module lock and the closing finish_call: the argument checks that need no module (precheck; *nothing:
-// the call has no ciphertext to write), then the call itself (pz_fhe_uint_execute_batched runs both halves under one lock)
-int bdd_circuit_execute_precheck(const pz_module* M, const pz_bdd_circuit* c, const int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                                 const pz_glwe_op_params* p, size_t batch, bool* nothing);
-int bdd_circuit_execute(pz_module* M, const pz_bdd_circuit* c, int64_t* out, size_t n_out, const double* const* bits, size_t nbits,
-                        const pz_glwe_op_params* p, void* tmp, size_t tmp_bytes, size_t batch);
-// ggsw_expand_row on `count` GGSWs (conversion/gglwe_to_ggsw.rs:116-268)
-int ggsw_expand_row(pz_module* M, int64_t* ggsw, size_t dnum, const double* const* tsk_pmat, const pz_glwe_op_params* p, size_t count);
-}

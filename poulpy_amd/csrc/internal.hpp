@@ -13,14 +13,19 @@
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
 //   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp), weighted sums by constants (device_lincomb.hpp)
 //   api.hip          C ABI: module, memory, key pinning / mirrors
-//   api_glwe.hip     C ABI: the batched GLWE product (glwe_op) and its direct callers
+//   api_glwe.hip     C ABI: the batched GLWE product (glwe_op), its host-container entry path, the hoisted rotations
+//   api_ggsw.hip     C ABI: GGSW and automorphism-key composites (loops of glwe_op over matrix entries)
+//   api_gates.hip    C ABI: CMUX, blind rotation by encrypted bits, conditional swap, blind retrieval
+//   api_bdd.hip      C ABI: BDD circuit object and executor
+//   api_trace.hip    C ABI: glwe_trace, glwe_pack
+//   api_fhe_uint.hip C ABI: FheUint pack / execute and the byte operations
 //   api_hal.hip      C ABI: the per-op HalImpl methods (VecZnxDft, SVP, VMP, VecZnxBig, i64 VecZnx family)
-//   api_br.hip       C ABI: blind rotation, circuit bootstrapping, GLWE packing (composites on glwe_op; HIP-graph replay)
+//   api_br.hip       C ABI: blind rotation, circuit bootstrapping (composites on glwe_op; HIP-graph replay)
 //   api_cnv.hip      C ABI: convolution family, GLWE tensoring, batched i64 family
 //   api_lincomb.hip  C ABI: weighted sums of GLWE batches by constants
 //   api_lwe.hip      C ABI: LWE glue of the gate bootstrap (+ its index kernels)
 //   api_dist.hip     C ABI: RCCL key broadcast (dlopen)
-//   api_common.hpp / api_glwe.hpp   what those share (staging, graph cache, glwe_op / glwe_trace / ggsw_expand_row)
+//   api_common.hpp / api_glwe.hpp / glwe_call.hpp   what those share (staging and argument checks; graph cache; GlweCall, glwe_op / glwe_trace / ...)
 //
 // Every kernel is instantiated in exactly one translation unit (the one that launches it), so the units compile
 // independently and in parallel; only plain functions cross unit boundaries.
@@ -176,7 +181,7 @@ constexpr size_t kMidDummyBytes = (size_t)256 * 64 * 128 * sizeof(cplx) + (1 << 
 bool mid_supported(const pz_module* M, int npi, int npo);
 int launch_permute_pmat(pz_module* M, const double* P, cplx* Pp, int npolys);
 // the row-sliced copy of phi_g(key), g odd: spectrum index q' of the copy reads index (mul q' + add) mod m of the key, conjugated if conj
-// (m2 = 128 plans; key_perm in api_glwe.hip derives the map from g)
+// (m2 = 128 plans; key_perm in api_ggsw.hip derives the map from g)
 struct KeyPerm { unsigned mul = 1, add = 0; bool conj = false; };
 int launch_permute_pmat_gal(pz_module* M, const double* P, cplx* Pp, int npolys, const KeyPerm& kp);
 // mul != 0: spectrum permutation of X -> X^p folded into the middle kernel (m2 = 128 plans only; see MidArgs and spectral_perm in api_glwe.hip);

@@ -193,7 +193,7 @@ struct pz_module {
     // API call returns (canary_verify, from PZ_ENTER's scope object).  An overrun into the slack between segments stays bit-exact
     // and therefore invisible to the parity tests (the spectral automorphism's body operand).
     std::vector<void*> guards;
-    // device copies of the level tables of the BDD circuits this module has run (api_glwe.hip, pz_bdd_circuit_execute_batched): found by the circuit's
+    // device copies of the level tables of the BDD circuits this module has run (api_bdd.hip, pz_bdd_circuit_execute_batched): found by the circuit's
     // id, never by its address - the handle may be freed and its address reused; freed with the module, the least recently used one beyond 16
     struct BddTables { uint64_t uid; void* gates; void* level_start; uint64_t stamp; };
     std::vector<BddTables> bdd_tables;

@@ -42,6 +42,23 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.pz_abi_version() == PZ_ABI_VERSION
 
 
+def test_library_defines_no_unprefixed_c_symbol(lib):
+    """Every defined dynamic symbol is part of the ABI (pz_*), a mangled C++ name, or one of the toolchain's own markers: an internal
+    function with C linkage (glwe_op, ...) would collide with any other library of the process that exports the same name."""
+    import shutil
+    import subprocess
+    path = lib._name
+    if not os.path.exists(path):
+        pytest.skip("the library is not built")
+    if shutil.which("nm") is None:
+        pytest.skip("nm is not installed")
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert len([n for n in names if n.startswith("pz_")]) >= len(_declared_symbols())
+    stray = sorted(n for n in names if not (n.startswith("pz_") or n.startswith("_Z") or n.startswith("__hip_cuid_")))
+    assert not stray, f"defined with C linkage outside the pz_ prefix: {stray}"
+
+
 def _expected_ctype(ctype, ret=False):
     """the fixed C -> ctypes mapping of the binding (poulpy_amd/abi.py), restated"""
     from poulpy_amd import abi
