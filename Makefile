@@ -59,14 +59,19 @@ cpp-test-word:
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_word_ops.cpp $(CSRC)/word_ops.cpp -o tests/cpp/test_word_ops
 	tests/cpp/test_word_ops
 
+# host-only check of the middle-kernel and block-step form choice under the host sanitizers (tests/test_mid_forms_host.py builds and runs the same program)
+cpp-test-mid:
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_mid_forms.cpp -o tests/cpp/test_mid_forms
+	tests/cpp/test_mid_forms tests/golden/mid128_forms.txt
+
 # the per-coefficient walk of k_lincomb_const on the host under the host sanitizers; it reads its cases from a file that
 # tests/test_ckks_lincomb_host.py writes from the oracle (that test builds and runs the same program)
 tests/cpp/test_lincomb_walk: tests/cpp/test_lincomb_walk.cpp $(wildcard $(CSRC)/*.hpp)
 	$(HIPCC) -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -I $(CSRC) -I include $< -o $@ -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined
 
 clean:
-	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_lincomb_walk
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_mid_forms tests/cpp/test_lincomb_walk
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 
-.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack cpp-test-word kres test-cpu test-gpu bench clean
+.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack cpp-test-word cpp-test-mid kres test-cpu test-gpu bench clean

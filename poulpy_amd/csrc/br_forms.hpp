@@ -1,13 +1,48 @@
-// br_forms.hpp — the instantiations of the one-kernel blind rotation (k_br_fused, device_br.hpp) and the choice among them.  Included by two
-// translation units: launch_br.hip instantiates the product forms, launch_br_probe.hip the same forms with the rounding-margin probe compiled
-// in (a run-time test in the carry phase cost the reference's bench shape 5 %, profiles/r05_ab_br_probe.txt).
+// br_forms.hpp — the instantiations of the blind-rotation kernels and the choice among them: the fused block step of the composed path
+// (k_br_block / k_br_block_lds, device_br_ops.hpp) and the one-kernel rotation (k_br_fused, device_br.hpp).  The block-step part is plain C++
+// (tests/cpp/test_mid_forms.cpp sweeps it with the host compiler); the rest needs the HIP compiler.  Included by two translation units:
+// launch_br.hip instantiates the product forms, launch_br_probe.hip the one-kernel forms with the rounding-margin probe compiled in (a
+// run-time test in the carry phase cost the reference's bench shape 5 %, profiles/r05_ab_br_probe.txt).
 //
-// Forms (round 5: the census of what the GPU suite and every bench shape dispatch, tools/dbg/dispatch_census.sh, instead of the full cross
-// product of round 4 - 80 instantiations, 54 of them spilling, 14 ever dispatched):  rows x output-column groups (MR, CG) in {(4, 4), (6, 3)};
+// One-kernel forms (round 5: the census of what the GPU suite and every bench shape dispatch instead of the full cross product of round 4 -
+// 80 instantiations, 54 of them spilling, 14 ever dispatched):  rows x output-column groups (MR, CG) in {(4, 4), (6, 3)};
 // PJ = 2 product jobs per thread only where m * ceil(ncols / CG) > 512 can happen (m = 512); two ciphertexts per workgroup (CT = 2, with 64-
 // or 32-bit accumulators) for m >= 256; execute_standard (STD, block size 1) with one ciphertext.  A shape outside this list - more than 6
 // key rows, 7 - 8 output polynomials with 5 - 6 rows - runs the composed path (block step + transforms), which covers every shape.
 #pragma once
+#ifndef PZ_BRL_94
+#define PZ_BRL_94 1   // rank 2 (9 rows, 12 columns): three column groups of 4 instead of four of 3 - 21 stages instead of 28, 5.36 -> 5.22 ms per 82 block steps (profiles/r05_ab_brl94.txt)
+#endif
+
+namespace pz {
+
+// ---- the block step: (key rows kept in registers, output columns per workgroup) ------------------------------------------------------------
+struct BrBlockForm { int mr, cg; };
+// (MR, CG) of k_br_block_lds (keys staged in LDS: rings with m % 64 == 0) and of k_br_block (the others)
+#define PZ_BR_BLOCK_LDS_FORMS(X) X(12, 2) X(9, 3) X(9, 4) X(6, 3) X(8, 3) X(4, 4) X(8, 4)
+#define PZ_BR_BLOCK_FORMS(X) X(12, 2) X(9, 3) X(6, 3) X(8, 3) X(4, 4) X(8, 4)
+
+inline bool br_block_form_exists(const BrBlockForm& f, bool use_lds) {
+#define X(MR_, CG_) if (f.mr == MR_ && f.cg == CG_) return true;
+    if (use_lds) { PZ_BR_BLOCK_LDS_FORMS(X) }
+    else { PZ_BR_BLOCK_FORMS(X) }
+#undef X
+    return false;
+}
+// rank 2 with 3-4 decomposition rows (the circuit-bootstrapping shape) has 9 or 12 inputs, so fewer columns per workgroup there.
+// {0, 0}: the kernel of this use_lds has no instantiation of the form the shape asks for - the caller's composed loop runs instead
+inline BrBlockForm br_block_form(int row_max, int ncols, bool use_lds) {
+    BrBlockForm f;
+    if (row_max > 9 || (row_max > 8 && ncols % 3 != 0)) f = {12, 2};
+    else if (row_max > 8) f = {9, (ncols % 4 == 0 && PZ_BRL_94) ? 4 : 3};
+    else if (ncols % 3 == 0 && ncols % 4 != 0) f = {row_max <= 6 ? 6 : 8, 3};   // 3, 6 columns: groups of 3
+    else f = {row_max <= 4 ? 4 : 8, 4};
+    return br_block_form_exists(f, use_lds) ? f : BrBlockForm{0, 0};
+}
+
+}  // namespace pz
+
+#ifdef __HIPCC__
 #include <algorithm>
 
 #include "internal.hpp"
@@ -156,3 +191,4 @@ static int br_fused_launch(pz_module* M, const BrFusedArgs& g, const BrFusedPlan
 int br_fused_launch_probe(pz_module* M, const BrFusedArgs& g, const BrFusedPlan& pl);
 
 }  // namespace pz
+#endif  // __HIPCC__

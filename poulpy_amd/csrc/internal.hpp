@@ -3,13 +3,15 @@
 //   launch_fft.hip   the four passes of the two-pass negacyclic FFT (device_fft.hpp)
 //   launch_tail.hip  fused inverse column pass + carry chain (k_inv_tail)
 //   launch_mid.hip   fused row pass + VMP + inverse row pass (device_mid.hpp), key re-slicing
+//   mid_forms.hpp    which k_mid128 / k_mid128r instantiation a shape gets, and the list of them (plain C++, no HIP; launch_mid.hip walks it)
 //   launch_small.hip small-ring pipelines for N = 1024 / 2048 / 4096: whole polynomials in LDS (device_small.hpp, device_small_one.hpp)
 //   launch_bdd.hip   the BDD evaluator's gather table and the gathered forms of the small-ring CMUX kernels
 //   bdd_schedule.cpp the BDD circuit compiler (plain C++, no HIP)
 //   pack_levels.cpp  the level map of FheUint::pack (plain C++, no HIP)
 //   word_ops.cpp     the stage plan of the FheUint byte operations (plain C++, no HIP)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
-//   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_ops.hpp)
+//   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_br_ops.hpp)
+//   tail_forms.hpp / br_forms.hpp   the same for the fused tail and for the blind rotation (one-kernel forms; block-step forms in plain C++)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
 //   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp), weighted sums by constants (device_lincomb.hpp)
 //   api.hip          C ABI: module, memory, key pinning / mirrors

@@ -9,9 +9,6 @@
 #include "device_br.hpp"
 #include "device_br_ops.hpp"
 #include "br_forms.hpp"
-#ifndef PZ_BRL_94
-#define PZ_BRL_94 1   // rank 2 (9 rows, 12 columns): three column groups of 4 instead of four of 3 - 21 stages instead of 28, 5.36 -> 5.22 ms per 82 block steps (profiles/r05_ab_brl94.txt)
-#endif
 
 namespace pz {
 
@@ -41,53 +38,44 @@ int br_block_step(pz_module* M, const double* acc_dft, long long a_bs, double* a
                   bool* launched_out) {
     *launched_out = false;
     if (!(row_max <= 12 && blk <= 64)) return PZ_OK;
-                // zero + block_size x (vmp, svp, add, sub) in one kernel, nothing but acc_add written (:321-337)
-                BrBlockArgs g;
-                g.acc_dft = (const cplx*)acc_dft; g.acc_add = (cplx*)acc_add; g.a_bs = a_bs / 2; g.o_bs = o_bs / 2;
-                g.brk = (const cplx*)brk; g.key_stride = (long long)(pmat_doubles / 2);
-                g.row_max = row_max; g.ncols = ncols; g.m = (int)M->m; g.batch = B; g.i0 = i0; g.blk = blk;
-                g.lwe = (const long long*)lwe_2n; g.lwe_bs = lwe_bs; g.w2n = M->w2n;
-                g.gx = g.gy = g.gz = 1; g.xcd = 0; g.allcg = 0;
-                constexpr int CT = 2;
-                KTimer kt(M, PZ_K_VMP);
-                const int nc = ncols;
-                const unsigned gx = (unsigned)((B + CT - 1) / CT), gy = (unsigned)((M->m + 255) / 256);
-                // (input polynomials kept in registers, output columns per workgroup): rank 2 with 3-4 decomposition rows (the
-                // circuit-bootstrapping shape) has 9 or 12 inputs, so fewer columns per workgroup there
-                int mr, cgs;
-                if (row_max > 9 || (row_max > 8 && nc % 3 != 0)) { mr = 12; cgs = 2; }
-                else if (row_max > 8) { mr = 9; cgs = (nc % 4 == 0 && PZ_BRL_94) ? 4 : 3; }
-                else if (nc % 3 == 0 && nc % 4 != 0) { mr = row_max <= 6 ? 6 : 8; cgs = 3; }   // 3, 6 columns: groups of 3
-                else { mr = row_max <= 4 ? 4 : 8; cgs = 4; }
-                const int ngroups = (nc + cgs - 1) / cgs;
-                // keys staged in LDS once per 4 waves x 2 ciphertexts (k_br_block_lds) wherever m % 64 == 0
-                // (four ciphertexts per wave for <= 6 inputs - every staged key value serving 16 ciphertexts instead of 8, at 256 registers -
-                //  measured slower at N = 2048: 11.06 vs 9.68 ms per 82 block steps)
-                const bool use_lds = M->m % 64 == 0;
-                bool launched = false;
-                if (use_lds) {
-                    g.gx = (B + 7) / 8; g.gy = (int)(M->m / 64); g.gz = ngroups;
-                    g.allcg = 1;   // (one workgroup per tile and column group, placed by XCD, was 2-3 % slower: NOTEBOOK.md section 4)
-                    const unsigned total = (unsigned)(g.gx * g.gy);
-#define PZ_BRB(MR_, CG_)                                                                                           \
-    if (!launched && mr == MR_ && cgs == CG_) {                                                                    \
+    // keys staged in LDS once per 4 waves x 2 ciphertexts (k_br_block_lds) wherever m % 64 == 0
+    // (four ciphertexts per wave for <= 6 inputs - every staged key value serving 16 ciphertexts instead of 8, at 256 registers -
+    //  measured slower at N = 2048: 11.06 vs 9.68 ms per 82 block steps)
+    const bool use_lds = M->m % 64 == 0;
+    const BrBlockForm f = br_block_form(row_max, ncols, use_lds);
+    if (f.mr == 0) return PZ_OK;   // no instantiation: the caller's composed loop
+    // zero + block_size x (vmp, svp, add, sub) in one kernel, nothing but acc_add written (:321-337)
+    BrBlockArgs g;
+    g.acc_dft = (const cplx*)acc_dft; g.acc_add = (cplx*)acc_add; g.a_bs = a_bs / 2; g.o_bs = o_bs / 2;
+    g.brk = (const cplx*)brk; g.key_stride = (long long)(pmat_doubles / 2);
+    g.row_max = row_max; g.ncols = ncols; g.m = (int)M->m; g.batch = B; g.i0 = i0; g.blk = blk;
+    g.lwe = (const long long*)lwe_2n; g.lwe_bs = lwe_bs; g.w2n = M->w2n;
+    g.gx = g.gy = g.gz = 1; g.xcd = 0; g.allcg = 0;
+    constexpr int CT = 2;
+    KTimer kt(M, PZ_K_VMP);
+    const int ngroups = (ncols + f.cg - 1) / f.cg;
+    if (use_lds) {
+        g.gx = (B + 7) / 8; g.gy = (int)(M->m / 64); g.gz = ngroups;
+        g.allcg = 1;   // (one workgroup per tile and column group, placed by XCD, was 2-3 % slower: NOTEBOOK.md section 4)
+        const unsigned total = (unsigned)(g.gx * g.gy);
+#define X(MR_, CG_)                                                                                                \
+    if (f.mr == MR_ && f.cg == CG_) {                                                                              \
         hipLaunchKernelGGL((k_br_block_lds<2, MR_, CG_>), dim3(total), dim3(256), 0, M->stream, g);                \
         dispatch_note(M, "k_br_block_lds<2,MR=%d,CG=%d> (8 ciphertexts per staged key value)", MR_, CG_);          \
-        launched = true;                                                                                           \
     }
-                    PZ_BRB(12, 2) PZ_BRB(9, 3) PZ_BRB(9, 4) PZ_BRB(6, 3) PZ_BRB(8, 3) PZ_BRB(4, 4) PZ_BRB(8, 4)
-#undef PZ_BRB
-                } else {
-#define PZ_BRB(MR_, CG_)                                                                                           \
-    if (!launched && mr == MR_ && cgs == CG_) {                                                                    \
+        PZ_BR_BLOCK_LDS_FORMS(X)
+#undef X
+    } else {
+        const unsigned gx = (unsigned)((B + CT - 1) / CT), gy = (unsigned)((M->m + 255) / 256);
+#define X(MR_, CG_)                                                                                                \
+    if (f.mr == MR_ && f.cg == CG_) {                                                                              \
         hipLaunchKernelGGL((k_br_block<CT, MR_, CG_>), dim3(gx, gy, (unsigned)ngroups), dim3(256), 0, M->stream, g); \
         dispatch_note(M, "k_br_block<2,MR=%d,CG=%d>", MR_, CG_);                                                    \
-        launched = true;                                                                                           \
     }
-                    PZ_BRB(12, 2) PZ_BRB(9, 3) PZ_BRB(6, 3) PZ_BRB(8, 3) PZ_BRB(4, 4) PZ_BRB(8, 4)
-#undef PZ_BRB
-                }
-                PZ_HIP(hipGetLastError());
+        PZ_BR_BLOCK_FORMS(X)
+#undef X
+    }
+    PZ_HIP(hipGetLastError());
     *launched_out = true;
     return PZ_OK;
 }

@@ -6,6 +6,7 @@
 
 #include "internal.hpp"
 #include "device_mid.hpp"
+#include "mid_forms.hpp"
 
 namespace pz {
 
@@ -50,108 +51,44 @@ static int launch_mid256(pz_module* M, MidArgs g, int batch) {
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }
-// m2 = 128 plans: the persistent tile kernels k_mid128 / k_mid128r - which instantiation for this shape (tile geometry by the polynomials in and
-// out, the product form: plain / permuted / digit-selected / CGGI block step)
+// one launch of the instantiation `f` names (mid_forms.hpp): tile count, LDS bytes and grid follow from its (ct, np)
+static int mid128_launch_form(pz_module* M, MidArgs& g, int batch, int ncu, const Mid128Form& f) {
+    g.n_ct = (batch + f.ct - 1) / f.ct;
+    const size_t lds = ((size_t)f.ct * f.np * kMidRS + 384 + 32) * sizeof(cplx);   // tile | wL2 | two twiddle rows | exponents
+    const dim3 grid(std::min({ncu, 256, g.m1 * g.n_ct}));   // <= 256: one scratch tile per workgroup (kMidDummyBytes)
+    char note[160];
+    mid128_note(f, PZ_MIDR_KR, note, sizeof note);
+    if (f.ring) {
+#define X(CT_, NP_, PERM_, NR_, HALFIN_, DS_, C2_)                                                                           \
+    if (f.ct == CT_ && f.np == NP_ && f.perm == PERM_ && f.nr == NR_ && f.halfin == HALFIN_ && f.ds == DS_ && f.c2 == C2_) {  \
+        PZ_TRY(launch_k((k_mid128r<CT_, NP_, PERM_, NR_, HALFIN_, (NP_ == 32 ? 3 : PZ_MIDR_KR), DS_, C2_>), grid, dim3(512), lds, M->stream, g)); \
+        dispatch_note(M, "%s", note);                                                                                        \
+        return PZ_OK;                                                                                                        \
+    }
+        PZ_MID128R_FORMS(X)
+#undef X
+    } else {
+#define X(CT_, NP_, PERM_, DS_, BR_, SKIPW_, BRNEST_, NCO_)                                                                  \
+    if (f.ct == CT_ && f.np == NP_ && f.perm == PERM_ && f.ds == DS_ && f.br == BR_ && f.skipw == SKIPW_ && f.brnest == BRNEST_ && f.nco == NCO_) { \
+        PZ_TRY(launch_k((k_mid128<CT_, NP_, PERM_, DS_, BR_, SKIPW_, BRNEST_, NCO_>), grid, dim3(512), lds, M->stream, g));   \
+        dispatch_note(M, "%s", note);                                                                                        \
+        return PZ_OK;                                                                                                        \
+    }
+        PZ_MID128_FORMS(X)
+#undef X
+    }
+    return fail(PZ_ERR_UNSUPPORTED, "launch_mid: no instantiation of %s", note);
+}
+// m2 = 128 plans: the persistent tile kernels k_mid128 / k_mid128r, in the instantiation mid128_form chooses for this shape
 static int launch_mid128(pz_module* M, MidArgs& g, int batch, int npi, int npo, bool perm, bool ds, bool br) {
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, M->device);
     static const bool mid_r = (rt_knob("POULPY_DBG_MID_R", 1) != 0);   // 0: k_mid128 (the kernel of rounds 1-2) instead of k_mid128r (A/B)
+    Mid128Shape s;
+    s.npi = npi; s.npo = npo; s.row_max = g.row_max; s.ncols = g.ncols; s.ncomp = g.ncomp; s.ds_n = g.ds_n; s.br_rm = g.br_rm;
+    s.perm = perm; s.ds = ds; s.br = br; s.mid_r = mid_r;
     KTimer kt(M, PZ_K_FUSED_MID);
-#define PZ_MID128_GO(CT_, NP_, PERM_, SKIPW_)                                                                              \
-{                                                                                                                      \
-    PZ_TRY(launch_k((k_mid128<CT_, NP_, PERM_, false, false, ((SKIPW_) && (NP_ > 8))>), grid_, dim3(512), lds, M->stream, g)); \
-    dispatch_note(M, "k_mid128<CT=%d,NP=%d,PERM=%d,DS=0,BR=0,SKIPW=%d>", CT_, NP_, (int)(PERM_), (int)((SKIPW_) && (NP_ > 8))); \
-}
-#define PZ_MID128_GOR1(CT_, NP_, PERM_, NR_, HALF_)                                                                        \
-{                                                                                                                      \
-    PZ_TRY(launch_k((k_mid128r<CT_, NP_, PERM_, NR_, ((HALF_) && (NP_ >= 16))>), grid_, dim3(512), lds, M->stream, g)); \
-    dispatch_note(M, "k_mid128r<CT=%d,NP=%d,PERM=%d,NR=%d,HALFIN=%d,KR=%d>", CT_, NP_, (int)(PERM_), NR_, (int)((HALF_) && (NP_ >= 16)), NP_ == 32 ? 3 : PZ_MIDR_KR); \
-}
-/* k_mid128r: product rows = NP (no idle waves) or NP / 2 with the upper half of the slots without input (key switch) */ \
-/* or, 8-slot tile, 8 rows                                                                                             */
-#define PZ_MID128_GOR(CT_, NP_, PERM_)                                                                                     \
-{                                                                                                                      \
-    if (g.row_max == NP_) PZ_MID128_GOR1(CT_, NP_, PERM_, NP_, false)                                                  \
-    else if (NP_ >= 16 && npi <= NP_ / 2) PZ_MID128_GOR1(CT_, NP_, PERM_, ((NP_ >= 16) ? NP_ / 2 : NP_), true)          \
-    else PZ_MID128_GOR1(CT_, NP_, PERM_, ((NP_ >= 16) ? NP_ / 2 : NP_), false)                                         \
-}
-/* plain product: the interleaved kernel k_mid128r where it applies — 8 or 16 product rows, no idle waves or exactly the upper half */ \
-/* of a 16-slot tile without input (key switch) — k_mid128 otherwise                                                            */
-#define PZ_MID128_PICK(CT_, NP_, perm_, skipw_, ring_)                                                                     \
-if (ring_ && (!(skipw_) || (NP_ >= 16 && npi <= NP_ / 2 && npo > NP_ / 2))) {                                                      \
-    if (perm_) PZ_MID128_GOR(CT_, NP_, true) else PZ_MID128_GOR(CT_, NP_, false)                                       \
-} else {                                                                                                               \
-    if (perm_) { if (skipw_) PZ_MID128_GO(CT_, NP_, true, true) else PZ_MID128_GO(CT_, NP_, true, false) }             \
-    else       { if (skipw_) PZ_MID128_GO(CT_, NP_, false, true) else PZ_MID128_GO(CT_, NP_, false, false) }           \
-}
-#define PZ_MID128_LAUNCH(CT_, NP_)                                                                                         \
-{                                                                                                                      \
-    g.n_ct = (batch + CT_ - 1) / CT_;                                                                                  \
-    const size_t lds = ((size_t)CT_ * NP_ * kMidRS + 384 + 32) * sizeof(cplx);   /* tile | wL2 | two twiddle rows | exponents */                                         \
-    const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));   /* <= 256: one scratch tile per workgroup (kMidDummyBytes) */ \
-    if (br && NP_ == 8 && (g.br_rm & 1) == 0 && g.ncomp == 6 && npi <= 6) {   /* six output columns in an 8-slot tile: 2 x 3 per thread */ \
-        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true, false, (NP_ == 8 ? 2 : 0), (NP_ == 8 ? 3 : 0)>), grid_, dim3(512), lds, M->stream, g)); \
-        dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1,BRNEST=2,NCO=3> (%d ciphertexts per key value)", CT_, NP_, CT_);   \
-    } else if (br && NP_ < 32 && (g.br_rm & 1) == 0) {   /* an even number of key rows per coefficient: the nested form of the product loop */ \
-        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true, false, (NP_ < 32 ? 2 : 0)>), grid_, dim3(512), lds, M->stream, g)); \
-        dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1,BRNEST=2> (%d ciphertexts per key value)", CT_, NP_, CT_);         \
-    } else if (br) {                                                                                                   \
-        PZ_TRY(launch_k((k_mid128<CT_, NP_, false, false, true>), grid_, dim3(512), lds, M->stream, g)); \
-        dispatch_note(M, "k_mid128<CT=%d,NP=%d,BR=1> (%d ciphertexts per key value)", CT_, NP_, CT_);                  \
-    } else if (ds) {                                                                                                          \
-        /* 16-slot tile with 16 terms on 16 inputs (external product) or 8 terms on <= 8 inputs (key switch): k_mid128r */     \
-        bool done_ = false;                                                                                            \
-        if constexpr (CT_ == 4 && NP_ == 16) {                                                                         \
-            if (mid_r && g.ds_n == 16 && npi == 16) {                                                                  \
-                PZ_TRY(launch_k((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g)); \
-                dispatch_note(M, "k_mid128r<CT=4,NP=16,NR=16,HALFIN=0,KR=%d,DS=1>", PZ_MIDR_KR);                       \
-                done_ = true;                                                                                          \
-            } else if (mid_r && g.ds_n == 8 && npi <= 8 && npo > 8) {                                                  \
-                PZ_TRY(launch_k((k_mid128r<4, 16, false, 8, true, PZ_MIDR_KR, true>), grid_, dim3(512), lds, M->stream, g)); \
-                dispatch_note(M, "k_mid128r<CT=4,NP=16,NR=8,HALFIN=1,KR=%d,DS=1>", PZ_MIDR_KR);                        \
-                done_ = true;                                                                                          \
-            }                                                                                                          \
-        }                                                                                                              \
-        if (!done_) {                                                                                                  \
-            PZ_TRY(launch_k((k_mid128<CT_, NP_, false, true>), grid_, dim3(512), lds, M->stream, g)); \
-            dispatch_note(M, "k_mid128<CT=%d,NP=%d,DS=1>", CT_, NP_);                                                  \
-        }                                                                                                              \
-    } else {                                                                                                           \
-        const bool skipw_ = NP_ > 8 && (npi <= NP_ - 8 || npo <= NP_ - 8);   /* shapes with idle waves */              \
-        const bool ring_ = mid_r && (g.row_max == NP_ || (NP_ >= 16 && g.row_max == NP_ / 2));   /* product rows k_mid128r is built for */                      \
-        PZ_MID128_PICK(CT_, NP_, perm, skipw_, ring_)                                                                  \
-    }                                                                                                                  \
-}
-    // 16 polynomials in, 32 = 16 limbs x 2 columns out, 16 key rows of 32 columns (rank-1 key switch / automorphism / relinearization at 16 limbs:
-    // BASELINE configs[4]): 4 ciphertexts per tile and the two output columns as two passes over the same inputs - every key value serves 4
-    // ciphertexts instead of the 32-slot tile's 2 (k_mid128r<.., C2>; profiles/r06_ab_mid_c2.txt)
-    if (mid_r && !br && !ds && npi == 16 && npo == 32 && g.row_max == 16 && g.ncols == 32 && g.ncomp == 32) {
-        g.n_ct = (batch + 3) / 4;
-        const size_t lds = ((size_t)4 * 16 * kMidRS + 384 + 32) * sizeof(cplx);
-        const dim3 grid_(std::min({ncu, 256, g.m1 * g.n_ct}));
-        if (perm) {
-            PZ_TRY(launch_k((k_mid128r<4, 16, true, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g));
-        } else {
-            PZ_TRY(launch_k((k_mid128r<4, 16, false, 16, false, PZ_MIDR_KR, false, true>), grid_, dim3(512), lds, M->stream, g));
-        }
-        dispatch_note(M, "k_mid128r<CT=4,NP=16,PERM=%d,NR=16,HALFIN=0,KR=%d,C2=1> (two output-column passes per tile of 4 ciphertexts)", (int)perm, PZ_MIDR_KR);
-        PZ_HIP(hipGetLastError());
-        return PZ_OK;
-    }
-    if (npi <= 8 && npo <= 8) {
-        // <= 8 polynomials in and out (e.g. rank 1 with 4 limbs, BASELINE configs[1]): 8 ciphertexts x 8 slots per tile
-        PZ_MID128_LAUNCH(8, 8)
-    } else if (npi > 16 || npo > 16) {
-        // 17..32 polynomials in or out (rank 2-3 with 8 limbs, rank 1 with 16 limbs): 2 ciphertexts x 32 slots per tile
-        PZ_MID128_LAUNCH(2, 32)
-    } else {
-        PZ_MID128_LAUNCH(4, 16)
-    }
-#undef PZ_MID128_LAUNCH
-#undef PZ_MID128_PICK
-#undef PZ_MID128_GO
-#undef PZ_MID128_GOR
-#undef PZ_MID128_GOR1
+    PZ_TRY(mid128_launch_form(M, g, batch, ncu, mid128_form(s)));
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }

@@ -752,6 +752,32 @@ def test_blind_rotation_shapes(mods):
         assert np.array_equal(got, want), (n, rank, n_lwe, blk, dnum, bsz, rsz, k, batch)
 
 
+def test_blind_rotation_block_step_without_a_form_runs_the_composed_loop(mods):
+    """N = 64, rank 2, dnum 3, 4 key limbs: 9 key rows and 12 columns ask the block step for (MR, CG) = (9, 4), which only the LDS kernel
+    (rings with m % 64 == 0) is built for - br_block_form reports no form and the composed loop computes the block; bit-exact with the
+    default switches and with fusion off, and no block-step kernel in the notes."""
+    n, shape = 64, (2, 4, 2, 3, 4, 3, 12)
+    ref, hip = mods(n)
+    out = {}
+    hip.dispatch_notes(reset=True)
+    got, want = _run_blind_rotation(hip, ref, n, *shape, batch=3, seed=6409, out=out)
+    assert np.array_equal(got, want)
+    assert "k_br_block" not in out["notes"], out["notes"]
+    got2, _ = _run_blind_rotation(hip, ref, n, *shape, batch=3, seed=6409, fuse=(False, False))
+    assert np.array_equal(got2, want)
+
+
+def test_blind_rotation_block_step_without_lds_still_launches(mods):
+    """N = 64, rank 1, dnum 2, 2 key limbs: 4 key rows, 4 columns - k_br_block<2,4,4> from the list of the rings without the LDS kernel."""
+    n = 64
+    ref, hip = mods(n)
+    out = {}
+    hip.dispatch_notes(reset=True)
+    got, want = _run_blind_rotation(hip, ref, n, 1, 4, 2, 2, 2, 2, 12, batch=3, seed=6404, out=out)
+    assert np.array_equal(got, want)
+    assert "k_br_block<2,MR=4,CG=4>" in out["notes"], out["notes"]
+
+
 @pytest.mark.parametrize("block_size", [1, 7])
 def test_reference_blind_rotation_test_shape(mods, block_size):
     """the shape of poulpy-bin-fhe's own blind-rotation tests (blind_rotation/tests/fft64_ref.rs:24-35 `standard` / `block_binary`,
