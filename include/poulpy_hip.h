@@ -687,6 +687,28 @@ int pz_glwe_lincomb_const_batched(pz_module* m, int64_t* res, size_t rank, size_
                                   const int64_t* const* im, const size_t* b_size, const int* join, const size_t* k, const int* sign, size_t nterms,
                                   int init, int normalize, size_t batch);
 
+/* Normalized signed sum of up to 64 device-resident ciphertext batches, one pass over HBM: poulpy-ckks's ckks_add_many
+ * (leveled/delegates/composite.rs:63-93) and the join of its dot products (accumulate_unnormalized, :478-506; the mapping is
+ * poulpy_amd/ckks.py and DESIGN.md 4.6e).  res = batch GLWEs VecZnx(res_cols, res_size) at base2k, overwritten with the digits of this
+ * chain on a zero container acc of res_size limbs.  Term t, in order, with a = operands[t] (batch GLWEs VecZnx(res_cols, a_size[t]) back
+ * to back, or one when shared[t]) and sign[t] = +1 / -1:
+ *   PZ_JOIN_PLAIN     acc +- a: limbs as stored, 0 past a_size, the first res_size limbs of a longer operand (vec_znx_add_assign /
+ *                     sub_assign); k[t] must be 0
+ *   PZ_JOIN_LSH_TERM  glwe_lsh_add / glwe_lsh_sub of a by k[t] bits (term 0 of an add_many: glwe_lsh into the zero container)
+ *   PZ_JOIN_LSH_ACC   glwe_lsh_assign(acc, k[t]) on the un-normalized running sum, then acc +- a
+ * then glwe_normalize_assign, always (the un-normalized forms keep pz_glwe_combine_batched).  Bit-identical to that chain on every input
+ * on which none of its steps overflows i64.  Every array has nterms entries.
+ * PZ_ERR_INVALID: nterms = 0 or nterms > 2^(63 - base2k) (ensure_accumulation_fits, composite.rs:43-51), sizes or shifts out of range,
+ * k != 0 on a plain join.  PZ_ERR_UNSUPPORTED: more than 64 terms.  PZ_ERR_ALIAS: an operand that overlaps res, unless it is term 0 and
+ * IS res (same pointer, a_size = res_size, not shared: the partial sum a chunked dot product continues from).  Where a shift - term 0's
+ * own or a later PZ_JOIN_LSH_ACC - moves that in-place term by a limb or more, its limbs are staged in the thread's LDS slice, 32 limbs at
+ * the most; a longer one is refused with PZ_ERR_ALIAS (pz_glwe_combine_batched has the same limit for an in-place shift: sum into another
+ * container instead).
+ * Nothing is launched on a refusal.  Device pointers, 16-byte aligned.  No workspace; one launch, a kernel node: the term plans travel in
+ * the kernel's arguments. */
+int pz_glwe_sum_batched(pz_module* m, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                        const int* shared, const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch);
+
 /* BlindRotationExecute<CGGI>::blind_rotation_execute (poulpy-bin-fhe/src/blind_rotation/algorithms/cggi/algorithm.rs:76-118)
  * on `batch` LWE ciphertexts that share the lookup table and the prepared blind-rotation key:
  *   block_size > 1 : execute_block_binary  (:265-368)       block_size == 1 : execute_standard (:370-440)

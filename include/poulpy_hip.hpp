@@ -404,6 +404,11 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                                             nterms, init, normalize ? 1 : 0, batch),
               "glwe_lincomb_const_batched");
     }
+    // res = normalize(sum_t +- join_t(operands[t])) in one pass, up to 64 terms; every array has nterms entries (poulpy_hip.h)
+    void glwe_sum_batched(int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands, const int* shared,
+                          const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch) {
+        check(pz_glwe_sum_batched(m_, res, res_cols, res_size, base2k, operands, shared, a_size, join, k, sign, nterms, batch), "glwe_sum_batched");
+    }
 
   private:
     pz_module* m_ = nullptr;

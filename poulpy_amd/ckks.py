@@ -11,6 +11,10 @@ flag, new metadata) without touching a device; `Plan.launch` issues the call.  A
 Products and weighted sums by constants (mul.rs:342-415; leveled/delegates/composite.rs mul_add_pt_const / mul_sub_pt_const /
 dot_product_pt_const) are at the end of the file: plan_mul_pt_const_* launch pz_glwe_mul_const_batched, the composites one
 pz_glwe_lincomb_const_batched or, where that measured slower, the same sum term by term.
+
+Products by plaintext vectors (mul.rs:243-293), their composites and the normalized sums (composite.rs add_many, mul_add_pt_vec_znx,
+mul_sub_pt_vec_znx, dot_product_pt_vec_znx) come after the constants: the sums are ONE pz_glwe_sum_batched or, where that measured
+slower, the chain of pz_glwe_combine_batched calls.
 """
 from __future__ import annotations
 
@@ -44,11 +48,12 @@ class Ct:
 
 @dataclass
 class Pt:
-    """CKKSPlaintextVecZnx: a VecZnx(1, size) at base2k with its log_delta."""
+    """CKKSPlaintextVecZnx (layouts/plaintext/vec.rs): a VecZnx(1, size) at base2k with its log_delta and, for the products, its log_budget."""
     base2k: int
     size: int
     log_delta: int
     data: object = None
+    log_budget: int = 0
 
     @property
     def max_k(self) -> int:
@@ -494,3 +499,310 @@ def plan_dot_product_pt_const(dst: Ct, ops, csts) -> LincombPlan:
         terms.append(LinTerm(i, cnv_offset, join, k, 1, td, tb))
         log_delta, log_budget = min(log_delta, td), min(log_budget, tb)
     return LincombPlan(name, False, terms, n > 1, log_delta, log_budget)
+
+
+# ---- products by plaintext vectors, and the normalized sums (leveled/default/mul.rs:243-293, leveled/delegates/composite.rs) -------------
+def get_mul_pt_params(res: Ct, a: Ct, pt: Pt):
+    """leveled/default/mul.rs:480-496 -> (res_log_budget, res_log_delta, cnv_offset)."""
+    res_log_budget = checked_mul_pt_log_budget("mul", a.log_budget, pt.log_budget, a.log_delta, pt.log_delta)
+    res_log_delta = a.log_delta
+    res_offset = max(res_log_budget + res_log_delta - res.max_k, 0)
+    cnv_offset = pt.max_k + res_offset
+    return checked_log_budget_sub("mul", res_log_budget, res_offset), res_log_delta, cnv_offset
+
+
+def _mul_plain_shape(op: str, res: Ct, a: Ct, pt: Pt):
+    """what glwe_mul_plain asserts (poulpy-core operations/glwe.rs:207-209): one base2k, sizes that match the effective precisions"""
+    _same_layout(op, res, a)
+    ensure_base2k_match(op, a.base2k, pt.base2k)
+    if a.size != -(-a.effective_k // a.base2k):
+        raise CKKSError(f"{op}: ciphertext size {a.size} != effective_k {a.effective_k} / base2k {a.base2k}, rounded up")
+    if pt.size != -(-pt.max_k // pt.base2k):
+        raise CKKSError(f"{op}: plaintext size {pt.size} != max_k {pt.max_k} / base2k {pt.base2k}, rounded up")
+
+
+def _mul_plain_call(module, res_ptr, dst: Ct, a: Ct, a_ptr, pt: Pt, cnv_offset: int, pt_shared: bool, mode: str, batch: int):
+    from .hal import GlweTensorParams
+    p = GlweTensorParams(rank=dst.cols - 1, a_size=a.size, b_size=pt.size, ab_base2k=a.base2k, a_effective_k=a.effective_k,
+                         b_effective_k=pt.max_k, res_size=dst.size, res_base2k=dst.base2k, cnv_offset=cnv_offset)
+    module.glwe_mul_plain_batched(res_ptr, a_ptr, pt.data, pt_shared, p, mode, batch)
+
+
+@dataclass
+class PtMulPlan:
+    """ckks_mul_pt_vec_znx_into / _assign (mul.rs:243-293): one pz_glwe_mul_plain_batched."""
+    name: str
+    cnv_offset: int
+    log_delta: int
+    log_budget: int
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, a: Ct | None, pt: Pt, pt_shared=False):
+        """dst.data / a.data / pt.data: device pointers; pt_shared: one plaintext for the whole batch."""
+        assign = self.name.endswith("assign")
+        src = dst if assign else a
+        _mul_plain_call(module, dst.data, dst, src, None if assign else a.data, pt, self.cnv_offset, pt_shared, "assign" if assign else "into", batch)
+        self.apply_meta(dst)
+
+
+def plan_mul_pt_vec_znx_into(dst: Ct, a: Ct, pt: Pt) -> PtMulPlan:
+    """mul.rs:243-268."""
+    _mul_plain_shape("mul_pt_vec_znx_into", dst, a, pt)
+    log_budget, log_delta, cnv_offset = get_mul_pt_params(dst, a, pt)
+    return PtMulPlan("mul_pt_vec_znx_into", cnv_offset, log_delta, log_budget)
+
+
+def plan_mul_pt_vec_znx_assign(dst: Ct, pt: Pt) -> PtMulPlan:
+    """mul.rs:270-293."""
+    _mul_plain_shape("mul_pt_vec_znx_assign", dst, dst, pt)
+    log_budget, log_delta, cnv_offset = get_mul_pt_params(dst, dst, pt)
+    return PtMulPlan("mul_pt_vec_znx_assign", cnv_offset, log_delta, log_budget)
+
+
+@dataclass
+class PtMulAddPlan:
+    """ckks_mul_add_pt_vec_znx_into / ckks_mul_sub_pt_vec_znx_into (composite.rs:256-270, :389-403): the product into a scratch batch of
+    dst's layout with default metadata, then the normalizing ckks_add_assign / ckks_sub_assign - two launches."""
+    name: str
+    mul: PtMulPlan
+    add: Plan
+    log_delta: int
+    log_budget: int
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, a: Ct, pt: Pt, tmp, pt_shared=False):
+        """tmp: a device pointer to `batch` ciphertexts of dst's layout."""
+        if tmp is None:
+            raise CKKSError(f"{self.name}: needs a scratch batch of dst's layout")
+        prod = Ct(dst.base2k, dst.size, 0, 0, dst.cols, tmp)
+        self.mul.launch(module, prod, batch, a, pt, pt_shared)
+        self.add.launch(module, dst, batch, a=prod)
+
+
+def plan_mul_add_pt_vec_znx(dst: Ct, a: Ct, pt: Pt, sub=False) -> PtMulAddPlan:
+    name = "mul_sub_pt_vec_znx" if sub else "mul_add_pt_vec_znx"
+    prod = Ct(dst.base2k, dst.size, 0, 0, dst.cols)
+    mul = plan_mul_pt_vec_znx_into(prod, a, pt)
+    mul.apply_meta(prod)
+    add = plan_add_assign(dst, prod, sub=sub, normalize=True)
+    return PtMulAddPlan(name, mul, add, add.log_delta, add.log_budget)
+
+
+def plan_mul_sub_pt_vec_znx(dst: Ct, a: Ct, pt: Pt) -> PtMulAddPlan:
+    return plan_mul_add_pt_vec_znx(dst, a, pt, sub=True)
+
+
+@dataclass
+class SumTerm:
+    index: int                     # which input / product of the call
+    join: int = PLAIN
+    k: int = 0
+    sign: int = 1
+    log_delta: int = 0             # the term's own metadata
+    log_budget: int = 0
+    cnv_offset: int = 0            # dot products: the product's cnv_offset
+
+
+# Routing by measurement (tools/bench_ckks_sum.py, DESIGN.md 4.6e): the term counts at which ONE pz_glwe_sum_batched beat the chain of
+# pz_glwe_combine_batched calls by more than the spread between two runs of itself.  Measured at N = 2^16, 16 limbs, 256 ciphertexts
+# (profiles/ckks_sum_lines.jsonl): at 2 and 4 terms the chain is ONE combine call and the one-pass call takes 1.06 / 1.03 x its time; at 5, 8,
+# 16 and 32 terms it takes 0.76 / 0.70 / 0.67 / 0.60 x (0.58 x with mixed joins at 8), spread 0.1 %.  The counts between two measured wins
+# are routed with them; 3 terms (one combine call, like 2 and 4) and more than 32 (not measured) take the chain, the code as it stood
+# before the one-pass call.
+SUM_WINS = frozenset(range(5, 33))
+
+
+def sum_route(nterms: int) -> bool:
+    return nterms in SUM_WINS
+
+
+def _ensure_accumulation_fits(op: str, dst: Ct, n: int):                  # composite.rs:43-51
+    if dst.base2k >= 64 or n > (1 << (63 - dst.base2k)):
+        raise CKKSError(f"{op}: {n} terms risks i64 overflow at base2k={dst.base2k}")
+
+
+def chain_calls(terms, started=False):
+    """The joins of `terms` as today's sequence of pz_glwe_combine_batched calls: lists of (src, kind, k, sign) with src "dst" or a term,
+    at most four per call; every call but the first re-reads dst, a PZ_JOIN_LSH_ACC shifts it there.  started: dst already holds a
+    partial sum, so the first call re-reads it too."""
+    calls, cur = [], []
+    for t in terms:
+        if t.join == LSH_ACC and (started or cur):
+            if cur and not (len(cur) == 1 and cur[0][0] == "dst"):
+                calls.append(cur)
+                started = True
+            cur = [("dst", LSH, t.k, 1)]
+        elif not cur and started:
+            cur = [("dst", RAW, 0, 1)]
+        if len(cur) == 4:
+            calls.append(cur)
+            started = True
+            cur = [("dst", RAW, 0, 1)]
+        cur.append((t, LSH if t.join == LSH_TERM else RAW, t.k if t.join == LSH_TERM else 0, t.sign))
+    calls.append(cur)
+    return calls
+
+
+SUM_MAX_TERMS = 64       # terms of one pz_glwe_sum_batched
+INPLACE_MAX_LIMBS = 32   # limbs of res that either call can shift in place (staged in LDS: kSumMaxStage, kCombMaxStage)
+
+
+def _check_joins(name: str, dst: Ct, terms, route: str, continues=False):
+    """What the device calls of _launch_joins would refuse, raised before anything is launched: more than 64 terms in one
+    pz_glwe_sum_batched, and a running sum of more than 32 limbs shifted in place by a limb or more - by the one-pass call where it
+    continues from dst, by the chain in every call that re-reads dst.  Neither route serves the latter."""
+    if route == "sum":
+        if len(terms) + continues > SUM_MAX_TERMS:
+            raise CKKSError(f"{name}: {len(terms) + continues} terms in one pz_glwe_sum_batched (at most {SUM_MAX_TERMS}); take route=\"chain\" or fewer slots")
+        shifted = continues and sum(t.k for t in terms if t.join == LSH_ACC) >= dst.base2k
+    else:
+        shifted = any(t.join == LSH_ACC and t.k >= dst.base2k and (continues or u > 0) for u, t in enumerate(terms))
+    if shifted and dst.size > INPLACE_MAX_LIMBS:
+        raise CKKSError(f"{name}: the running sum ({dst.size} limbs) would be shifted in place by a limb or more; at most {INPLACE_MAX_LIMBS} limbs")
+
+
+def _launch_joins(module, dst: Ct, batch: int, terms, operand, route, continues=False):
+    """the normalized sum of `terms` into dst: operand(t) -> (device pointer, size, shared).  route "sum": one pz_glwe_sum_batched;
+    "chain": pz_glwe_combine_batched calls, the last one normalizing.  continues: the sum starts from dst's content."""
+    if route == "sum":
+        call = [dict(a=dst.data, a_size=dst.size)] if continues else []
+        for t in terms:
+            ptr, size, shared = operand(t)
+            call.append(dict(a=ptr, a_size=size, shared=shared, join=t.join, k=t.k, sign=t.sign))
+        module.glwe_sum_batched(dst.data, dst.cols, dst.size, dst.base2k, call, batch)
+        return
+    calls = chain_calls(terms, continues)
+    for n, c in enumerate(calls):
+        out = []
+        for src, kind, k, sign in c:
+            ptr, size, shared = (dst.data, dst.size, False) if isinstance(src, str) else operand(src)
+            out.append(dict(a=ptr, a_size=size, kind=kind, k=k, sign=sign, shared=shared))
+        module.glwe_combine_batched(dst.data, dst.cols, dst.size, dst.base2k, out, n == len(calls) - 1, batch)
+
+
+@dataclass
+class SumPlan:
+    """ckks_add_many (composite.rs:63-93): one pz_glwe_sum_batched, or the chain of pz_glwe_combine_batched calls."""
+    name: str
+    terms: list = field(default_factory=list)
+    normalize: bool = False
+    log_delta: int = 0
+    log_budget: int = 0
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, inputs, shared=(), route=None):
+        """inputs[i].data / dst.data: device pointers; shared: indices of the inputs that hold one ciphertext for the whole batch.
+        route: "sum" | "chain" | None (sum_route())."""
+        if route not in ("sum", "chain", None):
+            raise CKKSError(f"{self.name}: unknown route {route!r}")
+        op = lambda t: (inputs[t.index].data, inputs[t.index].size, t.index in shared)
+        if not self.normalize:                                            # n = 1: glwe_lsh, un-normalized
+            (t,) = self.terms
+            module.glwe_combine_batched(dst.data, dst.cols, dst.size, dst.base2k,
+                                        [dict(a=op(t)[0], a_size=op(t)[1], kind=LSH, k=t.k, shared=op(t)[2])], False, batch)
+        else:
+            if route is None:
+                route = "sum" if sum_route(len(self.terms)) else "chain"
+            _check_joins(self.name, dst, self.terms, route)
+            _launch_joins(module, dst, batch, self.terms, op, route)
+        self.apply_meta(dst)
+
+
+def plan_add_many(dst: Ct, inputs) -> SumPlan:
+    """composite.rs:63-93: add_into_unsafe on the first two inputs, add_assign_unsafe on each further one, the closing normalize."""
+    name = "add_many"
+    n = len(inputs)
+    if n == 0:
+        raise CKKSError("ckks_add_many: inputs must contain at least one ciphertext")
+    for x in inputs:
+        _same_layout(name, dst, x)
+    if n == 1:
+        offset = offset_unary(dst, inputs[0])
+        log_budget = checked_log_budget_sub("ckks_add_many", inputs[0].log_budget, offset)
+        return SumPlan(name, [SumTerm(0, LSH_TERM, offset, 1, inputs[0].log_delta, inputs[0].log_budget)], False, inputs[0].log_delta,
+                       log_budget)
+    _ensure_accumulation_fits("ckks_add_many", dst, n)
+    first = plan_add_into(dst, inputs[0], inputs[1], normalize=False)     # add.rs:76-104, terms in the reference's order
+    terms = []
+    for t in first.terms:
+        i = 0 if t.src == "a" else 1
+        terms.append(SumTerm(i, PLAIN if t.kind == RAW else LSH_TERM, t.k, 1, inputs[i].log_delta, inputs[i].log_budget))
+    log_delta, log_budget = first.log_delta, first.log_budget
+    for i in range(2, n):
+        join, k = _join(log_budget, inputs[i].log_budget)
+        terms.append(SumTerm(i, join, k, 1, inputs[i].log_delta, inputs[i].log_budget))
+        log_delta, log_budget = min(log_delta, inputs[i].log_delta), min(log_budget, inputs[i].log_budget)
+    return SumPlan(name, terms, True, log_delta, log_budget)
+
+
+@dataclass
+class DotPlan:
+    """ckks_dot_product_pt_vec_znx (composite.rs:705-729): pz_glwe_mul_plain_batched per product into scratch slots, joined `slots` at a
+    time by one pz_glwe_sum_batched (or the chain) per chunk; later chunks continue from dst, stored normalized, as term 0."""
+    name: str
+    terms: list = field(default_factory=list)
+    normalize: bool = False
+    log_delta: int = 0
+    log_budget: int = 0
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, ops, pts, tmp=None, slots=None, pt_shared=(), route=None):
+        """ops[i].data / pts[i].data / dst.data: device pointers; pt_shared: indices of the plaintexts that hold one item for the whole
+        batch; tmp: a device pointer to slots x batch ciphertexts of dst's layout, 1 <= slots <= n (not needed for n = 1)."""
+        if route not in ("sum", "chain", None):
+            raise CKKSError(f"{self.name}: unknown route {route!r}")
+        n = len(self.terms)
+        if not self.normalize:                                            # n = 1: the plain product into dst
+            (t,) = self.terms
+            _mul_plain_call(module, dst.data, dst, ops[t.index], ops[t.index].data, pts[t.index], t.cnv_offset, t.index in pt_shared, "into", batch)
+            self.apply_meta(dst)
+            return
+        if tmp is None or slots is None or not 1 <= slots <= n:
+            raise CKKSError(f"{self.name}: needs a scratch of slots x batch ciphertexts of dst's layout, 1 <= slots <= {n}")
+        base = tmp.value if hasattr(tmp, "value") else int(tmp)
+        slot_bytes = batch * dst.cols * dst.size * module.n() * 8
+        chunks = []                                                       # (first term, terms, route): by the terms of the chunk's own call
+        for lo in range(0, n, slots):
+            chunk = self.terms[lo:lo + slots]
+            chunks.append((lo, chunk, route or ("sum" if sum_route(len(chunk) + (lo > 0)) else "chain")))
+            _check_joins(self.name, dst, chunk, chunks[-1][2], continues=lo > 0)
+        for lo, chunk, by in chunks:
+            where = {}
+            for s, t in enumerate(chunk):
+                where[id(t)] = base + s * slot_bytes
+                _mul_plain_call(module, where[id(t)], dst, ops[t.index], ops[t.index].data, pts[t.index], t.cnv_offset, t.index in pt_shared,
+                                "into", batch)
+            _launch_joins(module, dst, batch, chunk, lambda t: (where[id(t)], dst.size, False), by, continues=lo > 0)
+        self.apply_meta(dst)
+
+
+def plan_dot_product_pt_vec_znx(dst: Ct, ops, pts) -> DotPlan:
+    """composite.rs:705-729 with accumulate_unnormalized (:478-506): dst = sum_i pts[i] * ops[i].  n = 1 is the plain product."""
+    name = "dot_product_pt_vec_znx"
+    if len(ops) == 0:                                                     # check_lengths, :468-476
+        raise CKKSError(f"{name}: inputs must contain at least one pair")
+    if len(ops) != len(pts):
+        raise CKKSError(f"{name}: length mismatch between ct vector ({len(ops)}) and weight vector ({len(pts)})")
+    n = len(ops)
+    _ensure_accumulation_fits(name, dst, n)
+    terms = []
+    log_delta = log_budget = 0
+    for i, (a, pt) in enumerate(zip(ops, pts)):
+        _mul_plain_shape(name, dst, a, pt)
+        tb, td, cnv_offset = get_mul_pt_params(dst, a, pt)
+        if i == 0:
+            terms.append(SumTerm(0, PLAIN, 0, 1, td, tb, cnv_offset))
+            log_delta, log_budget = td, tb
+            continue
+        join, k = _join(log_budget, tb)
+        terms.append(SumTerm(i, join, k, 1, td, tb, cnv_offset))
+        log_delta, log_budget = min(log_delta, td), min(log_budget, tb)
+    return DotPlan(name, terms, n > 1, log_delta, log_budget)

@@ -25,6 +25,7 @@
 //   api_br.hip       C ABI: blind rotation, circuit bootstrapping (composites on glwe_op; HIP-graph replay)
 //   api_cnv.hip      C ABI: convolution family, GLWE tensoring, batched i64 family
 //   api_lincomb.hip  C ABI: weighted sums of GLWE batches by constants
+//   api_sum.hip      C ABI and launcher: normalized signed sums of GLWE batches, one pass (device_sum.hpp)
 //   api_lwe.hip      C ABI: LWE glue of the gate bootstrap (+ its index kernels)
 //   api_dist.hip     C ABI: RCCL key broadcast (dlopen)
 //   api_common.hpp / api_glwe.hpp / glwe_call.hpp   what those share (staging and argument checks; graph cache; GlweCall, glwe_op / glwe_trace / ...)

@@ -848,6 +848,23 @@ class Module:
         self._ck(self.lib.pz_glwe_lincomb_const_batched(self.handle, res, rank, res_size, base2k, ops, shared, a_size, cnv, rp, ip, b_size, join, k,
                                                         sign, len(terms), init, int(bool(normalize)), batch))
 
+    def glwe_sum_batched(self, res: c_void_p, res_cols: int, res_size: int, base2k: int, terms, batch: int):
+        """res = glwe_normalize_assign of the terms joined in order to a zero GLWE batch, in one pass, up to 64 terms (include/poulpy_hip.h,
+        DESIGN.md 4.6e): poulpy-ckks's add_many and the join of its dot products.  terms: dicts with keys a (device pointer), a_size and
+        optional shared, join ("plain" | "lsh_term" | "lsh_acc"), k, sign (+1 / -1).  Term 0 may be res itself."""
+        nt = max(len(terms), 1)
+        ops = (c_void_p * nt)()
+        shared, join, sign = (C.c_int * nt)(), (C.c_int * nt)(), (C.c_int * nt)()
+        a_size, k = (C.c_size_t * nt)(), (C.c_size_t * nt)()
+        for i, t in enumerate(terms):
+            a = t["a"]
+            ops[i] = a.value if isinstance(a, c_void_p) else a
+            shared[i], a_size[i] = int(bool(t.get("shared", False))), int(t["a_size"])
+            j = t.get("join", "plain")
+            join[i] = self.JOIN_KINDS[j] if isinstance(j, str) else int(j)
+            k[i], sign[i] = int(t.get("k", 0)), int(t.get("sign", 1))
+        self._ck(self.lib.pz_glwe_sum_batched(self.handle, res, res_cols, res_size, base2k, ops, shared, a_size, join, k, sign, len(terms), batch))
+
     def _shift_acc(self, name, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col):
         self._ck(getattr(self.lib, name)(self.handle, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col))
 
