@@ -74,8 +74,13 @@ tests/cpp/test_lincomb_walk: tests/cpp/test_lincomb_walk.cpp $(wildcard $(CSRC)/
 tests/cpp/test_sum_walk: tests/cpp/test_sum_walk.cpp $(wildcard $(CSRC)/*.hpp)
 	$(HIPCC) -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -I $(CSRC) -I include $< -o $@ -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined
 
+# the shared carry steps, the same-base normalization plan and its walk (znx_steps.hpp) on the host under the host sanitizers; it reads
+# its cases from a file that tests/test_znx_steps_host.py writes from the oracle (that test builds and runs the same program)
+tests/cpp/test_znx_steps: tests/cpp/test_znx_steps.cpp $(CSRC)/znx_steps.hpp
+	$(HIPCC) -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -I $(CSRC) $< -o $@ -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined
+
 clean:
-	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_mid_forms tests/cpp/test_lincomb_walk tests/cpp/test_sum_walk
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_mid_forms tests/cpp/test_lincomb_walk tests/cpp/test_sum_walk tests/cpp/test_znx_steps
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 

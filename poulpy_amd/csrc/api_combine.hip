@@ -22,7 +22,7 @@ struct TermIn {                 // one term, as the entry points describe it
 void plan_term(const TermIn& in, int res_size, int base2k, CombTerm& t) {
     t.a = (const long long*)in.a + in.col_off;
     t.bs = in.bs; t.ls = in.ls; t.cstep = in.cstep; t.size = in.size; t.neg = in.neg; t.stage = 0;
-    t.kind = in.kind; t.lsh = 0; t.kk = base2k; t.steps = 0; t.pro = in.size; t.lo = 0; t.hi = 0;
+    t.kind = in.kind; t.lsh = 0; t.pad = 0; t.steps = 0; t.pro = in.size; t.lo = 0; t.hi = 0;
     const int a_size = in.size;
     if (in.kind == CB_LSH) {
         const size_t steps = in.k / (size_t)base2k;
@@ -30,7 +30,7 @@ void plan_term(const TermIn& in, int res_size, int base2k, CombTerm& t) {
         if (steps >= (size_t)std::max(res_size, a_size)) { t.kind = CB_NONE; return; }   // :92-100: nothing is added
         const int st = (int)steps;
         const int min_size = std::min(res_size, std::max(a_size - st, 0));
-        t.steps = st; t.lsh = k_rem; t.kk = k_rem == 0 ? base2k : base2k - k_rem;
+        t.steps = st; t.lsh = k_rem;
         t.lo = min_size;
         t.pro = std::min(st + min_size, a_size);   // carry_only_start
     } else if (in.kind == CB_RSH) {
@@ -39,7 +39,7 @@ void plan_term(const TermIn& in, int res_size, int base2k, CombTerm& t) {
         if (k_rem != 0) steps += 1;
         const int lsh = (base2k - k_rem) % base2k;
         const int st = (int)std::min(steps, (size_t)res_size + (size_t)a_size);   // beyond that every range below is empty or full
-        t.steps = st; t.lsh = lsh; t.kk = lsh == 0 ? base2k : base2k - lsh;
+        t.steps = st; t.lsh = lsh;
         t.lo = std::min(res_size, st);                          // res_end
         t.hi = (int)std::min((long long)res_size, (long long)a_size + st);   // res_start
         t.pro = std::min(a_size, std::max(res_size - st, 0));   // a_start

@@ -10,11 +10,12 @@
 //  * RAW / LSH / the middle range of RSH add (or subtract) a digit computed from the operand alone (normalization.rs:179-260);
 //  * the low range of RSH (limbs < min(res_size, steps)) renormalizes the running value with the term's carry (shift.rs:326-340).
 // An LSH term whose operand IS res reads limb j + steps after limb j + steps was stored: that operand's limbs are staged once, before the
-// walk, in the thread's own LDS slice.  Arithmetic is wrapping i64, digit for digit the reference step functions.
+// walk, in the thread's own LDS slice.  The steps themselves are those of znx_steps.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "internal.hpp"
+#include "znx_steps.hpp"
 
 namespace pz {
 
@@ -28,7 +29,7 @@ struct CombTerm {
     long long bs, ls;     // scalars between ciphertexts (0: one operand for the batch) and between limbs
     int cstep;            // 1: column c of res reads column c of a; 0: column 0 only (plaintext terms; other columns skip the term)
     int size, kind, neg, stage;
-    int lsh, kk, steps;   // the digit split of the shift (shift.rs:90 / :282-293)
+    int lsh, pad, steps;  // the digit split of the shift (shift.rs:90 / :282-293); pad keeps the layout
     int pro;              // carry-only prologue over limbs [pro, size) of a (shift.rs:108-119 / :300-309)
     int lo, hi;           // LSH: output limbs [0, lo = min_size) (shift.rs:107).  RSH: middle range [lo = res_end, hi = res_start) (:294-295)
 };
@@ -38,13 +39,6 @@ struct CombArgs {
     int n, batch, cols, res_size, k, nterms, normalize;
     CombTerm t[kCombMaxTerms];
 };
-
-__device__ __forceinline__ unsigned long long cb_digit(int k, unsigned long long x) {
-    return (unsigned long long)((long long)(x << (64 - k)) >> (64 - k));
-}
-__device__ __forceinline__ unsigned long long cb_carry(int k, unsigned long long x, unsigned long long d) {
-    return (unsigned long long)((long long)(x - d) >> k);
-}
 
 __global__ void __launch_bounds__(kCombBlock) k_glwe_combine(CombArgs g) {
     extern __shared__ ulonglong2 cb_lds[];
@@ -59,7 +53,7 @@ __global__ void __launch_bounds__(kCombBlock) k_glwe_combine(CombArgs g) {
     unsigned long long* r = (unsigned long long*)g.res + b * g.res_bs + (long long)c * g.n + x;
 
     const ulonglong2* ap[kCombMaxTerms];
-    unsigned long long cr[kCombMaxTerms][2];
+    long long cr[kCombMaxTerms][2];
     int kind[kCombMaxTerms];
 #pragma unroll
     for (int u = 0; u < kCombMaxTerms; ++u) {
@@ -72,35 +66,29 @@ __global__ void __launch_bounds__(kCombBlock) k_glwe_combine(CombArgs g) {
             for (int l = 0; l < t.size; ++l) cb_lds[l * kCombBlock + threadIdx.x] = ap[u][(long long)l * (t.ls >> 1)];
         }
         if (kind[u] == CB_LSH || kind[u] == CB_RSH) {
-            // znx_normalize_first_step_carry_only on the last limb, middle_step_carry_only above it (normalization.rs:24-41, :107-129)
-            for (int l = t.size - 1; l >= t.pro; --l) {
+            for (int l = t.size - 1; l >= t.pro; --l) {   // the limbs below the window: their carry only
                 const ulonglong2 v = t.stage ? cb_lds[l * kCombBlock + threadIdx.x] : ap[u][(long long)l * (t.ls >> 1)];
-                const unsigned long long xv[2] = {v.x, v.y};
+                const long long xv[2] = {(long long)v.x, (long long)v.y};
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const unsigned long long d = cb_digit(t.kk, xv[e]), cy = cb_carry(t.kk, xv[e], d);
-                    if (l == t.size - 1) {
-                        cr[u][e] = cy;
-                    } else {
-                        const unsigned long long dpc = (d << t.lsh) + cr[u][e];
-                        cr[u][e] = cy + cb_carry(k, dpc, cb_digit(k, dpc));
-                    }
+                    if (l == t.size - 1) cr[u][e] = znx_first_step_carry_only(k, t.lsh, xv[e]);
+                    else znx_middle_step_carry_only(k, t.lsh, xv[e], cr[u][e]);
                 }
             }
         }
     }
 
-    unsigned long long nc[2] = {0, 0};
+    long long nc[2] = {0, 0};
     for (int j = g.res_size - 1; j >= 0; --j) {
-        unsigned long long v[2] = {0, 0};
+        long long v[2] = {0, 0};
 #pragma unroll
         for (int u = 0; u < kCombMaxTerms; ++u) {
             const CombTerm& t = g.t[u];
             if (kind[u] == CB_RAW) {
                 if (j < t.size) {
                     const ulonglong2 a = ap[u][(long long)j * (t.ls >> 1)];
-                    if (t.neg) { v[0] -= a.x; v[1] -= a.y; }
-                    else { v[0] += a.x; v[1] += a.y; }
+                    if (t.neg) { v[0] = wsub(v[0], (long long)a.x); v[1] = wsub(v[1], (long long)a.y); }
+                    else { v[0] = wadd(v[0], (long long)a.x); v[1] = wadd(v[1], (long long)a.y); }
                 }
             } else if (kind[u] == CB_LSH || (kind[u] == CB_RSH && j >= t.lo && j < t.hi)) {
                 // LSH: output limb j < min_size from a[j + steps]; RSH middle range: a[j - steps]
@@ -108,49 +96,27 @@ __global__ void __launch_bounds__(kCombBlock) k_glwe_combine(CombArgs g) {
                 if (lsh_term && j >= t.lo) continue;
                 const int l = lsh_term ? j + t.steps : j - t.steps;
                 const ulonglong2 a = t.stage ? cb_lds[l * kCombBlock + threadIdx.x] : ap[u][(long long)l * (t.ls >> 1)];
-                const unsigned long long xv[2] = {a.x, a.y};
+                const long long xv[2] = {(long long)a.x, (long long)a.y};
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const unsigned long long d = cb_digit(t.kk, xv[e]);
-                    unsigned long long x1;
-                    if (lsh_term && j == 0) {   // znx_normalize_final_step<false> / _sub (normalization.rs:275-330)
-                        x1 = cb_digit(k, (d << t.lsh) + cr[u][e]);
-                    } else {                    // znx_normalize_middle_step<false> / _sub (normalization.rs:179-260)
-                        const unsigned long long cy = cb_carry(t.kk, xv[e], d);
-                        const unsigned long long dpc = (d << t.lsh) + cr[u][e];
-                        x1 = cb_digit(k, dpc);
-                        cr[u][e] = cy + cb_carry(k, dpc, x1);
-                    }
-                    v[e] = t.neg ? v[e] - x1 : v[e] + x1;
+                for (int e = 0; e < 2; ++e) {   // the top limb of an LSH term takes the final step
+                    const long long x1 = lsh_term && j == 0 ? znx_final_step(k, t.lsh, xv[e], cr[u][e]) : znx_middle_step(k, t.lsh, xv[e], cr[u][e]);
+                    v[e] = t.neg ? wsub(v[e], x1) : wadd(v[e], x1);
                 }
             } else if (kind[u] == CB_RSH && j < t.lo) {
                 // limbs below the shifted operand: the running value renormalized with the term's carry, negated first by rsh_sub
-                // (shift.rs:326-340 and vec_znx_rsh_sub; middle_step_assign / final_step_assign with lsh 0, normalization.rs:132-157, :254-272)
+                // (shift.rs:326-340 and vec_znx_rsh_sub: the _assign steps with lsh 0)
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    if (j == t.lo - 1 && t.neg) cr[u][e] = 0ull - cr[u][e];
-                    const unsigned long long d = cb_digit(k, v[e]);
-                    if (j == 0) {
-                        v[e] = cb_digit(k, d + cr[u][e]);
-                    } else {
-                        const unsigned long long cy = cb_carry(k, v[e], d);
-                        const unsigned long long dpc = d + cr[u][e];
-                        v[e] = cb_digit(k, dpc);
-                        cr[u][e] = cy + cb_carry(k, dpc, v[e]);
-                    }
+                    if (j == t.lo - 1 && t.neg) cr[u][e] = wsub(0, cr[u][e]);
+                    v[e] = j == 0 ? znx_final_step(k, 0, v[e], cr[u][e]) : znx_middle_step(k, 0, v[e], cr[u][e]);
                 }
             }
         }
         if (g.normalize) {   // vec_znx_normalize_assign: first / middle / final step_assign with lsh 0 (normalize.rs:403-425)
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const unsigned long long d = cb_digit(k, v[e]), cy = cb_carry(k, v[e], d);
-                const unsigned long long dpc = d + nc[e];
-                v[e] = cb_digit(k, dpc);
-                nc[e] = cy + cb_carry(k, dpc, v[e]);
-            }
+            for (int e = 0; e < 2; ++e) v[e] = znx_middle_step(k, 0, v[e], nc[e]);
         }
-        *reinterpret_cast<ulonglong2*>(r + (long long)j * g.res_ls) = make_ulonglong2(v[0], v[1]);
+        *reinterpret_cast<ulonglong2*>(r + (long long)j * g.res_ls) = make_ulonglong2((unsigned long long)v[0], (unsigned long long)v[1]);
     }
 }
 

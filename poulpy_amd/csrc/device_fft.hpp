@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "znx_steps.hpp"
+
 namespace pz {
 
 typedef double2 cplx;
@@ -578,8 +580,6 @@ struct TailArgs {
     // form (NZF = 7) reads the copies and returns at once if the flag is up; an operand form (SMALL) launched with this pointer returns at once if it is down
     const unsigned* body16_wide;
 };
-__device__ __forceinline__ long long tz_digit(int k, long long x) { return (long long)((unsigned long long)x << (64 - k)) >> (64 - k); }
-__device__ __forceinline__ long long tz_carry(int k, long long x, long long d) { return (long long)((unsigned long long)x - (unsigned long long)d) >> k; }
 // (modes 1 / 2 are written once and read by a LATER launch at the earliest: streaming stores, as the product tails - with plain stores the
 //  PMC write traffic of the tensoring tail was 1.45 x its bytes, profiles/r04_tensor_traffic.json)
 __device__ __forceinline__ void tz_put(long long* p, int mode, long long v) {
@@ -1049,17 +1049,17 @@ k_inv_tail(TailArgs g) {
                 if (j >= g.nz_a_end) {                                                                       \
                     long long& c_ = carry[2 * n1 + h];                                                       \
                     const int kk_ = g.nz_lsh == 0 ? k : k - g.nz_lsh;                                        \
-                    const long long d_ = tz_digit(kk_, x);                                                   \
-                    const long long cr_ = tz_carry(kk_, x, d_);                                              \
+                    const long long d_ = znx_digit(kk_, x);                                                  \
+                    const long long cr_ = znx_carry(kk_, x, d_);                                             \
                     const long long dpc_ = (long long)(((unsigned long long)d_ << g.nz_lsh) + (unsigned long long)c_); \
-                    const long long x1_ = tz_digit(k, dpc_);                                                 \
+                    const long long x1_ = znx_digit(k, dpc_);                                                \
                     if (j < g.nz_a_start) {                                                                  \
                         if (d5 && D16ONLY) g.d16w[PZ_TAIL_D16_AT(j - g.nz_a_start + g.nz_res_start, n1, h, idx)] = (short)((int)x1_ - d5a[NZ == 2 ? 2 * n1 + h : 0]); \
                         else if (d5) tz_put(res_col + (long long)(j - g.nz_a_start + g.nz_res_start) * res_ls + idx, g.nz_mode,  \
                                        (long long)((unsigned long long)x1_ - (unsigned long long)(long long)d5a[NZ == 2 ? 2 * n1 + h : 0])); \
                         else if constexpr (!D16R) PZ_TAIL_NZ_STORE(j - g.nz_a_start + g.nz_res_start, idx, x1_, n1, h)   /* (D16R: every digit limb has its prefetch) */ \
                     }                                                                                        \
-                    c_ = (long long)((unsigned long long)cr_ + (unsigned long long)tz_carry(k, dpc_, x1_));  \
+                    c_ = (long long)((unsigned long long)cr_ + (unsigned long long)znx_carry(k, dpc_, x1_)); \
                 }                                                                                            \
                 continue;                                                                                    \
             }                                                                                                \
@@ -1180,9 +1180,9 @@ k_inv_tail(TailArgs g) {
                 const long long idx = (long long)j1 * g.m2 + c0 + b_c + (h ? m : 0);
                 long long c_ = ((NZ == 1 || (D16R && PZ_TAIL_D16R_F64)) && !icarry) ? fast_i64_from_integral(__longlong_as_double(carry[2 * n1 + h])) : carry[2 * n1 + h];
                 for (int jj = 0; jj < g.nz_res_end; ++jj) {
-                    const long long x1_ = tz_digit(k, c_);
+                    const long long x1_ = znx_digit(k, c_);
                     PZ_TAIL_NZ_STORE(g.nz_res_end - jj - 1, idx, x1_, n1, h)
-                    if (jj != g.nz_res_end - 1) c_ = tz_carry(k, c_, x1_);
+                    if (jj != g.nz_res_end - 1) c_ = znx_carry(k, c_, x1_);
                 }
             }
         }

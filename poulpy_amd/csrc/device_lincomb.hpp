@@ -9,8 +9,8 @@
 //
 // The product digits are mc_walk's (device_plain.hpp, what k_mul_const_nz stores).  A join that shifts nothing adds them straight into the
 // accumulator (wrapping i64 sums commute); glwe_lsh_add / glwe_lsh_sub walk the product from the bottom limb up with the carry in a register
-// (shift.rs:68-180 with equal sizes: no carry-only range); glwe_lsh_assign on the running, un-normalized accumulator reads limb j + steps
-// for limb j, so its result goes to the product's buffer and the two buffers trade places.
+// (shift.rs:68-180 with equal sizes: no carry-only range; the steps are znx_steps.hpp's); glwe_lsh_assign on the running, un-normalized
+// accumulator reads limb j + steps for limb j, so its result goes to the product's buffer and the two buffers trade places.
 //
 // lc_walk is __host__ __device__: tests/cpp/test_lincomb_walk.cpp runs it on the host against the oracle's digits.
 #pragma once
@@ -94,16 +94,10 @@ __host__ __device__ __forceinline__ void lc_product(const LinTerm& t, const long
     }
 }
 
-// digit j of vec_znx_lsh of `src` (res_size limbs, equal sizes) and the carry into limb j - 1: znx_normalize_middle_step / final_step
-// (normalization.rs:179-260, :275-330), as k_glwe_combine's LSH terms
+// digit j of vec_znx_lsh of `src` (res_size limbs, equal sizes) and the carry into limb j - 1, as k_glwe_combine's LSH terms
 __host__ __device__ __forceinline__ long long lc_lsh_digit(const LinTerm& t, int k, const long long* src, int j, long long& c) {
-    const int kk = t.k_rem == 0 ? k : k - t.k_rem;
     const long long x = src[(long long)(j + t.steps) * kMulConstBlock];
-    const long long d = mc_digit(kk, x);
-    const long long dpc = mc_add(mc_shl(d, t.k_rem), c);
-    const long long x1 = mc_digit(k, dpc);
-    if (j != 0) c = mc_add(mc_carry(kk, x, d), mc_carry(k, dpc, x1));
-    return x1;
+    return j == 0 ? znx_final_step(k, t.k_rem, x, c) : znx_middle_step(k, t.k_rem, x, c);
 }
 // acc +- lsh(tmp, k): glwe_lsh_add / glwe_lsh_sub
 __host__ __device__ __forceinline__ void lc_join_lsh_tmp(const LinTerm& t, int k, long long* acc, const long long* tmp) {
@@ -111,7 +105,7 @@ __host__ __device__ __forceinline__ void lc_join_lsh_tmp(const LinTerm& t, int k
     for (int j = t.min_size - 1; j >= 0; --j) {
         const long long x1 = lc_lsh_digit(t, k, tmp, j, c);
         long long* r = acc + (long long)j * kMulConstBlock;
-        *r = t.neg ? (long long)((unsigned long long)*r - (unsigned long long)x1) : mc_add(*r, x1);
+        *r = t.neg ? wsub(*r, x1) : wadd(*r, x1);
     }
 }
 // tmp = lsh(acc, k) +- tmp: glwe_lsh_assign on the accumulator (limbs >= min_size become zero), then glwe_add_assign / glwe_sub_assign
@@ -120,7 +114,7 @@ __host__ __device__ __forceinline__ void lc_join_lsh_acc(const LinTerm& t, int k
     for (int j = res_size - 1; j >= 0; --j) {
         const long long x1 = j < t.min_size ? lc_lsh_digit(t, k, acc, j, c) : 0;
         long long* r = tmp + (long long)j * kMulConstBlock;
-        *r = t.neg ? (long long)((unsigned long long)x1 - (unsigned long long)*r) : mc_add(x1, *r);
+        *r = t.neg ? wsub(x1, *r) : wadd(x1, *r);
     }
 }
 
@@ -176,14 +170,8 @@ __host__ __device__ inline void lc_walk(const LinArgs& g, const LinTerm* terms, 
     for (int j = rs - 1; j >= 0; --j) {
         long long v0 = acc0[j * S], v1 = pair ? acc1[j * S] : 0;
         if (g.normalize) {
-            const long long d0 = mc_digit(k, v0), cy0 = mc_carry(k, v0, d0), dpc0 = mc_add(d0, nc0);
-            v0 = mc_digit(k, dpc0);
-            nc0 = mc_add(cy0, mc_carry(k, dpc0, v0));
-            if (pair) {
-                const long long d1 = mc_digit(k, v1), cy1 = mc_carry(k, v1, d1), dpc1 = mc_add(d1, nc1);
-                v1 = mc_digit(k, dpc1);
-                nc1 = mc_add(cy1, mc_carry(k, dpc1, v1));
-            }
+            v0 = znx_middle_step(k, 0, v0, nc0);
+            if (pair) v1 = znx_middle_step(k, 0, v1, nc1);
         }
         r[(long long)j * rls] = v0;
         if (pair) r[(long long)j * rls + h] = v1;

@@ -537,22 +537,10 @@ __global__ void __launch_bounds__(256) k_rotate(RotArgs g) {
 }
 
 // =================================================================================
-// normalize: reference/vec_znx/normalize.rs + reference/znx/normalization.rs.
+// normalize: reference/vec_znx/normalize.rs on the step functions of znx_steps.hpp.
 // The carry chain runs across limbs, never across coefficients, so one thread owns
-// one coefficient and walks the limbs with the carry in a register.  Arithmetic is
-// exact-integer and mirrors the reference step functions bit for bit.
+// one coefficient and walks the limbs with the carry in a register.
 // =================================================================================
-__device__ __forceinline__ long long nz_digit(int k, long long x) {
-    return (long long)((unsigned long long)x << (64 - k)) >> (64 - k);
-}
-__device__ __forceinline__ long long nz_carry(int k, long long x, long long d) {
-    return (long long)((unsigned long long)x - (unsigned long long)d) >> k;
-}
-__device__ __forceinline__ long long wadd(long long a, long long b) {
-    return (long long)((unsigned long long)a + (unsigned long long)b);
-}
-__device__ __forceinline__ long long wshl(long long a, int s) { return (long long)((unsigned long long)a << s); }
-
 struct NzArgs {
     long long* res; const long long* a;
     long long res_bs, a_bs;      // batch strides (scalars)
@@ -560,7 +548,7 @@ struct NzArgs {
     int res_cols, res_size, res_col;
     int a_cols, a_size, a_col;
     int res_base2k, a_base2k;
-    // same-base plan (normalize.rs:83-101)
+    // same-base plan (ZnxInterPlan, znx_steps.hpp)
     int lsh, res_end, res_start, a_end, a_start;
     // k_normalize_inter<COMBINE>: how the digits reach `res` (mode) and up to two further columns of the same container that take them too
     // (GLWE tensoring: the diagonal terms are stored in their own column and subtracted from the cross columns, operations/glwe.rs:762-805
@@ -587,60 +575,25 @@ __global__ void __launch_bounds__(256) k_normalize_inter(NzArgs g) {
     long long* r = g.res + b * g.res_bs + (long long)g.res_col * g.n + i;
     long long* r2a = COMBINE && g.mode2[0] ? g.res + b * g.res_bs + (long long)g.col2[0] * g.n + i : nullptr;
     long long* r2b = COMBINE && g.mode2[1] ? g.res + b * g.res_bs + (long long)g.col2[1] * g.n + i : nullptr;
-#define PZ_NZ_STORE(J_, V_)                                                                        \
-    {                                                                                              \
-        const long long off_ = (long long)(J_) * rls;                                              \
-        const long long v_ = (V_);                                                                 \
-        if constexpr (COMBINE) {                                                                   \
-            if (g.mode2[0] == 5) {   /* the further columns' digits are subtracted on the way to the main column */ \
-                long long w_ = (long long)((unsigned long long)v_ - (unsigned long long)r2a[off_]); \
-                if (r2b) w_ = (long long)((unsigned long long)w_ - (unsigned long long)r2b[off_]);  \
-                nz_put(r + off_, g.mode, w_);                                                      \
-            } else {                                                                               \
-                nz_put(r + off_, g.mode, v_);                                                      \
-                if (r2a) nz_put(r2a + off_, g.mode2[0], v_);                                       \
-                if (r2b) nz_put(r2b + off_, g.mode2[1], v_);                                       \
-            }                                                                                      \
-        } else r[off_] = v_;                                                                       \
-    }
     const long long als = (long long)g.a_cols * g.n;
     const long long rls = (long long)g.res_cols * g.n;
-    const int k = g.res_base2k;
-    const int lsh = g.lsh;
-    const int kk = lsh == 0 ? k : k - lsh;
-
-    long long c = 0;
-    const int a_out_range = g.a_size > g.a_start ? g.a_size - g.a_start : 0;
-    for (int j = 0; j < a_out_range; ++j) {
-        const long long x = a[(long long)(g.a_size - j - 1) * als];
-        const long long d = nz_digit(kk, x);
-        const long long cr = nz_carry(kk, x, d);
-        if (j == 0) {
-            c = cr;  // znx_normalize_first_step_carry_only, normalization.rs:24-41
-        } else {     // znx_normalize_middle_step_carry_only, normalization.rs:107-129
-            const long long dpc = wadd(wshl(d, lsh), c);
-            c = wadd(cr, nz_carry(k, dpc, nz_digit(k, dpc)));
-        }
-    }
-    for (int j = g.res_start; j < g.res_size; ++j) PZ_NZ_STORE(j, 0)
-    const int mid = g.a_start > g.a_end ? g.a_start - g.a_end : 0;
-    for (int j = 0; j < mid; ++j) {  // znx_normalize_middle_step<true>, normalization.rs:179-221
-        const long long x = a[(long long)(g.a_start - j - 1) * als];
-        const long long d = nz_digit(kk, x);
-        const long long cr = nz_carry(kk, x, d);
-        const long long dpc = wadd(wshl(d, lsh), c);
-        const long long x1 = nz_digit(k, dpc);
-        PZ_NZ_STORE(g.res_start - j - 1, x1)
-        c = wadd(cr, nz_carry(k, dpc, x1));
-    }
-    for (int j = 0; j < g.res_end; ++j) {
-        // limb zeroed, then middle_step_assign / final_step_assign on a zero limb:
-        // digit(kk, 0) = 0 -> dpc = c  (normalization.rs:132-157, 254-272)
-        const long long x1 = nz_digit(k, c);
-        PZ_NZ_STORE(g.res_end - j - 1, x1)
-        if (j != g.res_end - 1) c = nz_carry(k, c, x1);
-    }
-#undef PZ_NZ_STORE
+    const ZnxInterPlan plan{g.lsh, g.res_end, g.res_start, g.a_end, g.a_start};
+    znx_normalize_inter_walk(
+        plan, g.res_base2k, g.res_size, g.a_size, [&](int l) { return a[(long long)l * als]; },
+        [&](int j, long long v) {
+            const long long off = (long long)j * rls;
+            if constexpr (COMBINE) {
+                if (g.mode2[0] == 5) {   // the further columns' digits are subtracted on the way to the main column
+                    long long w = wsub(v, r2a[off]);
+                    if (r2b) w = wsub(w, r2b[off]);
+                    nz_put(r + off, g.mode, w);
+                } else {
+                    nz_put(r + off, g.mode, v);
+                    if (r2a) nz_put(r2a + off, g.mode2[0], v);
+                    if (r2b) nz_put(r2b + off, g.mode2[1], v);
+                }
+            } else r[off] = v;
+        });
 }
 
 // normalize.rs:147-401 (vec_znx_normalize_cross_base2k).  The control flow depends
@@ -682,17 +635,10 @@ __global__ void __launch_bounds__(256) k_normalize_cross(NzArgs g, long long res
     for (int j = 0; j < res_size; ++j) r[(long long)j * rls] = 0;
     if (res_start == 0) return;
 
-    const int kk = lsh_pos == 0 ? ak : ak - lsh_pos;
-    const int a_out_range = a_size > a_start ? a_size - a_start : 0;
-    for (int j = 0; j < a_out_range; ++j) {
-        const long long x = a[(long long)(a_size - j - 1) * als];
-        const long long d = nz_digit(kk, x);
-        const long long cr = nz_carry(kk, x, d);
-        if (j == 0) a_carry = cr;
-        else {
-            const long long dpc = wadd(wshl(d, lsh_pos), a_carry);
-            a_carry = wadd(cr, nz_carry(ak, dpc, nz_digit(ak, dpc)));
-        }
+    for (int l = a_size - 1; l >= a_start; --l) {
+        const long long x = a[(long long)l * als];
+        if (l == a_size - 1) a_carry = znx_first_step_carry_only(ak, lsh_pos, x);
+        else znx_middle_step_carry_only(ak, lsh_pos, x, a_carry);
     }
     int res_acc_left = rk;
     int res_limb = res_start - 1;
@@ -702,14 +648,7 @@ __global__ void __launch_bounds__(256) k_normalize_cross(NzArgs g, long long res
     for (int j = 0; j < mid && !done; ++j) {
         const int a_limb = a_start - j - 1;
         int a_take_left = ak;
-        {   // znx_normalize_middle_step<true>(a_base2k, lsh, a_norm, a_slice, a_carry)
-            const long long x = a[(long long)a_limb * als];
-            const long long d = nz_digit(kk, x);
-            const long long cr = nz_carry(kk, x, d);
-            const long long dpc = wadd(wshl(d, lsh_pos), a_carry);
-            a_norm = nz_digit(ak, dpc);
-            a_carry = wadd(cr, nz_carry(ak, dpc, a_norm));
-        }
+        a_norm = znx_middle_step(ak, lsh_pos, a[(long long)a_limb * als], a_carry);
         if (j == 0) {
             if ((a_tot_bits - a_start_bit) % ak != 0) {
                 const int take = (int)((a_tot_bits - a_start_bit) % ak);
@@ -726,8 +665,8 @@ __global__ void __launch_bounds__(256) k_normalize_cross(NzArgs g, long long res
             const int a_take = min(min(ak, a_take_left), res_acc_left);
             if (a_take != 0) {  // znx_extract_digit_addmul(a_take, scale, res_slice, a_norm)
                 const int scale = rk - res_acc_left;
-                const long long d = nz_digit(a_take, a_norm);
-                a_norm = nz_carry(a_take, a_norm, d);
+                const long long d = znx_digit(a_take, a_norm);
+                a_norm = znx_carry(a_take, a_norm, d);
                 cur = wadd(cur, wshl(d, scale));
                 a_take_left -= a_take;
                 res_acc_left -= a_take;
@@ -737,17 +676,11 @@ __global__ void __launch_bounds__(256) k_normalize_cross(NzArgs g, long long res
                     a_carry = wadd(a_carry, a_norm);
                     if (res_acc_left != 0) {
                         const int scale = rk - res_acc_left;
-                        const long long d = nz_digit(res_acc_left, a_carry);
-                        a_carry = nz_carry(res_acc_left, a_carry, d);
+                        const long long d = znx_digit(res_acc_left, a_carry);
+                        a_carry = znx_carry(res_acc_left, a_carry, d);
                         cur = wadd(cur, wshl(d, scale));
                     }
-                    {   // znx_normalize_middle_step_assign(res_base2k, 0, res_slice, res_carry)
-                        const long long d = nz_digit(rk, cur);
-                        const long long cr = nz_carry(rk, cur, d);
-                        const long long dpc = wadd(d, res_carry);
-                        cur = nz_digit(rk, dpc);
-                        res_carry = wadd(cr, nz_carry(rk, dpc, cur));
-                    }
+                    cur = znx_middle_step(rk, 0, cur, res_carry);
                     res_carry = wadd(res_carry, a_carry);
                     done = true;
                     break;
@@ -773,17 +706,7 @@ __global__ void __launch_bounds__(256) k_normalize_cross(NzArgs g, long long res
         long long c = (a_start == a_end) ? a_carry : res_carry;
         for (int j = 0; j < res_end; ++j) {
             long long* rp = r + (long long)(res_end - j - 1) * rls;
-            const long long x = *rp;
-            const long long d = nz_digit(rk, x);
-            if (j == res_end - 1) {
-                *rp = nz_digit(rk, wadd(d, c));
-            } else {
-                const long long cr = nz_carry(rk, x, d);
-                const long long dpc = wadd(d, c);
-                const long long x1 = nz_digit(rk, dpc);
-                *rp = x1;
-                c = wadd(cr, nz_carry(rk, dpc, x1));
-            }
+            *rp = j == res_end - 1 ? znx_final_step(rk, 0, *rp, c) : znx_middle_step(rk, 0, *rp, c);
         }
     }
 }
@@ -807,7 +730,6 @@ __global__ void __launch_bounds__(256) k_rsh_assign(RshArgs g) {
     const int k_rem = g.k % bk;
     if (k_rem != 0) steps += 1;
     const int lsh = (bk - k_rem) % bk;
-    const int kk = lsh == 0 ? bk : bk - lsh;
     if (steps > g.size) steps = g.size;
     const long long ls = (long long)g.cols * g.n;   // limb stride
     // grid = (blocks along a column, columns, batch): no per-thread division
@@ -820,28 +742,15 @@ __global__ void __launch_bounds__(256) k_rsh_assign(RshArgs g) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const long long v = h ? v2.y : v2.x;
-            const long long d = nz_digit(kk, v);
-            const long long cr = nz_carry(kk, v, d);
-            if (j == 0) {
-                carry[h] = cr;
-            } else {
-                const long long dpc = wadd(wshl(d, lsh), carry[h]);
-                carry[h] = wadd(cr, nz_carry(bk, dpc, nz_digit(bk, dpc)));
-            }
+            if (j == 0) carry[h] = znx_first_step_carry_only(bk, lsh, v);
+            else znx_middle_step_carry_only(bk, lsh, v, carry[h]);
         }
     }
     for (int j = 0; j + steps < g.size; ++j) {   // shifted normalization (:228-232)
         const longlong2 v2 = *reinterpret_cast<const longlong2*>(base + (long long)(g.size - steps - j - 1) * ls);
         long long nv[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long v = h ? v2.y : v2.x;
-            const long long d = nz_digit(kk, v);
-            const long long cr = nz_carry(kk, v, d);
-            const long long dpc = wadd(wshl(d, lsh), carry[h]);
-            nv[h] = nz_digit(bk, dpc);
-            carry[h] = wadd(cr, nz_carry(bk, dpc, nv[h]));
-        }
+        for (int h = 0; h < 2; ++h) nv[h] = znx_middle_step(bk, lsh, h ? v2.y : v2.x, carry[h]);
         *reinterpret_cast<longlong2*>(base + (long long)(g.size - j - 1) * ls) = make_longlong2(nv[0], nv[1]);
     }
     for (int j = 0; j < steps; ++j) {   // top limbs (:235-242), literally: zero limb j, then step limb steps-1-j
@@ -851,10 +760,7 @@ __global__ void __launch_bounds__(256) k_rsh_assign(RshArgs g) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const long long v = h ? v2.y : v2.x;
-            const long long d = nz_digit(kk, v);
-            const long long dpc = wadd(wshl(d, lsh), carry[h]);
-            nv[h] = nz_digit(bk, dpc);
-            if (j != 0) carry[h] = wadd(nz_carry(kk, v, d), nz_carry(bk, dpc, nv[h]));
+            nv[h] = j == 0 ? znx_final_step(bk, lsh, v, carry[h]) : znx_middle_step(bk, lsh, v, carry[h]);
         }
         *reinterpret_cast<longlong2*>(base + (long long)(steps - j - 1) * ls) = make_longlong2(nv[0], nv[1]);
     }
@@ -881,27 +787,6 @@ struct PackArgs {
     unsigned t;
     unsigned char lo[64], hi[64];
 };
-__device__ __forceinline__ long long wsub(long long a, long long b) {
-    return (long long)((unsigned long long)a - (unsigned long long)b);
-}
-// one step of the one-bit shift: limb value v in front of the carry; returns the limb's new value
-__device__ __forceinline__ long long pack_rsh_step(int bk, int lsh, long long v, long long& carry) {
-    const long long d = nz_digit(1, v);
-    const long long cr = nz_carry(1, v, d);
-    const long long dpc = wadd(wshl(d, lsh), carry);
-    const long long nv = nz_digit(bk, dpc);
-    carry = wadd(cr, nz_carry(bk, dpc, nv));
-    return nv;
-}
-// znx_normalize_middle_step<true> with lsh = 0 (normalization.rs:179-221)
-__device__ __forceinline__ long long pack_nz_step(int bk, long long x, long long& carry) {
-    const long long d = nz_digit(bk, x);
-    const long long cr = nz_carry(bk, x, d);
-    const long long dpc = wadd(d, carry);
-    const long long x1 = nz_digit(bk, dpc);
-    carry = wadd(cr, nz_carry(bk, dpc, x1));
-    return x1;
-}
 
 __global__ void __launch_bounds__(256) k_pack_pre(PackArgs g) {
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -919,7 +804,7 @@ __global__ void __launch_bounds__(256) k_pack_pre(PackArgs g) {
     long long av = a[(long long)(g.size - 1) * ls], bv = bp[(long long)(g.size - 1) * ls];
     if (neg) av = wsub(0, av);
     long long s = wadd(av, bv), d = wsub(av, bv);
-    long long cs = nz_carry(1, s, nz_digit(1, s)), cd = nz_carry(1, d, nz_digit(1, d));   // the limb that falls off: carry only
+    long long cs = znx_first_step_carry_only(bk, lsh, s), cd = znx_first_step_carry_only(bk, lsh, d);   // the limb that falls off
     long long cn = 0;
     for (int L = g.size - 1; L >= 1; --L) {
         av = a[(long long)(L - 1) * ls];
@@ -927,11 +812,11 @@ __global__ void __launch_bounds__(256) k_pack_pre(PackArgs g) {
         if (neg) av = wsub(0, av);
         s = wadd(av, bv);
         d = wsub(av, bv);
-        bp[(long long)L * ls] = pack_rsh_step(bk, lsh, s, cs);
-        dp[(long long)L * ls] = pack_nz_step(bk, pack_rsh_step(bk, lsh, d, cd), cn);
+        bp[(long long)L * ls] = znx_middle_step(bk, lsh, s, cs);
+        dp[(long long)L * ls] = znx_middle_step(bk, 0, znx_middle_step(bk, lsh, d, cd), cn);
     }
-    bp[0] = nz_digit(bk, cs);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
-    dp[0] = pack_nz_step(bk, nz_digit(bk, cd), cn);
+    bp[0] = znx_final_step(bk, lsh, 0, cs);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
+    dp[0] = znx_middle_step(bk, 0, znx_final_step(bk, lsh, 0, cd), cn);
 }
 
 __global__ void __launch_bounds__(256) k_pack_post(PackArgs g) {
@@ -949,7 +834,7 @@ __global__ void __launch_bounds__(256) k_pack_post(PackArgs g) {
     const int bk = g.base2k;
     long long cn = 0;
     for (int L = g.size - 1; L >= 0; --L) {
-        const long long x1 = pack_nz_step(bk, wsub(sp[(long long)L * ls], dp[(long long)L * ls]), cn);
+        const long long x1 = znx_middle_step(bk, 0, wsub(sp[(long long)L * ls], dp[(long long)L * ls]), cn);
         r[(long long)L * ls] = neg ? wsub(0, x1) : x1;
     }
 }
@@ -993,13 +878,13 @@ __global__ void __launch_bounds__(256) k_word_pre(WordPreArgs g) {
     const int bk = g.base2k, lsh = bk - 1;
     long long v = a[(long long)(g.size - 1) * ls];
     if (neg) v = wsub(0, v);
-    long long carry = nz_carry(1, v, nz_digit(1, v));   // the limb that falls off: carry only
+    long long carry = znx_first_step_carry_only(bk, lsh, v);   // the limb that falls off
     for (int L = g.size - 1; L >= 1; --L) {
         v = a[(long long)(L - 1) * ls];
         if (neg) v = wsub(0, v);
-        o[(long long)L * ls] = pack_rsh_step(bk, lsh, v, carry);
+        o[(long long)L * ls] = znx_middle_step(bk, lsh, v, carry);
     }
-    o[0] = nz_digit(bk, carry);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
+    o[0] = znx_final_step(bk, lsh, 0, carry);   // the top limb: zeroed, then the step on that zero (shift.rs:235-242)
 }
 
 struct WordPostArgs {

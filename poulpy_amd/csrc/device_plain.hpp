@@ -5,7 +5,7 @@
 // imaginary part stays inside the thread) walks every column.  A column's limbs at the thread's coefficients are read ONCE into the
 // thread's own LDS slice (the reference reads the whole column into res_big before it normalizes, so the assign forms may overwrite it
 // afterwards); the product limbs sum_j a[k + offset - j] * b[j] (wrapping i64, convolution.rs:147-203) are formed from that slice as the
-// carry chain of vec_znx_big_normalize asks for them (normalize.rs:50-144, same base2k, any res_offset) and never stored.
+// carry chain of vec_znx_big_normalize asks for them (znx_normalize_inter_walk of znx_steps.hpp: same base2k, any res_offset) and never stored.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +18,7 @@ constexpr int kMulConstMaxB = 32;       // constant digits carried in the kernel
 constexpr int kMulConstMaxA = 64;       // operand limbs staged in LDS
 constexpr int kMulConstBlock = 128;
 
-// the normalization plan of one arm (normalize.rs:83-101) and its product (convolution.rs:160-165)
+// the normalization plan of one arm (ZnxInterPlan without lsh, which the arms share) and its product (convolution.rs:160-165)
 struct MulConstArm {
     long long b[kMulConstMaxB];
     int b_size, big_size, min_size, offset;
@@ -33,11 +33,6 @@ struct MulConstArgs {
     int form;
     MulConstArm arm[2];
 };
-
-__host__ __device__ __forceinline__ long long mc_digit(int k, long long x) { return (long long)((unsigned long long)x << (64 - k)) >> (64 - k); }
-__host__ __device__ __forceinline__ long long mc_carry(int k, long long x, long long d) { return (long long)((unsigned long long)x - (unsigned long long)d) >> k; }
-__host__ __device__ __forceinline__ long long mc_add(long long a, long long b) { return (long long)((unsigned long long)a + (unsigned long long)b); }
-__host__ __device__ __forceinline__ long long mc_shl(long long a, int s) { return (long long)((unsigned long long)a << s); }
 
 // product limb kk of res_big (convolution.rs:395-421; limbs >= min_size are the zeroed tail, :199-202); `la` = the operand limbs of
 // this thread's coefficient, limb l at la[l * kMulConstBlock]
@@ -56,61 +51,29 @@ __host__ __device__ __forceinline__ long long mc_big(const MulConstArm& w, const
 __host__ __device__ __forceinline__ void mc_put(long long* r, int mode, long long v) {
     if (mode == 1) *r = v;
     else if (mode == 2) *r = (long long)(0ull - (unsigned long long)v);
-    else if (mode == 3) *r = mc_add(*r, v);
+    else if (mode == 3) *r = wadd(*r, v);
     else *r = (long long)((unsigned long long)*r - (unsigned long long)v);
 }
-// vec_znx_normalize_inter_base2k (normalize.rs:50-144), the walk of k_normalize_inter (device_ops.hpp) on the product limbs
+// vec_znx_normalize_inter_base2k on the product limbs, which are formed as the walk asks for them
 __host__ __device__ __forceinline__ void mc_walk(const MulConstArgs& g, const MulConstArm& w, const long long* la, long long* r, long long rls, int mode) {
-    const int k = g.k, lsh = g.lsh, kk = lsh == 0 ? k : k - lsh;
-    long long c = 0;
-    const int a_out_range = w.big_size > w.a_start ? w.big_size - w.a_start : 0;
-    for (int j = 0; j < a_out_range; ++j) {
-        const long long x = mc_big(w, la, g.a_size, w.big_size - j - 1);
-        const long long d = mc_digit(kk, x);
-        const long long cr = mc_carry(kk, x, d);
-        if (j == 0) c = cr;
-        else {
-            const long long dpc = mc_add(mc_shl(d, lsh), c);
-            c = mc_add(cr, mc_carry(k, dpc, mc_digit(k, dpc)));
-        }
-    }
-    for (int j = w.res_start; j < g.res_size; ++j) mc_put(r + (long long)j * rls, mode, 0);
-    const int mid = w.a_start > w.a_end ? w.a_start - w.a_end : 0;
-    for (int j = 0; j < mid; ++j) {
-        const long long x = mc_big(w, la, g.a_size, w.a_start - j - 1);
-        const long long d = mc_digit(kk, x);
-        const long long cr = mc_carry(kk, x, d);
-        const long long dpc = mc_add(mc_shl(d, lsh), c);
-        const long long x1 = mc_digit(k, dpc);
-        mc_put(r + (long long)(w.res_start - j - 1) * rls, mode, x1);
-        c = mc_add(cr, mc_carry(k, dpc, x1));
-    }
-    for (int j = 0; j < w.res_end; ++j) {
-        const long long x1 = mc_digit(k, c);
-        mc_put(r + (long long)(w.res_end - j - 1) * rls, mode, x1);
-        if (j != w.res_end - 1) c = mc_carry(k, c, x1);
-    }
+    const ZnxInterPlan plan{g.lsh, w.res_end, w.res_start, w.a_end, w.a_start};
+    znx_normalize_inter_walk(
+        plan, g.k, g.res_size, w.big_size, [&](int l) { return mc_big(w, la, g.a_size, l); },
+        [&](int j, long long v) { mc_put(r + (long long)j * rls, mode, v); });
 }
 
-// the normalization plan of a product (normalize.rs:83-101) and of its arms (convolution.rs:160-162) into g: everything but the pointers,
-// the strides and the grid
+// the normalization plan of a product and of its arms (convolution.rs:160-162) into g: everything but the pointers, the strides and the grid
 inline void mul_const_plan(MulConstArgs& g, int a_size, int res_size, int base2k, long long res_offset, int form, const MulConstArmSpec* arms) {
     g.a_size = a_size; g.res_size = res_size; g.k = base2k; g.form = form;
-    const long long k = base2k;
-    long long lsh = res_offset % k, lo = res_offset / k;   // normalize.rs:83-101
-    if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
-    g.lsh = (int)lsh;
-    auto cl = [](long long v, long long lo_, long long hi_) { return v < lo_ ? lo_ : (v > hi_ ? hi_ : v); };
     for (int u = 0; u < (form == 2 ? 2 : 1); ++u) {
         const MulConstArmSpec& s = arms[u];
         MulConstArm& w = g.arm[u];
         for (int j = 0; j < kMulConstMaxB; ++j) w.b[j] = j < s.b_size ? (long long)s.b[j] : 0;
         const int bound = a_size + s.b_size - 1;   // convolution.rs:160-162
         w.b_size = s.b_size; w.big_size = s.big_size; w.min_size = (s.big_size < bound ? s.big_size : bound); w.offset = (s.hi < bound ? s.hi : bound);
-        w.res_end = (int)cl(-lo, 0, res_size);
-        w.res_start = (int)cl((long long)s.big_size - lo, 0, res_size);
-        w.a_end = (int)cl(lo, 0, s.big_size);
-        w.a_start = (int)cl((long long)res_size + lo, 0, s.big_size);
+        const ZnxInterPlan p = znx_inter_plan(res_size, s.big_size, base2k, res_offset);
+        g.lsh = p.lsh;
+        w.res_end = p.res_end; w.res_start = p.res_start; w.a_end = p.a_end; w.a_start = p.a_start;
     }
     if (form != 2) g.arm[1] = g.arm[0];
 }

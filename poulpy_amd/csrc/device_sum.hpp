@@ -11,7 +11,7 @@
 //   sum_t sign_t 2^(T_t) ( sum_{j < min_size} (a[j + steps] << k_rem) 2^((res_size-1-j) base2k) + c_t 2^((res_size-min_size) base2k) )
 //
 // with steps / k_rem / min_size of shift.rs:90-104 (a plain join: 0 / 0 / min(res_size, a_size), no prologue), c_t the prologue's carry
-// computed by the reference's own steps, and T_t the bits by which later PZ_JOIN_LSH_ACC joins shift the running sum.  sum_plan folds
+// computed by the reference's own steps (znx_steps.hpp), and T_t the bits by which later PZ_JOIN_LSH_ACC joins shift the running sum.  sum_plan folds
 // T_t into the term on the host: output limb j reads operand limb j + off, shifted left by sh < base2k bits, while that limb lies in the
 // term's window [lo, hi); the prologue's carry enters output limb cj shifted by csh.
 //
@@ -25,6 +25,8 @@
 // sum_plan and sum_walk are __host__ __device__: tests/cpp/test_sum_walk.cpp runs them on the host against the oracle chain's digits.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "znx_steps.hpp"
 
 namespace pz {
 
@@ -133,12 +135,6 @@ __host__ __device__ __forceinline__ unsigned long long acc_take_digit(Acc128& a,
     a.hi = (unsigned long long)((long long)hi >> k);
     return d;
 }
-__host__ __device__ __forceinline__ unsigned long long sum_digit(int k, unsigned long long x) {
-    return (unsigned long long)((long long)(x << (64 - k)) >> (64 - k));
-}
-__host__ __device__ __forceinline__ unsigned long long sum_carry(int k, unsigned long long x, unsigned long long d) {
-    return (unsigned long long)((long long)(x - d) >> k);
-}
 
 // Coefficients x, x + 1 of column c of ciphertext bt.  `stage`: this thread's slice for term 0 when g.stage (limb l at stage[l * ss]).
 __host__ __device__ inline void sum_walk(const SumArgs& g, long long bt, int c, int x, ulonglong2* stage, int ss) {
@@ -156,23 +152,19 @@ __host__ __device__ inline void sum_walk(const SumArgs& g, long long bt, int c, 
             const unsigned long long* a =
                 (const unsigned long long*)t.a + ((t.flags & SUM_F_SHARED) ? 0 : bt * ls * t.size) + at;
             if (j == t.cj) {
-                // znx_normalize_first_step_carry_only on the last limb, middle_step_carry_only above it (normalization.rs:24-41, :107-129)
-                const int kk = t.k_rem == 0 ? k : k - t.k_rem;
-                unsigned long long c0 = 0, c1 = 0;
+                long long c0 = 0, c1 = 0;   // the carry of the operand limbs below the window
                 for (int l = t.size - 1; l >= t.hi; --l) {
                     const ulonglong2 v = staged ? stage[l * ss] : *reinterpret_cast<const ulonglong2*>(a + (long long)l * ls);
-                    const unsigned long long d0 = sum_digit(kk, v.x), d1 = sum_digit(kk, v.y);
-                    const unsigned long long y0 = sum_carry(kk, v.x, d0), y1 = sum_carry(kk, v.y, d1);
                     if (l == t.size - 1) {
-                        c0 = y0; c1 = y1;
+                        c0 = znx_first_step_carry_only(k, t.k_rem, (long long)v.x);
+                        c1 = znx_first_step_carry_only(k, t.k_rem, (long long)v.y);
                     } else {
-                        const unsigned long long p0 = (d0 << t.k_rem) + c0, p1 = (d1 << t.k_rem) + c1;
-                        c0 = y0 + sum_carry(k, p0, sum_digit(k, p0));
-                        c1 = y1 + sum_carry(k, p1, sum_digit(k, p1));
+                        znx_middle_step_carry_only(k, t.k_rem, (long long)v.x, c0);
+                        znx_middle_step_carry_only(k, t.k_rem, (long long)v.y, c1);
                     }
                 }
-                acc_add_shl(a0, c0, t.csh, neg);
-                acc_add_shl(a1, c1, t.csh, neg);
+                acc_add_shl(a0, (unsigned long long)c0, t.csh, neg);
+                acc_add_shl(a1, (unsigned long long)c1, t.csh, neg);
             }
             const int l = j + t.off;
             if (l >= t.lo && l < t.hi) {

@@ -277,15 +277,8 @@ int dev_normalize(pz_module* M, int batch, DV res, int res_base2k, long long res
     if (blocks == 0) return PZ_OK;
     KTimer kt(M, PZ_K_NORMALIZE);
     if (res_base2k == a_base2k) {
-        const long long k = res_base2k;
-        long long lsh = res_offset % k, lo = res_offset / k;
-        if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
-        auto cl = [](long long v, long long lo_, long long hi_) { return v < lo_ ? lo_ : (v > hi_ ? hi_ : v); };
-        g.lsh = (int)lsh;
-        g.res_end = (int)cl(-lo, 0, res.size);
-        g.res_start = (int)cl((long long)a.size - lo, 0, res.size);
-        g.a_end = (int)cl(lo, 0, a.size);
-        g.a_start = (int)cl((long long)res.size + lo, 0, a.size);
+        const ZnxInterPlan p = znx_inter_plan(res.size, a.size, res_base2k, res_offset);
+        g.lsh = p.lsh; g.res_end = p.res_end; g.res_start = p.res_start; g.a_end = p.a_end; g.a_start = p.a_start;
         if (cb) hipLaunchKernelGGL(k_normalize_inter<true>, dim3(blocks), dim3(256), 0, M->stream, g);
         else hipLaunchKernelGGL(k_normalize_inter<false>, dim3(blocks), dim3(256), 0, M->stream, g);
     } else {

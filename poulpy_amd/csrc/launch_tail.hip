@@ -197,19 +197,11 @@ int launch_inv_tail(pz_module* M, const TailCall& c) {
 // kernel in one; TailArgs::nz)
 int launch_inv_tail_nz(pz_module* M, int batch, const NzTailCall& s) {
     const int nlimbs = s.nlimbs, res_size = s.res_size, base2k = s.base2k, a_size = s.a_size;
-    const long long res_offset = s.res_offset;
     const NzCombine* cb = s.cb;
     const TailD16* d16 = s.d16;
-    const long long k = base2k;
-    long long lsh = res_offset % k, lo = res_offset / k;
-    if (res_offset < 0 && lsh != 0) { lsh = (lsh + k) % k; lo -= 1; }
-    auto cl = [](long long v, long long lo_, long long hi_) { return v < lo_ ? lo_ : (v > hi_ ? hi_ : v); };
+    const ZnxInterPlan p = znx_inter_plan(res_size, a_size, base2k, s.res_offset);
     TailNz nz;
-    nz.lsh = (int)lsh;
-    nz.res_end = (int)cl(-lo, 0, res_size);
-    nz.res_start = (int)cl((long long)a_size - lo, 0, res_size);
-    nz.a_end = (int)cl(lo, 0, a_size);
-    nz.a_start = (int)cl((long long)res_size + lo, 0, a_size);
+    nz.lsh = p.lsh; nz.res_end = p.res_end; nz.res_start = p.res_start; nz.a_end = p.a_end; nz.a_start = p.a_start;
     nz.zero_from = nz.res_start - std::max(0, nz.a_start - std::max(nlimbs, nz.a_end));
     nz.col = s.res_col;
     nz.mode = cb ? cb->mode : 1;
