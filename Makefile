@@ -64,6 +64,11 @@ cpp-test-mid:
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_mid_forms.cpp -o tests/cpp/test_mid_forms
 	tests/cpp/test_mid_forms tests/golden/mid128_forms.txt
 
+# host-only check of the fused tail's launch plan under the host sanitizers (tests/test_tail_plan_host.py builds and runs the same program)
+cpp-test-tail:
+	$(CXX) -std=c++17 -O2 -g -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/cpp/test_tail_plan.cpp -o tests/cpp/test_tail_plan
+	tests/cpp/test_tail_plan tests/golden/tail_plans.txt
+
 # the per-coefficient walk of k_lincomb_const on the host under the host sanitizers; it reads its cases from a file that
 # tests/test_ckks_lincomb_host.py writes from the oracle (that test builds and runs the same program)
 tests/cpp/test_lincomb_walk: tests/cpp/test_lincomb_walk.cpp $(wildcard $(CSRC)/*.hpp)
@@ -80,8 +85,8 @@ tests/cpp/test_znx_steps: tests/cpp/test_znx_steps.cpp $(CSRC)/znx_steps.hpp
 	$(HIPCC) -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -I $(CSRC) $< -o $@ -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined
 
 clean:
-	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_mid_forms tests/cpp/test_lincomb_walk tests/cpp/test_sum_walk tests/cpp/test_znx_steps
+	rm -f $(LIB) tests/cpp/test_abi tests/cpp/test_bdd_schedule tests/cpp/test_pack_levels tests/cpp/test_word_ops tests/cpp/test_mid_forms tests/cpp/test_tail_plan tests/cpp/test_lincomb_walk tests/cpp/test_sum_walk tests/cpp/test_znx_steps
 	rm -rf $(CSRC)/_obj
 	rm -rf oracle/_build
 
-.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack cpp-test-word cpp-test-mid kres test-cpu test-gpu bench clean
+.PHONY: all oracle cpp-test cpp-test-bdd cpp-test-pack cpp-test-word cpp-test-mid cpp-test-tail kres test-cpu test-gpu bench clean

@@ -11,7 +11,8 @@
 //   word_ops.cpp     the stage plan of the FheUint byte operations (plain C++, no HIP)
 //   launch_ops.hip   elementwise / permutation / normalize / VMP kernels (device_ops.hpp)
 //   launch_br.hip    blind-rotation kernels (device_br.hpp + the block step of device_br_ops.hpp)
-//   tail_forms.hpp / br_forms.hpp   the same for the fused tail and for the blind rotation (one-kernel forms; block-step forms in plain C++)
+//   tail_plan.hpp    which launches of k_inv_tail a call becomes: columns, role, form, refusals (plain C++, no HIP; launch_tail.hip runs the plan)
+//   tail_forms.hpp / br_forms.hpp   the launch of one form of the fused tail; the forms of the blind rotation (one-kernel forms; block-step forms in plain C++)
 //   launch_cnv.hip   bivariate convolution kernels (device_cnv.hpp)
 //   launch_plain.hip GLWE x constant / plaintext kernels (device_plain.hpp), weighted sums by constants (device_lincomb.hpp)
 //   api.hip          C ABI: module, memory, key pinning / mirrors

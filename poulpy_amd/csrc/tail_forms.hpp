@@ -1,22 +1,11 @@
-// tail_forms.hpp — the instantiations of the fused tail (k_inv_tail, device_fft.hpp) and the choice among them.  Included by two translation
-// units: launch_tail.hip instantiates the product forms (PROBE = false), launch_tail_probe.hip the same forms with the rounding-margin block
-// compiled in (PROBE = true) - they compile side by side.
+// tail_forms.hpp — the launch of one instantiation of the fused tail (k_inv_tail, device_fft.hpp); the lists of them and the choice among them are
+// tail_plan.hpp's.  Included by two translation units: launch_tail.hip instantiates the product forms (PROBE = false), launch_tail_probe.hip the
+// same forms with the rounding-margin block compiled in (PROBE = true) - they compile side by side.
 #pragma once
 #include "internal.hpp"
+#include "tail_plan.hpp"
 
 namespace pz {
-
-#define PZ_P1F_CASES(X) X(4, 1, 4) X(8, 1, 4) X(8, 1, 16) X(16, 1, 16) X(4, 4, 16) X(4, 8, 16) X(8, 8, 16) X(8, 16, 16) X(16, 16, 16) X(8, 16, 8)
-// the forms beyond the plain one - digits leaving through a one-bit vec_znx_rsh (glwe_trace), the sign-only tail of a spectral automorphism,
-// the tensoring tails - are instantiated for the 128-point-row plans (N = 2^13 .. 2^16)
-#define PZ_RSH_CASES(X) X(4, 8, 16) X(8, 8, 16) X(8, 16, 16) X(16, 16, 16)
-// the 32-bit-accumulator form (blind rotation on the pipeline): every 128-point-row plan it runs on, N = 2^12 .. 2^16
-#define PZ_ACC32_CASES(X) X(4, 4, 16) PZ_RSH_CASES(X)
-
-struct TailForm {
-    enum Kind { PLAIN, RSH, SGN, NZ1, NZ2, ACC32, NZ1W, NZ2R, NZ1O, NZ2O, SGN16, SGN16R } kind = PLAIN;   // SGN16: the sign-only form with a 16-bit operand; SGN16R: + the shifted store   // NZ1W / NZ2R: the tensoring tails with 16-bit side copies (write / read); NZ1O / NZ2O: 16-bit digits ONLY   // ACC32: 32-bit accumulator digits (blind rotation's pipeline path)
-    bool rowmajor = false, has_small = false;   // PLAIN: one instantiation per (row-major, body add) combination
-};
 
 template <bool PROBE>
 static int tail_launch_form(pz_module* M, const TailArgs& g, int blocks, const TailForm& f) {
