@@ -610,6 +610,40 @@ int pz_glwe_tensor_relinearize_batched(pz_module* m, int64_t* res, const int64_t
  * plans) the tensor only exists as 16-bit copies in the workspace: 2 B per coefficient written and read instead of 8.  Device pointers. */
 int pz_glwe_tensor_mul_relinearize_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
                                            const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, int mode, size_t batch);
+/* The same product on operands that sit in larger containers, in place, or joined to res: what poulpy-ckks's ckks_mul_assign /
+ * ckks_square_assign (leveled/default/mul.rs:86-200), ckks_mul_add_ct_into / ckks_mul_sub_ct_into and ckks_mul_many
+ * (leveled/delegates/composite.rs:239-254, :103-165) need beyond ckks_mul_into (the mapping is poulpy_amd/ckks.py and DESIGN.md 4.6f).
+ * tp, rp, mode, tsk_pmat: as above.
+ *   Operands.  a_stride / b_stride: limbs per ciphertext of the CONTAINERS of a / b (0: tp->a_size / tp->b_size; never below them).
+ *     Ciphertext i of a starts at a + i n cols a_stride and its first tp->a_size limbs are the operand (limbs are outermost inside a
+ *     ciphertext, so the limbs a rescale leaves in use are a prefix); b alike; PZ_TENSOR_SQUARE ignores b and b_stride.  The digits are
+ *     those of pz_glwe_tensor_mul_relinearize_batched on compacted copies (the reference reallocates there: ckks_compact_limbs,
+ *     layouts/ciphertext.rs:216-232; glwe_tensor_apply asserts size == effective_k.div_ceil(base2k), operations/glwe.rs:722-723).
+ *   accumulate = 0: res = the product; join, k, sign and normalize are ignored.  res may BE a and / or b: the same pointer, and that
+ *     operand's stride equal to rp->res_size (dst = dst a, dst = dst^2).  Only the first pass of a wave reads the operands and every store
+ *     to res comes behind it, so at equal strides a wave overwrites exactly what it has read and nothing is staged; at unequal strides a
+ *     wave would overwrite ciphertexts that later waves still read, which is refused.  Any other overlap of res with an operand:
+ *     PZ_ERR_ALIAS.
+ *   accumulate = 1: wave by wave (pz_module_set_chunk) the product - a normalized GLWE of rp->res_size limbs - goes to a segment of the
+ *     module's workspace, never to caller memory, and is joined to res while it is hot, with sign = +1 / -1:
+ *       PZ_JOIN_PLAIN     res +- product (k must be 0)          PZ_JOIN_LSH_TERM  res +- lsh(product, k)
+ *       PZ_JOIN_LSH_ACC   lsh(res, k), then +- product
+ *     (ckks_add_assign_unsafe / ckks_sub_assign_unsafe, leveled/default/add.rs:122-146, sub.rs alike).  normalize = 1: the join is
+ *     pz_glwe_sum_batched's two-term chain - term 0 res in place, term 1 the product - so glwe_normalize_assign follows (ckks_add_assign /
+ *     ckks_sub_assign); normalize = 0: the same two terms through pz_glwe_combine_batched's kernel, un-normalized.  The limits of those
+ *     calls hold (a PZ_JOIN_LSH_ACC by a limb or more shifts res in place: 32 limbs at the most).  res must not overlap a or b:
+ *     PZ_ERR_ALIAS.  No caller-owned scratch batch: the workspace holds one wave's product.
+ * PZ_ERR_INVALID: a stride below the operand's size, accumulate / normalize not 0 or 1, an unknown join, k != 0 on a plain join, a shift
+ * out of range, sign not +1 / -1, and whatever pz_glwe_tensor_mul_relinearize_batched refuses.  Nothing is launched on a refusal.
+ * Device pointers, 16-byte aligned.  Kernel nodes only: a call repeated with the same arguments is replayed as one HIP graph
+ * (pz_module_set_graphs); the buffers' contents may change between calls.  _workspace_bytes: what the call needs of the module's two
+ * workspaces for `batch` ciphertexts at the module's chunk setting.
+ * (The seven values that describe operands and join are plain arguments, not a struct: the parameter blocks of this header are a fixed list.) */
+size_t pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(const pz_module* m, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp,
+                                                          int accumulate, int mode, size_t batch);
+int pz_glwe_tensor_mul_relinearize_acc_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
+                                               const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t a_stride, size_t b_stride,
+                                               int accumulate, int join, size_t k, int sign, int normalize, int mode, size_t batch);
 
 /* GLWE x plaintext polynomial on `batch` device-resident ciphertexts (poulpy-core/src/operations/glwe.rs): PZ_MUL_PLAIN glwe_mul_plain
  * :184-248, PZ_MUL_PLAIN_ASSIGN glwe_mul_plain_assign :250-303.  The tensor params are reused: a / res = batch GLWEs

@@ -409,6 +409,19 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                           const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch) {
         check(pz_glwe_sum_batched(m_, res, res_cols, res_size, base2k, operands, shared, a_size, join, k, sign, nterms, batch), "glwe_sum_batched");
     }
+    // tensoring + relinearization in one call on strided operands: res = a b (accumulate = false; res may be a and / or b at equal strides)
+    // or res = join(res, a b) with the product of a wave kept in the module's workspace (poulpy_hip.h)
+    void glwe_tensor_mul_relinearize_acc_batched(int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
+                                                 const pz_glwe_tensor_params& tp, const pz_glwe_op_params& rp, size_t a_stride, size_t b_stride,
+                                                 bool accumulate, int join, size_t k, int sign, bool normalize, int mode, size_t batch) {
+        check(pz_glwe_tensor_mul_relinearize_acc_batched(m_, res, a, b, tsk_pmat, &tp, &rp, a_stride, b_stride, accumulate ? 1 : 0, join, k, sign,
+                                                         normalize ? 1 : 0, mode, batch),
+              "glwe_tensor_mul_relinearize_acc_batched");
+    }
+    size_t glwe_tensor_mul_relinearize_acc_workspace_bytes(const pz_glwe_tensor_params& tp, const pz_glwe_op_params& rp, bool accumulate, int mode,
+                                                           size_t batch) const {
+        return pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(m_, &tp, &rp, accumulate ? 1 : 0, mode, batch);
+    }
 
   private:
     pz_module* m_ = nullptr;

@@ -15,6 +15,10 @@ pz_glwe_lincomb_const_batched or, where that measured slower, the same sum term 
 Products by plaintext vectors (mul.rs:243-293), their composites and the normalized sums (composite.rs add_many, mul_add_pt_vec_znx,
 mul_sub_pt_vec_znx, dot_product_pt_vec_znx) come after the constants: the sums are ONE pz_glwe_sum_batched or, where that measured
 slower, the chain of pz_glwe_combine_batched calls.
+
+Products of two ciphertexts (mul.rs:47-200; composite.rs mul_add_ct / mul_sub_ct / mul_many) close the file: every product is ONE
+pz_glwe_tensor_mul_relinearize_acc_batched, which reads operands in larger containers by stride, runs in place, and joins the product to
+dst from the module's workspace.
 """
 from __future__ import annotations
 
@@ -806,3 +810,291 @@ def plan_dot_product_pt_vec_znx(dst: Ct, ops, pts) -> DotPlan:
         terms.append(SumTerm(i, join, k, 1, td, tb, cnv_offset))
         log_delta, log_budget = min(log_delta, td), min(log_budget, tb)
     return DotPlan(name, terms, n > 1, log_delta, log_budget)
+
+
+# ---- products of two ciphertexts (leveled/default/mul.rs:47-200, leveled/delegates/composite.rs:103-165, :239-254) -------------------------
+def checked_mul_ct_log_budget(op: str, lhs_log_budget: int, rhs_log_budget: int, lhs_log_delta: int, rhs_log_delta: int) -> int:   # error.rs:155-175
+    if max(lhs_log_delta, rhs_log_delta) > min(lhs_log_budget, rhs_log_budget):
+        raise CKKSError(f"{op}: multiplication precision underflow (lhs log_budget {lhs_log_budget}, log_delta {lhs_log_delta}; "
+                        f"rhs log_budget {rhs_log_budget}, log_delta {rhs_log_delta})")
+    return min(lhs_log_budget, rhs_log_budget) - max(lhs_log_delta, rhs_log_delta)
+
+
+def get_mul_ct_params(res: Ct, a: Ct, b: Ct):
+    """leveled/default/mul.rs:461-478 -> (res_log_budget, res_log_delta, cnv_offset)."""
+    res_log_budget = checked_mul_ct_log_budget("mul", a.log_budget, b.log_budget, a.log_delta, b.log_delta)
+    res_log_delta = min(a.log_delta, b.log_delta)
+    res_offset = max(res_log_budget + res_log_delta - res.max_k, 0)
+    cnv_offset = max(a.effective_k, b.effective_k) + res_offset
+    return checked_log_budget_sub("mul", res_log_budget, res_offset), res_log_delta, cnv_offset
+
+
+def ceil_log2(n: int) -> int:                                             # composite.rs:98-101
+    return 0 if n <= 1 else (n - 1).bit_length()
+
+
+def _operand_size(op: str, x: Ct) -> int:
+    """the limbs of x that enter glwe_tensor_apply: effective_k.div_ceil(base2k) (poulpy-core operations/glwe.rs:722-723).  The container
+    may hold more (after a rescale): the device call then takes the container's size as the stride; the reference would reallocate
+    (ckks_compact_limbs, layouts/ciphertext.rs:216-232).  It may not hold fewer."""
+    size = -(-x.effective_k // x.base2k)
+    if size < 1:
+        raise CKKSError(f"{op}: an operand of effective_k {x.effective_k} has no limb")
+    if size > x.size:
+        raise CKKSError(f"{op}: the container ({x.size} limbs) is smaller than effective_k {x.effective_k} / base2k {x.base2k}, rounded up")
+    return size
+
+
+@dataclass
+class MulPlan:
+    """ckks_mul_into / _assign, ckks_square_into / _assign (mul.rs:47-200), and with `join` ckks_mul_add_ct_into / ckks_mul_sub_ct_into
+    (composite.rs:239-254, :372-387): ONE pz_glwe_tensor_mul_relinearize_acc_batched.  which: where a / b come from at launch ("a" | "b" |
+    "dst"); b is None for a square."""
+    name: str
+    cnv_offset: int
+    log_delta: int                 # metadata of dst after the operation
+    log_budget: int
+    which: tuple = ("a", "b")
+    a_size: int = 0                # limbs of the operands (effective_k.div_ceil(base2k)) ...
+    b_size: int = 0
+    a_stride: int = 0              # ... and of their containers
+    b_stride: int = 0
+    a_effective_k: int = 0
+    b_effective_k: int = 0
+    tensor_size: int = 0           # limbs of the tensor layout: k = max(a.max_k, b.max_k)
+    join: int | None = None        # mul_add / mul_sub: the join of the product to dst, (join, k, sign), always normalized
+    k: int = 0
+    sign: int = 1
+    prod_log_delta: int = 0        # mul_add / mul_sub: what the scratch ciphertext carries (take_mul_tmp)
+    prod_log_budget: int = 0
+
+    @property
+    def square(self) -> bool:
+        return self.which[1] is None
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def params(self, dst: Ct, tsk):
+        """(pz_glwe_tensor_params, pz_glwe_op_params) of the call; tsk: the prepared tensor key's (dnum, dsize, key_size, key_base2k)"""
+        from .hal import GlweOpParams, GlweTensorParams
+        dnum, dsize, key_size, key_base2k = tsk
+        rank = dst.cols - 1
+        tp = GlweTensorParams(rank=rank, a_size=self.a_size, b_size=self.b_size, ab_base2k=dst.base2k, a_effective_k=self.a_effective_k,
+                              b_effective_k=self.b_effective_k, res_size=self.tensor_size, res_base2k=dst.base2k, cnv_offset=self.cnv_offset)
+        rp = GlweOpParams(rank=rank, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_base2k, a_size=self.tensor_size,
+                          a_base2k=dst.base2k, res_size=dst.size, res_base2k=dst.base2k, rank_out=rank)
+        return tp, rp
+
+    def launch(self, module, dst: Ct, batch: int, a: Ct | None = None, b: Ct | None = None, tsk_ptr=None, tsk=None):
+        """dst.data / a.data / b.data / tsk_ptr: device pointers; tsk = (dnum, dsize, key_size, key_base2k) of the prepared tensor key.
+        The operands named "dst" in `which` are dst itself (the _assign forms)."""
+        ops = {"a": a, "b": b, "dst": dst, None: None}
+        x, y = ops[self.which[0]], ops[self.which[1]]
+        tp, rp = self.params(dst, tsk)
+        module.glwe_tensor_mul_relinearize_acc_batched(dst.data, x.data, None if y is None else y.data, tsk_ptr, tp, rp, "square" if self.square else "apply",
+                                                       batch, a_stride=self.a_stride, b_stride=self.b_stride, accumulate=self.join is not None,
+                                                       join=self.join or PLAIN, k=self.k, sign=self.sign, normalize=True)
+        self.apply_meta(dst)
+
+
+def _mul_plan(name: str, res: Ct, a: Ct, b: Ct | None, which) -> MulPlan:
+    """get_mul_ct_params on (res, a, b) and the shapes of the call; b None: the square (get_mul_ct_params(res, a, a))"""
+    y = a if b is None else b
+    _same_layout(name, res, a, y)
+    log_budget, log_delta, cnv_offset = get_mul_ct_params(res, a, y)
+    a_size, b_size = _operand_size(name, a), _operand_size(name, y)
+    return MulPlan(name, cnv_offset, log_delta, log_budget, which, a_size, b_size, a.size, y.size, a.effective_k, y.effective_k,
+                   max(a.size, y.size))
+
+
+def plan_mul_into(dst: Ct, a: Ct, b: Ct) -> MulPlan:
+    """mul.rs:47-84."""
+    return _mul_plan("mul_into", dst, a, b, ("a", "b"))
+
+
+def plan_mul_assign(dst: Ct, a: Ct) -> MulPlan:
+    """mul.rs:86-122: dst = dst a."""
+    return _mul_plan("mul_assign", dst, dst, a, ("dst", "a"))
+
+
+def plan_square_into(dst: Ct, a: Ct) -> MulPlan:
+    """mul.rs:145-172."""
+    return _mul_plan("square_into", dst, a, None, ("a", None))
+
+
+def plan_square_assign(dst: Ct) -> MulPlan:
+    """mul.rs:174-200: dst = dst^2."""
+    return _mul_plan("square_assign", dst, dst, None, ("dst", None))
+
+
+def plan_mul_add_ct(dst: Ct, a: Ct, b: Ct, sub=False) -> MulPlan:
+    """composite.rs:239-254 / :372-387: ckks_mul_into on a scratch ciphertext of dst's layout with default metadata (take_mul_tmp), then
+    ckks_add_assign / ckks_sub_assign (normalized).  On the device the scratch product exists one wave at a time in the module's workspace."""
+    name = "mul_sub_ct" if sub else "mul_add_ct"
+    tmp = Ct(dst.base2k, dst.size, 0, 0, dst.cols)
+    p = _mul_plan(name, tmp, a, b, ("a", "b"))
+    p.prod_log_delta, p.prod_log_budget = p.log_delta, p.log_budget
+    p.join, p.k = _join(dst.log_budget, p.prod_log_budget)
+    p.sign = -1 if sub else 1
+    if p.join == LSH_ACC and p.k >= dst.base2k and dst.size > INPLACE_MAX_LIMBS:
+        raise CKKSError(f"{name}: dst ({dst.size} limbs) would be shifted in place by a limb or more; at most {INPLACE_MAX_LIMBS} limbs")
+    p.log_delta, p.log_budget = min(dst.log_delta, p.prod_log_delta), min(dst.log_budget, p.prod_log_budget)
+    return p
+
+
+def plan_mul_sub_ct(dst: Ct, a: Ct, b: Ct) -> MulPlan:
+    return plan_mul_add_ct(dst, a, b, sub=True)
+
+
+@dataclass
+class MulManyNode:
+    """one step of mul_many_rec in the reference's evaluation order.  out / a / b: "dst", ("in", i) or ("slot", s); ct: the layout and
+    metadata of the node's result (a scratch ciphertext of the recursion, or dst); op: "lsh" (one input: glwe_lsh by `shift`) | "mul"."""
+    op: str
+    out: object
+    a: object
+    b: object = None
+    ct: Ct = None
+    shift: int = 0
+    mul: MulPlan | None = None
+
+
+@dataclass
+class MulManyPlan:
+    """ckks_mul_many (composite.rs:103-198).  Every "mul" node is ONE pz_glwe_tensor_mul_relinearize_acc_batched on `batch` ciphertexts,
+    every "lsh" node one pz_glwe_combine_batched.  The intermediate products live in scratch slots (slot s: slot_limbs[s] limbs per
+    ciphertext); a slot is free again once the node that reads it has run.  Where a node's operand has fewer effective limbs than its
+    container (the reference's glwe_tensor_apply would fail its size == effective_k.div_ceil(base2k) assertion there, and the caller
+    would reallocate with ckks_compact_limbs), the call gets stride = the container's size and size = the effective one."""
+    name: str
+    nodes: list = field(default_factory=list)
+    slot_limbs: list = field(default_factory=list)
+    log_delta: int = 0
+    log_budget: int = 0
+    cols: int = 2
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def slot_offsets(self, batch: int, n: int):
+        """byte offset of every slot in the scratch buffer (256-byte aligned) and the total"""
+        offs, at = [], 0
+        for limbs in self.slot_limbs:
+            offs.append(at)
+            at += -(-(batch * self.cols * limbs * n * 8) // 256) * 256
+        return offs, at
+
+    def scratch_bytes(self, batch: int, n: int) -> int:
+        return self.slot_offsets(batch, n)[1]
+
+    def launch(self, module, dst: Ct, batch: int, inputs, tsk_ptr=None, tsk=None, tmp=None):
+        """dst.data / inputs[i].data / tsk_ptr: device pointers; tmp: a device pointer to scratch_bytes(batch, module.n()) bytes (not needed
+        for one or two inputs)."""
+        offs, total = self.slot_offsets(batch, module.n())
+        if total and tmp is None:
+            raise CKKSError(f"{self.name}: needs {total} bytes of scratch")
+        base = 0 if tmp is None else (tmp.value if hasattr(tmp, "value") else int(tmp))
+
+        def where(ref):
+            if ref == "dst":
+                return dst.data
+            if ref[0] == "in":
+                return inputs[ref[1]].data
+            return base + offs[ref[1]]
+        for nd in self.nodes:
+            out = Ct(nd.ct.base2k, nd.ct.size, 0, 0, nd.ct.cols, where(nd.out))
+            if nd.op == "lsh":
+                src = inputs[nd.a[1]]
+                module.glwe_combine_batched(out.data, out.cols, out.size, out.base2k, [dict(a=src.data, a_size=src.size, kind=LSH, k=nd.shift)], False, batch)
+                continue
+            a = Ct(0, 0, 0, 0, data=where(nd.a))
+            b = Ct(0, 0, 0, 0, data=where(nd.b))
+            nd.mul.launch(module, out, batch, a, b, tsk_ptr, tsk)
+        self.apply_meta(dst)
+
+
+def plan_mul_many(dst: Ct, inputs) -> MulManyPlan:
+    """composite.rs:103-198, mul_many_rec literally: one input is glwe_lsh by offset_unary; two are one multiplication; otherwise the
+    halves [0, len/2) and [len/2, len) into scratch ciphertexts of k = min effective_k - ceil_log2(len) log_delta (saturating), left
+    first, then their product."""
+    name = "mul_many"
+    if len(inputs) == 0:
+        raise CKKSError("ckks_mul_many: inputs must contain at least one ciphertext")
+    plan = MulManyPlan(name, cols=dst.cols)
+    live = []                                                             # slot -> in use
+
+    def take(limbs):
+        for s, used in enumerate(live):
+            if not used and plan.slot_limbs[s] == limbs:
+                live[s] = True
+                return s
+        live.append(True)
+        plan.slot_limbs.append(limbs)
+        return len(live) - 1
+
+    def rec(out_ref, out: Ct, lo: int, hi: int):
+        """writes the node(s) that leave the product of inputs[lo:hi] in `out`; returns out with its metadata"""
+        xs = inputs[lo:hi]
+        if any(c.log_delta != xs[0].log_delta for c in xs):
+            raise CKKSError("ckks_mul_many: all inputs must have the same log_delta")
+        for c in xs:
+            _same_layout(name, out, c)
+        if len(xs) == 1:
+            offset = offset_unary(out, xs[0])
+            out.log_delta = xs[0].log_delta
+            out.log_budget = checked_log_budget_sub("ckks_mul_many", xs[0].log_budget, offset)
+            plan.nodes.append(MulManyNode("lsh", out_ref, ("in", lo), None, Ct(out.base2k, out.size, out.log_delta, out.log_budget, out.cols), offset))
+            return out
+        if len(xs) == 2:
+            a_ref, b_ref, a, b = ("in", lo), ("in", lo + 1), xs[0], xs[1]
+            freed = ()
+        else:
+            mid = len(xs) // 2
+            log_delta = xs[0].log_delta
+            layouts = []
+            for part in (xs[:mid], xs[mid:]):
+                k = max(min(c.effective_k for c in part) - ceil_log2(len(part)) * log_delta, 0)
+                layouts.append(-(-k // out.base2k))
+            # take_glwe(left), take_glwe(right), then the two recursions on what is left of the scratch (composite.rs:154-160)
+            ls, rs = take(layouts[0]), take(layouts[1])
+            a = rec(("slot", ls), Ct(out.base2k, layouts[0], 0, 0, out.cols), lo, lo + mid)
+            b = rec(("slot", rs), Ct(out.base2k, layouts[1], 0, 0, out.cols), lo + mid, hi)
+            a_ref, b_ref, freed = ("slot", ls), ("slot", rs), (ls, rs)
+        mul = _mul_plan(name, out, a, b, ("a", "b"))
+        mul.apply_meta(out)
+        plan.nodes.append(MulManyNode("mul", out_ref, a_ref, b_ref, Ct(out.base2k, out.size, out.log_delta, out.log_budget, out.cols), 0, mul))
+        for s in freed:
+            live[s] = False
+        return out
+
+    top = rec("dst", Ct(dst.base2k, dst.size, 0, 0, dst.cols), 0, len(inputs))
+    plan.log_delta, plan.log_budget = top.log_delta, top.log_budget
+    return plan
+
+
+@dataclass
+class CompactPlan:
+    """ckks_compact_limbs into another container (layouts/ciphertext.rs:216-232: reallocate to effective_k.div_ceil(base2k) limbs): one
+    pz_vec_znx_copy_batched per column.  For callers who want the memory back; the products above read a larger container in place."""
+    name: str
+    size: int
+    log_delta: int
+    log_budget: int
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def launch(self, module, dst: Ct, batch: int, src: Ct):
+        for c in range(dst.cols):
+            module.vec_znx_copy_batched(batch, dst.data, dst.cols, dst.size, c, src.data, src.cols, src.size, c)
+        self.apply_meta(dst)
+
+
+def plan_compact_limbs_copy(dst: Ct, src: Ct) -> CompactPlan:
+    """dst: a container of exactly src.effective_k.div_ceil(base2k) limbs; takes src's first limbs and its metadata."""
+    _same_layout("compact_limbs", dst, src)
+    size = _operand_size("compact_limbs", src)
+    if dst.size != size:
+        raise CKKSError(f"compact_limbs: dst has {dst.size} limbs, effective_k {src.effective_k} / base2k {src.base2k} rounds up to {size}")
+    return CompactPlan("compact_limbs_copy", size, src.log_delta, src.log_budget)

@@ -199,6 +199,9 @@ struct TensorWave {
     TensorPlan t;
     bool square, add;
     long long n;
+    // i64 elements between consecutive ciphertexts of a / b; 0: packed (n cols a_size).  Only pass 1 reads the operands, so a container
+    // with more limbs than the operand uses (a rescaled ciphertext: the used limbs are a prefix) is read in place
+    long long a_cs = 0, b_cs = 0;
     // workspace of a wave
     double *pa = nullptr, *pb = nullptr, *rd = nullptr;
     int64_t *tmp = nullptr, *diag = nullptr;
@@ -255,7 +258,7 @@ struct TensorWave {
     // (POULPY_DBG_TENSOR_FUSED=0).  Rank 1, 16 / 8 limbs (round 4): the three terms in ONE launch - operand rows loaded and forward-transformed
     // once, the limb convolution with one operand vector in registers (k_mid_cnv3; POULPY_DBG_TENSOR_ALLTERMS=0: k_mid_cnv per term)
     int prepare(const int64_t* ab, const int64_t* bb) {
-        const long long a_ct = n * t.cols * t.a_size, b_ct = n * t.cols * t.b_size;
+        const long long a_ct = a_cs ? a_cs : n * t.cols * t.a_size, b_ct = b_cs ? b_cs : n * t.cols * t.b_size;
         static const bool fused_env = (rt_knob("POULPY_DBG_TENSOR_FUSED", 1) != 0);
         static const bool combine_ok_env = (rt_knob("POULPY_DBG_TENSOR_COMBINE", 1) != 0);
         const int bound = t.a_size + t.b_size - 1;
@@ -400,13 +403,16 @@ struct TensorWave {
     }
 };
 
-static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const pz_glwe_tensor_params* p, int mode, size_t batch);
+// a_cs / b_cs: i64 elements between consecutive ciphertexts of a / b, 0: packed (TensorWave::a_cs)
+static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const pz_glwe_tensor_params* p, int mode, size_t batch,
+                               long long a_cs = 0, long long b_cs = 0);
 int pz_glwe_tensor_apply_batched(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const pz_glwe_tensor_params* p, int mode,
                                  size_t batch) {
     PZ_ENTER(M);
     return tensor_apply_nolock(M, res, a, b, p, mode, batch);
 }
-static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const pz_glwe_tensor_params* p, int mode, size_t batch) {
+static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const pz_glwe_tensor_params* p, int mode, size_t batch,
+                               long long a_cs, long long b_cs) {
     TensorPlan t;
     PZ_TRY(tensor_plan(M, p, mode, t));
     const bool square = mode == PZ_TENSOR_SQUARE;
@@ -418,7 +424,8 @@ static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, con
     w.M = M; w.p = p; w.t = t; w.square = square; w.add = mode == PZ_TENSOR_APPLY_ADD_ASSIGN; w.n = (long long)M->n;
     const size_t chunk = tensor_chunk(M, t, batch);
     PZ_TRY(w.take_workspace(chunk));
-    const long long a_ct = w.n * t.cols * t.a_size, b_ct = w.n * t.cols * t.b_size;
+    w.a_cs = a_cs; w.b_cs = b_cs;
+    const long long a_ct = a_cs ? a_cs : w.n * t.cols * t.a_size, b_ct = b_cs ? b_cs : w.n * t.cols * t.b_size;
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         w.nb = (int)std::min(chunk, batch - b0);
         w.rb = res + (long long)b0 * w.r_ct;
@@ -433,57 +440,184 @@ static int tensor_apply_nolock(pz_module* M, int64_t* res, const int64_t* a, con
     return PZ_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// what pz_glwe_tensor_mul_relinearize_acc_batched adds to the one-call product; null: pz_glwe_tensor_mul_relinearize_batched itself
+struct MulAcc {
+    size_t a_stride, b_stride;   // limbs per ciphertext of the operand containers, 0: the operand's size
+    int accumulate, join;
+    size_t k;
+    int sign, normalize;
+};
+// everything the one-call product derives from its shapes before it launches anything
+struct MulRelinPlan {
+    TensorPlan t;
+    bool compact;                // the tensor as 16-bit digits in tile order
+    size_t chunk;
+    long long t16_cs;            // int16 elements between the tensor columns of a wave (compact)
+    size_t tensor_bytes;         // ws2: the tensor of a wave ...
+    size_t prod_bytes;           // ... and, behind it, the product of a wave (accumulate)
+};
+int mul_relin_plan(const pz_module* M, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, int mode, bool accumulate, size_t batch, MulRelinPlan& q) {
+    PZ_REQUIRE(mode == PZ_TENSOR_APPLY || mode == PZ_TENSOR_SQUARE, "glwe_tensor_mul_relinearize: mode is apply or square");
+    PZ_TRY(tensor_plan(M, tp, mode, q.t));
+    const TensorPlan& t = q.t;
+    PZ_REQUIRE(rp != nullptr, "null params");
+    PZ_REQUIRE(rp->rank == tp->rank && rp->rank_out == rp->rank, "glwe_tensor_mul_relinearize: the tensor key maps rank (rank + 1) / 2 -> rank");
+    PZ_REQUIRE(rp->a_size == tp->res_size && rp->a_base2k == tp->res_base2k, "glwe_tensor_mul_relinearize: (a_size, a_base2k) of the relinearization describe the tensor");
+    static const bool combine_env = (rt_knob("POULPY_DBG_TENSOR_COMBINE", 1) != 0), fused_env = (rt_knob("POULPY_DBG_TENSOR_FUSED", 1) != 0);
+    q.compact = combine_env && fused_env && tp->res_base2k <= 14 && tp->res_base2k == tp->ab_base2k && t.cols <= 3 && t.dft_size >= 1 &&
+                mid_cnv_supported(M, t.a_size, t.b_size, std::min(t.dft_size, t.a_size + t.b_size - 1)) && glwe_relin_t16_supported(M, rp);
+    q.chunk = std::min(tensor_chunk(M, t, batch), glwe_relin_chunk(M, rp, batch));
+    // the tensor of a wave: ws2 (the two halves of the call carve the main workspace one after the other).  16-bit form: the columns of a wave
+    // sit a fraction of the 4 MiB channel interleave out of phase - the pairwise tail reads two columns and writes the third at the same offset,
+    // the relinearization's tail reads one beside its spectrum and result streams (as T2' against the result, kT2Phase in api_glwe.hip)
+    static constexpr long long t16_phase = 768 * 1024 / 2;
+    q.t16_cs = (long long)q.chunk * t.res_size * (long long)M->n + t16_phase;
+    const size_t tensor_ct = (size_t)M->n * t.tcols * t.res_size;
+    q.tensor_bytes = q.compact ? (size_t)q.t16_cs * t.tcols * 2 : q.chunk * tensor_ct * 8;
+    q.prod_bytes = accumulate ? q.chunk * (size_t)M->n * t.cols * (size_t)rp->res_size * 8 : 0;
+    return PZ_OK;
+}
+bool ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const char *a = (const char*)p, *b = (const char*)q;
+    return a < b + qn && b < a + pn;
+}
+// the join of a wave's product (in the workspace) to res: pz_glwe_sum_batched's two-term chain - term 0 res in place, term 1 the product
+// with (join, k, sign) - or, un-normalized, the same two terms through pz_glwe_combine_batched's kernel
+int mul_acc_join(pz_module* M, int64_t* res, const int64_t* prod, const pz_glwe_op_params* rp, const MulAcc& ap, size_t nb, bool dry) {
+    const size_t cols = rp->rank + 1, size = rp->res_size, base2k = rp->res_base2k;
+    const int64_t* ops[2] = {res, prod};
+    if (ap.normalize) {
+        const int shared[2] = {0, 0}, join[2] = {PZ_JOIN_PLAIN, ap.join}, sign[2] = {1, ap.sign};
+        const size_t a_size[2] = {size, size}, k[2] = {0, ap.k};
+        return glwe_sum_nolock(M, res, cols, size, base2k, ops, shared, a_size, join, k, sign, 2, nb, dry);
+    }
+    const bool acc = ap.join == PZ_JOIN_LSH_ACC, term = ap.join == PZ_JOIN_LSH_TERM;
+    const pz_glwe_term terms[2] = {{size, acc ? ap.k : 0, base2k, acc ? PZ_TERM_LSH : PZ_TERM_RAW, 1, 0, 0},
+                                   {size, term ? ap.k : 0, base2k, term ? PZ_TERM_LSH : PZ_TERM_RAW, ap.sign, 0, 0}};
+    return glwe_combine_nolock(M, res, cols, size, base2k, ops, terms, 2, 0, nb, dry);
+}
+
 // glwe_tensor_apply (or _square_apply) followed by glwe_tensor_relinearize with the GLWETensor in scratch - poulpy-ckks's multiplication
 // (poulpy-ckks/src/leveled/default/mul.rs:49-85 ckks_mul_into_default, :131-170 the square: `tmp` is taken from the scratch space, filled by
 // glwe_tensor_apply and consumed by glwe_tensor_relinearize; operations/glwe.rs:609-913 and :541-607).  The tensor never reaches the caller, so
 // where its digits fit 16 bits (one base2k <= 14 throughout, pipeline plans) it only ever exists as int16 copies in the tails' own tile
 // order: the tensoring tails write 2 B per coefficient instead of 8, the relinearization's forward pass and tail read 2 B instead of 8
 // (9.6 GB less HBM traffic per 256 multiplications at N = 2^16, 16 limbs).  Everywhere else: the i64 tensor in the workspace, the two calls as they are.
+// ap (pz_glwe_tensor_mul_relinearize_acc_batched): strided operands, the alias rule, the product joined to res wave by wave.
+int mul_relin_run(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat, const pz_glwe_tensor_params* tp,
+                  const pz_glwe_op_params* rp, const MulAcc* ap, int mode, size_t batch) {
+    const bool accumulate = ap && ap->accumulate;
+    MulRelinPlan q;
+    PZ_TRY(mul_relin_plan(M, tp, rp, mode, accumulate, batch, q));
+    const TensorPlan& t = q.t;
+    const bool square = mode == PZ_TENSOR_SQUARE;
+    if (square) b = a;
+    const long long n = (long long)M->n;
+    size_t a_stride = t.a_size, b_stride = t.b_size;
+    if (ap) {
+        PZ_REQUIRE(batch <= (size_t)1 << 24, "glwe_tensor_mul_relinearize_acc: batch out of range");
+        PZ_REQUIRE(ap->accumulate == 0 || ap->accumulate == 1, "glwe_tensor_mul_relinearize_acc: accumulate must be 0 or 1");
+        if (ap->a_stride) a_stride = ap->a_stride;
+        if (square) b_stride = a_stride;
+        else if (ap->b_stride) b_stride = ap->b_stride;
+        PZ_REQUIRE(a_stride >= (size_t)t.a_size && b_stride >= (size_t)t.b_size && a_stride <= 4096 && b_stride <= 4096,
+                   "glwe_tensor_mul_relinearize_acc: a stride (%zu, %zu limbs) is below the operand's size (%d, %d) or out of range", a_stride, b_stride,
+                   t.a_size, t.b_size);
+        if (accumulate) {
+            PZ_REQUIRE(ap->join == PZ_JOIN_PLAIN || ap->join == PZ_JOIN_LSH_TERM || ap->join == PZ_JOIN_LSH_ACC, "glwe_tensor_mul_relinearize_acc: unknown join");
+            PZ_REQUIRE(ap->sign == 1 || ap->sign == -1, "glwe_tensor_mul_relinearize_acc: sign must be +1 or -1");
+            PZ_REQUIRE(ap->normalize == 0 || ap->normalize == 1, "glwe_tensor_mul_relinearize_acc: normalize must be 0 or 1");
+            PZ_REQUIRE(ap->join == PZ_JOIN_PLAIN ? ap->k == 0 : ap->k <= ((size_t)1 << 40), "glwe_tensor_mul_relinearize_acc: shift out of range (a plain join takes k = 0)");
+        }
+    }
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && is_device_ptr(b) && is_device_ptr(tsk_pmat), "batched entry points take device pointers");
+    const long long a_ct = n * t.cols * (long long)a_stride, b_ct = n * t.cols * (long long)b_stride, res_ct = n * t.cols * (long long)rp->res_size;
+    if (ap) {
+        // Only pass 1 of a wave reads the operands, and it is issued in front of every kernel of the wave that stores (the relinearization's
+        // tail alone writes caller memory).  With res == an operand at equal strides wave w stores exactly the ciphertexts it has read and
+        // later waves read other ones: no case needs staging.  At unequal strides wave w's stores would reach ciphertexts a later wave
+        // still reads - refused, like every partial overlap.
+        const size_t res_ext = batch * (size_t)res_ct * 8;
+        const struct { const int64_t* p; size_t stride, ext; const char* name; } opnd[2] = {{a, a_stride, batch * (size_t)a_ct * 8, "a"}, {b, b_stride, batch * (size_t)b_ct * 8, "b"}};
+        for (int u = 0; u < (square ? 1 : 2); ++u) {
+            const bool same = (const void*)opnd[u].p == (const void*)res && opnd[u].stride == rp->res_size && !accumulate;
+            if (!same && batch > 0 && ranges_overlap(opnd[u].p, opnd[u].ext, res, res_ext))
+                return fail(PZ_ERR_ALIAS, "glwe_tensor_mul_relinearize_acc: res overlaps %s (accumulate = 0 takes res == %s at a stride of res_size limbs)", opnd[u].name, opnd[u].name);
+        }
+    }
+    if (batch == 0) return PZ_OK;
+    PZ_TRY(ws2_reserve(M, accumulate ? align256(q.tensor_bytes) + q.prod_bytes : q.tensor_bytes));
+    void* tensor = M->ws2;
+    int64_t* prod = nullptr;
+    if (accumulate) {   // (the plain product keeps the tensor at the head of ws2, without a segment of its own, as before)
+        char* base = (char*)M->ws2;
+        PZ_TRY(ws_take(M, base, align256(q.tensor_bytes), &tensor));
+        PZ_TRY(ws_take(M, base, q.prod_bytes, &prod));
+        PZ_TRY(mul_acc_join(M, res, prod, rp, *ap, std::min(q.chunk, batch), true));   // what the join would refuse, before anything is launched
+    }
+    if (q.compact) dispatch_note(M, "glwe_tensor_mul_relinearize: 16-bit tensor in tile order");
+    auto waves = [&]() -> int {
+        TensorWave w;
+        w.M = M; w.p = tp; w.t = t; w.square = square; w.add = false; w.n = n;
+        w.a_cs = a_ct; w.b_cs = b_ct;
+        for (size_t b0 = 0; b0 < batch; b0 += q.chunk) {
+            const size_t nb = std::min(q.chunk, batch - b0);
+            int64_t* rw = res + (long long)b0 * res_ct;
+            int64_t* r0 = accumulate ? prod : rw;
+            if (!q.compact) {
+                // (not through the public entry points: the module lock is held)
+                PZ_TRY(tensor_apply_nolock(M, (int64_t*)tensor, a + (long long)b0 * a_ct, b + (long long)b0 * b_ct, tp, mode, nb, a_ct, b_ct));
+                PZ_TRY(glwe_op(M, GlweKind::TensorRelin, r0, (const int64_t*)tensor, tsk_pmat, rp, nb));
+            } else {
+                PZ_TRY(w.take_workspace(nb));
+                w.nb = (int)nb; w.rb = nullptr; w.t16 = (short*)tensor; w.t16_cs = q.t16_cs;
+                PZ_TRY(w.prepare(a + (long long)b0 * a_ct, b + (long long)b0 * b_ct));
+                PZ_REQUIRE(w.fused, "glwe_tensor_mul_relinearize: the fused tensoring path was expected here");
+                PZ_TRY(w.combine_in_stores());
+                PZ_TRY(glwe_relin_t16(M, r0, (const short*)tensor, q.t16_cs, tsk_pmat, rp, nb));
+            }
+            if (accumulate) PZ_TRY(mul_acc_join(M, rw, prod, rp, *ap, nb, false));
+        }
+        return PZ_OK;
+    };
+    if (!ap) return waves();
+    // kernel nodes only: a call repeated with the same arguments replays as one graph
+    KeyHash key = graph_key(M, GRAPH_TENSOR_MUL_ACC, res, a, b, tsk_pmat, *tp, *rp, a_stride, b_stride, ap->accumulate, mode, batch);
+    if (accumulate) { key.add(ap->join); key.add(ap->k); key.add(ap->sign); key.add(ap->normalize); }
+    return with_graph(M, key.h, waves);
+}
+
+}  // namespace
+
+extern "C" {
+
 int pz_glwe_tensor_mul_relinearize_batched(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
                                            const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, int mode, size_t batch) {
     PZ_ENTER(M);
-    PZ_REQUIRE(mode == PZ_TENSOR_APPLY || mode == PZ_TENSOR_SQUARE, "glwe_tensor_mul_relinearize: mode is apply or square");
-    TensorPlan t;
-    PZ_TRY(tensor_plan(M, tp, mode, t));
-    PZ_REQUIRE(rp != nullptr, "null params");
-    PZ_REQUIRE(rp->rank == tp->rank && rp->rank_out == rp->rank, "glwe_tensor_mul_relinearize: the tensor key maps rank (rank + 1) / 2 -> rank");
-    PZ_REQUIRE(rp->a_size == tp->res_size && rp->a_base2k == tp->res_base2k, "glwe_tensor_mul_relinearize: (a_size, a_base2k) of the relinearization describe the tensor");
-    const bool square = mode == PZ_TENSOR_SQUARE;
-    if (square) b = a;
-    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(a) && is_device_ptr(b) && is_device_ptr(tsk_pmat), "batched entry points take device pointers");
-    if (batch == 0) return PZ_OK;
-    TensorWave w;
-    w.M = M; w.p = tp; w.t = t; w.square = square; w.add = false; w.n = (long long)M->n;
-    static const bool combine_env = (rt_knob("POULPY_DBG_TENSOR_COMBINE", 1) != 0), fused_env = (rt_knob("POULPY_DBG_TENSOR_FUSED", 1) != 0);
-    const bool compact = combine_env && fused_env && tp->res_base2k <= 14 && tp->res_base2k == tp->ab_base2k && t.cols <= 3 && t.dft_size >= 1 &&
-                         mid_cnv_supported(M, t.a_size, t.b_size, std::min(t.dft_size, t.a_size + t.b_size - 1)) && glwe_relin_t16_supported(M, rp);
-    const size_t chunk = std::min(tensor_chunk(M, t, batch), glwe_relin_chunk(M, rp, batch));
-    const long long a_ct = w.n * t.cols * t.a_size, b_ct = w.n * t.cols * t.b_size, res_ct = w.n * t.cols * (long long)rp->res_size;
-    const long long tensor_ct = w.n * t.tcols * t.res_size;
-    // the tensor of a wave: ws2 (the two halves of the call carve the main workspace one after the other).  16-bit form: the columns of a wave
-    // sit a fraction of the 4 MiB channel interleave out of phase - the pairwise tail reads two columns and writes the third at the same offset,
-    // the relinearization's tail reads one beside its spectrum and result streams (as T2' against the result, kT2Phase in api_glwe.hip)
-    static constexpr long long t16_phase = 768 * 1024 / 2;
-    const long long t16_cs = (long long)chunk * t.res_size * w.n + t16_phase;
-    PZ_TRY(ws2_reserve(M, compact ? (size_t)t16_cs * t.tcols * 2 : chunk * (size_t)tensor_ct * 8));
-    if (compact) dispatch_note(M, "glwe_tensor_mul_relinearize: 16-bit tensor in tile order");
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = std::min(chunk, batch - b0);
-        int64_t* r0 = res + (long long)b0 * res_ct;
-        if (!compact) {
-            // (not through the public entry points: the module lock is held)
-            PZ_TRY(tensor_apply_nolock(M, (int64_t*)M->ws2, a + (long long)b0 * a_ct, b + (long long)b0 * b_ct, tp, mode, nb));
-            PZ_TRY(glwe_op(M, GlweKind::TensorRelin, r0, (const int64_t*)M->ws2, tsk_pmat, rp, nb));
-            continue;
-        }
-        PZ_TRY(w.take_workspace(nb));
-        w.nb = (int)nb; w.rb = nullptr; w.t16 = (short*)M->ws2; w.t16_cs = t16_cs;
-        PZ_TRY(w.prepare(a + (long long)b0 * a_ct, b + (long long)b0 * b_ct));
-        PZ_REQUIRE(w.fused, "glwe_tensor_mul_relinearize: the fused tensoring path was expected here");
-        PZ_TRY(w.combine_in_stores());
-        PZ_TRY(glwe_relin_t16(M, r0, (const short*)M->ws2, t16_cs, tsk_pmat, rp, nb));
-    }
-    return PZ_OK;
+    return mul_relin_run(M, res, a, b, tsk_pmat, tp, rp, nullptr, mode, batch);
+}
+
+// The one-call product on strided operands, in place, or joined to res wave by wave (include/poulpy_hip.h): the plans of
+// poulpy-ckks's ckks_mul_* / ckks_square_* / ckks_mul_add_ct_into / ckks_mul_sub_ct_into / ckks_mul_many (poulpy_amd/ckks.py)
+int pz_glwe_tensor_mul_relinearize_acc_batched(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
+                                               const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t a_stride, size_t b_stride,
+                                               int accumulate, int join, size_t k, int sign, int normalize, int mode, size_t batch) {
+    PZ_ENTER(M);
+    const MulAcc ap{a_stride, b_stride, accumulate, join, k, sign, normalize};
+    return mul_relin_run(M, res, a, b, tsk_pmat, tp, rp, &ap, mode, batch);
+}
+// the module's two workspaces as that call sizes them: the larger of the tensoring's and the relinearization's carve of the main one, and
+// the tensor of a wave with (accumulate) the product of a wave behind it
+size_t pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(const pz_module* M, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp,
+                                                          int accumulate, int mode, size_t batch) {
+    MulRelinPlan q;
+    if (!M || mul_relin_plan(M, tp, rp, mode, accumulate != 0, std::max<size_t>(batch, 1), q) != PZ_OK) return 0;
+    const size_t main_ws = std::max(q.chunk * (q.t.per_ct + 6 * 256), pz_glwe_op_workspace_bytes(M, rp, q.chunk, (int)GlweKind::TensorRelin));
+    return main_ws + kGuardSlack + align256(q.tensor_bytes) + q.prod_bytes + kGuardSlack;
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // (device_combine.hpp): the shifts are the combination RAW(res) + LSH / RSH(a) on one column.  The step plans below are shift.rs's
 // (poulpy-cpu-ref reference/vec_znx/shift.rs:68-180 for LSH, :245-... for RSH), computed once per call on the host.
 #include "api_common.hpp"
+#include "glwe_call.hpp"
 #include "device_combine.hpp"
 
 namespace {
@@ -53,7 +54,7 @@ bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
 
 // validates, plans and launches; `res_col_off` = scalars to res column 0 of the walk
 int run_combine(pz_module* M, int64_t* res, long long res_bs, long long res_ls, long long res_col_off, size_t res_extent, int cols, int res_size,
-                int base2k, const TermIn* in, int nterms, int normalize, size_t batch) {
+                int base2k, const TermIn* in, int nterms, int normalize, size_t batch, bool dry = false) {
     CombArgs g;
     g.res = (long long*)res + res_col_off;
     g.res_bs = res_bs; g.res_ls = res_ls;
@@ -78,7 +79,7 @@ int run_combine(pz_module* M, int64_t* res, long long res_bs, long long res_ls, 
             staged = u;
         }
     }
-    if (batch == 0) return PZ_OK;
+    if (batch == 0 || dry) return PZ_OK;
     const long long threads = (long long)batch * cols * (M->n / 2);
     const size_t lds = staged >= 0 ? (size_t)g.t[staged].size * kCombBlock * sizeof(ulonglong2) : 0;
     KTimer kt(M, PZ_K_NORMALIZE);
@@ -115,11 +116,11 @@ int shift_acc_batched(pz_module* M, int kind, bool neg, const char* what, size_t
 
 }  // namespace
 
-extern "C" {
+namespace pz {
 
-int pz_glwe_combine_batched(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
-                            const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch) {
-    PZ_ENTER(M);
+// pz_glwe_combine_batched for a caller who holds the module lock; dry: every check and the plan, no launch
+int glwe_combine_nolock(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                        const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch, bool dry) {
     PZ_REQUIRE(res != nullptr && operands != nullptr && terms != nullptr, "glwe_combine: null argument");
     PZ_REQUIRE(nterms >= 1 && nterms <= (size_t)kCombMaxTerms, "glwe_combine: %zu terms (1 to %d)", nterms, kCombMaxTerms);
     PZ_REQUIRE(res_cols >= 1 && res_cols <= 64 && res_size >= 1 && res_size <= 4096, "glwe_combine: res shape out of range");
@@ -150,7 +151,17 @@ int pz_glwe_combine_batched(pz_module* M, int64_t* res, size_t res_cols, size_t 
     for (size_t u = 0; u < nterms; ++u) PZ_REQUIRE(is_device_ptr(operands[u]), "batched entry points take device pointers");
     const long long res_ls = (long long)res_cols * n, res_bs = res_ls * (long long)res_size;
     return run_combine(M, res, res_bs, res_ls, 0, (size_t)batch * res_cols * res_size * (size_t)n * 8, (int)res_cols, (int)res_size, (int)base2k, in,
-                       (int)nterms, normalize, batch);
+                       (int)nterms, normalize, batch, dry);
+}
+
+}  // namespace pz
+
+extern "C" {
+
+int pz_glwe_combine_batched(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                            const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch) {
+    PZ_ENTER(M);
+    return glwe_combine_nolock(M, res, res_cols, res_size, base2k, operands, terms, nterms, normalize, batch, false);
 }
 
 int pz_vec_znx_lsh_add_into_batched(pz_module* M, size_t batch, size_t base2k, size_t k, int64_t* res, size_t res_cols, size_t res_size,

@@ -3,6 +3,7 @@
 // chain of joins is folded into per-term walk plans on the host (sum_plan); the plans travel in the kernel's arguments, so the call is a
 // single kernel node (DESIGN.md 4.4f "The graph rule", 4.6e).
 #include "api_common.hpp"
+#include "glwe_call.hpp"
 #include "device_sum.hpp"
 
 namespace {
@@ -31,11 +32,11 @@ int launch_glwe_sum(pz_module* M, const SumArgs& g) {
 
 }  // namespace
 
-extern "C" {
+namespace pz {
 
-int pz_glwe_sum_batched(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
-                        const int* shared, const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch) {
-    PZ_ENTER(M);
+// pz_glwe_sum_batched for a caller who holds the module lock; dry: every check and the plan, no launch
+int glwe_sum_nolock(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                    const int* shared, const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch, bool dry) {
     PZ_REQUIRE(res && operands && shared && a_size && join && k && sign, "glwe_sum: null argument");
     PZ_REQUIRE(res_cols >= 1 && res_cols <= 64 && res_size >= 1 && res_size <= 4096, "glwe_sum: res shape out of range");
     PZ_REQUIRE(base2k >= 1 && base2k <= 63, "glwe_sum: base2k %zu out of range", base2k);
@@ -77,8 +78,18 @@ int pz_glwe_sum_batched(pz_module* M, int64_t* res, size_t res_cols, size_t res_
         return fail(PZ_ERR_ALIAS, "glwe_sum: term 0 is res and is shifted: at most %d limbs can be staged (got %d)", kSumMaxStage, g.stage);
     PZ_REQUIRE(is_device_ptr(res), "batched entry points take device pointers");
     for (size_t u = 0; u < nterms; ++u) PZ_REQUIRE(is_device_ptr(operands[u]), "batched entry points take device pointers");
-    if (batch == 0) return PZ_OK;
+    if (batch == 0 || dry) return PZ_OK;
     return launch_glwe_sum(M, g);
+}
+
+}  // namespace pz
+
+extern "C" {
+
+int pz_glwe_sum_batched(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                        const int* shared, const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch) {
+    PZ_ENTER(M);
+    return glwe_sum_nolock(M, res, res_cols, res_size, base2k, operands, shared, a_size, join, k, sign, nterms, batch, false);
 }
 
 }  // extern "C"

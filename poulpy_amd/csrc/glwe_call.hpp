@@ -115,6 +115,11 @@ int glwe_trace(pz_module* M, int64_t* res, size_t nsteps, const int64_t* gals, c
 bool glwe_relin_t16_supported(const pz_module* M, const pz_glwe_op_params* p);
 size_t glwe_relin_chunk(const pz_module* M, const pz_glwe_op_params* p, size_t batch);
 int glwe_relin_t16(pz_module* M, int64_t* res, const short* a16, long long a16_cs, const double* pmat, const pz_glwe_op_params* p, size_t batch);
+// pz_glwe_sum_batched / pz_glwe_combine_batched (api_sum.hip, api_combine.hip); dry: every check and the plan, nothing launched
+int glwe_sum_nolock(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                    const int* shared, const size_t* a_size, const int* join, const size_t* k, const int* sign, size_t nterms, size_t batch, bool dry);
+int glwe_combine_nolock(pz_module* M, int64_t* res, size_t res_cols, size_t res_size, size_t base2k, const int64_t* const* operands,
+                        const pz_glwe_term* terms, size_t nterms, int normalize, size_t batch, bool dry);
 // pz_bdd_circuit_execute_batched without the module lock and the closing finish_call: the argument checks that need no module (precheck; *nothing:
 // the call has no ciphertext to write), then the call itself (pz_fhe_uint_execute_batched runs both halves under one lock)
 int bdd_circuit_execute_precheck(const pz_module* M, const pz_bdd_circuit* c, const int64_t* out, size_t n_out, const double* const* bits, size_t nbits,

@@ -780,6 +780,23 @@ class Module:
         self._ck(self.lib.pz_glwe_tensor_mul_relinearize_batched(self.handle, res, a, b if b is not None else a, tsk_pmat, C.byref(tparams),
                                                                  C.byref(rparams), mode, batch))
 
+    def glwe_tensor_mul_relinearize_acc_batched(self, res: c_void_p, a: c_void_p, b, tsk_pmat: c_void_p, tparams: GlweTensorParams,
+                                                rparams: GlweOpParams, mode, batch: int, a_stride: int = 0, b_stride: int = 0, accumulate=False,
+                                                join="plain", k: int = 0, sign: int = 1, normalize=True):
+        """The one-call product on operands in containers of a_stride / b_stride limbs (0: the operand's size), in place (res is a and / or
+        b at equal strides), or - accumulate - joined to res wave by wave with the product kept in the module's workspace: join "plain" |
+        "lsh_term" | "lsh_acc", k, sign +1 / -1, normalize (include/poulpy_hip.h).  mode: "apply" | "square"."""
+        mode = self.TENSOR_MODES[mode] if isinstance(mode, str) else int(mode)
+        join = self.JOIN_KINDS[join] if isinstance(join, str) else int(join)
+        self._ck(self.lib.pz_glwe_tensor_mul_relinearize_acc_batched(self.handle, res, a, b if b is not None else a, tsk_pmat, C.byref(tparams),
+                                                                     C.byref(rparams), a_stride, b_stride, int(bool(accumulate)), join, k, sign,
+                                                                     int(bool(normalize)), mode, batch))
+
+    def glwe_tensor_mul_relinearize_acc_workspace_bytes(self, tparams: GlweTensorParams, rparams: GlweOpParams, accumulate, mode, batch: int) -> int:
+        mode = self.TENSOR_MODES[mode] if isinstance(mode, str) else int(mode)
+        return self.lib.pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(self.handle, C.byref(tparams), C.byref(rparams), int(bool(accumulate)),
+                                                                           mode, batch)
+
     MUL_PLAIN_MODES = {"into": abi.PZ_MUL_PLAIN, "assign": abi.PZ_MUL_PLAIN_ASSIGN}   # = PZ_MUL_CONST / PZ_MUL_CONST_ASSIGN
 
     def glwe_mul_plain_workspace_bytes(self, params: GlweTensorParams, mode, pt_shared: bool, batch: int) -> int:
@@ -867,6 +884,10 @@ class Module:
 
     def _shift_acc(self, name, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col):
         self._ck(getattr(self.lib, name)(self.handle, batch, base2k, k, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col))
+
+    def vec_znx_copy_batched(self, batch, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
+        """vec_znx_copy (poulpy-cpu-ref vec_znx/copy.rs) on every object of the batch: the common limbs copied, the rest of res zeroed."""
+        self._ck(self.lib.pz_vec_znx_copy_batched(self.handle, batch, res, res_cols, res_size, res_col, a, a_cols, a_size, a_col))
 
     def vec_znx_lsh_add_into_batched(self, batch, base2k, k, res: c_void_p, res_cols, res_size, res_col, a: c_void_p, a_cols, a_size, a_col):
         """vec_znx_lsh::<false> (poulpy-cpu-ref vec_znx/shift.rs:68-135) on every object of the batch."""
