@@ -644,6 +644,31 @@ size_t pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(const pz_module* m, co
 int pz_glwe_tensor_mul_relinearize_acc_batched(pz_module* m, int64_t* res, const int64_t* a, const int64_t* b, const double* tsk_pmat,
                                                const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t a_stride, size_t b_stride,
                                                int accumulate, int join, size_t k, int sign, int normalize, int mode, size_t batch);
+/* The sum of npairs products in ONE GLWETensor, relinearized once - the fast branch of poulpy-ckks's ckks_dot_product_ct
+ * (leveled/delegates/composite.rs:671-699).  For every ciphertext index t of the batch: tensor = glwe_tensor_apply(a[0][t], b[0][t]), then
+ * glwe_tensor_apply_add_assign(a[i][t], b[i][t]) for i = 1 .. npairs - 1 (operations/glwe.rs:700-917), all with the one tp, then
+ * glwe_tensor_relinearize into res[t] (tp, rp, tsk_pmat as for pz_glwe_tensor_mul_relinearize_batched).  The digits are those of npairs calls of
+ * pz_glwe_tensor_apply_batched (PZ_TENSOR_APPLY, then PZ_TENSOR_APPLY_ADD_ASSIGN) on one i64 tensor followed by
+ * pz_glwe_tensor_relinearize_batched.  The accumulated tensor of a wave (pz_module_set_chunk) lives in the module's workspace and never
+ * reaches caller memory; npairs = 1 is pz_glwe_tensor_mul_relinearize_batched.
+ *   Operands.  a, b: HOST arrays of npairs device pointers; the same pointer may appear in several pairs.  a_stride / b_stride: host
+ *     arrays, per pair the limbs per ciphertext of the CONTAINERS (NULL, or an entry 0: tp->a_size / tp->b_size; never below them):
+ *     ciphertext t of pair i starts at a[i] + t n cols a_stride[i] and its first tp->a_size limbs are the operand, b alike.
+ *   Aliasing.  res must not overlap any of the 2 npairs operand ranges: PZ_ERR_ALIAS.
+ *   The accumulated tensor.  Everywhere: an i64 tensor, the two calls above as they are.  Where the one-call product keeps its tensor as
+ *     16-bit digits (one base2k <= 14 throughout, pipeline plans) AND every accumulated value provably fits an int16 - a pairwise column
+ *     holds pair - d_i - d_j, three digits, so npairs 3 2^(base2k-1) <= 2^15 - 1: 5 pairs at base2k 12, 2 at 13 - pair 0 goes straight into
+ *     the accumulated 16-bit tensor, the others into term tensors that one streaming kernel adds to it, four per launch.
+ * PZ_ERR_INVALID: npairs = 0 or above 64, a stride below the operand's size, and whatever pz_glwe_tensor_mul_relinearize_batched refuses.
+ * Nothing is launched on a refusal.  Device pointers, 16-byte aligned.  Kernel nodes only: a call repeated with the same arguments (every
+ * pointer and stride of every pair) is replayed as one HIP graph; the buffers' contents may change between calls.  _workspace_bytes: what
+ * the call needs of the module's two workspaces for `batch` ciphertexts at the module's chunk setting.
+ * (Plain arguments, not a struct: the parameter blocks of this header are a fixed list.) */
+size_t pz_glwe_tensor_dot_relinearize_workspace_bytes(const pz_module* m, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp,
+                                                      size_t npairs, size_t batch);
+int pz_glwe_tensor_dot_relinearize_batched(pz_module* m, int64_t* res, const int64_t* const* a, const int64_t* const* b, size_t npairs,
+                                           const size_t* a_stride, const size_t* b_stride, const double* tsk_pmat,
+                                           const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t batch);
 
 /* GLWE x plaintext polynomial on `batch` device-resident ciphertexts (poulpy-core/src/operations/glwe.rs): PZ_MUL_PLAIN glwe_mul_plain
  * :184-248, PZ_MUL_PLAIN_ASSIGN glwe_mul_plain_assign :250-303.  The tensor params are reused: a / res = batch GLWEs

@@ -422,6 +422,17 @@ class Module {  // Module<FFT64Hip>, poulpy-hal/src/layouts/module.rs:97-189
                                                            size_t batch) const {
         return pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(m_, &tp, &rp, accumulate ? 1 : 0, mode, batch);
     }
+    // res = relinearize(sum_i a[i] (x) b[i]): npairs products in one accumulated tensor, one relinearization; a / b: host arrays of npairs
+    // device pointers, a_stride / b_stride: limbs of the containers per pair or nullptr (poulpy_hip.h)
+    void glwe_tensor_dot_relinearize_batched(int64_t* res, const int64_t* const* a, const int64_t* const* b, size_t npairs, const size_t* a_stride,
+                                             const size_t* b_stride, const double* tsk_pmat, const pz_glwe_tensor_params& tp,
+                                             const pz_glwe_op_params& rp, size_t batch) {
+        check(pz_glwe_tensor_dot_relinearize_batched(m_, res, a, b, npairs, a_stride, b_stride, tsk_pmat, &tp, &rp, batch),
+              "glwe_tensor_dot_relinearize_batched");
+    }
+    size_t glwe_tensor_dot_relinearize_workspace_bytes(const pz_glwe_tensor_params& tp, const pz_glwe_op_params& rp, size_t npairs, size_t batch) const {
+        return pz_glwe_tensor_dot_relinearize_workspace_bytes(m_, &tp, &rp, npairs, batch);
+    }
 
   private:
     pz_module* m_ = nullptr;

@@ -18,7 +18,8 @@ slower, the chain of pz_glwe_combine_batched calls.
 
 Products of two ciphertexts (mul.rs:47-200; composite.rs mul_add_ct / mul_sub_ct / mul_many) close the file: every product is ONE
 pz_glwe_tensor_mul_relinearize_acc_batched, which reads operands in larger containers by stride, runs in place, and joins the product to
-dst from the module's workspace.
+dst from the module's workspace.  ckks_dot_product_ct (composite.rs:563-703) is plan_dot_product_ct: its fast branch
+tensors every pair into one accumulated tensor and relinearizes once - ONE pz_glwe_tensor_dot_relinearize_batched.
 """
 from __future__ import annotations
 
@@ -1071,6 +1072,157 @@ def plan_mul_many(dst: Ct, inputs) -> MulManyPlan:
     top = rec("dst", Ct(dst.base2k, dst.size, 0, 0, dst.cols), 0, len(inputs))
     plan.log_delta, plan.log_budget = top.log_delta, top.log_budget
     return plan
+
+
+DOT_MAX_PAIRS = 64       # pairs of one pz_glwe_tensor_dot_relinearize_batched (kDotMaxPairs)
+
+
+@dataclass
+class DotCtPlan:
+    """ckks_dot_product_ct (composite.rs:563-703).  branch:
+    "single"   n = 1 (:585-587): muls[0] = plan_mul_into, ONE pz_glwe_tensor_mul_relinearize_acc_batched;
+    "fallback" non-uniform log_delta on either side (:600-603): muls[0] = plan_mul_into(dst, a0, b0), muls[i] = the product of pair i into a
+               scratch ciphertext of dst's layout joined to dst by ckks_add_assign_unsafe's branch (accumulate_unnormalized, :478-506) - one
+               pz_glwe_tensor_mul_relinearize_acc_batched each, accumulate = 1, normalize = 0, and normalize = 1 on the last one: the closing
+               glwe_normalize_assign;
+    "fast"     (:605-702) on an unaligned side EVERY input is rescaled into a scratch ciphertext of ceil(target_eff_k / base2k) limbs (one
+               pz_glwe_combine_batched each, rescales[side][i]); then ONE pz_glwe_tensor_dot_relinearize_batched: all pairs tensored into one
+               accumulated GLWETensor of tensor_size limbs, one relinearization.  An aligned side is read in place, by the stride of its containers."""
+    name: str
+    branch: str
+    log_delta: int = 0             # metadata of dst after the operation
+    log_budget: int = 0
+    muls: list = field(default_factory=list)
+    n: int = 0
+    cnv_offset: int = 0
+    a_size: int = 0                # limbs of the operands: target_eff_k.div_ceil(base2k)
+    b_size: int = 0
+    a_effective_k: int = 0         # a_target_eff_k / b_target_eff_k
+    b_effective_k: int = 0
+    tensor_size: int = 0           # max(a_target_eff_k, b_target_eff_k).div_ceil(base2k): NOT the mul_into rule
+    a_strides: list = field(default_factory=list)   # limbs of the containers the call reads, per pair
+    b_strides: list = field(default_factory=list)
+    rescales: dict = field(default_factory=dict)    # "a" / "b" -> [Plan per input] on an unaligned side
+    cols: int = 2
+    base2k: int = 0
+
+    def apply_meta(self, dst: Ct):
+        dst.log_delta, dst.log_budget = self.log_delta, self.log_budget
+
+    def scratch_offsets(self, batch: int, n: int):
+        """byte offset of every rescaled copy, {(side, i): offset} (256-byte aligned), and the total"""
+        offs, at = {}, 0
+        for side, limbs in (("a", self.a_size), ("b", self.b_size)):
+            for i in range(len(self.rescales.get(side, ()))):
+                offs[(side, i)] = at
+                at += -(-(batch * self.cols * limbs * n * 8) // 256) * 256
+        return offs, at
+
+    def scratch_bytes(self, batch: int, n: int) -> int:
+        """the rescaled copies' footprint: 0 when both sides are aligned (and on the other branches)"""
+        return self.scratch_offsets(batch, n)[1]
+
+    def params(self, dst: Ct, tsk):
+        """(pz_glwe_tensor_params, pz_glwe_op_params) of the fast branch's call; tsk: the prepared tensor key's (dnum, dsize, key_size, key_base2k)"""
+        from .hal import GlweOpParams, GlweTensorParams
+        dnum, dsize, key_size, key_base2k = tsk
+        rank = dst.cols - 1
+        tp = GlweTensorParams(rank=rank, a_size=self.a_size, b_size=self.b_size, ab_base2k=dst.base2k, a_effective_k=self.a_effective_k,
+                              b_effective_k=self.b_effective_k, res_size=self.tensor_size, res_base2k=dst.base2k, cnv_offset=self.cnv_offset)
+        rp = GlweOpParams(rank=rank, dnum=dnum, dsize=dsize, key_size=key_size, key_base2k=key_base2k, a_size=self.tensor_size,
+                          a_base2k=dst.base2k, res_size=dst.size, res_base2k=dst.base2k, rank_out=rank)
+        return tp, rp
+
+    def launch(self, module, dst: Ct, batch: int, a_list, b_list, tsk_ptr=None, tsk=None, tmp=None):
+        """dst.data / a_list[i].data / b_list[i].data / tsk_ptr: device pointers; tsk = (dnum, dsize, key_size, key_base2k) of the prepared
+        tensor key; tmp: a device pointer to scratch_bytes(batch, module.n()) bytes (fast branch with an unaligned side only)."""
+        if len(a_list) != self.n or len(b_list) != self.n:
+            raise CKKSError(f"{self.name}: planned for {self.n} pairs")
+        if self.branch != "fast":
+            for i, p in enumerate(self.muls):
+                tp, rp = p.params(dst, tsk)
+                module.glwe_tensor_mul_relinearize_acc_batched(dst.data, a_list[i].data, b_list[i].data, tsk_ptr, tp, rp, "apply", batch,
+                                                               a_stride=p.a_stride, b_stride=p.b_stride, accumulate=p.join is not None,
+                                                               join=p.join or PLAIN, k=p.k, sign=1, normalize=i == len(self.muls) - 1)
+            self.apply_meta(dst)
+            return
+        offs, total = self.scratch_offsets(batch, module.n())
+        if total and tmp is None:
+            raise CKKSError(f"{self.name}: needs {total} bytes of scratch for the rescaled inputs")
+        base = 0 if tmp is None else (tmp.value if hasattr(tmp, "value") else int(tmp))
+        ptrs = {"a": [x.data for x in a_list], "b": [x.data for x in b_list]}
+        for side, xs, limbs in (("a", a_list, self.a_size), ("b", b_list, self.b_size)):       # :643-654: the a side first
+            for i, rs in enumerate(self.rescales.get(side, ())):
+                out = Ct(dst.base2k, limbs, 0, 0, dst.cols, base + offs[(side, i)])
+                rs.launch(module, out, batch, a=xs[i])
+                ptrs[side][i] = out.data
+        tp, rp = self.params(dst, tsk)
+        module.glwe_tensor_dot_relinearize_batched(dst.data, ptrs["a"], ptrs["b"], tsk_ptr, tp, rp, batch, a_strides=self.a_strides,
+                                                   b_strides=self.b_strides)
+        self.apply_meta(dst)
+
+
+def plan_dot_product_ct(dst: Ct, a_list, b_list) -> DotCtPlan:
+    """composite.rs:563-703, literally: check_lengths, ensure_accumulation_fits, n = 1 -> ckks_mul_into; non-uniform log_delta -> the
+    product of pair 0 into dst and accumulate_unnormalized over the others; otherwise the fast branch: align every side to its lowest
+    log_budget, tensor all pairs into one accumulated tensor, relinearize once."""
+    name = "dot_product_ct"
+    if len(a_list) == 0:                                                  # check_lengths, :468-476
+        raise CKKSError(f"ckks_{name}: inputs must contain at least one pair")
+    if len(a_list) != len(b_list):
+        raise CKKSError(f"ckks_{name}: length mismatch between ct vector ({len(a_list)}) and weight vector ({len(b_list)})")
+    n = len(a_list)
+    _ensure_accumulation_fits(f"ckks_{name}", dst, n)                     # :583
+    for x in (*a_list, *b_list):
+        _same_layout(name, dst, x)
+    if n == 1:                                                            # :585-587
+        p = plan_mul_into(dst, a_list[0], b_list[0])
+        return DotCtPlan(name, "single", p.log_delta, p.log_budget, [p], 1, cols=dst.cols, base2k=dst.base2k)
+    a_min_lhr = min(c.log_budget for c in a_list)                         # :589-598
+    b_min_lhr = min(c.log_budget for c in b_list)
+    uniform_ld = all(c.log_delta == a_list[0].log_delta for c in a_list) and all(c.log_delta == b_list[0].log_delta for c in b_list)
+    a_aligned = uniform_ld and all(c.log_budget == a_min_lhr for c in a_list)
+    b_aligned = uniform_ld and all(c.log_budget == b_min_lhr for c in b_list)
+    if not uniform_ld:                                                    # :600-603
+        first = plan_mul_into(dst, a_list[0], b_list[0])
+        acc = Ct(dst.base2k, dst.size, first.log_delta, first.log_budget, dst.cols)
+        muls = [first]
+        for i in range(1, n):                                             # accumulate_unnormalized: mul_into(tmp), add_assign_unsafe(dst, tmp)
+            p = plan_mul_add_ct(acc, a_list[i], b_list[i])
+            p.name = name
+            p.apply_meta(acc)
+            muls.append(p)
+        return DotCtPlan(name, "fallback", acc.log_delta, acc.log_budget, muls, n, cols=dst.cols, base2k=dst.base2k)
+    B = dst.base2k
+    a_ld, b_ld = a_list[0].log_delta, b_list[0].log_delta                 # :605-608
+    a_target_eff_k, b_target_eff_k = a_min_lhr + a_ld, b_min_lhr + b_ld
+    a_size, b_size = -(-a_target_eff_k // B), -(-b_target_eff_k // B)     # the scratch layouts, :610-621
+    rescales = {}
+    for side, aligned, xs, min_lhr, limbs in (("a", a_aligned, a_list, a_min_lhr, a_size), ("b", b_aligned, b_list, b_min_lhr, b_size)):
+        if not aligned:                                                   # :643-654: every input of the side, shift 0 included
+            rescales[side] = [plan_rescale_into(Ct(B, limbs, 0, 0, dst.cols), x, x.log_budget - min_lhr) for x in xs]
+    res_log_delta = min(a_ld, b_ld)                                       # :656-661
+    lhr0 = checked_mul_ct_log_budget(name, a_min_lhr, b_min_lhr, a_ld, b_ld)
+    res_offset = max(lhr0 + res_log_delta - dst.max_k, 0)
+    res_log_budget = checked_log_budget_sub(name, lhr0, res_offset)
+    cnv_offset = max(a_target_eff_k, b_target_eff_k) + res_offset
+    tensor_size = -(-max(a_target_eff_k, b_target_eff_k) // B)            # :663-669
+    if a_size < 1 or b_size < 1:
+        raise CKKSError(f"{name}: an operand of effective_k {min(a_target_eff_k, b_target_eff_k)} has no limb")
+
+    def strides(side, xs, limbs):
+        """a rescaled side is read from its scratch copies; an aligned side in place: every input has effective_k = the target, in a
+        container that may hold more limbs (never fewer: _operand_size)"""
+        if side in rescales:
+            return [limbs] * n
+        for x in xs:
+            _operand_size(name, x)
+        return [x.size for x in xs]
+    a_strides, b_strides = strides("a", a_list, a_size), strides("b", b_list, b_size)
+    if n > DOT_MAX_PAIRS:
+        raise CKKSError(f"{name}: {n} pairs in one pz_glwe_tensor_dot_relinearize_batched (at most {DOT_MAX_PAIRS})")
+    return DotCtPlan(name, "fast", res_log_delta, res_log_budget, [], n, cnv_offset, a_size, b_size, a_target_eff_k, b_target_eff_k, tensor_size,
+                     a_strides, b_strides, rescales, dst.cols, B)
 
 
 @dataclass

@@ -3,6 +3,7 @@
 // (poulpy-core/src/operations/glwe.rs:609-913), SURVEY.md §8f rank 4 / BASELINE configs[4].
 #include "api_common.hpp"
 #include "glwe_call.hpp"
+#include "dot_form.hpp"
 
 // CnvPVecL / CnvPVecR bytes in this backend: polynomial (col, limb) = its spectrum in device order at (col*size + limb)*n doubles.
 static inline size_t cnv_bytes(const pz_module* M, size_t cols, size_t size) { return (size_t)M->n * cols * size * 8; }
@@ -591,6 +592,131 @@ int mul_relin_run(pz_module* M, int64_t* res, const int64_t* a, const int64_t* b
     return with_graph(M, key.h, waves);
 }
 
+// everything pz_glwe_tensor_dot_relinearize_batched derives from its shapes before it launches anything
+struct DotRelinPlan {
+    MulRelinPlan q;              // the one-call product of one pair: shapes, chunk, the 16-bit column stride
+    DotTensorForm form;          // of the accumulated tensor of a wave (dot_form.hpp)
+    int group;                   // 16-bit form: term tensors beside the accumulated one = terms of one k_t16_sum launch
+    size_t tensor_bytes;         // one tensor of a wave in its form
+    size_t slot_bytes;           // 16-bit form: bytes between the tensors of a wave in ws2
+    size_t ws2_bytes;
+};
+// 16-bit form: the accumulated tensor and the term tensors of a wave start a multiple of the 4 MiB channel interleave plus s x 832 KiB apart
+// (s = 0 .. 4): k_t16_sum streams all of them at one (column, offset), five streams 832 KiB apart modulo 4 MiB.  The columns inside a tensor
+// keep their own 768 KiB (mul_relin_plan: t16_phase), which is what a tail - three columns of ONE tensor at one offset - streams.  (The launches
+// of a wave run one after the other on the module stream: no kernel streams two tensors at two columns.)
+constexpr size_t kDotChannel = (size_t)4 << 20, kDotSlotPhase = (size_t)832 << 10;
+int dot_relin_plan(const pz_module* M, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t npairs, size_t batch, DotRelinPlan& d) {
+    PZ_REQUIRE(npairs >= 1 && npairs <= kDotMaxPairs, "glwe_tensor_dot_relinearize: %zu pairs (1 .. %zu per call)", npairs, kDotMaxPairs);
+    PZ_TRY(mul_relin_plan(M, tp, rp, PZ_TENSOR_APPLY, false, batch, d.q));
+    d.form = dot_tensor_form(npairs, tp->res_base2k, d.q.compact);
+    const TensorPlan& t = d.q.t;
+    if (d.form == DOT_TENSOR_T16) {
+        d.group = dot_sum_group(npairs);
+        d.tensor_bytes = (size_t)d.q.t16_cs * t.tcols * 2;
+        d.slot_bytes = (d.tensor_bytes + kDotChannel - 1) / kDotChannel * kDotChannel + kDotSlotPhase;
+        d.ws2_bytes = (size_t)d.group * d.slot_bytes + align256(d.tensor_bytes);
+    } else {
+        d.group = 0;
+        d.tensor_bytes = d.q.chunk * (size_t)M->n * t.tcols * t.res_size * 8;
+        d.slot_bytes = 0;
+        d.ws2_bytes = d.tensor_bytes;
+    }
+    return PZ_OK;
+}
+
+// glwe_tensor_apply on pair 0, glwe_tensor_apply_add_assign on every further pair - all into ONE GLWETensor - and one
+// glwe_tensor_relinearize: the fast branch of poulpy-ckks's ckks_dot_product_ct (leveled/delegates/composite.rs:671-699; poulpy-core
+// operations/glwe.rs:700-917, :541-607).  The accumulated tensor of a wave lives in ws2.
+//   i64 form: tensor_apply_nolock per pair (PZ_TENSOR_APPLY, then PZ_TENSOR_APPLY_ADD_ASSIGN) into the wave's i64 tensor, then the i64
+//     relinearization, which reads the un-normalized limbs as they are.
+//   16-bit form (dot_form.hpp: compact shapes, every accumulated value inside int16): pair 0 through the one-call product's own launches into
+//     the accumulated 16-bit tensor, every later pair through the same launches into a term tensor, k_t16_sum adds up to four term tensors
+//     per launch, glwe_relin_t16 reads the accumulated tensor.  glwe_relin_t16 takes any int16: its forward pass converts the value to f64, its
+//     tail (k_inv_tail's ACC32 form, acc32 bit 2) sign-extends it into the 64-bit carry chain - neither uses |digit| <= 2^(base2k-1); the
+//     tensoring tails, whose side-copy forms are compiled as "normalizing, never raw", run per pair exactly as in the one-call product.
+int dot_relin_run(pz_module* M, int64_t* res, const int64_t* const* a, const int64_t* const* b, size_t npairs, const size_t* a_stride,
+                  const size_t* b_stride, const double* tsk_pmat, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t batch) {
+    DotRelinPlan d;
+    PZ_TRY(dot_relin_plan(M, tp, rp, npairs, batch, d));
+    const MulRelinPlan& q = d.q;
+    const TensorPlan& t = q.t;
+    const long long n = (long long)M->n;
+    PZ_REQUIRE(a != nullptr && b != nullptr, "glwe_tensor_dot_relinearize: null operand list");
+    PZ_REQUIRE(batch <= (size_t)1 << 24, "glwe_tensor_dot_relinearize: batch out of range");
+    PZ_REQUIRE(is_device_ptr(res) && is_device_ptr(tsk_pmat), "batched entry points take device pointers");
+    long long a_ct[kDotMaxPairs], b_ct[kDotMaxPairs];
+    size_t as[kDotMaxPairs], bs[kDotMaxPairs];
+    const long long res_ct = n * t.cols * (long long)rp->res_size;
+    for (size_t i = 0; i < npairs; ++i) {
+        as[i] = a_stride && a_stride[i] ? a_stride[i] : (size_t)t.a_size;
+        bs[i] = b_stride && b_stride[i] ? b_stride[i] : (size_t)t.b_size;
+        PZ_REQUIRE(as[i] >= (size_t)t.a_size && bs[i] >= (size_t)t.b_size && as[i] <= 4096 && bs[i] <= 4096,
+                   "glwe_tensor_dot_relinearize: pair %zu: a stride (%zu, %zu limbs) is below the operand's size (%d, %d) or out of range", i, as[i], bs[i],
+                   t.a_size, t.b_size);
+        PZ_REQUIRE(is_device_ptr(a[i]) && is_device_ptr(b[i]), "batched entry points take device pointers");
+        a_ct[i] = n * t.cols * (long long)as[i];
+        b_ct[i] = n * t.cols * (long long)bs[i];
+    }
+    // res is written by the relinearization of wave w while later waves still read every operand: no overlap with any of the 2 npairs ranges
+    for (size_t i = 0; i < npairs && batch > 0; ++i)
+        if (ranges_overlap(a[i], batch * (size_t)a_ct[i] * 8, res, batch * (size_t)res_ct * 8) ||
+            ranges_overlap(b[i], batch * (size_t)b_ct[i] * 8, res, batch * (size_t)res_ct * 8))
+            return fail(PZ_ERR_ALIAS, "glwe_tensor_dot_relinearize: res overlaps an operand of pair %zu", i);
+    if (batch == 0) return PZ_OK;
+    PZ_TRY(ws2_reserve(M, d.ws2_bytes));
+    const bool t16 = d.form == DOT_TENSOR_T16;
+    short *acc16 = nullptr, *term16[kDotSumTerms] = {};
+    int64_t* acc64 = nullptr;
+    {
+        char* base = (char*)M->ws2;
+        if (t16) {
+            PZ_TRY(ws_take(M, base, align256(d.tensor_bytes), &acc16));
+            char* slot = (char*)M->ws2;
+            for (int s = 0; s < d.group; ++s) {
+                slot += d.slot_bytes;
+                base = std::max(base, slot);
+                PZ_TRY(ws_take(M, base, align256(d.tensor_bytes), &term16[s]));
+            }
+        } else PZ_TRY(ws_take(M, base, d.tensor_bytes, &acc64));
+    }
+    dispatch_note(M, t16 ? "glwe_tensor_dot_relinearize: 16-bit accumulated tensor, term tensors summed by k_t16_sum" : "glwe_tensor_dot_relinearize: i64 accumulated tensor");
+    auto waves = [&]() -> int {
+        TensorWave w;
+        w.M = M; w.p = tp; w.t = t; w.square = false; w.add = false; w.n = n;
+        for (size_t b0 = 0; b0 < batch; b0 += q.chunk) {
+            const size_t nb = std::min(q.chunk, batch - b0);
+            int64_t* rw = res + (long long)b0 * res_ct;
+            if (!t16) {
+                // (not through the public entry points: the module lock is held)
+                for (size_t i = 0; i < npairs; ++i)
+                    PZ_TRY(tensor_apply_nolock(M, acc64, a[i] + (long long)b0 * a_ct[i], b[i] + (long long)b0 * b_ct[i], tp,
+                                               i == 0 ? PZ_TENSOR_APPLY : PZ_TENSOR_APPLY_ADD_ASSIGN, nb, a_ct[i], b_ct[i]));
+                PZ_TRY(glwe_op(M, GlweKind::TensorRelin, rw, acc64, tsk_pmat, rp, nb));
+                continue;
+            }
+            PZ_TRY(w.take_workspace(nb));
+            w.nb = (int)nb; w.rb = nullptr; w.t16_cs = q.t16_cs;
+            for (size_t i = 0; i < npairs; ++i) {
+                const int slot = i == 0 ? -1 : (int)((i - 1) % (size_t)d.group);
+                w.t16 = slot < 0 ? acc16 : term16[slot];
+                w.a_cs = a_ct[i]; w.b_cs = b_ct[i];
+                PZ_TRY(w.prepare(a[i] + (long long)b0 * a_ct[i], b[i] + (long long)b0 * b_ct[i]));
+                PZ_REQUIRE(w.fused, "glwe_tensor_dot_relinearize: the fused tensoring path was expected here");
+                PZ_TRY(w.combine_in_stores());
+                if (slot >= 0 && (slot == d.group - 1 || i == npairs - 1))
+                    PZ_TRY(launch_t16_sum(M, acc16, term16, slot + 1, t.tcols, (long long)nb * t.res_size * n, q.t16_cs));
+            }
+            PZ_TRY(glwe_relin_t16(M, rw, acc16, q.t16_cs, tsk_pmat, rp, nb));
+        }
+        return PZ_OK;
+    };
+    // kernel nodes only: a call repeated with the same arguments replays as one graph
+    KeyHash key = graph_key(M, GRAPH_TENSOR_DOT, res, npairs, tsk_pmat, *tp, *rp, batch);
+    for (size_t i = 0; i < npairs; ++i) { key.add(a[i]); key.add(b[i]); key.add(as[i]); key.add(bs[i]); }
+    return with_graph(M, key.h, waves);
+}
+
 }  // namespace
 
 extern "C" {
@@ -618,6 +744,24 @@ size_t pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(const pz_module* M, co
     if (!M || mul_relin_plan(M, tp, rp, mode, accumulate != 0, std::max<size_t>(batch, 1), q) != PZ_OK) return 0;
     const size_t main_ws = std::max(q.chunk * (q.t.per_ct + 6 * 256), pz_glwe_op_workspace_bytes(M, rp, q.chunk, (int)GlweKind::TensorRelin));
     return main_ws + kGuardSlack + align256(q.tensor_bytes) + q.prod_bytes + kGuardSlack;
+}
+
+// Sum of npairs tensor products in ONE accumulated GLWETensor, relinearized once (include/poulpy_hip.h): the fast branch of
+// poulpy-ckks's ckks_dot_product_ct (poulpy_amd/ckks.py plan_dot_product_ct)
+int pz_glwe_tensor_dot_relinearize_batched(pz_module* M, int64_t* res, const int64_t* const* a, const int64_t* const* b, size_t npairs,
+                                           const size_t* a_stride, const size_t* b_stride, const double* tsk_pmat, const pz_glwe_tensor_params* tp,
+                                           const pz_glwe_op_params* rp, size_t batch) {
+    PZ_ENTER(M);
+    return dot_relin_run(M, res, a, b, npairs, a_stride, b_stride, tsk_pmat, tp, rp, batch);
+}
+// the module's two workspaces as that call sizes them: the larger of the tensoring's and the relinearization's carve of the main one, and
+// the accumulated tensor of a wave with (16-bit form) its term tensors behind it
+size_t pz_glwe_tensor_dot_relinearize_workspace_bytes(const pz_module* M, const pz_glwe_tensor_params* tp, const pz_glwe_op_params* rp, size_t npairs,
+                                                      size_t batch) {
+    DotRelinPlan d;
+    if (!M || dot_relin_plan(M, tp, rp, npairs, std::max<size_t>(batch, 1), d) != PZ_OK) return 0;
+    const size_t main_ws = std::max(d.q.chunk * (d.q.t.per_ct + 6 * 256), pz_glwe_op_workspace_bytes(M, rp, d.q.chunk, (int)GlweKind::TensorRelin));
+    return main_ws + kGuardSlack + d.ws2_bytes + kGuardSlack;
 }
 
 }  // extern "C"

@@ -56,9 +56,11 @@ static int fhe_uint_pack_refusals(pz_module* M, const int64_t* res, const int64_
     PZ_REQUIRE(tmp_bytes >= need, "fhe_uint_pack: tmp too small (%zu bytes, %zu needed)", tmp_bytes, need);
     const size_t cols = p->rank + 1, ctb = batch * (size_t)M->n * cols * p->res_size * 8, bits_bytes = word_bits * ctb;
     const size_t key_bytes = glwe_key_bytes(M, p);
+    // (bits against tmp first: bits is the longest range - word_bits ciphertext batches - so a bits pointer that is really tmp reaches past tmp's
+    // end into whatever the allocator put there, res included, and the refusal named whichever pair was tested first)
+    if (ranges_overlap(bits, bits_bytes, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: bits overlaps tmp");
     if (ranges_overlap(res, ctb, bits, bits_bytes)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps bits");
     if (ranges_overlap(res, ctb, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: res overlaps tmp");
-    if (ranges_overlap(bits, bits_bytes, tmp, need)) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: bits overlaps tmp");
     const size_t hit = std::min({trace_keys_overlap(tk, key_bytes, res, ctb), trace_keys_overlap(tk, key_bytes, bits, bits_bytes),
                                  trace_keys_overlap(tk, key_bytes, tmp, need)});
     if (hit < tk.nsteps) return fail(PZ_ERR_ALIAS, "fhe_uint_pack: the key of trace step %zu overlaps res, bits or tmp", hit);

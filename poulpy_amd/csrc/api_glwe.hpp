@@ -35,6 +35,7 @@ enum GraphTag : int {
     GRAPH_FHE_UINT_WORD = 12,         // api_fhe_uint.hip
     GRAPH_LINCOMB_CONST = 31,         // api_lincomb.hip (builds its key by hand)
     GRAPH_TENSOR_MUL_ACC = 32,        // api_cnv.hip
+    GRAPH_TENSOR_DOT = 33,            // api_cnv.hip (adds every pair's pointers and strides to its key)
 };
 // the key of a call from its tag, the arguments that are always there, and the module's state; the caller adds what is special to it
 template <typename... Args>

@@ -260,6 +260,35 @@ __global__ void __launch_bounds__(256) k_ew(EwArgs g) {
 }
 
 // =================================================================================
+// Sum of GLWETensors held as 16-bit digits in the fused tail's tile order (pz_glwe_tensor_dot_relinearize_batched, api_cnv.hip):
+// acc += term[0] + ... + term[NT - 1].  All tensors have the identical layout - column c at c * col_stride, col_vecs
+// 16-byte vectors of it in use - so the sum is blind to the tile order: a streaming add of int16, eight per 16-byte load, packed 16-bit adds
+// (wrapping; the caller has checked that no sum leaves the int16 range: dot_form.hpp).  blockIdx.y = column.  The terms are read once
+// (non-temporal); the accumulated tensor is read again by the next group or by the relinearization.
+// =================================================================================
+constexpr int kT16SumMax = 4;
+struct T16SumArgs {
+    short* acc;
+    const short* term[kT16SumMax];
+    long long col_vecs, col_stride;   // 16-byte vectors in use per column / between columns
+};
+template <int NT>
+__global__ void __launch_bounds__(256) k_t16_sum(T16SumArgs g) {
+    typedef unsigned short pz_u16x8 __attribute__((ext_vector_type(8)));
+    const long long base = (long long)blockIdx.y * g.col_stride;
+    pz_u16x8* acc = reinterpret_cast<pz_u16x8*>(g.acc) + base;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < g.col_vecs; v += (long long)gridDim.x * 256) {
+        pz_u16x8 t[NT];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) t[u] = __builtin_nontemporal_load(reinterpret_cast<const pz_u16x8*>(g.term[u]) + base + v);
+        pz_u16x8 s = acc[v];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) s += t[u];
+        acc[v] = s;
+    }
+}
+
+// =================================================================================
 // vec_znx_automorphism / vec_znx_big_automorphism  X -> X^p on i64 polynomials
 // (reference/znx/automorphism.rs:1-17: res[(i*p) mod 2n] = a[i], negated when the index wraps past n).
 // Gather form, so that stores are coalesced: with g = p^-1 mod 2n,  i0 = (j*g) mod 2n,

@@ -318,6 +318,9 @@ int launch_small_inv_gather(pz_module* M, int batch, const SmallGatherShape& s, 
 // ---- launch_ops.hip -----------------------------------------------------------------------------------------------
 int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_ls, const void* a, long long a_bs,
               long long a_ls, const void* b, long long b_bs, long long b_ls, int nlimbs, int batch);
+// acc += terms[0] + ... + terms[nterms - 1] on GLWETensors held as 16-bit digits, all of one layout: `cols` columns col_stride int16 apart,
+// the first col_elems of each in use (both multiples of 8, the pointers 16-byte aligned); 1 <= nterms <= 4 (k_t16_sum)
+int launch_t16_sum(pz_module* M, short* acc, const short* const* terms, int nterms, int cols, long long col_elems, long long col_stride);
 // zero-fill as a kernel node (not hipMemsetAsync: see launch_ops.hip) - for everything that can run under graph capture
 int launch_zero_bytes(pz_module* M, void* ptr, size_t bytes);
 // dst = +-src(X^p-gather with multiplier mul) [+ add]; see k_automorphism

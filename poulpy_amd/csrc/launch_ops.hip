@@ -6,12 +6,15 @@
 
 #include "internal.hpp"
 #include "device_ops.hpp"
+#include "dot_form.hpp"
 
 #ifndef PZ_VMP_RB
 #define PZ_VMP_RB 2
 #endif
 
 namespace pz {
+
+static_assert(kDotSumTerms <= kT16SumMax, "k_t16_sum: one launch takes every term tensor of a group (dot_form.hpp)");
 
 int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_ls, const void* a, long long a_bs,
                      long long a_ls, const void* b, long long b_bs, long long b_ls, int nlimbs, int batch) {
@@ -24,6 +27,32 @@ int launch_ew(pz_module* M, int op, void* res, long long res_bs, long long res_l
     const int blocks = (int)std::min<long long>((total + 255) / 256, 256 * 16);
     KTimer kt(M, PZ_K_ELEMENTWISE);
     hipLaunchKernelGGL(k_ew, dim3(blocks), dim3(256), 0, M->stream, g);
+    PZ_HIP(hipGetLastError());
+    return PZ_OK;
+}
+
+int launch_t16_sum(pz_module* M, short* acc, const short* const* terms, int nterms, int cols, long long col_elems, long long col_stride) {
+    if (cols <= 0 || col_elems <= 0) return PZ_OK;
+    if (nterms < 1 || nterms > kT16SumMax || !acc || !terms) return fail(PZ_ERR_INVALID, "t16_sum: 1 .. %d term tensors per launch (got %d)", kT16SumMax, nterms);
+    if (col_elems % 8 || col_stride % 8 || col_elems > col_stride || ((uintptr_t)acc & 15))
+        return fail(PZ_ERR_INVALID, "t16_sum: columns of 16-byte vectors (%lld of %lld int16 in use)", col_elems, col_stride);
+    T16SumArgs g{};
+    g.acc = acc;
+    for (int u = 0; u < nterms; ++u) {
+        if (!terms[u] || ((uintptr_t)terms[u] & 15) || terms[u] == acc) return fail(PZ_ERR_INVALID, "t16_sum: term %d is null, unaligned or the accumulated tensor", u);
+        g.term[u] = terms[u];
+    }
+    g.col_vecs = col_elems / 8; g.col_stride = col_stride / 8;
+    // 16 B per thread and step; capped at 2048 workgroups over the columns, the rest by the grid stride
+    const int per_col = std::max(1, 2048 / cols);
+    const dim3 grid((unsigned)std::min<long long>((g.col_vecs + 255) / 256, per_col), (unsigned)cols);
+    KTimer kt(M, PZ_K_ELEMENTWISE);
+    switch (nterms) {
+        case 1: hipLaunchKernelGGL(k_t16_sum<1>, grid, dim3(256), 0, M->stream, g); break;
+        case 2: hipLaunchKernelGGL(k_t16_sum<2>, grid, dim3(256), 0, M->stream, g); break;
+        case 3: hipLaunchKernelGGL(k_t16_sum<3>, grid, dim3(256), 0, M->stream, g); break;
+        default: hipLaunchKernelGGL(k_t16_sum<4>, grid, dim3(256), 0, M->stream, g); break;
+    }
     PZ_HIP(hipGetLastError());
     return PZ_OK;
 }

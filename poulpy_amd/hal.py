@@ -797,6 +797,31 @@ class Module:
         return self.lib.pz_glwe_tensor_mul_relinearize_acc_workspace_bytes(self.handle, C.byref(tparams), C.byref(rparams), int(bool(accumulate)),
                                                                            mode, batch)
 
+    @staticmethod
+    def _dot_lists(a_ptrs, b_ptrs, a_strides, b_strides):
+        n = len(a_ptrs)
+        if len(b_ptrs) != n or any(s is not None and len(s) != n for s in (a_strides, b_strides)):
+            raise ValueError("glwe_tensor_dot_relinearize: one b pointer and one stride per a pointer")
+        m = max(n, 1)
+        pa, pb = (c_void_p * m)(), (c_void_p * m)()
+        for i in range(n):
+            pa[i] = a_ptrs[i].value if isinstance(a_ptrs[i], c_void_p) else a_ptrs[i]
+            pb[i] = b_ptrs[i].value if isinstance(b_ptrs[i], c_void_p) else b_ptrs[i]
+        sa = None if a_strides is None else (C.c_size_t * m)(*[int(s) for s in a_strides])
+        sb = None if b_strides is None else (C.c_size_t * m)(*[int(s) for s in b_strides])
+        return n, pa, pb, sa, sb
+
+    def glwe_tensor_dot_relinearize_batched(self, res: c_void_p, a_ptrs, b_ptrs, tsk_pmat: c_void_p, tparams: GlweTensorParams,
+                                            rparams: GlweOpParams, batch: int, a_strides=None, b_strides=None):
+        """sum_i a_ptrs[i] (x) b_ptrs[i] in ONE accumulated GLWETensor (glwe_tensor_apply, then glwe_tensor_apply_add_assign), relinearized
+        once: the fast branch of poulpy-ckks's ckks_dot_product_ct (include/poulpy_hip.h).  a_ptrs / b_ptrs: device pointers,
+        one per pair; a_strides / b_strides: limbs of the containers per pair (None: the operands' sizes)."""
+        n, pa, pb, sa, sb = self._dot_lists(a_ptrs, b_ptrs, a_strides, b_strides)
+        self._ck(self.lib.pz_glwe_tensor_dot_relinearize_batched(self.handle, res, pa, pb, n, sa, sb, tsk_pmat, C.byref(tparams), C.byref(rparams), batch))
+
+    def glwe_tensor_dot_relinearize_workspace_bytes(self, tparams: GlweTensorParams, rparams: GlweOpParams, npairs: int, batch: int) -> int:
+        return self.lib.pz_glwe_tensor_dot_relinearize_workspace_bytes(self.handle, C.byref(tparams), C.byref(rparams), npairs, batch)
+
     MUL_PLAIN_MODES = {"into": abi.PZ_MUL_PLAIN, "assign": abi.PZ_MUL_PLAIN_ASSIGN}   # = PZ_MUL_CONST / PZ_MUL_CONST_ASSIGN
 
     def glwe_mul_plain_workspace_bytes(self, params: GlweTensorParams, mode, pt_shared: bool, batch: int) -> int:
