@@ -1166,7 +1166,7 @@ const char* pz_kernel_class_name(int kclass);
 int pz_module_set_margin_probe(pz_module* m, int enable);
 int pz_module_get_margin(pz_module* m, double* max_frac);
 
-/* Which kernel instantiations the hot dispatch sites (middle kernel, blind-rotation kernels) have chosen since the last reset, as one
+/* Which kernel instantiations the hot dispatch sites (middle kernel, fused tail, blind-rotation kernels) have chosen since the last reset, as one
  * "; "-separated string: measurement tools print it next to their numbers. */
 int pz_module_dispatch_notes(pz_module* m, char* buf, size_t len, int reset);
 

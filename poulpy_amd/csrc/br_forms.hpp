@@ -42,6 +42,18 @@ inline BrBlockForm br_block_form(int row_max, int ncols, bool use_lds) {
 
 }  // namespace pz
 
+// (R0, CT, PJ, MR, CG, A32) of the block-binary forms and (R0, PJ, MR, CG) of the standard forms
+#define PZ_BR_FORMS(X)                                                                                                       \
+    X(2, 1, 1, 4, 4, false) X(2, 1, 1, 6, 3, false)                                                                          \
+    X(4, 1, 1, 4, 4, false) X(4, 1, 1, 6, 3, false) X(4, 2, 1, 4, 4, false) X(4, 2, 1, 6, 3, false) X(4, 2, 1, 4, 4, true) X(4, 2, 1, 6, 3, true) \
+    X(8, 1, 1, 4, 4, false) X(8, 1, 1, 6, 3, false) X(8, 1, 2, 4, 4, false) X(8, 1, 2, 6, 3, false)                          \
+    X(8, 2, 1, 4, 4, false) X(8, 2, 1, 6, 3, false) X(8, 2, 2, 6, 3, false)                                                  \
+    X(8, 2, 1, 4, 4, true) X(8, 2, 1, 6, 3, true) X(8, 2, 2, 6, 3, true)   /* (8, 2, 2, 4, 4, *): 16 work polynomials of 512 points never fit */
+// (R0, PJ, MR, CG) of the 256-thread forms: one ciphertext per workgroup, two workgroups per CU whose barriers do not line up
+#define PZ_BR_HALF_FORMS(X) X(4, 2, 4, 4, false) X(4, 2, 6, 3, false)
+#define PZ_BR_STD_FORMS(X)                                                                                                   \
+    X(2, 1, 4, 4) X(2, 1, 6, 3) X(4, 1, 4, 4) X(4, 1, 6, 3) X(8, 1, 4, 4) X(8, 1, 6, 3) X(8, 2, 4, 4) X(8, 2, 6, 3)
+
 #ifdef __HIPCC__
 #include <algorithm>
 
@@ -56,18 +68,6 @@ struct BrFusedPlan {
     size_t lds = 0, pmat_doubles = 0;
 };
 constexpr int kBrNT = 512;
-
-// (R0, CT, PJ, MR, CG, A32) of the block-binary forms and (R0, PJ, MR, CG) of the standard forms
-#define PZ_BR_FORMS(X)                                                                                                       \
-    X(2, 1, 1, 4, 4, false) X(2, 1, 1, 6, 3, false)                                                                          \
-    X(4, 1, 1, 4, 4, false) X(4, 1, 1, 6, 3, false) X(4, 2, 1, 4, 4, false) X(4, 2, 1, 6, 3, false) X(4, 2, 1, 4, 4, true) X(4, 2, 1, 6, 3, true) \
-    X(8, 1, 1, 4, 4, false) X(8, 1, 1, 6, 3, false) X(8, 1, 2, 4, 4, false) X(8, 1, 2, 6, 3, false)                          \
-    X(8, 2, 1, 4, 4, false) X(8, 2, 1, 6, 3, false) X(8, 2, 2, 6, 3, false)                                                  \
-    X(8, 2, 1, 4, 4, true) X(8, 2, 1, 6, 3, true) X(8, 2, 2, 6, 3, true)   /* (8, 2, 2, 4, 4, *): 16 work polynomials of 512 points never fit */
-// (R0, PJ, MR, CG) of the 256-thread forms: one ciphertext per workgroup, two workgroups per CU whose barriers do not line up
-#define PZ_BR_HALF_FORMS(X) X(4, 2, 4, 4, false) X(4, 2, 6, 3, false)
-#define PZ_BR_STD_FORMS(X)                                                                                                   \
-    X(2, 1, 4, 4) X(2, 1, 6, 3) X(4, 1, 4, 4) X(4, 1, 6, 3) X(8, 1, 4, 4) X(8, 1, 6, 3) X(8, 2, 4, 4) X(8, 2, 6, 3)
 
 inline bool br_form_exists(const BrFusedPlan& pl) {
     if (pl.std_variant) {

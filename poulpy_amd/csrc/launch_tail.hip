@@ -89,6 +89,9 @@ static int launch_tail_plan(pz_module* M, const TailCall& c, const TailNz* nz) {
         // the rounding-margin instantiation of the same form when the module's probe is on (pz_module_set_margin_probe): the same source with the
         // probe block compiled in, so that the margin is measured on the form the product path dispatches (launch_tail_probe.hip)
         PZ_TRY(M->probe ? tail_launch_form_probe(M, g, blocks, l.form) : tail_launch_form<false>(M, g, blocks, l.form));
+        char note[64];
+        tail_note(l.form, pl.f1a, pl.f1b, pl.cb, note, sizeof note);
+        dispatch_note(M, M->probe ? "%s PROBE" : "%s", note);
     }
     return PZ_OK;
 }

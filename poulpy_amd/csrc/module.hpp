@@ -245,7 +245,7 @@ inline void dispatch_note(pz_module* M, const char* fmt, ...) {
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
     for (auto& s : M->notes) if (s == buf) return;
-    if (M->notes.size() < 32) M->notes.emplace_back(buf);
+    if (M->notes.size() < 64) M->notes.emplace_back(buf);   // (the fused tail alone names several forms per composite call)
 }
 
 // Two-stream section of one API call: independent halves of a batch whose kernels are bound by different units (a compute-bound product beside a

@@ -3,6 +3,9 @@
 // same three lists to launch, tests/cpp/test_tail_plan.cpp compiles all of it with the host compiler and sweeps it (every form chosen has an
 // entry; every column is written by exactly one launch; the launches are the ones tests/golden/tail_plans.txt records).
 #pragma once
+#include <cstddef>
+#include <cstdio>
+
 #include "../../include/poulpy_hip.h"
 
 namespace pz {
@@ -33,6 +36,14 @@ inline bool tail_plan_whole_waves(int f1b, int cb) { return (f1b * cb) % 64 == 0
 inline bool tail_form_exists(const TailForm& f, int f1a, int f1b, int cb) {
     if (f.kind == TailForm::ACC32) return tail_plan_acc32(f1a, f1b, cb);
     return f.kind == TailForm::PLAIN ? tail_plan_plain(f1a, f1b, cb) : tail_plan_rsh(f1a, f1b, cb);
+}
+
+// the dispatch note of a form on a plan, worded as tests/golden/tail_plans.txt names forms (tests and the bench tools match on these); the
+// rounding-margin instantiation of the same form (launch_tail_probe.hip) adds " PROBE"
+inline void tail_note(const TailForm& f, int f1a, int f1b, int cb, char* buf, size_t n) {
+    static const char* const kind[] = {"PLAIN", "RSH", "SGN", "NZ1", "NZ2", "ACC32", "NZ1W", "NZ2R", "NZ1O", "NZ2O", "SGN16", "SGN16R"};
+    if (f.kind == TailForm::PLAIN) snprintf(buf, n, "k_inv_tail<%d,%d,%d> PLAIN(%d,%d)", f1a, f1b, cb, (int)f.rowmajor, (int)f.has_small);
+    else snprintf(buf, n, "k_inv_tail<%d,%d,%d> %s", f1a, f1b, cb, kind[f.kind]);
 }
 
 // What the plan reads of a call: the scalars of a TailCall under their own names, "is set" for its pointers, the widths of its digits, the

@@ -196,8 +196,8 @@ class Module:
 
     def dispatch_notes(self, reset: bool = False) -> str:
         """Kernel instantiations chosen by the hot dispatch sites since the last reset (include/poulpy_hip.h)."""
-        buf = C.create_string_buffer(4096)
-        self._ck(self.lib.pz_module_dispatch_notes(self.handle, buf, 4096, 1 if reset else 0))
+        buf = C.create_string_buffer(16384)
+        self._ck(self.lib.pz_module_dispatch_notes(self.handle, buf, 16384, 1 if reset else 0))
         return buf.value.decode()
 
     def set_kernel_timing(self, enable: bool):

@@ -680,9 +680,11 @@ def test_ggsw_from_gglwe_batched(mods, n, rank, cols_in, fill=None):
 # SURVEY.md 8f rank 2 / BASELINE configs[3]: CGGI blind rotation on a batch of LWE ciphertexts
 # ------------------------------------------------------------------------------------------
 def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, res_size, base2k, batch, seed, fuse=(True, True), lut_size=None,
-                        lut_fill=None, out=None):
+                        lut_fill=None, out=None, lwe_span=None):
     """lut_fill(0, data, rng) overwrites the test vector's digits in place (tests/unnormalized.py); out (a dict) receives the rounding margins
-    of the oracle and of the device (`oracle_margin`, `gpu_margin`), and the dispatch notes of the main call (`notes`)."""
+    of the oracle and of the device (`oracle_margin`, `gpu_margin`), and the dispatch notes of the main call (`notes`).  lwe_span: the mask
+    coefficients are drawn from [0, lwe_span) instead of [-n, n) and the oracle's table of prepared monomials holds those rows alone (the whole
+    table is 2n x n doubles: 16 GiB at N = 2^15)."""
     from poulpy_amd.hal import BlindRotationParams
     rng = seeded(seed)
     cols = rank + 1
@@ -697,9 +699,19 @@ def _run_blind_rotation(hip, ref, n, rank, n_lwe, block_size, dnum, brk_size, re
         brk_r[i] = pr.data.reshape(-1)
         brk_h[i] = ph.data.reshape(-1)
     lwe = rng.integers(-n, n, (batch, n_lwe + 1), dtype=np.int64)   # mod_switch_2n output range
+    if lwe_span is not None:
+        lwe[:, 1:] = rng.integers(0, lwe_span, (batch, n_lwe), dtype=np.int64)
     lwe[0, 1] = 0        # X^0 - 1 = 0: a coefficient that contributes nothing
     lwe[-1, 0] = n - 1
-    xpa = ref.blind_rotation_x_pow_a() if block_size > 1 else np.zeros((1, 1))
+    if lwe_span is not None and block_size > 1:   # rows [0, lwe_span) of blind_rotation_x_pow_a: svp_prepare(X^i)
+        xpa = np.zeros((lwe_span, n))
+        for i in range(lwe_span):
+            mono, pp = ScalarZnx(n, 1), SvpPPol(n, 1)
+            mono.data[0, 0, i] = 1
+            ref.svp_prepare(pp, 0, mono, 0)
+            xpa[i] = pp.data.reshape(-1)
+    else:
+        xpa = ref.blind_rotation_x_pow_a() if block_size > 1 else np.zeros((1, 1))
     want = np.empty((batch, res_size, cols, n), dtype=np.int64)
     for b in range(batch):
         res = VecZnx(n, cols, res_size)
@@ -1555,6 +1567,7 @@ def _trace_shifted_stores(mods, n, size, key_size, res_gals, k):
         hip.sync()
         got = d_res.download(np.int64, want.size).reshape(want.shape)
     assert np.array_equal(got, want)
+    return got, want
 
 
 @pytest.mark.parametrize("n,rank,res_k,key_k,kbits,batch,nsteps", [
